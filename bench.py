@@ -7,6 +7,7 @@ batch that is already resident in HBM.  The known-certificate table is cleared i
 timed step, so every step does the same "first sighting" work.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR    # … and what the last timed step computed, as DIR/*.npy
     python bench.py --gpus N                       # spawns its own N rank processes (one per GPU), rank 0 prints the line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W          # … or runs under a launcher's RANK/WORLD_SIZE
@@ -25,6 +26,7 @@ every rank's shard (+ the out-of-shard sources of its duplicates) against the or
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -603,6 +605,9 @@ def run_stream(args, ctmr, synth, N, torch, np, dev, local, rank, world, cfg, fi
         tot_bytes += int(st.payload_bytes) + ALG_BYTES_FIXED * n + ALG_BYTES_PROBE * int(st.by_status[0])
         first += n_wave
         waves += 1
+    dumped = None
+    if args.dump_outputs and rank == 0:      # the last wave: its records and NEW list; the sets' counts after it
+        dumped = dump_outputs(args.dump_outputs, torch, np, dev, n, d_rec, d_new, int(st.n_new), eng.issuer_counts(), st)
     wb_out = None
     if wbs is not None:
         t0 = time.perf_counter()
@@ -643,6 +648,8 @@ def run_stream(args, ctmr, synth, N, torch, np, dev, local, rank, world, cfg, fi
            "result": {"n_new": tot_new, "n_dup": tot_dup, "n_pass": tot_pass, "total_count": total_count,
                       "entries_disagreeing_with_generator": bad_entries,
                       "duplicate_structure_matches_generator_in_every_wave": bool(ok)}}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if group is not None:
         out["exchange"] = {"mode": mode, "transport": "rccl", "wire_bytes_sent_by_rank0_over_the_stream": wire}
     if wb_out is not None:
@@ -700,6 +707,53 @@ def oracle_sample_check(np, torch, ctmr, synth, N, cfg, dup_permille, issuers, f
             "status_mismatches": int((rec["status"] != ost_m).sum()),
             "was_unknown_mismatches": int((gnew != (ounk_m != 0)).sum())}
     return cpu, info, arrays, ranges
+
+
+# per-entry arrays of --dump-outputs: this many records, 116 B each as written (sample_index 8, status / flags / serial_len
+# 3 x 4, exp_hour and issuer_idx 2 x 8, serial 20 x 4; 124 B with the raw mode's timestamps), and as many NEW entries,
+# 16 B each (new_pos, new_idx): ≈37 MB at most
+DUMP_SAMPLE = 1 << 18
+DUMP_SEED = 20260921
+
+
+def dump_outputs(outdir, torch, np, dev, E, d_rec, d_new, n_new, counts, stats, timestamps=None):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as float32 / float64 .npy files
+    (under 40 MB).  The per-entry record fields and the NEW list are a fixed, seeded sample when they are longer than
+    DUMP_SAMPLE; records_digest.npy and new_digest.npy are sums over ALL records and the WHOLE NEW list, so two
+    builds that differ anywhere outside the sample still differ there."""
+    from ct_mapreduce_amd.engine import RECORD_DTYPE
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.arange(E) if E <= DUMP_SAMPLE else np.sort(rng.choice(E, DUMP_SAMPLE, replace=False))
+    recs = d_rec.view(-1, 32)[:E]
+    rec = recs[torch.from_numpy(idx).to(dev)].cpu().numpy().reshape(-1).view(RECORD_DTYPE)
+    out = {"sample_index": idx.astype(np.float64),
+           "status": rec["status"].astype(np.float32), "flags": rec["flags"].astype(np.float32),
+           "serial_len": rec["serial_len"].astype(np.float32), "exp_hour": rec["exp_hour"].astype(np.float64),
+           "issuer_idx": rec["issuer_idx"].astype(np.float64), "serial": rec["serial"].astype(np.float32)}
+    if timestamps is not None:
+        out["timestamp"] = timestamps[:E][torch.from_numpy(idx).to(dev)].cpu().numpy().astype(np.float64)
+    # digest of every record: per byte column, the plain sum and the sum weighted by (i mod 65521) + 1
+    dig = torch.zeros(2, 32, dtype=torch.int64, device=dev)
+    for lo in range(0, E, 1 << 20):
+        c = recs[lo:lo + (1 << 20)].to(torch.int64)
+        w = torch.arange(lo, lo + c.shape[0], dtype=torch.int64, device=dev) % 65521 + 1
+        dig[0] += c.sum(0)
+        dig[1] += (c * w[:, None]).sum(0)
+    out["records_digest"] = dig.cpu().numpy().astype(np.float64)
+    new = d_new[:n_new]
+    pos = np.arange(n_new) if n_new <= DUMP_SAMPLE else np.sort(rng.choice(n_new, DUMP_SAMPLE, replace=False))
+    out["new_pos"] = pos.astype(np.float64)
+    out["new_idx"] = new[torch.from_numpy(pos).to(dev)].cpu().numpy().astype(np.float64)
+    out["new_digest"] = np.array([n_new, int(new.sum().item()) if n_new else 0,
+                                  int((new % 65521).sum().item()) if n_new else 0], np.float64)
+    out["issuer_counts"] = np.asarray(counts, np.uint64).astype(np.float64)
+    out["stats"] = np.array([int(stats.n), int(stats.n_new), int(stats.n_dup), int(stats.n_host_set)]
+                            + [int(x) for x in stats.by_status], np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": outdir, "files": sorted(n + ".npy" for n in out), "records_sampled": int(len(idx)),
+            "bytes": int(sum(a.nbytes for a in out.values()))}
 
 
 def main():
@@ -810,6 +864,11 @@ def main():
     ap.add_argument("--sample-per-slice", type=int, default=0,
                     help="… of this many entries each (default: --cpu-sample / ranks / --sample-slices), plus every entry "
                          "outside the slices whose key a sampled duplicate repeats")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's records, NEW list, "
+                         "per-issuer counts and stats; a fixed seeded sample of the per-entry arrays plus digests over all "
+                         "of them) as DIR/<name>.npy in float32/float64, under 40 MB: same arguments, same inputs, so two "
+                         "builds can be compared output for output")
     args = ap.parse_args()
 
     if args.stream and (args.raw or args.global_dedup or args.meta or args.pem or args.fingerprint):
@@ -1076,6 +1135,10 @@ def main():
         dt = float(group.all_reduce_u64([int(dt * 1e9)], op_max=True)[0]) * 1e-9      # the slowest rank's time
     if world == 1:
         global_counts[0] = eng.issuer_counts()[:len(issuers)]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, torch, np, dev, E, d_rec, d_new, int(stats.n_new), global_counts[0], stats,
+                              timestamps=d_iss if args.raw else None)
 
     # ---- the run checks itself, at every N ------------------------------------------------------------------------
     # (a) every entry's WasUnknown and Σ NEW against the generator's duplicate structure: entry i repeats an EARLIER
@@ -1209,6 +1272,8 @@ def main():
     }
     if checks is not None:
         out["checks"] = checks
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if out["roofline"]["frac"] > 1.0 or out["roofline"]["frac_algorithmic"] > 1.0:
         out["roofline"]["invalid"] = "a fraction above 1 is a pricing error, not a result"
     if args.pem:
@@ -1348,17 +1413,22 @@ def main():
             offs_k = arrays[1][:k + 1]
             certs_k = [arrays[0][int(offs_k[i]):int(offs_k[i + 1])].tobytes() for i in range(k)]
             starts_k = d_off[ranges[0][0]:ranges[0][0] + k].cpu().numpy()
-            nb, nl = needed_bytes_per_cert(certs_k, starts_k, filt, args.profile == "reference")
-            n_pass = int(stats.by_status[0])
-            fixed = ALG_BYTES_FIXED * E + 4 * E + ALG_BYTES_PROBE * n_pass      # arrays + record + ent[] word; slot read + write
-            out["roofline"]["needed_bytes"] = nb * E + fixed
-            out["roofline"]["needed_line_bytes"] = nl * E + fixed + 64 * n_pass   # … when every touched 128-B line moves whole (slot lines too)
-            out["roofline"]["needed_note"] = (f"per certificate the walk's reads cover {nb:.0f} bytes lying in {nl / 128:.2f} lines of 128 B "
-                                              f"(product walk on the host with a marking reader, first {k} sampled certificates); "
-                                              "+ 45 B arrays/record + 4 B reduce state per entry + the 64-B slot (a 128-B line) per PASS entry")
-            if traffic:
-                out["roofline"]["over_fetch_vs_needed_bytes"] = traffic / out["roofline"]["needed_bytes"]
-                out["roofline"]["over_fetch_vs_needed_lines"] = traffic / out["roofline"]["needed_line_bytes"]
+            try:
+                nb, nl = needed_bytes_per_cert(certs_k, starts_k, filt, args.profile == "reference")
+            except (OSError, subprocess.CalledProcessError) as ex:    # the host walk could not be built or loaded here
+                nb = nl = None
+                out["roofline"]["needed_error"] = f"host build of the walk unavailable: {ex}"
+            if nb is not None:
+                n_pass = int(stats.by_status[0])
+                fixed = ALG_BYTES_FIXED * E + 4 * E + ALG_BYTES_PROBE * n_pass      # arrays + record + ent[] word; slot read + write
+                out["roofline"]["needed_bytes"] = nb * E + fixed
+                out["roofline"]["needed_line_bytes"] = nl * E + fixed + 64 * n_pass   # … when every touched 128-B line moves whole (slot lines too)
+                out["roofline"]["needed_note"] = (f"per certificate the walk's reads cover {nb:.0f} bytes lying in {nl / 128:.2f} lines of 128 B "
+                                                  f"(product walk on the host with a marking reader, first {k} sampled certificates); "
+                                                  "+ 45 B arrays/record + 4 B reduce state per entry + the 64-B slot (a 128-B line) per PASS entry")
+                if traffic:
+                    out["roofline"]["over_fetch_vs_needed_bytes"] = traffic / out["roofline"]["needed_bytes"]
+                    out["roofline"]["over_fetch_vs_needed_lines"] = traffic / out["roofline"]["needed_line_bytes"]
             quota_threads, quota = cpu_quota()
             threads = args.cpu_threads or quota_threads
             if threads > 1:

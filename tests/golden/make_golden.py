@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Regenerates / verifies the fixtures in this directory.
 
-  python tests/golden/make_golden.py            # verify (what the CPU test suite does through test_golden_files)
-  python tests/golden/make_golden.py --write    # rewrite them (needs /root/reference for the PEM literals)
+  python tests/golden/make_golden.py                         # verify (what the CPU test suite does through test_golden_files)
+  python tests/golden/make_golden.py --reference DIR         # … and the PEM literals against a checkout of the reference
+  python tests/golden/make_golden.py --write --reference DIR # rewrite them (the PEM literals come from the reference)
 
 1. The three PEM certificates are TEST DATA copied out of the reference's own unit tests
    (storage/types_test.go:21-39, storage/filesystemdatabase_test.go:17-33,35-64): the Go string literals
-   kLeadingZeroes / kEmptySPKI / kRealSPKI, byte for byte.
+   kLeadingZeroes / kEmptySPKI / kRealSPKI, byte for byte.  Without --reference they are verified against the
+   SHA-256 digests pinned below.
 2. synth_small.json freezes a small synthetic batch: the generator's bytes (SHA-256 of the packed payload, of the
    raw get-entries blob and of the issuer certificates) and what the oracle says about every entry — so that neither
    the benchmark workload nor the oracle can drift unnoticed."""
@@ -19,13 +21,21 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
 PEMS = {"kLeadingZeroes": "storage/types_test.go", "kEmptySPKI": "storage/filesystemdatabase_test.go",
         "kRealSPKI": "storage/filesystemdatabase_test.go"}
+PEM_SHA256 = {"kLeadingZeroes": "e6a51c12e1b9666e444e9e4422ff53d29ef7162b1514b27baa22eeb9b02c78df",
+              "kEmptySPKI": "d4ad996220f49dc92650601c06eaf2a4284a36e9c8827c7622a39f6fff209004",
+              "kRealSPKI": "05409821bccda225f6a243b3ebedd4be6251464e9d14e6268974ceaf70f30558"}
 
 
-def pem_from_reference(name, path):
-    src = open(os.path.join(REF, path)).read()
+def reference_dir():
+    if "--reference" in sys.argv:
+        return sys.argv[sys.argv.index("--reference") + 1]
+    return None
+
+
+def pem_from_reference(ref, name, path):
+    src = open(os.path.join(ref, path)).read()
     m = re.search(name + r"\s*=\s*`(-----BEGIN CERTIFICATE-----.*?-----END CERTIFICATE-----)`", src, re.S)
     return m.group(1).strip() + "\n"
 
@@ -54,16 +64,22 @@ def synth_small():
 
 def main():
     write = "--write" in sys.argv
+    ref = reference_dir()
+    if write and ref is None:
+        sys.exit("--write needs --reference DIR (the PEM literals are copied out of the reference's tests)")
     bad = 0
     for name, path in PEMS.items():
         f = os.path.join(HERE, name + ".pem")
-        if os.path.isdir(REF):
-            want = pem_from_reference(name, path)
+        if ref is not None:
+            want = pem_from_reference(ref, name, path)
             if write:
                 open(f, "w").write(want)
             elif open(f).read().strip() != want.strip():
                 print("MISMATCH", name)
                 bad += 1
+        if not write and hashlib.sha256(open(f, "rb").read()).hexdigest() != PEM_SHA256[name]:
+            print("MISMATCH", name, "(pinned SHA-256)")
+            bad += 1
     f = os.path.join(HERE, "synth_small.json")
     want = synth_small()
     if write:

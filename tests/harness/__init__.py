@@ -2,19 +2,56 @@
 import ctypes as C
 import os
 import subprocess
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(HERE, "..", "..", "ct_mapreduce_amd", "csrc")
+WALK_DEPS = [os.path.join(CSRC, h) for h in ("der_walk.h", "spki_key.h", "ec_curves.h", "entry_decode.h")]
 
 
-def _build(src, out, cmd):
-    outp = os.path.join(HERE, out)
+def _build(src, out, cmd, deps=(), libs=()):
+    """The library `out` built from `src` (+ `deps`): next to its source, where __graft_entry__.build() leaves it, or
+    rebuilt there when a source is newer.  A checkout that was built and is then only read (not writable) rebuilds a
+    stale library in this user's private cache directory (_cache_dir) instead of failing."""
     srcp = os.path.join(HERE, src)
-    csrc = os.path.join(HERE, "..", "..", "ct_mapreduce_amd", "csrc")
-    deps = [os.path.join(csrc, h) for h in ("der_walk.h", "spki_key.h", "ec_curves.h", "entry_decode.h")]
-    if (not os.path.exists(outp) or os.path.getmtime(outp) < os.path.getmtime(srcp)
-            or any(os.path.getmtime(outp) < os.path.getmtime(d) for d in deps)):
-        subprocess.check_call(cmd + [srcp, "-o", outp])
+    inputs = [srcp] + list(deps)
+
+    def fresh(p):
+        return os.path.exists(p) and all(os.path.getmtime(p) >= os.path.getmtime(d) for d in inputs)
+    outp = os.path.join(HERE, out)
+    if fresh(outp):
+        return outp
+    if not os.access(HERE, os.W_OK):
+        outp = os.path.join(_cache_dir(), out)
+        if fresh(outp):
+            return outp
+    subprocess.check_call(list(cmd) + [srcp, "-o", outp] + list(libs))
     return outp
+
+
+def _cache_dir():
+    """This user's private cache for harness libraries that cannot be rebuilt in place: $XDG_CACHE_HOME or ~/.cache, else
+    a fresh private temporary directory.  A directory another user owns or may write is refused: a library is loaded from it."""
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    d = os.path.join(base, "ctmr_harness")
+    try:
+        os.makedirs(d, mode=0o700, exist_ok=True)
+    except OSError:
+        d = tempfile.mkdtemp(prefix="ctmr_harness_")
+    st = os.stat(d)
+    if st.st_uid != os.getuid() or st.st_mode & 0o022:
+        raise PermissionError(f"{d}: not a private directory of this user; refusing to build or load a library there")
+    return d
+
+
+def _lib(name):
+    src, out, cmd, kw = LIBS[name]
+    return _build(src, out, cmd, **kw)
+
+
+def build_all():
+    """Every harness library (what __graft_entry__.build() compiles, so that tests and bench.py need no compiler)."""
+    return [_lib(name) for name in LIBS]
 
 
 class HarnessOut(C.Structure):
@@ -47,7 +84,7 @@ def product_decode_entry(leaf_input: bytes, extra_data: bytes, fill=0xA5, prefix
     """The product's decode_entry (host build) on blob = prefix ‖ leaf_input ‖ extra_data."""
     global _entry
     if _entry is None:
-        p = _build("entry_harness.cpp", "libentry_harness.so", ["g++", "-O2", "-std=c++17", "-shared", "-fPIC"])
+        p = _lib("entry")
         _entry = C.CDLL(p)
         _entry.harness_decode_entry.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint8,
                                                 C.POINTER(EntryOut)]
@@ -64,8 +101,7 @@ def product_walk(der: bytes, fill=0xA5, cn_filter=None) -> HarnessOut:
     """cn_filter=None: no issuerCNFilter (cn_match is True); bytes: the raw filter string."""
     global _walk
     if _walk is None:
-        p = _build("walk_harness.cpp", "libwalk_harness.so",
-                   ["g++", "-O2", "-std=c++17", "-shared", "-fPIC"])
+        p = _lib("walk")
         _walk = C.CDLL(p)
         _walk.harness_walk_f.argtypes = [C.c_char_p, C.c_uint32, C.c_uint8, C.c_char_p, C.c_uint32,
                                          C.c_int, C.POINTER(HarnessOut)]
@@ -163,11 +199,7 @@ def walk_window(der: bytes, phase: int = 0, wbytes: int = 224, strings: bool = F
 def ossl_extract(der: bytes):
     global _ossl
     if _ossl is None:
-        outp = os.path.join(HERE, "libossl_extract.so")
-        srcp = os.path.join(HERE, "ossl_extract.c")
-        if not os.path.exists(outp) or os.path.getmtime(outp) < os.path.getmtime(srcp):
-            subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", srcp, "-o", outp, "-lcrypto"])
-        _ossl = C.CDLL(outp)
+        _ossl = C.CDLL(_lib("ossl"))
         _ossl.ossl_extract.argtypes = [C.c_char_p, C.c_long, C.POINTER(OsslOut)]
         _ossl.ossl_pubkey_ok.argtypes = [C.c_char_p, C.c_long]
     o = OsslOut()
@@ -204,12 +236,7 @@ def host_keys_lib():
     """Host build of csrc/host_keys.h: the wire form and the verdict of a group round's long-serial settlement."""
     global _hk
     if _hk is None:
-        src = os.path.join(HERE, "host_keys_harness.cpp")
-        dep = os.path.join(HERE, "..", "..", "ct_mapreduce_amd", "csrc", "host_keys.h")
-        out = os.path.join(HERE, "libhost_keys_harness.so")
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(dep)):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", src, "-o", out])
-        _hk = C.CDLL(out)
+        _hk = C.CDLL(_lib("host_keys"))
         _hk.harness_host_keys_verdict.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint64),
                                                   C.POINTER(C.c_uint8), C.c_uint32]
         _hk.harness_host_keys_append.argtypes = [C.c_uint64, C.c_int32, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64),
@@ -221,10 +248,19 @@ def host_keys_lib():
 def build_fake_rccl() -> str:
     """The stand-in for librccl (fake_rccl.cpp: ranks as threads or processes on ONE GPU, bytes through POSIX shared
     memory), built on demand; hand the path to the library through CTMR_RCCL_LIB."""
-    import subprocess
-    src = os.path.join(HERE, "fake_rccl.cpp")
-    out = os.path.join(HERE, "libfake_rccl.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                               src, "-o", out, "-L/opt/rocm/lib", "-lamdhip64", "-pthread", "-lrt"])
-    return out
+    return _lib("fake_rccl")
+
+
+# name → (source, library, compiler command, {deps, libs})
+LIBS = {
+    "walk": ("walk_harness.cpp", "libwalk_harness.so", ["g++", "-O2", "-std=c++17", "-shared", "-fPIC"],
+             {"deps": WALK_DEPS}),
+    "entry": ("entry_harness.cpp", "libentry_harness.so", ["g++", "-O2", "-std=c++17", "-shared", "-fPIC"],
+              {"deps": WALK_DEPS}),
+    "ossl": ("ossl_extract.c", "libossl_extract.so", ["gcc", "-O2", "-shared", "-fPIC"], {"libs": ["-lcrypto"]}),
+    "host_keys": ("host_keys_harness.cpp", "libhost_keys_harness.so", ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall"],
+                  {"deps": [os.path.join(CSRC, "host_keys.h")]}),
+    "fake_rccl": ("fake_rccl.cpp", "libfake_rccl.so",
+                  ["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"],
+                  {"libs": ["-L/opt/rocm/lib", "-lamdhip64", "-pthread", "-lrt"]}),
+}

@@ -97,3 +97,43 @@ def test_the_torch_form_of_the_duplicate_predicate_is_the_numpy_one():
         want = bench.synth_is_dup(seed, first, n, permille, np)
         got = bench.synth_is_dup_torch(seed, first, n, permille, torch, torch.device("cpu")).numpy()
         assert (got == want).all() and 0 < want.sum() < n
+
+
+def test_dump_outputs_is_a_deterministic_float_sample_of_what_the_step_returned(tmp_path):
+    """--dump-outputs: float32 / float64 files only, a fixed seeded sample of the records (the same one every run), digests
+    over all of them, well under 64 MB even for a batch larger than the sample."""
+    import types
+    import torch
+    from ct_mapreduce_amd.engine import RECORD_DTYPE
+    E = 2 * bench.DUMP_SAMPLE + 12345
+    rng = np.random.default_rng(5)
+    rec_bytes = rng.integers(0, 256, size=(E, 32), dtype=np.uint8)
+    d_rec = torch.from_numpy(rec_bytes.reshape(-1).copy())
+    new = np.sort(rng.choice(E, 300_000, replace=False)).astype(np.int64)
+    d_new = torch.from_numpy(np.concatenate([new, np.zeros(E - len(new), np.int64)]))
+    st = types.SimpleNamespace(n=E, n_new=len(new), n_dup=7, n_host_set=0, by_status=[E - 9, 9, 0, 0, 0, 0, 0, 0])
+    counts = np.arange(256, dtype=np.uint64)
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        info = bench.dump_outputs(d, torch, np, torch.device("cpu"), E, d_rec, d_new, len(new), counts, st)
+        assert info["records_sampled"] == bench.DUMP_SAMPLE and info["bytes"] < 64 << 20
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) == info["files"]
+    total = 0
+    for n in names:
+        a, b = np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += os.path.getsize(os.path.join(dirs[0], n))
+    assert total < 64 << 20
+    load = lambda n: np.load(os.path.join(dirs[0], n + ".npy"))  # noqa: E731
+    idx = load("sample_index").astype(np.int64)
+    assert len(np.unique(idx)) == bench.DUMP_SAMPLE and idx.max() < E
+    rec = rec_bytes[idx].reshape(-1).view(RECORD_DTYPE)
+    assert (load("status") == rec["status"]).all() and (load("exp_hour") == rec["exp_hour"]).all()
+    assert (load("issuer_idx") == rec["issuer_idx"]).all() and (load("serial") == rec["serial"]).all()
+    w = np.arange(E, dtype=np.int64) % 65521 + 1
+    dig = load("records_digest")
+    assert (dig[0] == rec_bytes.astype(np.int64).sum(0)).all() and (dig[1] == (rec_bytes * w[:, None]).sum(0)).all()
+    assert (load("new_idx") == new[load("new_pos").astype(np.int64)]).all()
+    assert (load("new_digest") == [len(new), new.sum(), (new % 65521).sum()]).all()
+    assert (load("issuer_counts") == counts).all() and load("stats")[:3].tolist() == [E, len(new), 7]

@@ -201,7 +201,7 @@ def test_pem_encode_line_breaking_edges():
 
 def test_golden_files_are_current():
     """The committed fixtures equal what tests/golden/make_golden.py produces (PEM literals of the reference's tests
-    when /root/reference is present; the frozen synthetic batch always)."""
+    against their pinned SHA-256 digests; the frozen synthetic batch)."""
     import os
     import subprocess
     import sys

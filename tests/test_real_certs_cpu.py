@@ -1,41 +1,31 @@
-"""Real-world DER diversity without a network: the CA bundles shipped in the image (certifi's cacert.pem and
-/etc/ssl/certs/ca-certificates.crt — RSA-2048/4096 and EC P-256/P-384 keys, UTCTime and GeneralizedTime, Printable /
-UTF8 / T61 strings, names without a CommonName, 20-byte and 1-byte serials, v1 certificates).  Oracle, the product's
-walk (host build) and OpenSSL 3 must agree on every field the path consumes.  No GPU."""
+"""Real-world DER diversity without a network: public CA root certificates frozen in tests/golden/ca_roots.pem (the
+Mozilla root program's certificates as packaged by Debian ca-certificates and by certifi, tests/golden/README.md —
+RSA-2048/4096 and EC P-256/P-384 keys, UTCTime and GeneralizedTime, Printable / UTF8 / T61 strings, names without a
+CommonName, 20-byte and 1-byte serials, v1 certificates).  Oracle, the product's walk (host build) and OpenSSL 3 must agree on every field the path consumes.  No GPU."""
 import base64
 import hashlib
 import os
 import re
 
-import pytest
-
 from oracle import oracle as orc
 from tests import harness
 
+CA_ROOTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ca_roots.pem")
+
 
 def bundle_ders():
-    paths = ["/etc/ssl/certs/ca-certificates.crt"]
-    try:
-        import certifi
-        paths.append(certifi.where())
-    except ImportError:
-        pass
     seen, out = set(), []
-    for p in paths:
-        if not os.path.exists(p):
-            continue
-        for b in re.findall(r"-----BEGIN CERTIFICATE-----(.*?)-----END CERTIFICATE-----", open(p).read(), re.S):
-            d = base64.b64decode("".join(b.split()))
-            if d not in seen:
-                seen.add(d)
-                out.append(d)
+    for b in re.findall(r"-----BEGIN CERTIFICATE-----(.*?)-----END CERTIFICATE-----", open(CA_ROOTS).read(), re.S):
+        d = base64.b64decode("".join(b.split()))
+        if d not in seen:
+            seen.add(d)
+            out.append(d)
     return out
 
 
 def test_real_roots_oracle_product_openssl_agree():
     ders = bundle_ders()
-    if len(ders) < 50:
-        pytest.skip("no CA bundle in this image")
+    assert len(ders) >= 150
     n_cn = n_gt = n_ec = 0
     for d in ders:
         c = orc.parse_cert(d)
