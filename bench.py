@@ -8,9 +8,15 @@ timed step, so every step does the same "first sighting" work.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
     python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR    # … and what the last timed step computed, as DIR/*.npy
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full                # … and everything else the line measures and checks
     python bench.py --gpus N                       # spawns its own N rank processes (one per GPU), rank 0 prints the line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W          # … or runs under a launcher's RANK/WORLD_SIZE
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: `value`, `ms_per_step`, the
+kernel times and the algorithmic roofline.  --full adds what takes time or runs of its own: the PMC traffic passes
+(--traffic), the checks against the generator, the oracle-checked sample and the CPU baseline legs (--no-cpu), the
+bytes the walk needs, and the secondary legs of the one-GPU line (--no-secondary).
 
 N > 1 (BASELINE configs[3]): ONE batch of --total-entries (default 100 M) is split by log-index range — rank r owns
 [r·T/N, (r+1)·T/N), strong scaling — and the dedup is GLOBAL and exact by default (--dedup bloom: the all-gather of
@@ -19,7 +25,7 @@ the reference's processes (storage/rediscache.go:57-65; cmd/ct-fetch/ct-fetch.go
 sets and says so.  --entries E instead gives every GPU E entries (weak scaling).  Everything on the data path — shard
 maps, exchanges, the all-reduce of the per-issuer counts, barriers, the max of the step time — goes through the library's
 own RCCL group; the host only hands the 128-byte group id to its ranks (environment of the spawned processes, or one
-broadcast over the launcher's rendezvous).  At every N the run checks itself: Σ NEW and every entry's WasUnknown against
+broadcast over the launcher's rendezvous).  At every N a --full run checks itself: Σ NEW and every entry's WasUnknown against
 the generator's duplicate structure, the all-reduced per-issuer counts against the generator, and a strided sample of
 every rank's shard (+ the out-of-shard sources of its duplicates) against the oracle.
 """
@@ -625,9 +631,9 @@ def run_stream(args, ctmr, synth, N, torch, np, dev, local, rank, world, cfg, fi
     ok = ok and total_count == tot_new and bad_entries == 0
     achieved = tot_bytes / (t_map * 1e-3) / 1e9
     # measured HBM traffic of the map kernel in this mode: a 40 M-entry stream in 4 waves of 10 M under rocprofv3 --pmc
-    # (the table persists across the waves, as here; bytes per entry averaged over the launches)
+    # (the table persists across the waves, as here; bytes per entry averaged over the launches) — with --full
     traffic_info = traffic_err = None
-    if world == 1 and args.traffic == "auto" and not wb and not os.environ.get("CTMR_BENCH_CHILD"):
+    if args.full and world == 1 and args.traffic == "auto" and not wb and not os.environ.get("CTMR_BENCH_CHILD"):
         kname = MAP_KERNELS[args.variant or DEFAULT_VARIANT].split("<")[0]
         traffic_info, traffic_err = measure_traffic(args, 10_000_000, [kname], ["--stream", "40000000"])
     out = {"metric": "certificates/sec whole-node + achieved HBM GB/s, 100M-entry synthetic CT batch",
@@ -811,13 +817,13 @@ def main():
     ap.add_argument("--mixed", action="store_true",
                     help="the mixed synthetic corpus (half EC P-256 keys, 40%% OV-like subjects of 120-260 bytes, longer "
                          "issuer names, one GeneralizedTime in four) instead of the SURVEY §8(d) corpus: how the map "
-                         "behaves when the lanes of a wave do not walk identical layouts.  The default run reports it as "
+                         "behaves when the lanes of a wave do not walk identical layouts.  A --full run reports it as "
                          "secondary.mixed; this flag makes it the line's workload")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (mixed corpus, 128-byte aligned layout) of the default run")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (mixed corpus, 128-byte aligned layout, fast profile, raw entries) of a --full run")
     ap.add_argument("--profile", choices=("fast", "reference"), default="reference",
                     help="ctmr_set_profile: 'reference' (the engine's default and the headline) = strict_spki + strict_leaf + "
                          "strict_strings + strict_extensions — what the reference's x509.ParseCertificate decides, as far as it can be "
-                         "known here (DESIGN.md §3.1); 'fast' = strict_spki only, for a host that has parsed already.  The default "
+                         "known here (DESIGN.md §3.1); 'fast' = strict_spki only, for a host that has parsed already.  A --full "
                          "run reports it as secondary.fast_profile")
     ap.add_argument("--strict-extensions", action="store_true",
                     help="ctmr_set_strict_extensions(1) alone: the extension bodies Go parses (what it costs on top of the default walk)")
@@ -830,7 +836,7 @@ def main():
     ap.add_argument("--aligned", type=int, default=0, metavar="BYTES",
                     help="lay every certificate at a multiple of BYTES (an entry view instead of the packed layout; payload grows "
                          "by the padding): what the map moves per certificate depends on where certificates start inside "
-                         "128-byte lines.  The default run reports --aligned 128 as secondary.aligned128")
+                         "128-byte lines.  A --full run reports --aligned 128 as secondary.aligned128")
     ap.add_argument("--pem", action="store_true",
                     help="also time the PEM write-back kernels (k_pem_len + scan + k_pem_encode, SURVEY §8(f) N1) over "
                          "the first 16M entries of the NEW list")
@@ -848,7 +854,7 @@ def main():
                          "first sighting per call and identified by length + first/last 16 bytes afterwards "
                          "(include/ctmr.h); the default compares every byte of every entry's Chain[0]")
     ap.add_argument("--traffic", default="auto", choices=["auto", "off"],
-                    help="auto (default, N=1 only): after the timed steps re-execute this script on --traffic-entries "
+                    help="auto (default; with --full, N=1 only): after the timed steps re-execute this script on --traffic-entries "
                          "entries of the same corpus and mode under `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` "
                          "(separate passes) and report the measured HBM traffic of the line's kernels; off: roofline.traffic = null")
     ap.add_argument("--traffic-entries", type=int, default=10_000_000)
@@ -864,6 +870,11 @@ def main():
     ap.add_argument("--sample-per-slice", type=int, default=0,
                     help="… of this many entries each (default: --cpu-sample / ranks / --sample-slices), plus every entry "
                          "outside the slices whose key a sampled duplicate repeats")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, everything else the line measures and checks: the PMC traffic passes "
+                         "(--traffic), the checks against the generator, the oracle-checked sample and the CPU baseline legs "
+                         "(--no-cpu), the bytes the walk needs and the secondary legs (--no-secondary).  Without it a run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (rank 0's records, NEW list, "
                          "per-issuer counts and stats; a fixed seeded sample of the per-entry arrays plus digests over all "
@@ -1140,12 +1151,12 @@ def main():
         dumped = dump_outputs(args.dump_outputs, torch, np, dev, E, d_rec, d_new, int(stats.n_new), global_counts[0], stats,
                               timestamps=d_iss if args.raw else None)
 
-    # ---- the run checks itself, at every N ------------------------------------------------------------------------
+    # ---- with --full the run checks itself, at every N ------------------------------------------------------------
     # (a) every entry's WasUnknown and Σ NEW against the generator's duplicate structure: entry i repeats an EARLIER
     #     entry's key iff synth_is_dup(i), wherever in the log that earlier entry lies — so, with a global set, a rank's
     #     NEW entries are exactly its PASS ∧ ¬dup ones; (b) the all-reduced per-issuer vector against the same structure.
     checks = None
-    if not args.raw:
+    if args.full and not args.raw:
         recs = d_rec.view(-1, 32)[:E]
         passed = recs[:, 0] == 0
         is_new = (recs[:, 1] & 2) != 0
@@ -1183,7 +1194,7 @@ def main():
                     traffic_err = "traffic file refused: taken on another build of libctmr.so"
             except (ValueError, OSError) as ex:
                 traffic_err = f"traffic file unreadable: {ex}"
-        elif args.traffic == "auto":
+        elif args.full and args.traffic == "auto":
             t_tr = time.perf_counter()
             traffic_info, traffic_err = measure_traffic(args, min(E, args.traffic_entries), kernels, mode_args)
             if traffic_info:
@@ -1388,8 +1399,8 @@ def main():
         out["kernel_ms"]["decode"] = ds.ms_decode
         out["kernel_ms"]["match"] = ds.ms_match
 
-    # ---- oracle-checked sample of every rank's shard; the CPU baseline legs on rank 0 at N = 1
-    if not args.no_cpu and not args.raw and not args.aligned:
+    # ---- with --full: oracle-checked sample of every rank's shard; the CPU baseline legs on rank 0 at N = 1
+    if args.full and not args.no_cpu and not args.raw and not args.aligned:
         per_rank_sample = max(min(args.cpu_sample, total) // world, 1)
         per = args.sample_per_slice or max(1, min(per_rank_sample, E) // args.sample_slices)
         base_cpu, pinfo, arrays, ranges = oracle_sample_check(np, torch, ctmr, synth, N, cfg, dup_permille, issuers, filt, now, dev,
@@ -1456,10 +1467,10 @@ def main():
                     "one_core": {"value": base_cpu["value"], "sample": base_cpu["sample"]}}
                 del arrays_mt, pay_mt
 
-    # ---- secondary lines inside the default run (the driver's record carries them next to the headline):
+    # ---- secondary lines inside a --full run (the driver's record carries them next to the headline):
     #      mixed      the same batch on the corpus that looks like a real log
     #      aligned128 the headline corpus with every certificate laid at a multiple of 128 bytes (what the layout is worth)
-    if (rank == 0 and world == 1 and plain and not args.mixed and not args.aligned and not args.no_secondary
+    if (args.full and rank == 0 and world == 1 and plain and not args.mixed and not args.aligned and not args.no_secondary
             and not os.environ.get("CTMR_BENCH_CHILD") and not args.variant and not args.pem and not args.fingerprint):
         out["secondary"] = {}
         legs = (("mixed", 1, 0, "the same batch on the MIXED corpus (half EC P-256 keys, 40 % OV-like subjects of 120-260 B, longer "

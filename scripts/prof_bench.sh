@@ -13,5 +13,5 @@ done
 python $R/scripts/make_traffic.py $OUT $E ${V/#0/15} > $OUT/traffic.json 2> $OUT/traffic.err
 python $R/scripts/pmc_summary.py $OUT > $OUT/pmc_summary.txt 2>&1
 find $OUT -name "*kernel_trace.csv" -size +1M -delete; find $OUT -name "*counter_collection.csv" -size +1M -delete
-timeout 600 $CMD --traffic-file $OUT/traffic.json > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 $CMD --full --traffic-file $OUT/traffic.json > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json; cat $OUT/traffic.json; find $OUT -name "*kernel_stats.csv" | head -1 | xargs head -8 | cut -c1-200

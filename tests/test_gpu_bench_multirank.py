@@ -3,7 +3,7 @@ one reachable GPU over the stand-in for librccl (tests/harness/fake_rccl.cpp, PO
 through CTMR_RCCL_LIB).  What is under test is everything around the collectives that only exists at N > 1: the
 self-launch (the parent makes the group id and spawns the ranks), the launcher path (torchrun's RANK / WORLD_SIZE and
 one broadcast of the id), the log-index split of ONE batch (strong scaling, BASELINE configs[3]), exact global dedup by
-default, and the run's own checks at every N — Σ NEW and every entry's WasUnknown against the generator, the
+default, and the run's own checks at every N (--full) — Σ NEW and every entry's WasUnknown against the generator, the
 all-reduced per-issuer counts, the strided oracle sample of every rank's shard.  Real RCCL between devices stays
 unmeasured until a multi-GPU node exists."""
 import json
@@ -30,7 +30,7 @@ def run_bench(extra, launcher=None, timeout=300):
     return json.loads(lines[0])
 
 
-COMMON = ["--steps", "2", "--warmup", "1", "--traffic", "off", "--cpu-sample", "60000", "--sample-slices", "12",
+COMMON = ["--full", "--steps", "2", "--warmup", "1", "--traffic", "off", "--cpu-sample", "60000", "--sample-slices", "12",
           "--dup-permille", "100"]
 
 
@@ -86,6 +86,18 @@ def test_one_gpu_line_still_carries_its_checks():
     assert d["n_gpus"] == 1 and d["config"]["dedup"] == "plain" and "exchange" not in d
     assert d["checks"]["entries_disagreeing_with_generator"] == 0 and d["checks"]["per_issuer_counts_match_generator"]
     assert d["parity_vs_oracle_on_sample"] is True and d["cpu_baseline"]["value"] > 0
+
+
+def test_plain_one_gpu_line_does_only_what_its_headline_needs():
+    """Without --full: set up, warm up, time the steps, print the line — no PMC passes, checks, oracle sample, CPU
+    baseline or secondary legs."""
+    d = run_bench(["--gpus", "1", "--total-entries", "300000", "--steps", "2", "--warmup", "1"])
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "certificates/sec"
+    assert d["higher_is_better"] is True and d["dtype"] == "u8" and d["result"]["n_new"] > 0
+    assert abs(d["value"] - 300000 * 1000 / d["ms_per_step"]) < 1e-3 * d["value"]
+    for k in ("checks", "parity_vs_oracle_on_sample", "parity_sample", "cpu_baseline", "secondary"):
+        assert k not in d, k
+    assert d["roofline"]["traffic"] is None and "needed_bytes" not in d["roofline"]
 
 
 @pytest.mark.parametrize("dedup", ["auto", "bloom"])
