@@ -85,6 +85,16 @@ class TableInfo(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class KnownImageInfo(C.Structure):
+    _fields_ = [("members", C.c_uint64), ("sets", C.c_uint64), ("host_members", C.c_uint64), ("meta_bytes", C.c_uint64),
+                ("image_bytes", C.c_uint64), ("issuers", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KnownImportStats(C.Structure):
+    _fields_ = [("members", C.c_uint64), ("taken", C.c_uint64), ("inserted", C.c_uint64), ("known", C.c_uint64),
+                ("host_members", C.c_uint64), ("host_inserted", C.c_uint64)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_issuers", C.c_uint32), ("zipf", C.c_uint32),
                 ("dup_permille", C.c_uint32), ("ca_permille", C.c_uint32),
@@ -131,6 +141,11 @@ SIGNATURES = {
     "ctmr_issuer_counts_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint32)]),
     "ctmr_reset_known": (C.c_int, [_P]),
     "ctmr_table_info_get": (C.c_int, [_P, C.POINTER(TableInfo)]),
+    "ctmr_known_export": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(KnownImageInfo)]),
+    "ctmr_known_export_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.POINTER(KnownImageInfo)]),
+    "ctmr_known_import": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(KnownImportStats)]),
+    "ctmr_known_import_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, C.c_uint32,
+                                           C.POINTER(KnownImportStats)]),
     "ctmr_xchg_map_device": (C.c_int, [_P, C.POINTER(Shard), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]),
     "ctmr_xchg_map_chunk_device": (C.c_int, [_P, C.POINTER(Shard), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P,

@@ -644,5 +644,6 @@ extern "C" {
 #include "engine/sets.inc"
 #include "engine/group.inc"
 #include "engine/synth.inc"
+#include "engine/image.inc"
 
 }  // extern "C"

@@ -1,0 +1,544 @@
+// engine/image.inc — the known-certificate image: bulk export and import of the serials:: sets (include/ctmr.h,
+// DESIGN.md §12).  What a restart of a reference deployment finds still in Redis, carried across a restart of the engine.
+// Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after the engine state.
+
+extern "C++" {
+namespace {
+
+constexpr char KNOWN_MAGIC[8] = {'C', 'T', 'M', 'R', 'K', 'N', 'W', 'N'};
+constexpr uint32_t KNOWN_VERSION = 1, KNOWN_HEADER = 64;
+constexpr uint64_t KNOWN_CHUNK = 1ull << 27;  // import: records per pass (32-bit orders and slot ids, bounded scratch)
+
+struct KnownMeta {
+  uint32_t n_issuers = 0;
+  uint64_t n_sets = 0, n_members = 0, host_bytes = 0, n_host_members = 0, meta_bytes = 0;
+  const uint8_t* issuers = nullptr;  // n_issuers × 32
+  const uint8_t* sets = nullptr;     // n_sets × 24
+  std::vector<std::string> ids;      // Issuer.ID of each ordinal
+  std::vector<int32_t> set_hour;
+  std::vector<uint32_t> set_issuer;
+  std::vector<uint64_t> set_first;   // n_sets + 1
+  std::vector<std::pair<std::string, std::string>> host;  // (key, member)
+};
+
+// Hours whose ExpDate.ID has four year digits (0000-01-01-00 .. 9999-12-31-23): there the keys serials::<date>::<id>
+// order as (hour, id) do — the date part is fixed-width and chronological.  Other hours compare as strings.
+const int64_t KNOWN_HOUR_LO = days_from_civil(0, 1, 1) * 24, KNOWN_HOUR_HI = days_from_civil(10000, 1, 1) * 24;
+bool hour_fixed(int32_t h) { return h >= KNOWN_HOUR_LO && h < KNOWN_HOUR_HI; }
+bool key_less(int32_t ha, const std::string& ia, int32_t hb, const std::string& ib) {
+  if (hour_fixed(ha) && hour_fixed(hb)) return ha != hb ? ha < hb : ia < ib;
+  return "serials::" + exp_date_id(ha) + "::" + ia < "serials::" + exp_date_id(hb) + "::" + ib;
+}
+
+uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
+uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
+void put64(std::vector<uint8_t>& o, uint64_t v) { o.insert(o.end(), (const uint8_t*)&v, (const uint8_t*)&v + 8); }
+void put32(std::vector<uint8_t>& o, uint32_t v) { o.insert(o.end(), (const uint8_t*)&v, (const uint8_t*)&v + 4); }
+
+// The meta part of an image (header, issuers, sets, host section, padding): every check but the member records' own,
+// which the count pass makes on the device.  len = the meta part's length (device variant) or the whole image's.
+int known_parse_meta(ctmr_engine* e, const uint8_t* m, size_t len, bool whole, KnownMeta* km) {
+  if (!m || len < KNOWN_HEADER) return fail(e, CTMR_E_INVAL, "known image: shorter than its header");
+  if (memcmp(m, KNOWN_MAGIC, 8) != 0) return fail(e, CTMR_E_INVAL, "known image: bad magic");
+  if (rd32(m + 8) != KNOWN_VERSION) return fail(e, CTMR_E_INVAL, "known image: version %u, expected 1", rd32(m + 8));
+  if (rd32(m + 12) != KNOWN_HEADER || rd32(m + 20) != 0 || rd64(m + 56) != 0)
+    return fail(e, CTMR_E_INVAL, "known image: header size, flags or reserved field");
+  km->n_issuers = rd32(m + 16);
+  km->n_sets = rd64(m + 24);
+  km->n_members = rd64(m + 32);
+  km->host_bytes = rd64(m + 40);
+  km->n_host_members = rd64(m + 48);
+  const uint64_t L = len;
+  if (km->n_sets > L / 24 || km->host_bytes > L || km->n_members > (1ull << 56) / KNOWN_REC_BYTES)
+    return fail(e, CTMR_E_INVAL, "known image: section sizes disagree with its length");
+  const uint64_t content = KNOWN_HEADER + (uint64_t)km->n_issuers * 32 + km->n_sets * 24 + km->host_bytes;
+  km->meta_bytes = (content + 63) & ~63ull;
+  const uint64_t want = whole ? km->meta_bytes + km->n_members * KNOWN_REC_BYTES : km->meta_bytes;
+  if (want != L) return fail(e, CTMR_E_INVAL, "known image: %llu bytes, the header says %llu", (unsigned long long)L,
+                             (unsigned long long)want);
+  for (uint64_t p = content; p < km->meta_bytes; p++)
+    if (m[p]) return fail(e, CTMR_E_INVAL, "known image: padding before the members is not zero");
+  km->issuers = m + KNOWN_HEADER;
+  km->sets = km->issuers + (size_t)km->n_issuers * 32;
+  std::vector<std::string>& ids = km->ids;
+  ids.resize(km->n_issuers);
+  for (uint32_t k = 0; k < km->n_issuers; k++) ids[k] = b64url(km->issuers + (size_t)k * 32, 32);
+  km->set_hour.resize(km->n_sets);
+  km->set_issuer.resize(km->n_sets);
+  km->set_first.resize(km->n_sets + 1);
+  uint64_t at = 0;
+  for (uint64_t s = 0; s < km->n_sets; s++) {
+    const uint8_t* p = km->sets + s * 24;
+    const int32_t eh = (int32_t)rd32(p);
+    const uint32_t ord = rd32(p + 4);
+    const uint64_t first = rd64(p + 8), count = rd64(p + 16);
+    if (ord >= km->n_issuers) return fail(e, CTMR_E_INVAL, "known image: set %llu names issuer %u of %u", (unsigned long long)s, ord, km->n_issuers);
+    if (first != at || count == 0 || count > km->n_members - at)
+      return fail(e, CTMR_E_INVAL, "known image: set %llu does not follow its predecessor (gap, overlap or empty)", (unsigned long long)s);
+    if (s && !key_less(km->set_hour[s - 1], ids[km->set_issuer[s - 1]], eh, ids[ord]))
+      return fail(e, CTMR_E_INVAL, "known image: sets out of key order");
+    km->set_hour[s] = eh;
+    km->set_issuer[s] = ord;
+    km->set_first[s] = first;
+    at += count;
+  }
+  km->set_first[km->n_sets] = at;
+  if (at != km->n_members) return fail(e, CTMR_E_INVAL, "known image: the sets cover %llu of %llu members", (unsigned long long)at,
+                                       (unsigned long long)km->n_members);
+  const uint8_t* h = km->sets + km->n_sets * 24;
+  uint64_t q = 0;
+  while (q < km->host_bytes) {
+    if (km->host_bytes - q < 4) return fail(e, CTMR_E_INVAL, "known image: host section truncated");
+    const uint32_t kl = rd32(h + q);
+    if (km->host_bytes - q - 4 < (uint64_t)kl + 4) return fail(e, CTMR_E_INVAL, "known image: host section truncated");
+    std::string key((const char*)h + q + 4, kl);
+    q += 4 + kl;
+    const uint32_t ml = rd32(h + q);
+    if (km->host_bytes - q - 4 < ml) return fail(e, CTMR_E_INVAL, "known image: host section truncated");
+    std::string mem((const char*)h + q + 4, ml);
+    q += 4 + ml;
+    if (key.compare(0, 9, "serials::") != 0) return fail(e, CTMR_E_INVAL, "known image: a host-section key outside serials::");
+    if (!km->host.empty() && !(km->host.back() < std::make_pair(key, mem)))
+      return fail(e, CTMR_E_INVAL, "known image: host section out of (key, member) order");
+    km->host.emplace_back(std::move(key), std::move(mem));
+  }
+  if (km->host.size() != km->n_host_members) return fail(e, CTMR_E_INVAL, "known image: host section holds %llu members, the header says %llu",
+                                                         (unsigned long long)km->host.size(), (unsigned long long)km->n_host_members);
+  return CTMR_OK;
+}
+
+// ctmr_set_insert's host half (the engine mutex is held): a member that is not a device-table member
+bool known_host_insert(ctmr_engine* e, const std::string& key, const std::string& m) {
+  const bool ins = e->hstore[key].insert(m).second;
+  int32_t eh; uint32_t canon;
+  if (ins && table_key(e, key.data(), key.size(), &eh, &canon)) e->host_issuer_counts[canon]++;
+  return ins;
+}
+
+// Export, host side: the sets in key order with their first members, the issuers they name, the host section.
+struct KnownExport {
+  std::vector<uint8_t> meta;
+  std::vector<unsigned long long> cursor;   // per pair-table slot: the first member of its set
+  std::vector<std::pair<uint64_t, uint64_t>> set_range;  // (first, count) in key order
+  ctmr_known_image_info info{};
+};
+
+int known_export_prepare(ctmr_engine* e, KnownExport* x) {
+  int r;
+  if ((r = ensure_pairs(e))) return r;
+  std::vector<unsigned long long> pr;
+  for (size_t cap = 1 << 16;;) {
+    if ((r = ensure(e, SC_MISC, cap * 24))) return r;
+    HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
+    hipLaunchKernelGGL(k_pairs_slots, dim3((unsigned)((e->npairs + 255) / 256)), dim3(256), 0, e->stream, e->pairs, e->npairs,
+                       (unsigned long long*)e->d_scratch[SC_MISC], (uint64_t)cap, e->d_count);
+    unsigned long long cnt;
+    HIPCHK(e, hipMemcpyAsync(&cnt, e->d_count, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (cnt <= cap) {
+      pr.resize(cnt * 3);
+      if (cnt) HIPCHK(e, hipMemcpy(pr.data(), e->d_scratch[SC_MISC], cnt * 24, hipMemcpyDeviceToHost));
+      break;
+    }
+    cap = cnt + 1024;
+  }
+  struct S { uint32_t canon; int32_t eh; uint64_t count, slot; };
+  std::vector<S> sets;
+  for (size_t i = 0; i < pr.size(); i += 3) {
+    const uint32_t canon = (uint32_t)(pr[i] >> 32) - 1;
+    if (canon >= e->issuers.size()) continue;
+    sets.push_back({canon, (int32_t)(uint32_t)pr[i], pr[i + 1], pr[i + 2]});
+  }
+  // key order: (hour, rank of the Issuer.ID) as one integer when every hour has a four-digit year, else the strings
+  std::vector<uint32_t> by_id;
+  for (uint32_t c = 0; c < e->issuers.size(); c++) if (e->issuers[c].canon == c) by_id.push_back(c);
+  std::sort(by_id.begin(), by_id.end(), [e](uint32_t a, uint32_t b) { return e->issuers[a].id < e->issuers[b].id; });
+  std::vector<uint32_t> id_rank(e->issuers.size(), 0);
+  for (uint32_t k = 0; k < by_id.size(); k++) id_rank[by_id[k]] = k;
+  bool fixed = true;
+  for (auto& s : sets) fixed = fixed && hour_fixed(s.eh);
+  if (fixed) {
+    std::vector<std::pair<uint64_t, uint32_t>> ord(sets.size());
+    for (uint32_t k = 0; k < sets.size(); k++)
+      ord[k] = {((uint64_t)(sets[k].eh - KNOWN_HOUR_LO) << 24) | id_rank[sets[k].canon], k};
+    std::sort(ord.begin(), ord.end());
+    std::vector<S> sorted(sets.size());
+    for (size_t k = 0; k < ord.size(); k++) sorted[k] = sets[ord[k].second];
+    sets.swap(sorted);
+  } else {
+    std::sort(sets.begin(), sets.end(), [e](const S& a, const S& b) {
+      return key_less(a.eh, e->issuers[a.canon].id, b.eh, e->issuers[b.canon].id);
+    });
+  }
+  // issuer ordinals: the referenced issuers in digest order (process-independent, like the digests themselves)
+  std::vector<uint32_t> canons;
+  for (auto& s : sets) canons.push_back(s.canon);
+  std::sort(canons.begin(), canons.end());
+  canons.erase(std::unique(canons.begin(), canons.end()), canons.end());
+  std::sort(canons.begin(), canons.end(), [e](uint32_t a, uint32_t b) { return memcmp(e->issuers[a].digest, e->issuers[b].digest, 32) < 0; });
+  std::vector<uint32_t> ordinal(e->issuers.size(), 0);
+  for (uint32_t k = 0; k < canons.size(); k++) ordinal[canons[k]] = k;
+  std::vector<std::pair<std::string, std::string>> host;
+  for (auto& kv : e->hstore)
+    if (kv.first.compare(0, 9, "serials::") == 0)
+      for (auto& m : kv.second) host.emplace_back(kv.first, m);
+  std::vector<uint8_t>& o = x->meta;
+  o.reserve(KNOWN_HEADER + canons.size() * 32 + sets.size() * 24 + 64);
+  o.assign(KNOWN_MAGIC, KNOWN_MAGIC + 8);
+  put32(o, KNOWN_VERSION);
+  put32(o, KNOWN_HEADER);
+  put32(o, (uint32_t)canons.size());
+  put32(o, 0);
+  const size_t at_members = o.size();
+  put64(o, sets.size());
+  put64(o, 0);  // n_members, patched below
+  const size_t at_host = o.size();
+  put64(o, 0);  // host_bytes, patched below
+  put64(o, host.size());
+  put64(o, 0);
+  for (uint32_t c : canons) o.insert(o.end(), e->issuers[c].digest, e->issuers[c].digest + 32);
+  x->cursor.assign(e->npairs, 0ull);
+  uint64_t first = 0;
+  for (auto& s : sets) {
+    put32(o, (uint32_t)s.eh);
+    put32(o, ordinal[s.canon]);
+    put64(o, first);
+    put64(o, s.count);
+    x->cursor[s.slot] = first;
+    x->set_range.push_back({first, s.count});
+    first += s.count;
+  }
+  const size_t host_start = o.size();
+  for (auto& hm : host) {
+    put32(o, (uint32_t)hm.first.size());
+    o.insert(o.end(), hm.first.begin(), hm.first.end());
+    put32(o, (uint32_t)hm.second.size());
+    o.insert(o.end(), hm.second.begin(), hm.second.end());
+  }
+  const uint64_t host_bytes = o.size() - host_start;
+  o.resize((o.size() + 63) & ~(size_t)63, 0);
+  memcpy(&o[at_members + 8], &first, 8);
+  memcpy(&o[at_host], &host_bytes, 8);
+  x->info.members = first;
+  x->info.sets = sets.size();
+  x->info.host_members = host.size();
+  x->info.meta_bytes = o.size();
+  x->info.image_bytes = o.size() + first * KNOWN_REC_BYTES;
+  x->info.issuers = (uint32_t)canons.size();
+  x->info.reserved = 0;
+  return CTMR_OK;
+}
+
+// Export, device side: the member records of sets [s_lo, s_hi) into out (positions relative to the first of s_lo).
+int known_export_members(ctmr_engine* e, KnownExport& x, size_t s_lo, size_t s_hi, uint8_t* d_out) {
+  const uint64_t lo = s_lo < x.set_range.size() ? x.set_range[s_lo].first : x.info.members;
+  const uint64_t hi = s_hi < x.set_range.size() ? x.set_range[s_hi].first : x.info.members;
+  if (hi == lo) return CTMR_OK;
+  // sets outside [lo, hi) get a cursor far above the chunk: their members are counted but not written (the slots of no
+  // set are never reached by a live cell)
+  std::vector<unsigned long long> cur(x.cursor.size(), KNOWN_CURSOR_OFF);
+  for (size_t j = 0; j < x.cursor.size(); j++)
+    if (x.cursor[j] >= lo && x.cursor[j] < hi) cur[j] = x.cursor[j] - lo;
+  int r;
+  if ((r = ensure(e, SC_TMP, cur.size() * 8))) return r;
+  HIPCHK(e, hipMemcpyAsync(e->d_scratch[SC_TMP], cur.data(), cur.size() * 8, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_known_export, dim3((unsigned)((e->nslots + 255) / 256)), dim3(256), 0, e->stream, e->tbl(), e->nslots,
+                     (const PairSlot*)e->pairs, e->npairs - 1, (unsigned long long*)e->d_scratch[SC_TMP], d_out, hi - lo);
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  return CTMR_OK;
+}
+
+// Import: owner round check, issuer remap, then the members on the device (d_members: km.n_members records).
+int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, uint32_t world, uint32_t rank,
+                      ctmr_known_import_stats* st) {
+  if (world == 0 || rank >= world) return fail(e, CTMR_E_INVAL, "known import: rank %u of world %u", rank, world);
+  if (e->rd.valid && e->rd.mode == XM_OWNER && !e->rd.resolved)
+    return fail(e, CTMR_E_INVAL, "known import: an owner-computes round is open on this engine");
+  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "known import: null member records");
+  // image issuer ordinal → canonical index here (0xffffffff: not registered)
+  std::vector<uint32_t> remap(km.n_issuers, 0xffffffffu);
+  for (uint32_t k = 0; k < km.n_issuers; k++) {
+    auto it = e->id_to_canon.find(b64url(km.issuers + (size_t)k * 32, 32));
+    if (it != e->id_to_canon.end()) remap[k] = it->second;
+  }
+  std::vector<unsigned long long> set_meta(km.n_sets);
+  std::vector<size_t> unreg;
+  uint64_t unreg_members = 0;
+  for (uint64_t s = 0; s < km.n_sets; s++) {
+    const uint32_t c = remap[km.set_issuer[s]];
+    if (c == 0xffffffffu) {
+      unreg.push_back(s);
+      unreg_members += km.set_first[s + 1] - km.set_first[s];
+      set_meta[s] = 0ull;
+    } else {
+      set_meta[s] = key_meta(km.set_hour[s], c, 0);
+    }
+  }
+  if (world > 1 && !unreg.empty())
+    return fail(e, CTMR_E_INVAL, "known import: world %u needs every set's issuer registered (%zu sets are not)", world, unreg.size());
+  // host section (rank 0): members ctmr_set_insert would put into the device table are point inserts
+  uint64_t host_point = 0;
+  if (rank == 0)
+    for (auto& hm : km.host) {
+      int32_t eh; uint32_t cn;
+      if (hm.second.size() <= CTMR_MAX_SERIAL && table_key(e, hm.first.data(), hm.first.size(), &eh, &cn)) host_point++;
+    }
+  memset(st, 0, sizeof *st);
+  st->members = km.n_members;
+  // ---- device records: count (and validate) every chunk, reserve, then pack and insert chunk by chunk
+  const uint64_t N = km.n_members, nch = (N + KNOWN_CHUNK - 1) / KNOWN_CHUNK;
+  const uint64_t CH = N < KNOWN_CHUNK ? N : KNOWN_CHUNK, nbmax = (CH + 255) / 256;
+  void* tmp = nullptr;
+  const size_t off_meta = (km.n_sets + 1) * 8, off_cnt = (off_meta + km.n_sets * 8 + 63) & ~(size_t)63;
+  const size_t off_err = off_cnt + ((2 * nbmax + 1) * 8 + 63) / 64 * 64, off_stats = off_err + 64;
+  const size_t tmp_bytes = off_stats + sizeof(DevStats);
+  struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_tmp{tmp};
+  uint64_t taken = 0;
+  std::vector<uint64_t> n32(nch), n64(nch);
+  int r;
+  if (N) {
+    HIPCHK(e, hipMalloc(&tmp, tmp_bytes));
+    uint8_t* t8 = (uint8_t*)tmp;
+    HIPCHK(e, hipMemcpyAsync(t8, km.set_first.data(), off_meta, hipMemcpyHostToDevice, e->stream));
+    if (km.n_sets) HIPCHK(e, hipMemcpyAsync(t8 + off_meta, set_meta.data(), km.n_sets * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemsetAsync(t8 + off_err, 0, 64 + sizeof(DevStats), e->stream));
+    for (uint64_t c = 0; c < nch; c++) {
+      KnownImportArgs a{};
+      const uint64_t lo = c * KNOWN_CHUNK, n = std::min(N - lo, KNOWN_CHUNK), nb = (n + 255) / 256;
+      a.members = d_members + lo * KNOWN_REC_BYTES; a.n = n; a.base = lo;
+      a.set_first = (const uint64_t*)t8; a.set_meta = (const unsigned long long*)(t8 + off_meta);
+      a.n_sets = (uint32_t)km.n_sets; a.world = world; a.rank = rank;
+      a.cnt = (unsigned long long*)(t8 + off_cnt); a.nb = nb; a.err = (uint32_t*)(t8 + off_err);
+      HIPCHK(e, hipMemsetAsync(a.cnt + 2 * nb, 0, 8, e->stream));
+      hipLaunchKernelGGL(k_known_count, dim3((unsigned)nb), dim3(256), 0, e->stream, a);
+      if ((r = scan_u64(e, (uint64_t*)a.cnt, 2 * nb + 1, false, SC_TMP))) return r;
+      unsigned long long tot[2];
+      uint32_t err = 0;
+      HIPCHK(e, hipMemcpyAsync(&tot[0], a.cnt + nb, 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipMemcpyAsync(&tot[1], a.cnt + 2 * nb, 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipStreamSynchronize(e->stream));
+      HIPCHK(e, hipGetLastError());
+      if (err & 1u) return fail(e, CTMR_E_INVAL, "known import: a member record's serial_len is above %d", CTMR_MAX_SERIAL);
+      if (err) return fail(e, CTMR_E_INVAL, "known import: a member record's padding octets are not zero");
+      n32[c] = tot[0];
+      n64[c] = tot[1] - tot[0];
+      taken += tot[1];
+    }
+  }
+  st->taken = taken + unreg_members;
+  // every slot and cell the call may claim, before anything is applied ("applied completely or not at all")
+  if (taken + host_point) {
+    if ((r = ensure_capacity(e, taken + host_point))) return r;
+  }
+  uint64_t inserted = 0;
+  if (taken) {
+    uint8_t* t8 = (uint8_t*)tmp;
+    e->epoch++;
+    e->pairs_dirty = true;
+    DevStats* d_st = (DevStats*)(t8 + off_stats);
+    for (uint64_t c = 0; c < nch; c++) {
+      if (!n32[c] && !n64[c]) continue;
+      KnownImportArgs a{};
+      const uint64_t lo = c * KNOWN_CHUNK, n = std::min(N - lo, KNOWN_CHUNK), nb = (n + 255) / 256;
+      a.members = d_members + lo * KNOWN_REC_BYTES; a.n = n; a.base = lo;
+      a.set_first = (const uint64_t*)t8; a.set_meta = (const unsigned long long*)(t8 + off_meta);
+      a.n_sets = (uint32_t)km.n_sets; a.world = world; a.rank = rank;
+      a.cnt = (unsigned long long*)(t8 + off_cnt); a.nb = nb; a.err = (uint32_t*)(t8 + off_err);
+      if (nch > 1) {  // cnt[] holds the counts of the last chunk counted: with several chunks, each counts again
+        HIPCHK(e, hipMemsetAsync(a.cnt + 2 * nb, 0, 8, e->stream));
+        hipLaunchKernelGGL(k_known_count, dim3((unsigned)nb), dim3(256), 0, e->stream, a);
+        if ((r = scan_u64(e, (uint64_t*)a.cnt, 2 * nb + 1, false, SC_TMP))) return r;
+      }
+      const uint64_t m32 = n32[c], m64 = n64[c], M = m32 + m64;
+      void* recs = nullptr;
+      const size_t off64 = m32 * sizeof(KeyRec32), off_slot = off64 + m64 * sizeof(KeyRec), off_fl = off_slot + M * 4;
+      HIPCHK(e, hipMalloc(&recs, off_fl + M + 64));
+      Free free_recs{recs};
+      uint8_t* r8 = (uint8_t*)recs;
+      KeyRec32* k32 = (KeyRec32*)r8;
+      KeyRec* k64 = (KeyRec*)(r8 + off64);
+      uint32_t* d_slot = (uint32_t*)(r8 + off_slot);
+      uint8_t* d_fl = r8 + off_fl;
+      hipLaunchKernelGGL(k_known_pack, dim3((unsigned)nb), dim3(256), 0, e->stream, a, (const unsigned long long*)a.cnt, k32, k64);
+      // the owner-computes receive path outside a round: this chunk's cells start at ref0 — a word with a lower ref is an
+      // older key (compared at once), a same-tag word of the chunk is settled in pass 2 by the records' orders
+      const unsigned long long ref0 = e->arena_used;
+      e->arena_used += M;
+      InsertArgs loc{};
+      loc.t = e->tbl();
+      loc.ref0 = ref0;
+      loc.n = 0;  // no entries of a batch to mark
+      loc.ord_base = 0;
+      const Table t = e->tbl();
+      if (m32) hipLaunchKernelGGL((k_keys_insert<KeyRec32>), dim3((unsigned)((m32 + 255) / 256)), dim3(256), 0, e->stream,
+                                  (const KeyRec32*)k32, m32, t, ref0, ref0, d_slot);
+      if (m64) hipLaunchKernelGGL((k_keys_insert<KeyRec>), dim3((unsigned)((m64 + 255) / 256)), dim3(256), 0, e->stream,
+                                  (const KeyRec*)k64, m64, t, ref0, ref0 + m32, d_slot + m32);
+      if (m32) hipLaunchKernelGGL((k_keys_insert2<KeyRec32>), dim3((unsigned)((m32 + 255) / 256)), dim3(256), 0, e->stream,
+                                  (const KeyRec32*)k32, m32, loc, ref0, (ctmr_record*)nullptr, d_slot);
+      if (m64) hipLaunchKernelGGL((k_keys_insert2<KeyRec>), dim3((unsigned)((m64 + 255) / 256)), dim3(256), 0, e->stream,
+                                  (const KeyRec*)k64, m64, loc, ref0 + m32, (ctmr_record*)nullptr, d_slot + m32);
+      if (m32) {
+        const uint64_t nbr = (m32 + 1023) / 1024;
+        hipLaunchKernelGGL((k_keys_resolve<KeyRec32>), dim3((unsigned)(nbr < 512 ? nbr : 512)), dim3(1024), 0, e->stream,
+                           (const KeyRec32*)k32, m32, nbr, t, ref0, (const uint32_t*)d_slot, d_fl, e->issuer_counts, d_st);
+      }
+      if (m64) {
+        const uint64_t nbr = (m64 + 1023) / 1024;
+        hipLaunchKernelGGL((k_keys_resolve<KeyRec>), dim3((unsigned)(nbr < 512 ? nbr : 512)), dim3(1024), 0, e->stream,
+                           (const KeyRec*)k64, m64, nbr, t, ref0 + m32, (const uint32_t*)(d_slot + m32), d_fl + m32,
+                           e->issuer_counts, d_st);
+      }
+      if (e->d_bloom) {
+        if (m32) hipLaunchKernelGGL((k_known_bloom<KeyRec32>), dim3((unsigned)((m32 + 255) / 256)), dim3(256), 0, e->stream,
+                                    (const KeyRec32*)k32, m32, e->d_bloom, e->bloom_words - 1);
+        if (m64) hipLaunchKernelGGL((k_known_bloom<KeyRec>), dim3((unsigned)((m64 + 255) / 256)), dim3(256), 0, e->stream,
+                                    (const KeyRec*)k64, m64, e->d_bloom, e->bloom_words - 1);
+      }
+      DevStats ds;
+      HIPCHK(e, hipMemcpyAsync(&ds, d_st, sizeof ds, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipMemsetAsync(d_st, 0, sizeof ds, e->stream));
+      HIPCHK(e, hipStreamSynchronize(e->stream));
+      HIPCHK(e, hipGetLastError());
+      e->occupied += ds.n_new;
+      inserted += ds.n_new;
+      if (ds.n_full) return fail(e, CTMR_E_FULL, "known-certificate table full (%llu slots)", (unsigned long long)e->nslots);
+    }
+  }
+  // ---- sets of issuers not registered here (world = 1): their members go where ctmr_set_insert puts them
+  for (size_t s : unreg) {
+    const uint64_t f = km.set_first[s], cnt = km.set_first[s + 1] - f;
+    std::vector<uint8_t> buf(cnt * KNOWN_REC_BYTES);
+    HIPCHK(e, hipMemcpy(buf.data(), d_members + f * KNOWN_REC_BYTES, buf.size(), hipMemcpyDeviceToHost));
+    const std::string key = "serials::" + exp_date_id(km.set_hour[s]) + "::" + km.ids[km.set_issuer[s]];
+    for (uint64_t i = 0; i < cnt; i++) {
+      const uint8_t* p = &buf[i * KNOWN_REC_BYTES];
+      inserted += known_host_insert(e, key, std::string((const char*)p + 8, (size_t)rd64(p)));
+    }
+  }
+  st->inserted = inserted;
+  st->known = st->taken - inserted;
+  // ---- the host section (rank 0 alone): ctmr_set_insert, member by member
+  if (rank == 0) {
+    st->host_members = km.host.size();
+    for (auto& hm : km.host) {
+      int32_t eh; uint32_t cn;
+      if (hm.second.size() <= CTMR_MAX_SERIAL && table_key(e, hm.first.data(), hm.first.size(), &eh, &cn)) {
+        int was_new = 0;
+        if ((r = point_op(e, 0, eh, cn, (const uint8_t*)hm.second.data(), hm.second.size(), &was_new))) return r;
+        st->host_inserted += was_new;
+      } else {
+        st->host_inserted += known_host_insert(e, hm.first, hm.second);
+      }
+    }
+  }
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return CTMR_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int ctmr_known_export(ctmr_engine* e, uint8_t* out, size_t cap, ctmr_known_image_info* info) {
+  if (!e || !info) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownExport x;
+  int r;
+  if ((r = known_export_prepare(e, &x))) return r;
+  *info = x.info;
+  if (!out || cap < x.info.image_bytes) return fail(e, CTMR_E_RANGE, "known export: %llu bytes needed", (unsigned long long)x.info.image_bytes);
+  const uint64_t N = x.info.members;
+  if (N) {
+    // stage the member records on the device: all at once when that fits, else set range by set range
+    uint64_t stage = N;
+    void* d = nullptr;
+    while (hipMalloc(&d, stage * KNOWN_REC_BYTES) != hipSuccess) {
+      (void)hipGetLastError();
+      d = nullptr;
+      if (stage <= (1ull << 20)) return fail(e, CTMR_E_NOMEM, "known export: no device memory to stage the member records");
+      stage /= 2;
+    }
+    struct Free { void* p; ~Free() { (void)hipFree(p); } } free_d{d};
+    size_t s = 0;
+    while (s < x.set_range.size()) {
+      size_t t = s;
+      const uint64_t lo = x.set_range[s].first;
+      while (t < x.set_range.size() && x.set_range[t].first + x.set_range[t].second - lo <= stage) t++;
+      if (t == s) {  // one set larger than the staging buffer: stage it alone
+        void* big = nullptr;
+        if (hipMalloc(&big, x.set_range[s].second * KNOWN_REC_BYTES) != hipSuccess) {
+          (void)hipGetLastError();
+          return fail(e, CTMR_E_NOMEM, "known export: no device memory to stage a set of %llu members",
+                      (unsigned long long)x.set_range[s].second);
+        }
+        Free free_big{big};
+        if ((r = known_export_members(e, x, s, s + 1, (uint8_t*)big))) return r;
+        HIPCHK(e, hipMemcpy(out + x.info.meta_bytes + lo * KNOWN_REC_BYTES, big, x.set_range[s].second * KNOWN_REC_BYTES,
+                            hipMemcpyDeviceToHost));
+        s++;
+        continue;
+      }
+      const uint64_t hi = t < x.set_range.size() ? x.set_range[t].first : N;
+      if ((r = known_export_members(e, x, s, t, (uint8_t*)d))) return r;
+      HIPCHK(e, hipMemcpy(out + x.info.meta_bytes + lo * KNOWN_REC_BYTES, d, (hi - lo) * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
+      s = t;
+    }
+  }
+  memcpy(out, x.meta.data(), x.meta.size());
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return CTMR_OK;
+}
+
+int ctmr_known_export_device(ctmr_engine* e, uint8_t* meta, size_t meta_cap, void* d_members, uint64_t members_cap,
+                             ctmr_known_image_info* info) {
+  if (!e || !info) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownExport x;
+  int r;
+  if ((r = known_export_prepare(e, &x))) return r;
+  *info = x.info;
+  if (!meta || meta_cap < x.info.meta_bytes || members_cap < x.info.members || (x.info.members && !d_members))
+    return fail(e, CTMR_E_RANGE, "known export: %llu meta bytes and %llu member records needed",
+                (unsigned long long)x.info.meta_bytes, (unsigned long long)x.info.members);
+  if ((r = known_export_members(e, x, 0, x.set_range.size(), (uint8_t*)d_members))) return r;
+  memcpy(meta, x.meta.data(), x.meta.size());
+  return CTMR_OK;
+}
+
+int ctmr_known_import(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t world, uint32_t rank,
+                      ctmr_known_import_stats* st) {
+  if (!e || !image || !st) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  int r;
+  if ((r = known_parse_meta(e, image, len, true, &km))) return r;
+  void* d = nullptr;
+  if (km.n_members) {
+    if (hipMalloc(&d, km.n_members * KNOWN_REC_BYTES) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e, CTMR_E_NOMEM, "known import: no device memory for %llu member records", (unsigned long long)km.n_members);
+    }
+  }
+  struct Free { void* p; ~Free() { if (p) (void)hipFree(p); } } free_d{d};
+  if (km.n_members)
+    HIPCHK(e, hipMemcpyAsync(d, image + km.meta_bytes, km.n_members * KNOWN_REC_BYTES, hipMemcpyHostToDevice, e->stream));
+  return known_import_core(e, km, (const uint8_t*)d, world, rank, st);
+}
+
+int ctmr_known_import_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                             uint64_t n_members, uint32_t world, uint32_t rank, ctmr_known_import_stats* st) {
+  if (!e || !meta || !st) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  int r;
+  if ((r = known_parse_meta(e, meta, meta_len, false, &km))) return r;
+  if (km.n_members != n_members) return fail(e, CTMR_E_INVAL, "known import: %llu member records given, the header says %llu",
+                                             (unsigned long long)n_members, (unsigned long long)km.n_members);
+  return known_import_core(e, km, (const uint8_t*)d_members, world, rank, st);
+}

@@ -17,6 +17,7 @@
 //   kernels/meta.h      k_meta_new
 //   kernels/misc.h      k_fingerprint, k_set_op / k_sweep / k_rehash / k_arena_compact / k_build_pairs / k_list / k_pairs,
 //                       k_synth_*
+//   kernels/image.h     k_known_export / k_known_count / k_known_pack / k_known_bloom (the known-certificate image)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once
 #include "kernels/readers.h"
@@ -32,3 +33,4 @@
 #include "kernels/entries.h"
 #include "kernels/meta.h"
 #include "kernels/misc.h"
+#include "kernels/image.h"

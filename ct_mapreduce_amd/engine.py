@@ -109,6 +109,7 @@ class Engine:
         if rc != 0:
             raise CtmrError(rc, "ctmr_create failed (no usable HIP device? there is no CPU fallback)")
         self._h = h
+        self.device = device
         self.collect_meta = bool(collect_meta)
 
     # ---- lifecycle
@@ -585,6 +586,61 @@ class Engine:
         out = N.TableInfo()
         self._ck(self._lib.ctmr_table_info_get(self._h, C.byref(out)))
         return out
+
+    # ---- the known-certificate image (include/ctmr.h; parsed and written without a GPU by known_image.py)
+    @staticmethod
+    def _import_stats(st: N.KnownImportStats) -> dict:
+        return {f: getattr(st, f) for f, _ in N.KnownImportStats._fields_}
+
+    def _known_export_call(self, fn, alloc):
+        """One export call sized up front — the live members are at most table_info().occupied, the meta part as large
+        as last time — and a second one only when that was short (CTMR_E_RANGE fills `info` with the sizes)."""
+        info = N.KnownImageInfo()
+        meta_cap, members_cap = getattr(self, "_known_meta_cap", 1 << 16), max(self.table_info().occupied, 1)
+        for _ in range(2):
+            bufs = alloc(meta_cap, members_cap)
+            rc = fn(bufs, meta_cap, members_cap, info)
+            if rc != N.E_RANGE:
+                break
+            meta_cap, members_cap = max(info.meta_bytes, 64), max(info.members, 1)
+        self._ck(rc)
+        self._known_meta_cap = max(meta_cap, info.meta_bytes)
+        return bufs, info
+
+    def known_export(self) -> bytes:
+        """Snapshot of every serials:: set as one image (what a restarted reference finds in Redis)."""
+        (buf,), info = self._known_export_call(
+            lambda b, mc, nc, info: self._lib.ctmr_known_export(self._h, b[0].ctypes.data, b[0].nbytes, C.byref(info)),
+            lambda mc, nc: (np.empty(mc + 48 * nc, np.uint8),))
+        return buf[:info.image_bytes].tobytes()
+
+    def known_export_device(self):
+        """→ (meta bytes, torch uint8 tensor of the 48-byte member records on this engine's device; a view)."""
+        import torch
+        (meta, members), info = self._known_export_call(
+            lambda b, mc, nc, info: self._lib.ctmr_known_export_device(self._h, b[0].ctypes.data, mc,
+                                                                       C.c_void_p(b[1].data_ptr()), nc, C.byref(info)),
+            lambda mc, nc: (np.empty(mc, np.uint8), torch.empty(nc * 48, dtype=torch.uint8, device="cuda:%d" % self.device)))
+        return meta[:info.meta_bytes].tobytes(), members[:info.members * 48]
+
+    def known_import(self, image, world=1, rank=0) -> dict:
+        """Every member of `image` this rank takes, as SetInsert would add it (world = 1: all of them)."""
+        image = bytes(image)
+        st = N.KnownImportStats()
+        self._ck(self._lib.ctmr_known_import(self._h, image, len(image), world, rank, C.byref(st)))
+        return self._import_stats(st)
+
+    def known_import_device(self, meta, d_members, world=1, rank=0) -> dict:
+        """known_import with the member records in device memory: a torch uint8 tensor (or a device pointer)."""
+        meta = bytes(meta)
+        if hasattr(d_members, "data_ptr"):
+            n, ptr = d_members.numel() // 48, d_members.data_ptr()
+        else:
+            raise TypeError("d_members: a torch tensor on this engine's device")
+        st = N.KnownImportStats()
+        self._ck(self._lib.ctmr_known_import_device(self._h, meta, len(meta), C.c_void_p(ptr) if n else None, n, world, rank,
+                                                    C.byref(st)))
+        return self._import_stats(st)
 
     # ---- synthetic input (bench / tests)
     def synth_view_device(self, cfg: N.SynthConfig, first, n, align, d_starts, d_ends, d_payload, payload_cap,

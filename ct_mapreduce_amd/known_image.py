@@ -1,0 +1,249 @@
+"""The known-certificate image (include/ctmr.h) without a GPU: parse, write, and convert to and from the
+Redis protocol stream of remote_cache.redis_dump.
+
+An image is what `Engine.known_export` writes and `Engine.known_import` reads: every serials::<expDate>::<issuerID> set
+of the engine — what a restarted reference deployment still finds in its Redis.  `parse` checks exactly what the library
+checks before it applies an image; `build` is the canonical writer; `to_resp` / `from_resp` turn an image into the
+SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start from a reference deployment's Redis
+contents).  Pure Python + numpy.
+"""
+import base64
+import io
+import struct
+from dataclasses import dataclass, field
+
+import numpy as np
+
+MAGIC = b"CTMRKNWN"
+VERSION = 1
+HEADER_BYTES = 64
+SET_BYTES = 24
+MEMBER_BYTES = 48
+MAX_SERIAL = 40
+PREFIX = b"serials::"
+_HEADER = struct.Struct("<8sIIIIQQQQQ")
+_SET = struct.Struct("<iIQQ")
+MEMBER_DTYPE = np.dtype([("len", "<u8"), ("serial", "u1", (MAX_SERIAL,))])
+assert _HEADER.size == HEADER_BYTES and _SET.size == SET_BYTES and MEMBER_DTYPE.itemsize == MEMBER_BYTES
+
+
+class ImageError(ValueError):
+    """The image is malformed: the library refuses it with CTMR_E_INVAL."""
+
+
+@dataclass
+class KnownImage:
+    sets: dict = field(default_factory=dict)   # key bytes → sorted list of member bytes (both sections)
+    issuers: list = field(default_factory=list)  # 32-byte SPKI digests, by ordinal
+    n_sets: int = 0                            # sets of the members section
+    n_members: int = 0                         # member records
+    n_host_members: int = 0                    # host-section members
+
+    @property
+    def total(self):
+        return self.n_members + self.n_host_members
+
+
+# ExpDate.ID() "2006-01-02-15" of an hour count (storage/types.go:339-384), as the library formats it
+def _civil_from_days(z):
+    z += 719468
+    era = (z if z >= 0 else z - 146096) // 146097
+    doe = z - era * 146097
+    yoe = (doe - doe // 1460 + doe // 36524 - doe // 146096) // 365
+    doy = doe - (365 * yoe + yoe // 4 - yoe // 100)
+    mp = (5 * doy + 2) // 153
+    d = doy - (153 * mp + 2) // 5 + 1
+    m = mp + 3 if mp < 10 else mp - 9
+    return yoe + era * 400 + (m <= 2), m, d
+
+
+def exp_date_id(exp_hour: int) -> bytes:
+    days, hh = divmod(exp_hour, 24)
+    y, m, d = _civil_from_days(days)
+    return b"%04d-%02d-%02d-%02d" % (y, m, d, hh)
+
+
+def issuer_id(digest: bytes) -> bytes:
+    """Issuer.ID: the padded base64url of the SPKI digest (storage/types.go:155-159)."""
+    return base64.urlsafe_b64encode(digest)
+
+
+def set_key(exp_hour: int, digest: bytes) -> bytes:
+    return PREFIX + exp_date_id(exp_hour) + b"::" + issuer_id(digest)
+
+
+def _days_from_civil(y, m, d):
+    y -= m <= 2
+    era = (y if y >= 0 else y - 399) // 400
+    yoe = y - era * 400
+    doy = (153 * (m - 3 if m > 2 else m + 9) + 2) // 5 + d - 1
+    doe = yoe * 365 + yoe // 4 - yoe // 100 + doy
+    return era * 146097 + doe - 719468
+
+
+def parse_key(key: bytes):
+    """serials::<expDate>::<Issuer.ID> → (exp_hour, digest), or None when the key is not one the members section can
+    carry (then its members belong to the host section)."""
+    if not key.startswith(PREFIX) or len(key) < len(PREFIX) + 13 + 2 + 1 or key[22:24] != b"::":
+        return None
+    date, ident = key[9:22], key[24:]
+    try:
+        y, mo, d, h = (int(x) for x in date.split(b"-"))
+        digest = base64.urlsafe_b64decode(ident)
+    except Exception:
+        return None
+    if len(digest) != 32 or not (1 <= mo <= 12 and 1 <= d <= 31 and 0 <= h <= 23):
+        return None
+    hour = _days_from_civil(y, mo, d) * 24 + h
+    if not -2 ** 31 <= hour < 2 ** 31 or set_key(hour, digest) != key:
+        return None
+    return hour, digest
+
+
+def parse(image) -> KnownImage:
+    """Validates and reads an image (bytes-like): the checks the library makes before it applies one."""
+    b = memoryview(bytes(image))
+    if len(b) < HEADER_BYTES:
+        raise ImageError("shorter than its header")
+    magic, version, hdr, n_iss, flags, n_sets, n_mem, host_bytes, n_host, reserved = _HEADER.unpack_from(b, 0)
+    if magic != MAGIC:
+        raise ImageError("bad magic")
+    if version != VERSION:
+        raise ImageError("version %d, expected 1" % version)
+    if hdr != HEADER_BYTES or flags or reserved:
+        raise ImageError("header size, flags or reserved field")
+    content = HEADER_BYTES + n_iss * 32 + n_sets * SET_BYTES + host_bytes
+    meta = (content + 63) & ~63
+    if meta + n_mem * MEMBER_BYTES != len(b):
+        raise ImageError("%d bytes, the header says %d" % (len(b), meta + n_mem * MEMBER_BYTES))
+    if any(b[content:meta]):
+        raise ImageError("padding before the members is not zero")
+    issuers = [bytes(b[HEADER_BYTES + 32 * k:HEADER_BYTES + 32 * (k + 1)]) for k in range(n_iss)]
+    so = HEADER_BYTES + 32 * n_iss
+    rec = np.frombuffer(b[meta:], MEMBER_DTYPE, count=n_mem) if n_mem else np.zeros(0, MEMBER_DTYPE)
+    if n_mem:
+        lens = rec["len"]
+        if (lens > MAX_SERIAL).any():
+            raise ImageError("a member record's serial_len is above %d" % MAX_SERIAL)
+        pad = np.arange(MAX_SERIAL)[None, :] >= lens[:, None].astype(np.int64)
+        if rec["serial"][pad].any():
+            raise ImageError("a member record's padding octets are not zero")
+    out = KnownImage(issuers=issuers, n_sets=n_sets, n_members=n_mem, n_host_members=n_host)
+    at, prev = 0, None
+    for s in range(n_sets):
+        eh, ordinal, first, count = _SET.unpack_from(b, so + SET_BYTES * s)
+        if ordinal >= n_iss:
+            raise ImageError("set %d names issuer %d of %d" % (s, ordinal, n_iss))
+        if first != at or count == 0 or count > n_mem - at:
+            raise ImageError("set %d does not follow its predecessor (gap, overlap or empty)" % s)
+        key = set_key(eh, issuers[ordinal])
+        if prev is not None and not prev < key:
+            raise ImageError("sets out of key order")
+        prev = key
+        r = rec[first:first + count]
+        out.sets[key] = [bytes(m[:int(l)]) for l, m in zip(r["len"], r["serial"])]
+        at += count
+    if at != n_mem:
+        raise ImageError("the sets cover %d of %d members" % (at, n_mem))
+    h, q, hosts = so + SET_BYTES * n_sets, 0, []
+    while q < host_bytes:
+        if host_bytes - q < 4:
+            raise ImageError("host section truncated")
+        (kl,) = struct.unpack_from("<I", b, h + q)
+        if host_bytes - q - 4 < kl + 4:
+            raise ImageError("host section truncated")
+        key = bytes(b[h + q + 4:h + q + 4 + kl])
+        q += 4 + kl
+        (ml,) = struct.unpack_from("<I", b, h + q)
+        if host_bytes - q - 4 < ml:
+            raise ImageError("host section truncated")
+        mem = bytes(b[h + q + 4:h + q + 4 + ml])
+        q += 4 + ml
+        if not key.startswith(PREFIX):
+            raise ImageError("a host-section key outside serials::")
+        if hosts and not hosts[-1] < (key, mem):
+            raise ImageError("host section out of (key, member) order")
+        hosts.append((key, mem))
+    if len(hosts) != n_host:
+        raise ImageError("host section holds %d members, the header says %d" % (len(hosts), n_host))
+    for key, mem in hosts:
+        out.sets.setdefault(key, []).append(mem)
+    for key in out.sets:
+        out.sets[key] = sorted(set(out.sets[key]))
+    return out
+
+
+def build(sets) -> bytes:
+    """The canonical image of {key: members}: members of at most 40 octets under keys that name an expDate and an issuer
+    digest go to the members section (sorted), everything else to the host section; issuers in digest order."""
+    dev, host = {}, []
+    for key, members in sets.items():
+        key = bytes(key)
+        if not key.startswith(PREFIX):
+            raise ValueError("not a known-certificate set: %r" % key)
+        members = sorted(set(bytes(m) for m in members))
+        pk = parse_key(key)
+        for m in members:
+            if pk is not None and len(m) <= MAX_SERIAL:
+                dev.setdefault(key, (pk, []))[1].append(m)
+            else:
+                host.append((key, m))
+    host.sort()
+    keys = sorted(dev)
+    digests = sorted({dev[k][0][1] for k in keys})
+    ordinal = {d: i for i, d in enumerate(digests)}
+    set_part, members, first = [], [], 0
+    for k in keys:
+        (eh, dg), ms = dev[k]
+        set_part.append(_SET.pack(eh, ordinal[dg], first, len(ms)))
+        members += ms
+        first += len(ms)
+    host_part = b"".join(struct.pack("<I", len(k)) + k + struct.pack("<I", len(m)) + m for k, m in host)
+    body = b"".join(digests) + b"".join(set_part) + host_part
+    head = _HEADER.pack(MAGIC, VERSION, HEADER_BYTES, len(digests), 0, len(keys), first, len(host_part), len(host), 0)
+    meta = head + body
+    meta += b"\0" * (-len(meta) % 64)
+    rec = np.zeros(first, MEMBER_DTYPE)
+    for i, m in enumerate(members):
+        rec["len"][i] = len(m)
+        rec["serial"][i, :len(m)] = np.frombuffer(m, np.uint8)
+    return meta + rec.tobytes()
+
+
+class _SetsCache:
+    """The two RemoteCache methods redis_dump / redis_load use, over a dict of sets."""
+
+    def __init__(self, sets=None):
+        self.sets = sets if sets is not None else {}
+
+    def KeysToChan(self, pattern):
+        return iter(sorted(self.sets))        # an image holds serials:: keys only; redis_dump asks for serials::*
+
+    def SetToChan(self, key):
+        return iter(self.sets.get(bytes(key), ()))
+
+    def SetInsert(self, key, member):
+        s = self.sets.setdefault(bytes(key), set())
+        new = bytes(member) not in s
+        s.add(bytes(member))
+        return new
+
+    def ExpireAt(self, key, unix_seconds):
+        pass                                  # the image carries the expDate of every key: EXPIREAT is implied
+
+
+def to_resp(image, out) -> dict:
+    """Writes the bytes redis_dump(cache, out, patterns=("serials::*",)) writes for a cache holding the image's sets."""
+    from .remote_cache import redis_dump
+    return redis_dump(_SetsCache(parse(image).sets), out, patterns=("serials::*",))
+
+
+def from_resp(stream) -> bytes:
+    """An image of the serials:: sets of a redis_dump / redis-cli style stream of SADD (and EXPIREAT) commands.  Other
+    keys are skipped."""
+    from .remote_cache import redis_load
+    if isinstance(stream, (bytes, bytearray, memoryview)):
+        stream = io.BytesIO(bytes(stream))
+    c = _SetsCache()
+    redis_load(c, stream)
+    return build({k: v for k, v in c.sets.items() if k.startswith(PREFIX)})

@@ -248,6 +248,64 @@ typedef struct {
 } ctmr_table_info;
 int ctmr_table_info_get(ctmr_engine* e, ctmr_table_info* out);
 
+/* ---- the known-certificate image: bulk snapshot and restore of every serials::<expDate>::<issuerID> set.  Replaces
+ *      what a restart of the reference finds in its persistent RemoteCache (storage/rediscache.go: Redis outlives
+ *      ct-fetch restarts, redeploys and reshards): export on shutdown, import on start.  DESIGN.md §12.
+ *
+ * Image v1, little-endian: image = meta ‖ members.
+ *   header, 64 B   "CTMRKNWN" | u32 version = 1 | u32 header_bytes = 64 | u32 n_issuers | u32 flags = 0 | u64 n_sets |
+ *                  u64 n_members | u64 host_bytes | u64 n_host_members | u64 reserved = 0
+ *   issuers        n_issuers × 32 B: SHA-256(SPKI) of each issuer the sets name (Issuer.ID = its padded base64url);
+ *                  the ordinal is process-independent (export: digest order), canonical indices are not
+ *   sets           n_sets × 24 B {i32 exp_hour, u32 issuer_ordinal, u64 first_member, u64 count}, in bytewise order of
+ *                  the key serials::<expDate>::<Issuer.ID> (the order ctmr_keys returns); contiguous, covering the
+ *                  members exactly, none empty
+ *   host section   host_bytes of {u32 key_len, key, u32 member_len, member} sorted by (key, member): the serials::
+ *                  members of the host-side store (serials longer than CTMR_MAX_SERIAL; issuers not registered)
+ *   members        at the next multiple of 64 B: n_members × 48 B {u64 serial_len (0..40), serial[40] zero-padded}
+ *                  (k_list's record); the order inside a set is unspecified
+ * The bytes before the members ("meta") are small and live on the host; the device variants take meta and members as
+ * separate buffers.  Exported members are the live members SetList / SetCardinality see (a Bloom-mode rank's SHADOW
+ * keys are not: the union of a group's images holds each key once).  ExpireAt overrides, crl:: / issuer:: / log:: keys
+ * and the IssuerMetadata memo are not carried (redis_dump covers the RemoteCache keys). */
+typedef struct {
+  uint64_t members;       /* member records (device section) */
+  uint64_t sets;
+  uint64_t host_members;  /* members of the host section */
+  uint64_t meta_bytes;    /* header + issuers + sets + host section, padded to 64 */
+  uint64_t image_bytes;   /* meta_bytes + 48 × members */
+  uint32_t issuers, reserved;
+} ctmr_known_image_info;
+typedef struct {
+  uint64_t members;        /* member records of the image */
+  uint64_t taken;          /* … this rank took (its keys; world = 1: all) */
+  uint64_t inserted;       /* … of them new here (device table, or the host-side store for issuers not registered) */
+  uint64_t known;          /* taken − inserted: already present, or a repeat inside the image */
+  uint64_t host_members;   /* host-section members taken (rank 0 alone) */
+  uint64_t host_inserted;  /* … of them new here */
+} ctmr_known_import_stats;
+/* Export.  Fills *info; when out (cap bytes) is too small returns CTMR_E_RANGE and writes nothing.  Returns after the
+ * engine's stream has drained.  The member records are staged on the device (in set ranges when the whole does not fit). */
+int ctmr_known_export(ctmr_engine* e, uint8_t* out, size_t cap, ctmr_known_image_info* info);
+/* Export into a host meta buffer and a device buffer of members_cap 48-byte records (CTMR_E_RANGE as above). */
+int ctmr_known_export_device(ctmr_engine* e, uint8_t* meta, size_t meta_cap, void* d_members, uint64_t members_cap,
+                             ctmr_known_image_info* info);
+/* Import = ctmr_set_insert(key, member) for every member this rank takes — the union with what the engine holds;
+ * members of issuers not registered here and serials longer than CTMR_MAX_SERIAL go to the host-side store (registering
+ * the issuer later moves them, as it does after a redis_load).  Per-issuer counts, the pair statistics and the Bloom
+ * filter (when configured) come out as those inserts leave them.  world / rank: the rank takes the keys whose owner
+ * (the owner-computes exchange's owner function) is `rank` among `world` — every rank of a group restored from the same
+ * image(s) holds each key once, on its owner, whatever world size exported it; host-section members go to rank 0.
+ * world = 1, rank = 0 takes everything.  CTMR_E_INVAL, nothing applied: bad magic / version, sizes that disagree, sets
+ * out of order / overlapping / leaving gaps, an issuer ordinal out of range, a serial_len above 40 or non-zero padding
+ * (checked on the device before the first insert), world == 0 or rank >= world, world > 1 with a set whose issuer is not
+ * registered, an owner-computes round open on the engine.  CTMR_E_FULL / CTMR_E_NOMEM as for a batch: the call reserves
+ * for every member it takes before it inserts one. */
+int ctmr_known_import(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t world, uint32_t rank,
+                      ctmr_known_import_stats* st);
+int ctmr_known_import_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                             uint64_t n_members, uint32_t world, uint32_t rank, ctmr_known_import_stats* st);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner
