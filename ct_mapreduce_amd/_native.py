@@ -95,6 +95,11 @@ class KnownImportStats(C.Structure):
                 ("host_members", C.c_uint64), ("host_inserted", C.c_uint64)]
 
 
+class KnownListsInfo(C.Structure):
+    _fields_ = [("issuers", C.c_uint64), ("sets", C.c_uint64), ("members", C.c_uint64), ("host_members", C.c_uint64),
+                ("text_bytes", C.c_uint64), ("ids_bytes", C.c_uint64)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_issuers", C.c_uint32), ("zipf", C.c_uint32),
                 ("dup_permille", C.c_uint32), ("ca_permille", C.c_uint32),
@@ -146,6 +151,10 @@ SIGNATURES = {
     "ctmr_known_import": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(KnownImportStats)]),
     "ctmr_known_import_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, C.c_uint32,
                                            C.POINTER(KnownImportStats)]),
+    "ctmr_known_lists": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t,
+                                   C.POINTER(KnownListsInfo)]),
+    "ctmr_known_lists_device": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t,
+                                          C.POINTER(KnownListsInfo)]),
     "ctmr_xchg_map_device": (C.c_int, [_P, C.POINTER(Shard), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]),
     "ctmr_xchg_map_chunk_device": (C.c_int, [_P, C.POINTER(Shard), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P,

@@ -645,5 +645,6 @@ extern "C" {
 #include "engine/group.inc"
 #include "engine/synth.inc"
 #include "engine/image.inc"
+#include "engine/lists.inc"
 
 }  // extern "C"

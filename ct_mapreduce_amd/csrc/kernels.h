@@ -18,6 +18,7 @@
 //   kernels/misc.h      k_fingerprint, k_set_op / k_sweep / k_rehash / k_arena_compact / k_build_pairs / k_list / k_pairs,
 //                       k_synth_*
 //   kernels/image.h     k_known_export / k_known_count / k_known_pack / k_known_bloom (the known-certificate image)
+//   kernels/lists.h     k_lists_count / k_lists_write (per-issuer known-serial lists as text)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once
 #include "kernels/readers.h"
@@ -34,3 +35,4 @@
 #include "kernels/meta.h"
 #include "kernels/misc.h"
 #include "kernels/image.h"
+#include "kernels/lists.h"

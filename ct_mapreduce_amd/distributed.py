@@ -110,6 +110,12 @@ class Group:
         self._check(self._lib.ctmr_group_issuer_counts(self._h, out.ctypes.data, n))
         return out[:n]
 
+    def known_lists(self, now) -> list:
+        """The group's per-issuer known-serial lists: every local rank's Engine.known_lists(now), merged per Issuer.ID
+        (known_image.merge_lists).  In-process groups only: an RCCL group gathers its ranks' lists itself."""
+        from .known_image import merge_lists
+        return merge_lists([e.known_lists(now) for e in self.engines])
+
     def total_count(self) -> int:
         v = C.c_uint64(0)
         self._check(self._lib.ctmr_group_total_count(self._h, C.byref(v)))

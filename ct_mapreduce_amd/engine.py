@@ -642,6 +642,57 @@ class Engine:
                                                     C.byref(st)))
         return self._import_stats(st)
 
+    # ---- per-issuer known-serial lists (include/ctmr.h ctmr_known_lists*; CPU twin: known_image.known_lists)
+    def _known_lists_call(self, fn, alloc, now):
+        """One call sized by the bound (81 B per live member, the host-store text as large as last time), which writes
+        without a separate count pass, and a second, exact one only when that was short (CTMR_E_RANGE fills `info`)."""
+        info = N.KnownListsInfo()
+        occ = self.table_info().occupied
+        text_cap = 81 * occ + getattr(self, "_known_lists_host", 1 << 12)
+        ids_cap, n_offs = getattr(self, "_known_lists_ids", 1 << 12), getattr(self, "_known_lists_offs", 256)
+        for _ in range(2):
+            text = alloc(text_cap)
+            ids, offs = np.empty(max(ids_cap, 1), np.uint8), np.empty(max(n_offs, 2), np.uint64)
+            rc = fn(int(now), text, text_cap, ids.ctypes.data, ids_cap, offs.ctypes.data, n_offs, C.byref(info))
+            if rc != N.E_RANGE:
+                break
+            text_cap, ids_cap, n_offs = info.text_bytes, info.ids_bytes, 2 * (info.issuers + 1)
+        self._ck(rc)
+        self._known_lists_host = max(info.text_bytes - 81 * info.members, 1 << 12)
+        self._known_lists_ids, self._known_lists_offs = max(ids_cap, info.ids_bytes), max(n_offs, 2 * (info.issuers + 1))
+        g = info.issuers
+        return text, ids[:info.ids_bytes].tobytes(), offs[:g + 1].copy(), offs[g + 1:2 * g + 2].copy(), info
+
+    def known_lists_raw(self, now):
+        """→ (text: numpy uint8 of info.text_bytes, ids: bytes, text offsets, ID offsets (u64, issuers + 1 each), info)."""
+        text, ids, toff, ioff, info = self._known_lists_call(
+            lambda now, t, tc, *rest: self._lib.ctmr_known_lists(self._h, now, t.ctypes.data, tc, *rest),
+            lambda cap: np.empty(max(cap, 1), np.uint8), now)
+        return text[:info.text_bytes], ids, toff, ioff, info
+
+    def known_lists(self, now) -> list:
+        """[(Issuer.ID bytes, list text bytes)] in ID order: the serials of every set not expired at `now` (unix seconds),
+        one lowercase hex line each — what LocalDiskBackend.StoreKnownCertificateList writes per issuer."""
+        text, ids, toff, ioff, info = self.known_lists_raw(now)
+        return [(ids[ioff[k]:ioff[k + 1]], text[toff[k]:toff[k + 1]].tobytes()) for k in range(info.issuers)]
+
+    def known_lists_device(self, now):
+        """→ ([Issuer.ID bytes], text offsets (numpy u64, issuers + 1), torch uint8 tensor of the text on this engine's
+        device; a view)."""
+        import torch
+        dev = "cuda:%d" % self.device
+        text, ids, toff, ioff, info = self._known_lists_call(
+            lambda now, t, tc, *rest: self._lib.ctmr_known_lists_device(self._h, now, C.c_void_p(t.data_ptr()), tc, *rest),
+            lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), now)
+        return [ids[ioff[k]:ioff[k + 1]] for k in range(info.issuers)], toff, text[:info.text_bytes]
+
+    def store_known_lists(self, writer, now) -> int:
+        """StoreKnownCertificateList for every list at `now` through a host_writeback.HostWriter (LocalDiskBackend: one
+        file <root>/<Issuer.ID> per list; NoopBackend: nothing).  → the lists handed to the backend."""
+        text, ids, toff, ioff, info = self.known_lists_raw(now)
+        writer.store_known_lists(ids, ioff, text, toff)
+        return int(info.issuers)
+
     # ---- synthetic input (bench / tests)
     def synth_view_device(self, cfg: N.SynthConfig, first, n, align, d_starts, d_ends, d_payload, payload_cap,
                           d_issuer_idx, d_entry_type) -> int:

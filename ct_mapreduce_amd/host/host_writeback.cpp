@@ -150,6 +150,49 @@ int ctmr_host_writer_mark_dirty(ctmr_host_writer* w, const int32_t* days, uint32
   return 0;
 }
 
+// StoreKnownCertificateList for n per-issuer lists (ctmr_known_lists' output): list k is the Issuer.ID
+// ids[id_off[k], id_off[k+1]) with the text text[text_off[k], text_off[k+1]).  LocalDiskBackend writes <root>/<Issuer.ID>
+// (the root made first, the file truncated: storage/localdiskbackend.go); NoopBackend writes nothing.  Every ID is checked
+// before anything is written: an empty ID, "." or "..", or one holding '/' or NUL names no file of the root and is
+// refused (base64url IDs never do; odd host-store keys can).  The lists go out on the writer's threads.  Returns 0, or -1
+// with ctmr_host_writer_error().
+int ctmr_host_writer_store_known_lists(ctmr_host_writer* w, const char* ids, const uint64_t* id_off, uint64_t n,
+                                       const uint8_t* text, const uint64_t* text_off) {
+  if (!w || (n && (!ids || !id_off || !text_off || (text_off[n] > text_off[0] && !text)))) return -1;
+  for (uint64_t k = 0; k < n; k++) {
+    const std::string id(ids + id_off[k], id_off[k + 1] - id_off[k]);
+    if (id.empty() || id == "." || id == ".." || id.find('/') != std::string::npos || id.find('\0') != std::string::npos) {
+      w->err = "known list: issuer ID \"" + id + "\" names no file of the root";
+      return -1;
+    }
+  }
+  if (!w->disk || !n) return 0;
+  auto* disk = static_cast<LocalDiskBackend*>(w->backend.get());
+  std::atomic<uint64_t> next{0};
+  std::mutex mu;
+  std::string err;
+  std::vector<std::thread> ts;
+  const int T = (uint64_t)w->threads < n ? w->threads : (int)n;
+  for (int t = 0; t < T; t++)
+    ts.emplace_back([&]() {
+      for (uint64_t k; (k = next++) < n;) {
+        try {
+          disk->StoreKnownCertificateListText(Issuer::FromString(std::string(ids + id_off[k], id_off[k + 1] - id_off[k])),
+                                              (const char*)text + text_off[k], text_off[k + 1] - text_off[k]);
+        } catch (const std::exception& ex) {
+          std::lock_guard<std::mutex> g(mu);
+          if (err.empty()) err = ex.what();
+        }
+      }
+    });
+  for (auto& t : ts) t.join();
+  if (!err.empty()) {
+    w->err = err;
+    return -1;
+  }
+  return 0;
+}
+
 const char* ctmr_host_writer_error(ctmr_host_writer* w) { return w ? w->err.c_str() : "null writer"; }
 
 void ctmr_host_writer_close(ctmr_host_writer* w) {

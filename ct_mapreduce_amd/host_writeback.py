@@ -29,6 +29,8 @@ def lib():
         L.ctmr_host_writer_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.ctmr_host_writer_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.ctmr_host_writer_mark_dirty.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]
+        L.ctmr_host_writer_store_known_lists.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                          C.c_void_p]
         L.ctmr_host_writer_error.argtypes = [C.c_void_p]
         L.ctmr_host_writer_error.restype = C.c_char_p
         L.ctmr_host_writer_close.argtypes = [C.c_void_p]
@@ -71,6 +73,30 @@ class HostWriter:
         arr = (C.c_int32 * len(days))(*[int(d) for d in days])
         if self._L.ctmr_host_writer_mark_dirty(self._h, arr, len(days)):
             raise RuntimeError("markDirty failed: " + self._L.ctmr_host_writer_error(self._h).decode())
+
+    def store_known_lists(self, ids, id_off, text, text_off):
+        """StoreKnownCertificateList for every list of Engine.known_lists_raw: ids (bytes) with id_off, text (bytes-like)
+        with text_off (u64 arrays of lists + 1).  LocalDiskBackend: <root>/<Issuer.ID>, truncated; NoopBackend: nothing.
+        Raises before writing anything when an ID is empty, "." or "..", or holds '/' or NUL."""
+        if not self._h:
+            raise RuntimeError("host writer is closed")
+        import numpy as np
+        id_off = np.ascontiguousarray(id_off, np.uint64)
+        text_off = np.ascontiguousarray(text_off, np.uint64)
+        text = np.frombuffer(text, np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
+        n = max(len(id_off) - 1, 0)
+        if self._L.ctmr_host_writer_store_known_lists(self._h, bytes(ids), id_off.ctypes.data, n,
+                                                      text.ctypes.data if text.size else None, text_off.ctypes.data):
+            raise RuntimeError("StoreKnownCertificateList failed: " + self._L.ctmr_host_writer_error(self._h).decode())
+
+    def store_lists(self, lists):
+        """store_known_lists of [(Issuer.ID bytes, text bytes)] (Engine.known_lists, known_image.known_lists)."""
+        import numpy as np
+        ids = [bytes(i) for i, _ in lists]
+        texts = [bytes(t) for _, t in lists]
+        id_off = np.concatenate([[0], np.cumsum([len(i) for i in ids], dtype=np.uint64)]).astype(np.uint64)
+        text_off = np.concatenate([[0], np.cumsum([len(t) for t in texts], dtype=np.uint64)]).astype(np.uint64)
+        self.store_known_lists(b"".join(ids), id_off, b"".join(texts), text_off)
 
     def close(self):
         if self._h:

@@ -247,3 +247,79 @@ def from_resp(stream) -> bytes:
     c = _SetsCache()
     redis_load(c, stream)
     return build({k: v for k, v in c.sets.items() if k.startswith(PREFIX)})
+
+
+# ---- per-issuer known-serial lists (include/ctmr.h ctmr_known_lists), without a GPU
+
+class ListsError(ValueError):
+    """A serials:: key that does not split into three "::" parts: the library fails with CTMR_E_INVAL."""
+
+
+def exp_date_span(date: bytes):
+    """NewExpDate(date) (storage/types.go): → (first second, first second at which IsExpiredAt is true), or None when it
+    does not parse.  "2006-01-02-15" (one or two hour digits, as time.Parse takes them) or "2006-01-02"; four-digit
+    years."""
+    d = bytes(date)
+    if len(d) not in (10, 12, 13) or d[4:5] != b"-" or d[7:8] != b"-":
+        return None
+    if not (d[0:4] + d[5:7] + d[8:10]).isdigit():
+        return None
+    h = None
+    if len(d) > 10:
+        if d[10:11] != b"-" or not d[11:].isdigit():
+            return None
+        h = int(d[11:])
+    y, m, day = int(d[0:4]), int(d[5:7]), int(d[8:10])
+    if not (1 <= m <= 12 and 1 <= day <= 31) or (h is not None and h > 23):
+        return None
+    days = _days_from_civil(y, m, day)
+    if _civil_from_days(days) != (y, m, day):
+        return None
+    start = days * 86400 + (h or 0) * 3600
+    return start, start + (86400 if h is None else 3600)
+
+
+def list_blocks(sets, now) -> list:
+    """[(Issuer.ID, [(expDate, [members])])]: the sets of {key: members} kept at `now`, grouped per Issuer.ID (bytewise
+    ascending) and expDate (ascending: first second, then the date string) — GetIssuerAndDatesFromCache and
+    IsExpiredAt as the library applies them.  Members keep the order they have in `sets`."""
+    by_id = {}
+    for key, members in sets.items():
+        key = bytes(key)
+        if not key.startswith(PREFIX):
+            continue
+        parts = key.split(b"::")
+        if len(parts) != 3:
+            raise ListsError("unexpected key format: %r" % key)
+        span = exp_date_span(parts[1])
+        if span is None or now >= span[1]:
+            continue
+        by_id.setdefault(parts[2], {})[(span[0], parts[1])] = list(members)
+    return [(i, [(k[1], by_id[i][k]) for k in sorted(by_id[i])]) for i in sorted(by_id)]
+
+
+def line(serial: bytes) -> bytes:
+    """One line of a list: hex.EncodeToString(serial) + "\\n" (Serial.HexString, lowercase)."""
+    return bytes(serial).hex().encode() + b"\n"
+
+
+def lists_of_sets(sets, now) -> list:
+    """[(Issuer.ID, text)] of {key: members}: what Engine.known_lists returns for an engine holding those sets (the
+    order inside an expDate is the order of `sets`; the library's is unspecified)."""
+    return [(i, b"".join(line(m) for _, ms in blocks for m in ms)) for i, blocks in list_blocks(sets, now)]
+
+
+def known_lists(image, now) -> list:
+    """The per-issuer known-serial lists of an image at `now`: Engine.known_lists of the engine that exported it."""
+    return lists_of_sets(parse(image).sets, now)
+
+
+def merge_lists(per_rank) -> list:
+    """The lists of several ranks (each [(Issuer.ID, text)]) concatenated per Issuer.ID in rank order, IDs ascending.
+    The ranks of a group hold each key once (owner or Bloom mode), so this is the group's list up to the order inside
+    an expDate block.  Gathering the ranks' lists between processes is left to the caller."""
+    out = {}
+    for lists in per_rank:
+        for i, text in lists:
+            out.setdefault(bytes(i), []).append(bytes(text))
+    return [(i, b"".join(out[i])) for i in sorted(out)]

@@ -306,6 +306,51 @@ int ctmr_known_import(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t
 int ctmr_known_import_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
                              uint64_t n_members, uint32_t world, uint32_t rank, ctmr_known_import_stats* st);
 
+/* ---- per-issuer known-serial lists: what this map/reduce exists to produce.  For each Issuer.ID, the serials of its
+ *      certificates that have not expired, as FilesystemDatabase hands them to StorageBackend.StoreKnownCertificateList
+ *      (storage/types.go) — the composition of GetIssuerAndDatesFromCache (storage/filesystemdatabase.go), IsExpiredAt
+ *      and KnownCertificates.Known() per expDate.  LocalDiskBackend writes one list as the file <root>/<Issuer.ID>.
+ *      DESIGN.md §13.
+ *
+ * Which sets.  Every set the engine holds (the device table and the serials:: keys of the host-side store) whose expDate
+ *   is not expired at now_unix: !NewExpDate(<expDate of its key>).IsExpiredAt(now).  An hour-resolution key of exp hour h
+ *   is kept iff now_unix < (h + 1) × 3600 (lastGood = h·3600 + 1 h − 1 ms): kept at (h+1)·3600 − 1, dropped at
+ *   (h+1)·3600.  A day-resolution host key ("2006-01-02") uses lastGood = day + 24 h − 1 ms.  A key whose date NewExpDate
+ *   cannot parse is skipped, as GetIssuerAndDatesFromCache skips it — among them every hour outside the years 0000..9999.
+ *   A serials:: key that does not split into exactly three "::" parts fails the call with CTMR_E_INVAL (the reference
+ *   returns an error for it).  The call does not sweep: ctmr_expire_sweep(now) first gives Redis's TTL behaviour, and
+ *   ExpireAt overrides play no part.
+ * Grouping.  One list per Issuer.ID string: registered issuers that share an SPKI share one canonical ID and one list;
+ *   host-store keys of issuers not registered here give their key's issuer string; long-serial members (above
+ *   CTMR_MAX_SERIAL octets, in the host-side store) join their issuer's list.
+ * Lines.  hex.EncodeToString(serial) + "\n": lowercase, every raw octet, leading 00 kept; an empty serial is a line "\n".
+ *   One line per set member, not deduplicated: a serial known under two expDates of one issuer is listed twice.  Within
+ *   a list the lines of one expDate are contiguous and expDates ascend (by their first second, then bytewise as strings);
+ *   the order inside an expDate is unspecified.  Lists are ordered by Issuer.ID bytewise.
+ * Left out.  A Bloom-mode rank's SHADOW keys, as in the image: the union of a group's ranks holds each key once, so the
+ *   per-issuer concatenation of the ranks' lists is the group's list (up to the order inside an expDate).
+ * Read-only: table, pair statistics, counters, host-side store and expiry records are as before.
+ *
+ * Output: text = the lists back to back; ids = the Issuer.IDs back to back; offs = 2 × (issuers + 1) u64: the text
+ * offset of each list and text_bytes, then the offset of each ID in ids and ids_bytes (offs_cap counts u64).  Two-call
+ * convention as ctmr_known_export: when a buffer is too small, *info is filled and the call returns CTMR_E_RANGE and
+ * writes nothing.  text_bytes depends on every member's serial length: a call that cannot size by the bound
+ * 81 B × members counts on the device first.  The members are staged on the device in set ranges of at most 2^26
+ * records (a larger set alone).  Returns after the engine's stream has drained. */
+typedef struct {
+  uint64_t issuers;       /* lists */
+  uint64_t sets;          /* (expDate, Issuer.ID) sets kept */
+  uint64_t members;       /* lines from the device table */
+  uint64_t host_members;  /* lines from the host-side store */
+  uint64_t text_bytes;
+  uint64_t ids_bytes;
+} ctmr_known_lists_info;
+int ctmr_known_lists(ctmr_engine* e, int64_t now_unix, uint8_t* text, size_t text_cap, uint8_t* ids, size_t ids_cap,
+                     uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info);
+/* The same with text in device memory (of this engine's device); host-store lines are copied into it at their places. */
+int ctmr_known_lists_device(ctmr_engine* e, int64_t now_unix, void* d_text, size_t text_cap, uint8_t* ids, size_t ids_cap,
+                            uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner

@@ -1133,8 +1133,10 @@ class LocalDiskBackend : public StorageBackend {
   void StoreKnownCertificateList(const Issuer& i, const std::vector<Serial>& serials) override {
     std::string body;
     for (auto& s : serials) body += s.HexString() + "\n";
-    store_(join(rootPath_, i.ID()), body);
+    StoreKnownCertificateListText(i, body.data(), body.size());
   }
+  // The same file from the list's text, already encoded (one Serial.HexString() line per serial).
+  void StoreKnownCertificateListText(const Issuer& i, const char* text, size_t n) { store_(join(rootPath_, i.ID()), text, n); }
   std::string LoadCertificatePEM(const Serial&, const ExpDate&, const Issuer&) override { throw Error("Unimplemented"); }
   CertificateLog LoadLogState(const std::string& logURL) override {
     const std::string path = join(join(rootPath_, kStateDirName), CertificateLogIDFromShortURL(logURL));
@@ -1179,13 +1181,14 @@ class LocalDiskBackend : public StorageBackend {
         if (mkdir(part.c_str(), 0777) != 0 && errno != EEXIST) throw Error("mkdir " + part + ": " + strerror(errno));
       }
   }
-  void store_(const std::string& path, const std::string& data) {
+  void store_(const std::string& path, const std::string& data) { store_(path, data.data(), data.size()); }
+  void store_(const std::string& path, const char* data, size_t n) {
     mkdirs(dirname(path));
     const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, perms_);
     if (fd < 0) throw Error("open " + path + ": " + strerror(errno));
     size_t w = 0;
-    while (w < data.size()) {
-      const ssize_t r = write(fd, data.data() + w, data.size() - w);
+    while (w < n) {
+      const ssize_t r = write(fd, data + w, n - w);
       if (r < 0) { close(fd); throw Error("write " + path + ": " + strerror(errno)); }
       w += (size_t)r;
     }
