@@ -90,6 +90,11 @@ class KnownImageInfo(C.Structure):
                 ("image_bytes", C.c_uint64), ("issuers", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class KnownProbeStats(C.Structure):
+    _fields_ = [("members", C.c_uint64), ("taken", C.c_uint64), ("hits", C.c_uint64), ("host_members", C.c_uint64),
+                ("host_hits", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 class KnownImportStats(C.Structure):
     _fields_ = [("members", C.c_uint64), ("taken", C.c_uint64), ("inserted", C.c_uint64), ("known", C.c_uint64),
                 ("host_members", C.c_uint64), ("host_inserted", C.c_uint64)]
@@ -151,6 +156,13 @@ SIGNATURES = {
     "ctmr_known_import": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(KnownImportStats)]),
     "ctmr_known_import_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, C.c_uint32,
                                            C.POINTER(KnownImportStats)]),
+    "ctmr_known_query": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P, C.c_size_t, _P, C.c_size_t,
+                                   C.POINTER(KnownProbeStats)]),
+    "ctmr_known_query_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64,
+                                          _P, C.c_size_t, C.POINTER(KnownProbeStats)]),
+    "ctmr_known_remove": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(KnownProbeStats)]),
+    "ctmr_known_remove_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, C.c_uint32,
+                                           C.POINTER(KnownProbeStats)]),
     "ctmr_known_lists": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t,
                                    C.POINTER(KnownListsInfo)]),
     "ctmr_known_lists_device": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t,

@@ -249,34 +249,116 @@ int known_export_members(ctmr_engine* e, KnownExport& x, size_t s_lo, size_t s_h
   return CTMR_OK;
 }
 
-// Import: owner round check, issuer remap, then the members on the device (d_members: km.n_members records).
-int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, uint32_t world, uint32_t rank,
-                      ctmr_known_import_stats* st) {
-  if (world == 0 || rank >= world) return fail(e, CTMR_E_INVAL, "known import: rank %u of world %u", rank, world);
+// What the kernels' error word says about the member records (kernels/image.h: KnownImportArgs.err).
+int known_record_error(ctmr_engine* e, uint32_t err, const char* what) {
+  if (err & 1u) return fail(e, CTMR_E_INVAL, "%s: a member record's serial_len is above %d", what, CTMR_MAX_SERIAL);
+  if (err) return fail(e, CTMR_E_INVAL, "%s: a member record's padding octets are not zero", what);
+  return CTMR_OK;
+}
+
+// What import, query and remove share in front of the member records: the call's checks (`what` names it in messages),
+// the image's issuer ordinals mapped to canonical indices here, and per set the key meta (0: issuer not registered — the
+// host side takes the set, world = 1 only).
+struct KnownSets {
+  std::vector<unsigned long long> set_meta;
+  std::vector<size_t> unreg;
+  uint64_t unreg_members = 0;
+};
+
+int known_sets_prepare(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, uint32_t world, uint32_t rank,
+                       const char* what, KnownSets* ks) {
+  if (world == 0 || rank >= world) return fail(e, CTMR_E_INVAL, "%s: rank %u of world %u", what, rank, world);
   if (e->rd.valid && e->rd.mode == XM_OWNER && !e->rd.resolved)
-    return fail(e, CTMR_E_INVAL, "known import: an owner-computes round is open on this engine");
-  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "known import: null member records");
+    return fail(e, CTMR_E_INVAL, "%s: an owner-computes round is open on this engine", what);
+  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "%s: null member records", what);
   // image issuer ordinal → canonical index here (0xffffffff: not registered)
   std::vector<uint32_t> remap(km.n_issuers, 0xffffffffu);
   for (uint32_t k = 0; k < km.n_issuers; k++) {
     auto it = e->id_to_canon.find(b64url(km.issuers + (size_t)k * 32, 32));
     if (it != e->id_to_canon.end()) remap[k] = it->second;
   }
-  std::vector<unsigned long long> set_meta(km.n_sets);
-  std::vector<size_t> unreg;
-  uint64_t unreg_members = 0;
+  ks->set_meta.resize(km.n_sets);
   for (uint64_t s = 0; s < km.n_sets; s++) {
     const uint32_t c = remap[km.set_issuer[s]];
     if (c == 0xffffffffu) {
-      unreg.push_back(s);
-      unreg_members += km.set_first[s + 1] - km.set_first[s];
-      set_meta[s] = 0ull;
+      ks->unreg.push_back(s);
+      ks->unreg_members += km.set_first[s + 1] - km.set_first[s];
+      ks->set_meta[s] = 0ull;
     } else {
-      set_meta[s] = key_meta(km.set_hour[s], c, 0);
+      ks->set_meta[s] = key_meta(km.set_hour[s], c, 0);
     }
   }
-  if (world > 1 && !unreg.empty())
-    return fail(e, CTMR_E_INVAL, "known import: world %u needs every set's issuer registered (%zu sets are not)", world, unreg.size());
+  if (world > 1 && !ks->unreg.empty())
+    return fail(e, CTMR_E_INVAL, "%s: world %u needs every set's issuer registered (%zu sets are not)", what, world,
+                ks->unreg.size());
+  return CTMR_OK;
+}
+
+// The device side of the same: set_first[] and set_meta[], the per-block counts of a chunk of at most `chunk` records,
+// the error word and a DevStats, in one allocation; args(c) describes chunk c to the kernels of kernels/image.h.
+struct KnownDev {
+  void* tmp = nullptr;
+  size_t off_meta = 0, off_cnt = 0, off_err = 0, off_stats = 0;
+  uint64_t n = 0, chunk = 0, nch = 0, nbmax = 0;
+  const uint8_t* members = nullptr;
+  uint32_t n_sets = 0, world = 1, rank = 0;
+  ~KnownDev() { if (tmp) (void)hipFree(tmp); }
+  uint8_t* t8() const { return (uint8_t*)tmp; }
+  uint32_t* err() const { return (uint32_t*)(t8() + off_err); }
+  DevStats* stats() const { return (DevStats*)(t8() + off_stats); }
+  KnownImportArgs args(uint64_t c) const {
+    KnownImportArgs a{};
+    const uint64_t lo = c * chunk, cn = std::min(n - lo, chunk);
+    a.members = members + lo * KNOWN_REC_BYTES; a.n = cn; a.base = lo;
+    a.set_first = (const uint64_t*)t8(); a.set_meta = (const unsigned long long*)(t8() + off_meta);
+    a.n_sets = n_sets; a.world = world; a.rank = rank;
+    a.cnt = (unsigned long long*)(t8() + off_cnt); a.nb = (cn + 255) / 256; a.err = err();
+    return a;
+  }
+};
+
+int known_dev_upload(ctmr_engine* e, const KnownMeta& km, const KnownSets& ks, const uint8_t* d_members, uint32_t world,
+                     uint32_t rank, uint64_t chunk, KnownDev* kd) {
+  const uint64_t N = km.n_members, CH = N < chunk ? N : chunk;
+  kd->n = N; kd->chunk = chunk; kd->nch = (N + chunk - 1) / chunk; kd->nbmax = (CH + 255) / 256;
+  kd->members = d_members; kd->n_sets = (uint32_t)km.n_sets; kd->world = world; kd->rank = rank;
+  kd->off_meta = (km.n_sets + 1) * 8;
+  kd->off_cnt = (kd->off_meta + km.n_sets * 8 + 63) & ~(size_t)63;
+  kd->off_err = kd->off_cnt + ((2 * kd->nbmax + 1) * 8 + 63) / 64 * 64;
+  kd->off_stats = kd->off_err + 64;
+  if (!N) return CTMR_OK;
+  HIPCHK(e, hipMalloc(&kd->tmp, kd->off_stats + sizeof(DevStats)));
+  HIPCHK(e, hipMemcpyAsync(kd->t8(), km.set_first.data(), kd->off_meta, hipMemcpyHostToDevice, e->stream));
+  if (km.n_sets) HIPCHK(e, hipMemcpyAsync(kd->t8() + kd->off_meta, ks.set_meta.data(), km.n_sets * 8, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemsetAsync(kd->t8() + kd->off_err, 0, 64 + sizeof(DevStats), e->stream));
+  return CTMR_OK;
+}
+
+// The count pass over chunk c (k_known_count: validates every record) and its scan; drains the stream.
+// → tot[0] = records of at most 20 octets taken, tot[1] = all records taken.
+int known_count_chunk(ctmr_engine* e, const KnownDev& kd, uint64_t c, const char* what, unsigned long long tot[2]) {
+  const KnownImportArgs a = kd.args(c);
+  int r;
+  HIPCHK(e, hipMemsetAsync(a.cnt + 2 * a.nb, 0, 8, e->stream));
+  hipLaunchKernelGGL(k_known_count, dim3((unsigned)a.nb), dim3(256), 0, e->stream, a);
+  if ((r = scan_u64(e, (uint64_t*)a.cnt, 2 * a.nb + 1, false, SC_TMP))) return r;
+  uint32_t err = 0;
+  HIPCHK(e, hipMemcpyAsync(&tot[0], a.cnt + a.nb, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(&tot[1], a.cnt + 2 * a.nb, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  return known_record_error(e, err, what);
+}
+
+// Import: owner round check, issuer remap, then the members on the device (d_members: km.n_members records).
+int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, uint32_t world, uint32_t rank,
+                      ctmr_known_import_stats* st) {
+  KnownSets ks;
+  int r;
+  if ((r = known_sets_prepare(e, km, d_members, world, rank, "known import", &ks))) return r;
+  const std::vector<size_t>& unreg = ks.unreg;
+  const uint64_t unreg_members = ks.unreg_members;
   // host section (rank 0): members ctmr_set_insert would put into the device table are point inserts
   uint64_t host_point = 0;
   if (rank == 0)
@@ -287,45 +369,17 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
   memset(st, 0, sizeof *st);
   st->members = km.n_members;
   // ---- device records: count (and validate) every chunk, reserve, then pack and insert chunk by chunk
-  const uint64_t N = km.n_members, nch = (N + KNOWN_CHUNK - 1) / KNOWN_CHUNK;
-  const uint64_t CH = N < KNOWN_CHUNK ? N : KNOWN_CHUNK, nbmax = (CH + 255) / 256;
-  void* tmp = nullptr;
-  const size_t off_meta = (km.n_sets + 1) * 8, off_cnt = (off_meta + km.n_sets * 8 + 63) & ~(size_t)63;
-  const size_t off_err = off_cnt + ((2 * nbmax + 1) * 8 + 63) / 64 * 64, off_stats = off_err + 64;
-  const size_t tmp_bytes = off_stats + sizeof(DevStats);
-  struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_tmp{tmp};
+  KnownDev kd;
+  if ((r = known_dev_upload(e, km, ks, d_members, world, rank, KNOWN_CHUNK, &kd))) return r;
+  const uint64_t nch = kd.nch;
   uint64_t taken = 0;
   std::vector<uint64_t> n32(nch), n64(nch);
-  int r;
-  if (N) {
-    HIPCHK(e, hipMalloc(&tmp, tmp_bytes));
-    uint8_t* t8 = (uint8_t*)tmp;
-    HIPCHK(e, hipMemcpyAsync(t8, km.set_first.data(), off_meta, hipMemcpyHostToDevice, e->stream));
-    if (km.n_sets) HIPCHK(e, hipMemcpyAsync(t8 + off_meta, set_meta.data(), km.n_sets * 8, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemsetAsync(t8 + off_err, 0, 64 + sizeof(DevStats), e->stream));
-    for (uint64_t c = 0; c < nch; c++) {
-      KnownImportArgs a{};
-      const uint64_t lo = c * KNOWN_CHUNK, n = std::min(N - lo, KNOWN_CHUNK), nb = (n + 255) / 256;
-      a.members = d_members + lo * KNOWN_REC_BYTES; a.n = n; a.base = lo;
-      a.set_first = (const uint64_t*)t8; a.set_meta = (const unsigned long long*)(t8 + off_meta);
-      a.n_sets = (uint32_t)km.n_sets; a.world = world; a.rank = rank;
-      a.cnt = (unsigned long long*)(t8 + off_cnt); a.nb = nb; a.err = (uint32_t*)(t8 + off_err);
-      HIPCHK(e, hipMemsetAsync(a.cnt + 2 * nb, 0, 8, e->stream));
-      hipLaunchKernelGGL(k_known_count, dim3((unsigned)nb), dim3(256), 0, e->stream, a);
-      if ((r = scan_u64(e, (uint64_t*)a.cnt, 2 * nb + 1, false, SC_TMP))) return r;
-      unsigned long long tot[2];
-      uint32_t err = 0;
-      HIPCHK(e, hipMemcpyAsync(&tot[0], a.cnt + nb, 8, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(e, hipMemcpyAsync(&tot[1], a.cnt + 2 * nb, 8, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(e, hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-      HIPCHK(e, hipGetLastError());
-      if (err & 1u) return fail(e, CTMR_E_INVAL, "known import: a member record's serial_len is above %d", CTMR_MAX_SERIAL);
-      if (err) return fail(e, CTMR_E_INVAL, "known import: a member record's padding octets are not zero");
-      n32[c] = tot[0];
-      n64[c] = tot[1] - tot[0];
-      taken += tot[1];
-    }
+  for (uint64_t c = 0; c < nch; c++) {
+    unsigned long long tot[2];
+    if ((r = known_count_chunk(e, kd, c, "known import", tot))) return r;
+    n32[c] = tot[0];
+    n64[c] = tot[1] - tot[0];
+    taken += tot[1];
   }
   st->taken = taken + unreg_members;
   // every slot and cell the call may claim, before anything is applied ("applied completely or not at all")
@@ -334,18 +388,14 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
   }
   uint64_t inserted = 0;
   if (taken) {
-    uint8_t* t8 = (uint8_t*)tmp;
     e->epoch++;
     e->pairs_dirty = true;
-    DevStats* d_st = (DevStats*)(t8 + off_stats);
+    DevStats* d_st = kd.stats();
+    struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } };
     for (uint64_t c = 0; c < nch; c++) {
       if (!n32[c] && !n64[c]) continue;
-      KnownImportArgs a{};
-      const uint64_t lo = c * KNOWN_CHUNK, n = std::min(N - lo, KNOWN_CHUNK), nb = (n + 255) / 256;
-      a.members = d_members + lo * KNOWN_REC_BYTES; a.n = n; a.base = lo;
-      a.set_first = (const uint64_t*)t8; a.set_meta = (const unsigned long long*)(t8 + off_meta);
-      a.n_sets = (uint32_t)km.n_sets; a.world = world; a.rank = rank;
-      a.cnt = (unsigned long long*)(t8 + off_cnt); a.nb = nb; a.err = (uint32_t*)(t8 + off_err);
+      const KnownImportArgs a = kd.args(c);
+      const uint64_t nb = a.nb;
       if (nch > 1) {  // cnt[] holds the counts of the last chunk counted: with several chunks, each counts again
         HIPCHK(e, hipMemsetAsync(a.cnt + 2 * nb, 0, 8, e->stream));
         hipLaunchKernelGGL(k_known_count, dim3((unsigned)nb), dim3(256), 0, e->stream, a);
@@ -435,6 +485,166 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
     }
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
+  return CTMR_OK;
+}
+
+// ---- bulk SetContains / SetRemove over an image's member records (include/ctmr.h ctmr_known_query* / ctmr_known_remove*,
+// DESIGN.md §14)
+
+// ctmr_set_remove's host half (the engine mutex is held)
+bool known_host_erase(ctmr_engine* e, const std::string& key, const std::string& m) {
+  auto it = e->hstore.find(key);
+  if (it == e->hstore.end() || !it->second.erase(m)) return false;
+  int32_t eh; uint32_t canon;
+  if (table_key(e, key.data(), key.size(), &eh, &canon)) e->host_issuer_counts[canon]--;
+  if (it->second.empty()) e->hstore.erase(it);
+  return true;
+}
+bool known_host_contains(ctmr_engine* e, const std::string& key, const std::string& m) {
+  auto it = e->hstore.find(key);
+  return it != e->hstore.end() && it->second.count(m) != 0;
+}
+
+// records per pass, as import's; CTMR_KNOWN_PROBE_CHUNK (tests only) forces small passes
+uint64_t known_probe_chunk() {
+  if (const char* ev = getenv("CTMR_KNOWN_PROBE_CHUNK")) {
+    const unsigned long long v = strtoull(ev, nullptr, 10);
+    if (v) return v < KNOWN_CHUNK ? v : KNOWN_CHUNK;
+  }
+  return KNOWN_CHUNK;
+}
+
+// records per lane of k_known_query / k_known_remove: KNOWN_PROBE_RPL was the fastest of 1, 2, 4, 8 (DESIGN.md §14);
+// CTMR_KNOWN_PROBE_RPL selects another for scripts/bench_known_query.py's sweep and the tests of every instantiation
+constexpr uint32_t KNOWN_PROBE_RPL = 4;
+uint32_t known_probe_rpl() {
+  if (const char* ev = getenv("CTMR_KNOWN_PROBE_RPL")) {
+    const unsigned long v = strtoul(ev, nullptr, 10);
+    if (v == 1 || v == 2 || v == 4 || v == 8) return (uint32_t)v;
+  }
+  return KNOWN_PROBE_RPL;
+}
+
+template <int R>
+void known_probe_launch(ctmr_engine* e, const KnownImportArgs& a, bool remove, uint8_t* d_flags) {
+  if (remove) hipLaunchKernelGGL((k_known_remove<R>), dim3((unsigned)a.nb), dim3(256), 0, e->stream, a, e->tbl(), e->issuer_counts);
+  else hipLaunchKernelGGL((k_known_query<R>), dim3((unsigned)a.nb), dim3(256), 0, e->stream, a, e->tbl(), d_flags);
+}
+
+// Query (d_flags: km.n_members bytes of device memory, host_flags: km.host.size() bytes) or remove.  The callers have
+// checked the buffer sizes.
+int known_probe_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, uint32_t world, uint32_t rank,
+                     bool remove, uint8_t* d_flags, uint8_t* host_flags, ctmr_known_probe_stats* st) {
+  const char* what = remove ? "known remove" : "known query";
+  KnownSets ks;
+  int r;
+  if ((r = known_sets_prepare(e, km, d_members, world, rank, what, &ks))) return r;
+  const uint64_t N = km.n_members;
+  KnownDev kd;
+  if ((r = known_dev_upload(e, km, ks, d_members, world, rank, known_probe_chunk(), &kd))) return r;
+  uint64_t taken = 0, hits = 0;
+  if (remove) {  // every record of every chunk is validated before the first word is touched
+    for (uint64_t c = 0; c < kd.nch; c++) {
+      unsigned long long tot[2];
+      if ((r = known_count_chunk(e, kd, c, what, tot))) return r;
+      taken += tot[1];
+    }
+    if (taken) e->pairs_dirty = true;
+  }
+  const uint32_t R = known_probe_rpl();
+  for (uint64_t c = 0; c < kd.nch && (taken || !remove); c++) {
+    KnownImportArgs a = kd.args(c);
+    a.nb = (a.n + 256ull * R - 1) / (256ull * R);  // the probe kernels' blocks take 256 R records
+    uint8_t* fl = remove ? nullptr : d_flags + c * kd.chunk;
+    switch (R) {
+      case 1: known_probe_launch<1>(e, a, remove, fl); break;
+      case 2: known_probe_launch<2>(e, a, remove, fl); break;
+      case 8: known_probe_launch<8>(e, a, remove, fl); break;
+      default: known_probe_launch<4>(e, a, remove, fl); break;
+    }
+    // per block: remove cnt[blk] = removed; query cnt[blk] = taken, cnt[nb + blk] = found — summed by an inclusive scan
+    const uint64_t ncnt = remove ? a.nb : 2 * a.nb;
+    if ((r = scan_u64(e, (uint64_t*)a.cnt, ncnt, true, SC_TMP))) return r;
+    unsigned long long tot[2] = {0ull, 0ull};
+    uint32_t err = 0;
+    HIPCHK(e, hipMemcpyAsync(&tot[0], a.cnt + a.nb - 1, 8, hipMemcpyDeviceToHost, e->stream));
+    if (!remove) {
+      HIPCHK(e, hipMemcpyAsync(&tot[1], a.cnt + 2 * a.nb - 1, 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipGetLastError());
+    if ((r = known_record_error(e, err, what))) return r;
+    if (remove) {
+      hits += tot[0];
+    } else {
+      taken += tot[0];
+      hits += tot[1] - tot[0];
+    }
+  }
+  // ---- sets of issuers not registered here (world = 1): where ctmr_set_insert puts their members, the host-side store
+  for (size_t s : ks.unreg) {
+    const uint64_t f = km.set_first[s], cnt = km.set_first[s + 1] - f;
+    std::vector<uint8_t> buf(cnt * KNOWN_REC_BYTES), fl(cnt);
+    HIPCHK(e, hipMemcpy(buf.data(), d_members + f * KNOWN_REC_BYTES, buf.size(), hipMemcpyDeviceToHost));
+    const std::string key = "serials::" + exp_date_id(km.set_hour[s]) + "::" + km.ids[km.set_issuer[s]];
+    for (uint64_t i = 0; i < cnt; i++) {
+      const uint8_t* p = &buf[i * KNOWN_REC_BYTES];
+      const std::string m((const char*)p + 8, (size_t)rd64(p));
+      fl[i] = remove ? known_host_erase(e, key, m) : known_host_contains(e, key, m);
+      hits += fl[i];
+    }
+    if (!remove) HIPCHK(e, hipMemcpy(d_flags + f, fl.data(), cnt, hipMemcpyHostToDevice));
+  }
+  memset(st, 0, sizeof *st);
+  st->members = N;
+  st->taken = taken + ks.unreg_members;
+  st->hits = hits;
+  // ---- the host section (rank 0 alone): ctmr_set_contains / ctmr_set_remove, member by member
+  if (!remove && rank != 0) memset(host_flags, 2, km.host.size());
+  if (rank == 0) {
+    st->host_members = km.host.size();
+    for (size_t i = 0; i < km.host.size(); i++) {
+      const auto& hm = km.host[i];
+      int32_t eh; uint32_t cn;
+      int hit = 0;
+      if (hm.second.size() <= CTMR_MAX_SERIAL && table_key(e, hm.first.data(), hm.first.size(), &eh, &cn)) {
+        if ((r = point_op(e, remove ? 2 : 1, eh, cn, (const uint8_t*)hm.second.data(), hm.second.size(), &hit))) return r;
+      } else {
+        hit = remove ? known_host_erase(e, hm.first, hm.second) : known_host_contains(e, hm.first, hm.second);
+      }
+      if (!remove) host_flags[i] = (uint8_t)(hit != 0);
+      st->host_hits += hit != 0;
+    }
+  }
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return CTMR_OK;
+}
+
+// a query's buffers against the image: CTMR_E_RANGE with the stats filled as far as known, nothing written
+int known_query_room(ctmr_engine* e, const KnownMeta& km, uint32_t rank, const void* flags, uint64_t flags_cap,
+                     const uint8_t* host_flags, size_t host_flags_cap, ctmr_known_probe_stats* st) {
+  if (flags_cap >= km.n_members && host_flags_cap >= km.host.size() && (flags || !km.n_members) &&
+      (host_flags || km.host.empty()))
+    return CTMR_OK;
+  memset(st, 0, sizeof *st);
+  st->members = km.n_members;
+  st->host_members = rank == 0 ? km.host.size() : 0;
+  return fail(e, CTMR_E_RANGE, "known query: %llu flags and %llu host flags needed", (unsigned long long)km.n_members,
+              (unsigned long long)km.host.size());
+}
+
+// the member records of a whole image, copied to the device (+ extra bytes behind them: a query's flags)
+int known_stage_members(ctmr_engine* e, const KnownMeta& km, const uint8_t* image, size_t extra, const char* what, void** d) {
+  *d = nullptr;
+  const size_t bytes = km.n_members * KNOWN_REC_BYTES;
+  if (!km.n_members) return CTMR_OK;
+  if (hipMalloc(d, bytes + extra) != hipSuccess) {
+    (void)hipGetLastError();
+    *d = nullptr;
+    return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu member records", what, (unsigned long long)km.n_members);
+  }
+  HIPCHK(e, hipMemcpyAsync(*d, image + km.meta_bytes, bytes, hipMemcpyHostToDevice, e->stream));
   return CTMR_OK;
 }
 
@@ -541,4 +751,64 @@ int ctmr_known_import_device(ctmr_engine* e, const uint8_t* meta, size_t meta_le
   if (km.n_members != n_members) return fail(e, CTMR_E_INVAL, "known import: %llu member records given, the header says %llu",
                                              (unsigned long long)n_members, (unsigned long long)km.n_members);
   return known_import_core(e, km, (const uint8_t*)d_members, world, rank, st);
+}
+
+int ctmr_known_query(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t world, uint32_t rank, uint8_t* flags,
+                     size_t flags_cap, uint8_t* host_flags, size_t host_flags_cap, ctmr_known_probe_stats* st) {
+  if (!e || !image || !st) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  int r;
+  if ((r = known_parse_meta(e, image, len, true, &km))) return r;
+  if ((r = known_query_room(e, km, rank, flags, flags_cap, host_flags, host_flags_cap, st))) return r;
+  void* d = nullptr;
+  struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_d{d};
+  if ((r = known_stage_members(e, km, image, km.n_members, "known query", &d))) return r;
+  uint8_t* d_flags = d ? (uint8_t*)d + km.n_members * KNOWN_REC_BYTES : nullptr;
+  if ((r = known_probe_core(e, km, (const uint8_t*)d, world, rank, false, d_flags, host_flags, st))) return r;
+  if (km.n_members) HIPCHK(e, hipMemcpy(flags, d_flags, km.n_members, hipMemcpyDeviceToHost));
+  return CTMR_OK;
+}
+
+int ctmr_known_query_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                            uint64_t n_members, uint32_t world, uint32_t rank, void* d_flags, uint64_t flags_cap,
+                            uint8_t* host_flags, size_t host_flags_cap, ctmr_known_probe_stats* st) {
+  if (!e || !meta || !st) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  int r;
+  if ((r = known_parse_meta(e, meta, meta_len, false, &km))) return r;
+  if (km.n_members != n_members) return fail(e, CTMR_E_INVAL, "known query: %llu member records given, the header says %llu",
+                                             (unsigned long long)n_members, (unsigned long long)km.n_members);
+  if ((r = known_query_room(e, km, rank, d_flags, flags_cap, host_flags, host_flags_cap, st))) return r;
+  return known_probe_core(e, km, (const uint8_t*)d_members, world, rank, false, (uint8_t*)d_flags, host_flags, st);
+}
+
+int ctmr_known_remove(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t world, uint32_t rank,
+                      ctmr_known_probe_stats* st) {
+  if (!e || !image || !st) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  int r;
+  if ((r = known_parse_meta(e, image, len, true, &km))) return r;
+  void* d = nullptr;
+  struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_d{d};
+  if ((r = known_stage_members(e, km, image, 0, "known remove", &d))) return r;
+  return known_probe_core(e, km, (const uint8_t*)d, world, rank, true, nullptr, nullptr, st);
+}
+
+int ctmr_known_remove_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                             uint64_t n_members, uint32_t world, uint32_t rank, ctmr_known_probe_stats* st) {
+  if (!e || !meta || !st) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  int r;
+  if ((r = known_parse_meta(e, meta, meta_len, false, &km))) return r;
+  if (km.n_members != n_members) return fail(e, CTMR_E_INVAL, "known remove: %llu member records given, the header says %llu",
+                                             (unsigned long long)n_members, (unsigned long long)km.n_members);
+  return known_probe_core(e, km, (const uint8_t*)d_members, world, rank, true, nullptr, nullptr, st);
 }

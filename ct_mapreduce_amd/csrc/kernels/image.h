@@ -109,15 +109,17 @@ struct KnownImportArgs {
   uint32_t* err;               // bit 0: a serial_len above 40, bit 1: padding octets that are not zero
 };
 
+// The sets records [wfirst, wlast] of the chunk lie in: what every lane of a wave searches between.
+__device__ __forceinline__ void known_set_span(const KnownImportArgs& a, uint64_t wfirst, uint64_t wlast, uint32_t& s_lo,
+                                               uint32_t& s_hi) {
+  s_lo = known_set_of(a.set_first, 0u, a.n_sets - 1u, a.base + wfirst);
+  s_hi = known_set_of(a.set_first, s_lo, a.n_sets - 1u, a.base + wlast);
+}
+
 // class of record i: 0 = not taken here, 1 = a KeyRec32 (serial of at most 20 octets), 2 = a KeyRec (21..40)
-// (call with i < a.n; bad: as err)
-__device__ __forceinline__ uint32_t known_record(const KnownImportArgs& a, uint64_t i, unsigned long long& meta,
-                                                 unsigned long long s[5], uint32_t& bad) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wfirst = i - lane;
-  const uint64_t wlast = (wfirst + 63u < a.n ? wfirst + 63u : a.n - 1u);
-  const uint32_t s_lo = known_set_of(a.set_first, 0u, a.n_sets - 1u, a.base + wfirst);
-  const uint32_t s_hi = known_set_of(a.set_first, s_lo, a.n_sets - 1u, a.base + wlast);
+// (call with i < a.n, its set among s_lo..s_hi; bad: as err)
+__device__ __forceinline__ uint32_t known_record_in(const KnownImportArgs& a, uint64_t i, uint32_t s_lo, uint32_t s_hi,
+                                                    unsigned long long& meta, unsigned long long s[5], uint32_t& bad) {
   bad = 0u;
   const uint4* p = (const uint4*)(a.members + i * KNOWN_REC_BYTES);
   const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
@@ -144,6 +146,17 @@ __device__ __forceinline__ uint32_t known_record(const KnownImportArgs& a, uint6
   meta = sm | ((unsigned long long)len << 56);
   if (a.world > 1u && key_owner_h(key_hash(meta, s), a.world) != a.rank) return 0u;
   return len <= 20u ? 1u : 2u;
+}
+
+// … of a kernel that gives lane l of a wave record (wave's first + l)
+__device__ __forceinline__ uint32_t known_record(const KnownImportArgs& a, uint64_t i, unsigned long long& meta,
+                                                 unsigned long long s[5], uint32_t& bad) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wfirst = i - lane;
+  const uint64_t wlast = (wfirst + 63u < a.n ? wfirst + 63u : a.n - 1u);
+  uint32_t s_lo, s_hi;
+  known_set_span(a, wfirst, wlast, s_lo, s_hi);
+  return known_record_in(a, i, s_lo, s_hi, meta, s, bad);
 }
 
 // Count pass: validates every record and counts the taken ones per 256-record block, by class.
@@ -215,6 +228,178 @@ __global__ void __launch_bounds__(256) k_known_bloom(const Rec* keys, uint64_t n
   unsigned long long bits;
   bloom_pos(key_hash(k.meta, k.s), wmask, word, bits);
   atomicOr(&bloom[word], bits);
+}
+
+// ---- bulk SetContains / SetRemove over an image's member records.  A taken record costs a chain of two
+// dependent random reads — its index word, then on a tag match 48 of the cell's 64 bytes — and nothing else, so the time
+// is memory latency ÷ reads in flight: every lane takes R CONSECUTIVE records and the probe advances all of them in
+// rounds — the index words of every record still probing are requested before the first is looked at, then the cells of
+// those whose tag matched.  A round is one step of index_upsert(insert = false): an empty word ends the probe (absent), a
+// tombstone or another key is stepped over.  Records that are not taken (another rank's, an unregistered issuer's, a bad
+// one) make no table access.
+//   res[k]  0 = absent (remove: nothing removed), 1 = present (remove: this record removed it), 2 = not taken
+//   dec[k]  remove: the canonical issuer whose counter goes down for record k, ~0u when none does (nothing removed, or
+//           a SHADOW cell: counted by another rank)
+// REMOVE: atomicCAS(word, the live word observed, IDX_TOMB) — of two presenters of one key exactly one sees its word.
+template <int R, bool REMOVE>
+__device__ __forceinline__ void known_probe(const KnownImportArgs& a, const Table& t, uint64_t i0, uint32_t nvalid,
+                                            uint32_t (&res)[R], uint32_t (&dec)[R], uint32_t& bad) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wfirst = i0 - (uint64_t)lane * R;
+  uint32_t s_lo = 0u, s_hi = 0u;
+  if (wfirst < a.n) known_set_span(a, wfirst, wfirst + 64u * R <= a.n ? wfirst + 64u * R - 1u : a.n - 1u, s_lo, s_hi);
+  unsigned long long meta[R], s[R][5];
+  uint32_t tag[R], j[R], act = 0u;
+  bad = 0u;
+#pragma unroll
+  for (int k = 0; k < R; k++) {
+    res[k] = 2u;
+    dec[k] = ~0u;
+    meta[k] = 0ull;
+    tag[k] = j[k] = 0u;
+    if ((uint32_t)k < nvalid) {
+      uint32_t b;
+      if (known_record_in(a, i0 + k, s_lo, s_hi, meta[k], s[k], b)) {
+        const unsigned long long h = key_hash(meta[k], s[k]);
+        tag[k] = key_tag(h);
+        j[k] = (uint32_t)(h & t.mask);  // (at most 2^31 slots)
+        res[k] = 0u;
+        act |= 1u << k;
+      }
+      bad |= b;
+    }
+  }
+  for (uint64_t round = 0; act && round <= t.mask; round++) {
+    unsigned long long w[R];
+#pragma unroll
+    for (int k = 0; k < R; k++)
+      if ((act >> k) & 1u) w[k] = REMOVE ? ld_agent(&t.index[j[k]]) : t.index[j[k]];
+    uint32_t cmp = 0u;
+#pragma unroll
+    for (int k = 0; k < R; k++)
+      if ((act >> k) & 1u) {
+        if (w[k] == 0ull) act &= ~(1u << k);
+        else if (w[k] != IDX_TOMB && (uint32_t)(w[k] >> 40) == tag[k]) cmp |= 1u << k;
+      }
+    uint4 c0[R], c1[R], c2[R];
+#pragma unroll
+    for (int k = 0; k < R; k++)
+      if ((cmp >> k) & 1u) {
+        const uint4* c = (const uint4*)(t.arena + (w[k] & REF_MASK));
+        c0[k] = c[0];
+        c1[k] = c[1];
+        c2[k] = c[2];
+      }
+#pragma unroll
+    for (int k = 0; k < R; k++)
+      if ((cmp >> k) & 1u) {
+        const unsigned long long cm = (unsigned long long)c0[k].x | ((unsigned long long)c0[k].y << 32);
+        const bool eq = ((cm & ~CELL_SHADOW) == meta[k]) &
+                        (((unsigned long long)c0[k].z | ((unsigned long long)c0[k].w << 32)) == s[k][0]) &
+                        (((unsigned long long)c1[k].x | ((unsigned long long)c1[k].y << 32)) == s[k][1]) &
+                        (((unsigned long long)c1[k].z | ((unsigned long long)c1[k].w << 32)) == s[k][2]) &
+                        (((unsigned long long)c2[k].x | ((unsigned long long)c2[k].y << 32)) == s[k][3]) &
+                        (((unsigned long long)c2[k].z | ((unsigned long long)c2[k].w << 32)) == s[k][4]);
+        if (eq) {
+          act &= ~(1u << k);
+          if constexpr (REMOVE) {
+            if (atomicCAS(&t.index[j[k]], w[k], IDX_TOMB) == w[k]) {
+              res[k] = 1u;
+              if ((cm & CELL_SHADOW) == 0ull) dec[k] = (uint32_t)(meta[k] >> 32) & 0xffffffu;
+            }
+          } else {
+            res[k] = 1u;
+          }
+        }
+      }
+#pragma unroll
+    for (int k = 0; k < R; k++)
+      if ((act >> k) & 1u) j[k] = (uint32_t)probe_next(j[k], round, t.mask);
+  }
+}
+
+// Query: flags[i] = res of record i.  A lane's R flags are adjacent: one 1-, 2-, 4- or 8-byte store per lane (bytes at
+// the ragged end of the chunk and under a flags pointer that is not R-aligned).  cnt[blk] = records taken,
+// cnt[nb + blk] = taken records found, per block of 256 R records; errors as k_known_count reports them.
+template <int R>
+__global__ void __launch_bounds__(256) k_known_query(KnownImportArgs a, Table t, uint8_t* flags) {
+  __shared__ uint32_t wc[2][4];
+  const uint64_t i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * R;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t nvalid = i0 >= a.n ? 0u : (a.n - i0 >= (uint64_t)R ? (uint32_t)R : (uint32_t)(a.n - i0));
+  uint32_t res[R], dec[R], bad;
+  known_probe<R, false>(a, t, i0, nvalid, res, dec, bad);
+  uint8_t* out = flags + i0;
+  if (nvalid == (uint32_t)R && ((uintptr_t)out & (uintptr_t)(R - 1)) == 0) {
+    uint32_t lo = 0u, hi = 0u;
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+      if (k < 4) lo |= res[k] << (8 * k);
+      else hi |= res[k] << (8 * (k - 4));
+    }
+    if constexpr (R == 1) out[0] = (uint8_t)lo;
+    else if constexpr (R == 2) *(uint16_t*)out = (uint16_t)lo;
+    else if constexpr (R == 4) *(uint32_t*)out = lo;
+    else *(uint2*)out = make_uint2(lo, hi);
+  } else {
+#pragma unroll
+    for (int k = 0; k < R; k++)
+      if ((uint32_t)k < nvalid) out[k] = (uint8_t)res[k];
+  }
+  uint32_t n_taken = 0u, n_hit = 0u;
+#pragma unroll
+  for (int k = 0; k < R; k++) {
+    n_taken += (uint32_t)__popcll(__ballot(res[k] != 2u));
+    n_hit += (uint32_t)__popcll(__ballot(res[k] == 1u));
+  }
+  const unsigned long long mb1 = __ballot((bad & 1u) != 0u), mb2 = __ballot((bad & 2u) != 0u);
+  if (lane == 0) {
+    wc[0][wv] = n_taken;
+    wc[1][wv] = n_hit;
+    if (mb1 | mb2) atomicOr(a.err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const uint32_t c = threadIdx.x;
+    a.cnt[(uint64_t)c * a.nb + blockIdx.x] = (unsigned long long)(wc[c][0] + wc[c][1] + wc[c][2] + wc[c][3]);
+  }
+}
+
+// Remove (behind k_known_count, which has validated every record of the image): cnt[blk] = members removed per block.
+// The per-issuer counters go down by ONE atomic per (wave, canonical issuer): the match loop of wave_agg_add over the
+// wave's 64 R (lane, record) pairs — the records of a wave lie in one or two sets, so it runs once or twice.
+template <int R>
+__global__ void __launch_bounds__(256) k_known_remove(KnownImportArgs a, Table t, unsigned long long* issuer_counts) {
+  __shared__ uint32_t wc[4];
+  const uint64_t i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * R;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t nvalid = i0 >= a.n ? 0u : (a.n - i0 >= (uint64_t)R ? (uint32_t)R : (uint32_t)(a.n - i0));
+  uint32_t res[R], dec[R], bad;
+  known_probe<R, true>(a, t, i0, nvalid, res, dec, bad);
+  uint32_t n_hit = 0u;
+  unsigned long long todo[R];
+#pragma unroll
+  for (int k = 0; k < R; k++) {
+    n_hit += (uint32_t)__popcll(__ballot(res[k] == 1u));
+    todo[k] = __ballot(dec[k] != ~0u);
+  }
+#pragma unroll
+  for (int k = 0; k < R; k++)
+    while (todo[k]) {
+      const int leader = __ffsll((long long)todo[k]) - 1;
+      const uint32_t c = __shfl(dec[k], leader);
+      uint32_t tot = 0u;
+#pragma unroll
+      for (int q = 0; q < R; q++) {
+        const unsigned long long same = __ballot(dec[q] == c) & todo[q];
+        tot += (uint32_t)__popcll(same);
+        todo[q] &= ~same;
+      }
+      if ((int)lane == leader) atomicAdd(&issuer_counts[c], (unsigned long long)-(long long)tot);
+    }
+  if (lane == 0) wc[wv] = n_hit;
+  __syncthreads();
+  if (threadIdx.x == 0) a.cnt[blockIdx.x] = (unsigned long long)(wc[0] + wc[1] + wc[2] + wc[3]);
 }
 
 }  // namespace ctmr

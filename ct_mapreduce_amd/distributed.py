@@ -116,6 +116,21 @@ class Group:
         from .known_image import merge_lists
         return merge_lists([e.known_lists(now) for e in self.engines])
 
+    def known_query(self, image):
+        """SetContains over the group for every member of `image` → (flags, host_flags): numpy uint8, 1 where ANY local
+        rank holds the member (every rank is asked about every record: a Bloom-mode rank keeps a key where it was first
+        seen, not on its owner).  In-process groups only."""
+        out = None
+        for e in self.engines:
+            fl, hf, _ = e.known_query(image)
+            got = ((fl == 1).astype(np.uint8), (hf == 1).astype(np.uint8))
+            out = got if out is None else (out[0] | got[0], out[1] | got[1])
+        return out
+
+    def known_remove(self, image) -> list:
+        """SetRemove on every local rank for every member of `image` → the per-rank stats.  In-process groups only."""
+        return [e.known_remove(image) for e in self.engines]
+
     def total_count(self) -> int:
         v = C.c_uint64(0)
         self._check(self._lib.ctmr_group_total_count(self._h, C.byref(v)))

@@ -642,6 +642,64 @@ class Engine:
                                                     C.byref(st)))
         return self._import_stats(st)
 
+    # ---- bulk SetContains / SetRemove over an image's member records (include/ctmr.h ctmr_known_query* /
+    # ctmr_known_remove*; CPU twins: known_image.query / known_image.subtract)
+    @staticmethod
+    def _probe_stats(st: N.KnownProbeStats) -> dict:
+        return {f: getattr(st, f) for f, _ in N.KnownProbeStats._fields_ if f != "reserved"}
+
+    @staticmethod
+    def _members_ptr(d_members):
+        if not hasattr(d_members, "data_ptr"):
+            raise TypeError("d_members: a torch tensor on this engine's device")
+        n = d_members.numel() // 48
+        return n, (C.c_void_p(d_members.data_ptr()) if n else None)
+
+    def known_query(self, image, world=1, rank=0):
+        """SetContains for every member of `image` → (flags: numpy uint8 per member record, 1 = held, 0 = not, 2 = another
+        rank's; host_flags: the same per host-section member; stats dict).  Read-only."""
+        from .known_image import _HEADER
+        image = bytes(image)
+        n, n_host = (_HEADER.unpack_from(image, 0)[6], _HEADER.unpack_from(image, 0)[8]) if len(image) >= 64 else (0, 0)
+        n, n_host = min(n, len(image) // 48), min(n_host, len(image) // 8)      # (a damaged header: the library refuses it)
+        flags, host_flags = np.empty(max(n, 1), np.uint8), np.empty(max(n_host, 1), np.uint8)
+        st = N.KnownProbeStats()
+        self._ck(self._lib.ctmr_known_query(self._h, image, len(image), world, rank, flags.ctypes.data, n,
+                                            host_flags.ctypes.data, n_host, C.byref(st)))
+        return flags[:n], host_flags[:n_host], self._probe_stats(st)
+
+    def known_query_device(self, meta, d_members, world=1, rank=0):
+        """known_query with the member records in device memory (a torch uint8 tensor) → (flags: torch uint8 tensor on
+        this engine's device, host_flags: numpy uint8, stats dict)."""
+        import torch
+        from .known_image import _HEADER
+        meta = bytes(meta)
+        n, ptr = self._members_ptr(d_members)
+        n_host = min(_HEADER.unpack_from(meta, 0)[8], len(meta) // 8) if len(meta) >= 64 else 0
+        flags = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda:%d" % self.device)
+        host_flags = np.empty(max(n_host, 1), np.uint8)
+        st = N.KnownProbeStats()
+        self._ck(self._lib.ctmr_known_query_device(self._h, meta, len(meta), ptr, n, world, rank,
+                                                   C.c_void_p(flags.data_ptr()), n, host_flags.ctypes.data, n_host,
+                                                   C.byref(st)))
+        return flags[:n], host_flags[:n_host], self._probe_stats(st)
+
+    def known_remove(self, image, world=1, rank=0) -> dict:
+        """SetRemove for every member of `image` this rank takes; all or nothing on a malformed image.  → stats dict
+        (hits = members removed)."""
+        image = bytes(image)
+        st = N.KnownProbeStats()
+        self._ck(self._lib.ctmr_known_remove(self._h, image, len(image), world, rank, C.byref(st)))
+        return self._probe_stats(st)
+
+    def known_remove_device(self, meta, d_members, world=1, rank=0) -> dict:
+        """known_remove with the member records in device memory (a torch uint8 tensor)."""
+        meta = bytes(meta)
+        n, ptr = self._members_ptr(d_members)
+        st = N.KnownProbeStats()
+        self._ck(self._lib.ctmr_known_remove_device(self._h, meta, len(meta), ptr, n, world, rank, C.byref(st)))
+        return self._probe_stats(st)
+
     # ---- per-issuer known-serial lists (include/ctmr.h ctmr_known_lists*, DESIGN.md §13; CPU twin: known_image.known_lists)
     def _known_lists_call(self, fn, alloc, now):
         """One call sized by the bound (81 B per live member, the host-store text as large as last time), which writes

@@ -3,7 +3,8 @@ Redis protocol stream of remote_cache.redis_dump.
 
 An image is what `Engine.known_export` writes and `Engine.known_import` reads: every serials::<expDate>::<issuerID> set
 of the engine — what a restarted reference deployment still finds in its Redis.  `parse` checks exactly what the library
-checks before it applies an image; `build` is the canonical writer; `to_resp` / `from_resp` turn an image into the
+checks before it applies an image; `build` is the canonical writer; `query` / `subtract` are the twins of
+`Engine.known_query` / `Engine.known_remove` over a dict of sets; `to_resp` / `from_resp` turn an image into the
 SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start from a reference deployment's Redis
 contents).  Pure Python + numpy.
 """
@@ -208,6 +209,56 @@ def build(sets) -> bytes:
         rec["len"][i] = len(m)
         rec["serial"][i, :len(m)] = np.frombuffer(m, np.uint8)
     return meta + rec.tobytes()
+
+
+# ---- bulk SetContains / SetRemove with an image as the batch (include/ctmr.h ctmr_known_query / ctmr_known_remove;
+# DESIGN.md §14), without a GPU.  world = 1: which records another rank owns depends on the engine's issuer numbering.
+
+def records(image):
+    """→ ([(key, member)] per member record in image order, [(key, member)] per host-section member in section order) of
+    a valid image.  `parse` merges the two sections and drops repeats; this keeps every record where it is."""
+    parse(image)
+    b = bytes(image)
+    _, _, _, n_iss, _, n_sets, n_mem, host_bytes, n_host, _ = _HEADER.unpack_from(b, 0)
+    so = HEADER_BYTES + 32 * n_iss
+    rec = np.frombuffer(b, MEMBER_DTYPE, count=n_mem, offset=len(b) - n_mem * MEMBER_BYTES)
+    dev = []
+    for s in range(n_sets):
+        eh, ordinal, first, count = _SET.unpack_from(b, so + SET_BYTES * s)
+        key = set_key(eh, b[HEADER_BYTES + 32 * ordinal:HEADER_BYTES + 32 * (ordinal + 1)])
+        r = rec[first:first + count]
+        dev += [(key, bytes(m[:int(l)])) for l, m in zip(r["len"], r["serial"])]
+    h, q, host = so + SET_BYTES * n_sets, 0, []
+    while q < host_bytes:
+        (kl,) = struct.unpack_from("<I", b, h + q)
+        key = b[h + q + 4:h + q + 4 + kl]
+        q += 4 + kl
+        (ml,) = struct.unpack_from("<I", b, h + q)
+        host.append((key, b[h + q + 4:h + q + 4 + ml]))
+        q += 4 + ml
+    return dev, host
+
+
+def query(image, sets):
+    """Engine.known_query(image) of an engine holding exactly `sets` ({key: members}) → (flags, host_flags): numpy uint8,
+    1 where sets[key] holds the member, else 0."""
+    dev, host = records(image)
+    held = {bytes(k): set(bytes(m) for m in v) for k, v in sets.items()}
+    return tuple(np.fromiter((m in held.get(k, ()) for k, m in part), np.uint8, len(part)) for part in (dev, host))
+
+
+def subtract(sets, image) -> dict:
+    """The sets an engine holding `sets` is left with by Engine.known_remove(image): members sorted, empty sets gone."""
+    dev, host = records(image)
+    gone = {}
+    for k, m in dev + host:
+        gone.setdefault(k, set()).add(m)
+    out = {}
+    for k, v in sets.items():
+        left = sorted(set(bytes(m) for m in v) - gone.get(bytes(k), set()))
+        if left:
+            out[bytes(k)] = left
+    return out
 
 
 class _SetsCache:

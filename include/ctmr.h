@@ -306,6 +306,50 @@ int ctmr_known_import(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t
 int ctmr_known_import_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
                              uint64_t n_members, uint32_t world, uint32_t rank, ctmr_known_import_stats* st);
 
+/* ---- bulk SetContains / SetRemove (storage/types.go:83-102) with an image as the batch: one call asks about, or
+ *      removes, every member record of an image v1 (above; nothing about the format changes).  DESIGN.md §14.
+ *
+ * world / rank as for import: the rank is asked about exactly the records ctmr_known_import with the same world / rank
+ * would take (the keys it owns; host-section members: rank 0 alone); world > 1 with a set whose issuer is not registered
+ * here is CTMR_E_INVAL.  Records of sets whose issuer is not registered (world = 1) and the host section are answered
+ * from / erased in the host-side store, where ctmr_set_insert would have put them.
+ *
+ * Query: flags[i], one byte per member record in image order: 1 = ctmr_set_contains(key of record i's set, member i)
+ *   would answer true at the time of the call, 0 = it would answer false, 2 = this rank was not asked.  A Bloom-mode
+ *   rank's SHADOW keys count as present, as they do for ctmr_set_contains.  host_flags: one byte per host-section member
+ *   in section order (rank 0; every other rank: 2).  Duplicate records get the same answer each.  A flags or host_flags
+ *   buffer that is too small: CTMR_E_RANGE, *st filled as far as known (members, host_members), nothing written.
+ *   Read-only: table, arena, pair statistics, counters, Bloom filter, host-side store, expiry records and
+ *   ctmr_table_info are as before.  The records are validated in the pass that probes: on CTMR_E_INVAL the flags are
+ *   unspecified.
+ * Remove: the effect of ctmr_set_remove(key, member) for every record the rank takes, in any order: the member's index
+ *   word becomes a tombstone, its canonical issuer's counter goes down by one (not for a SHADOW key: another rank counts
+ *   it), the pair statistics are rebuilt before their next use, a host-side member is erased (its key with its last
+ *   member); Bloom bits stay, as after a point remove.  A member the image names twice is removed and counted once:
+ *   hits = members removed, taken − hits = records that found nothing (absent, or a repeat).  All or nothing on a bad
+ *   image: everything ctmr_known_import rejects (magic, version, sizes, set order / gaps / overlaps, ordinals, a
+ *   serial_len above 40 or non-zero padding — checked on the device before the first word is touched — world == 0,
+ *   rank >= world, an open owner-computes round) is CTMR_E_INVAL with nothing removed.
+ * Both return after the engine's stream has drained.  Images above 2^27 records are worked through in passes of 2^27. */
+typedef struct {
+  uint64_t members;       /* member records of the image */
+  uint64_t taken;         /* … this rank was asked about (world = 1: all) */
+  uint64_t hits;          /* query: taken records whose member is held; remove: members removed */
+  uint64_t host_members;  /* host-section members taken (rank 0 alone) */
+  uint64_t host_hits;     /* … of them held / removed */
+  uint64_t reserved;
+} ctmr_known_probe_stats;
+int ctmr_known_query(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t world, uint32_t rank, uint8_t* flags,
+                     size_t flags_cap, uint8_t* host_flags, size_t host_flags_cap, ctmr_known_probe_stats* st);
+/* … the member records (meta's n_members × 48 B) and the flags (flags_cap bytes) in device memory */
+int ctmr_known_query_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                            uint64_t n_members, uint32_t world, uint32_t rank, void* d_flags, uint64_t flags_cap,
+                            uint8_t* host_flags, size_t host_flags_cap, ctmr_known_probe_stats* st);
+int ctmr_known_remove(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t world, uint32_t rank,
+                      ctmr_known_probe_stats* st);
+int ctmr_known_remove_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                             uint64_t n_members, uint32_t world, uint32_t rank, ctmr_known_probe_stats* st);
+
 /* ---- per-issuer known-serial lists: what this map/reduce exists to produce.  For each Issuer.ID, the serials of its
  *      certificates that have not expired, as FilesystemDatabase hands them to StorageBackend.StoreKnownCertificateList
  *      (storage/types.go) — the composition of GetIssuerAndDatesFromCache (storage/filesystemdatabase.go), IsExpiredAt
