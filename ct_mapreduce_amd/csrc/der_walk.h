@@ -1022,10 +1022,11 @@ template <class R>
 struct has_coop_refill<R, std::void_t<decltype(std::declval<R&>().coop_refill(0u, false))>> : std::true_type {};
 template <class R>
 CTMR_HD void ext_san_coop(R& r, uint32_t L, uint32_t cv, uint32_t ev, bool& ok, uint32_t& nf) {
-  if (!R::whole_wave()) {  // the batch's last wave: lane by lane
-    if (cv < ev) ext_san_check(r, L, cv, ev, ok, nf);
-    return;
-  }
+  // The batch's last wave walks lane by lane: `alone` from the start, `act` false, so the loop below ends at its first
+  // any_lane().  (No early return: ext_san_check is inlined, and ONE call site behind the loop serves both the partial wave and
+  // the lanes the loop lets go — a second copy of it grows the reference-profile map kernels, which sit at their register step.)
+  const bool whole = R::whole_wave();
+  bool alone = !whole & (cv < ev);
   // Round 6.  (a) A lane goes on in the window it has — the extension window usually still holds the head of the
   // subjectAltName — and takes part in a refill only when the next header lies outside (round 5 refilled every lane at the
   // start of every round).  (b) A refill brings the two 128-byte LINES from the one the next header lies in
@@ -1036,13 +1037,22 @@ CTMR_HD void ext_san_coop(R& r, uint32_t L, uint32_t cv, uint32_t ev, bool& ok, 
   // element — and only a window in which a URI, an iPAddress, a high tag number or a long-form length turned up (the
   // masks say so; the hops behind such an element are garbage, and harmless: p only grows and stops at the window's or
   // the value's end) is walked again, element by element, by round 5's loop.
-  bool act = ok & (cv < ev), first = true, again = false;
+  bool act = whole & ok & (cv < ev), first = true, again = false;
   uint32_t p = cv;
   for (;;) {
-    const bool want = act & (p < ev);
+    bool want = act & (p < ev);
     if (!R::any_lane(want)) break;  // (wave-uniform)
     const bool need = want & (again | !r.holds(p, 2u));
     if (R::any_lane(need)) r.coop_refill_lines_to(p, need, ev);  // (what is left of the value, not a whole window)
+    // A cooperative refill may do NOTHING for a lane (kernels/readers.h: a certificate out of reach of the wave's buffer
+    // descriptor — an entry view in no order).  A refilled window begins at most a line in front of p and holds the sixteen
+    // octets every step below asks for; a lane that asked and does not hold them would ask again every round, for ever: it
+    // leaves the loop here and walks its value alone, from the start, behind the loop (ok is still true for it, and the
+    // finding bits in nf are set, never cleared: walking the elements it has seen once more changes nothing).
+    if (need & !r.holds(p, 16u)) {
+      alone = true;
+      act = want = false;
+    }
     again = false;
     if (want) {
       if (first) {  // one element filling the value: a universal constructed SEQUENCE
@@ -1095,6 +1105,7 @@ CTMR_HD void ext_san_coop(R& r, uint32_t L, uint32_t cv, uint32_t ev, bool& ok, 
       act = ok;
     }
   }
+  if (alone) ext_san_check(r, L, cv, ev, ok, nf);
 }
 
 // cRLDistributionPoints: [cv, ev) = the extension's value, []distributionPoint by encoding/asn1's struct rules — fields in

@@ -146,7 +146,10 @@ struct WaveBuf {
 // lo0: a payload offset at or below every certificate of the wave IN THE FIRST ACTIVE LANE (a packed batch, a decoded
 // get-entries blob: the first lane's own certificate — offsets ascend); other lanes' values are not looked at.  A lane
 // whose certificate lies below it or ≥ REL_SPAN beyond (a caller-made entry view in no order) gets REL_NONE from
-// wave_rel() and is handed to the exact reader by its kernel.
+// wave_rel(): "out of reach".  Such a lane is exact and slow — the cooperative fills and refills leave its window alone
+// (coop_refill*, touch_coop: window and grel unchanged) or take it away (coop_fill: zeros, grel = "no window"); it reads
+// through its own refill() and global memory (WinReaderC) or is repeated with the exact reader (WinReaderS); the walk's
+// cooperative loops let it go (der_walk.h ext_san_coop).  tests/test_gpu_view_order.py, tests/test_view_order_cpu.py.
 __device__ __forceinline__ WaveBuf wave_buf(const uint8_t* payload, uint64_t limit, uint64_t lo0) {
   const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)lo0), h = __builtin_amdgcn_readfirstlane((uint32_t)(lo0 >> 32));
   const uint64_t b128 = (((uint64_t)h << 32) | l) & ~127ull;
@@ -385,7 +388,11 @@ struct WinReaderC : WinReader<WCH> {
       return;
     }
     const uint32_t w = this->wrel(pos, 4u);  // (a chunk load needs dword alignment only: the window begins AT pos, give or take 3)
-    if (w != REL_NONE) this->grel = (int32_t)(w - this->lrel);
+    // A lane out of the descriptor's reach (every lane of a whole wave is live): coop_fill stores zeros into its window, so
+    // the window an earlier refill() placed is gone — grel says "no window" (what the kernel starts such a lane with), every
+    // read of this reader takes the global-memory path, and the next touch() refills on the lane's own.  (WinReaderS: such
+    // a lane's miss is ~0 from the start, its reads clamp into the zeros and the exact reader decides — nothing to change there.)
+    this->grel = w != REL_NONE ? (int32_t)(w - this->lrel) : (int32_t)0x80000000;
     coop_fill<WCH, true>(this->wb, w, threadIdx.x & 63u);
   }
   // der_walk.h touch_all (round 6) — a hint at a point of the walk EVERY lane passes (the walk never returns early): the lanes

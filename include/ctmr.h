@@ -605,6 +605,12 @@ int ctmr_pem_new(ctmr_engine* e, uint8_t* out, size_t cap, uint64_t* pem_offsets
  *           An entry ct.LogEntryFromLeaf would reject gets entry_type CTMR_ENTRY_INVALID.
  *   map_view: the batched map + reduce of ctmr_map_batch_device over such a view (certificates addressed by
  *           [cert_start, cert_end) instead of n+1 packed offsets).
+ *           The ranges of a view may lie in the blob in ANY order — descending, permuted, with gaps, several entries
+ *           on one range, empty ones — and the result is exact and that of the packed batch in ENTRY order (the first entry
+ *           carrying a key is the unknown one).  The same holds for every call that takes offsets + ends.  Ascending
+ *           cert_start is the FAST path: a wave of 64 entries reads through one descriptor based on its first entry's
+ *           certificate, and an entry whose certificate lies below that one (or 0x7e000000 bytes or more beyond it) is read
+ *           lane by lane and, by the default kernel, walked twice.
  *   map_entries: decode + map_view in one call; host variant stages the blob through the engine's buffers. ---- */
 typedef struct {
   uint64_t* cert_start;   /* n: first byte of the certificate inside the blob */

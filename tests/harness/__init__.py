@@ -196,6 +196,27 @@ def walk_window(der: bytes, phase: int = 0, wbytes: int = 224, strings: bool = F
     return bool(ok), out[0], out[1], out[2], out[3], out[4], out[5]
 
 
+class DidNotTerminate(Exception):
+    """The simulated out-of-reach lane passed its round cap: on the device that wave never ends."""
+
+
+def walk_window_noreach(der: bytes, phase: int = 0, wbytes: int = 224, flavour: str = "C", strings: bool = True, ext: bool = True,
+                        cap: int = 10_000, fill: int = 0xA5):
+    """The walk as a lane OUT OF REACH of its wave's buffer descriptor runs it (kernels/readers.h lrel == REL_NONE: an entry
+    view in no order): cooperative refills do nothing, the lane's own refills work; flavour "C" = WinReaderC (reads outside
+    the window are global reads), "S" = WinReaderS (clamped and counted; the exact reader then decides).  Returns
+    (HarnessOut, stats) with stats = (per-lane refills, misses, cooperative refills asked for in vain, defer_exact calls,
+    exact rerun, window reads outside the window); raises DidNotTerminate past `cap` calls of holds / coop_refill_lines_to."""
+    product_walk(b"\x30\x00")
+    fn = _walk.harness_walk_window_noreach
+    fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint8,
+                   C.POINTER(HarnessOut), C.POINTER(C.c_uint32)]
+    o, st = HarnessOut(), (C.c_uint32 * 6)()
+    if not fn(der, len(der), phase, wbytes, {"C": 0, "S": 1}[flavour], int(strings), int(ext), cap, fill, C.byref(o), st):
+        raise DidNotTerminate(f"phase {phase}, window {wbytes}, flavour {flavour}: more than {cap} rounds")
+    return o, tuple(st)
+
+
 def ossl_extract(der: bytes):
     global _ossl
     if _ossl is None:

@@ -288,6 +288,138 @@ extern "C" int harness_walk_window_skip(const uint8_t* der, uint32_t len, uint32
   return ok;
 }
 
+// An OUT-OF-REACH lane (kernels/readers.h: lrel == REL_NONE — the certificate lies below the base of its wave's buffer
+// descriptor, or REL_SPAN or more beyond it: an entry view in no order), for a wave of one lane.  What the device readers do
+// for such a lane: the cooperative refills do NOTHING (window and grel stay as they are), touch() — WinReader::refill, the
+// lane's own loads — works, touch_tail() on a whole wave leaves the lane without a window.  Two flavours, as on the device:
+//   C  WinReaderC (k_map_winc): a read outside the window is a correct global read; no defer_exact, no key tail
+//   S  WinReaderS (k_map_fused): a read outside the window is clamped into it and counted; the caller then repeats the
+//      certificate with the exact reader
+// What the model does NOT see: ld4 returns the certificate's true bytes in both flavours' "outside" paths and touch_tail
+// simply drops the window — the behaviour kernels/readers.h has SINCE its fix (before it, touch_tail zero-filled the window
+// and kept its position, so reads were served from zeros).  That defect lives in readers.h alone and is the GPU tests'
+// business (tests/test_gpu_view_order.py, map_variant 13); this model is about TERMINATION of the walk in der_walk.h.
+// Flavour S starts without a window, as on the device (miss = ~0 from the start): its first read misses, so the exact rerun
+// always decides its verdict — S checks that the clamped walk ENDS, whatever garbage it reads; the fields are checked by C.
+// A walk that waits for a cooperative refill to move the window never ends on the device; here holds() and
+// coop_refill_lines_to() count their calls and throw past `cap`, so that no input can spin the calling process.
+struct DidNotTerminate {};
+struct NoReachSimC {
+  const uint8_t* p;
+  uint32_t base_phase, wbytes, size;
+  uint64_t cap;
+  mutable bool have = false;  // a window at all (the kernel starts such a lane with none)
+  mutable int64_t grel = 0;
+  mutable uint64_t rounds = 0;
+  mutable uint32_t refills = 0, misses = 0, coop_asked = 0, stray = 0;
+  uint32_t at(uint32_t pos) const {
+    uint32_t v = 0;
+    if ((uint64_t)pos + 4u <= size) memcpy(&v, p + pos, 4);
+    return v;
+  }
+  bool inside(uint32_t pos, uint32_t need) const {
+    const int64_t rel = (int64_t)pos - grel;
+    return have && rel >= 0 && rel <= (int64_t)wbytes - (int64_t)need;
+  }
+  void tick() const {
+    if (++rounds > cap) throw DidNotTerminate{};
+  }
+  uint32_t ld4(uint32_t pos) const { return at(pos); }  // window or global memory: the same bytes
+  uint32_t ldg(uint32_t pos) const { return at(pos); }
+  ctmr::RawCert raw() const { return ctmr::RawCert{(const uint32_t*)p, 0}; }
+  void touch(uint32_t pos, uint32_t need) const {
+    if (need > wbytes - 16u) need = wbytes - 16u;
+    if (!inside(pos, need)) {
+      refills++;
+      have = true;
+      grel = (int64_t)pos - (int64_t)((base_phase + pos) & 15u);
+    }
+  }
+  void touch_tail(uint32_t, uint32_t) const { have = false; }
+  static bool whole_wave() { return true; }
+  static bool any_lane(bool x) { return x; }
+  void coop_refill(uint32_t, bool want) const { coop_asked += want; }
+  void coop_refill_lines(uint32_t, bool want) const { coop_asked += want; }
+  void coop_refill_lines_to(uint32_t, bool want, uint32_t) const {
+    tick();
+    coop_asked += want;
+  }
+  bool holds(uint32_t pos, uint32_t need) const {
+    tick();
+    return inside(pos, need);
+  }
+  // (the device reads its LDS window whatever it holds: outside the window that is anything but the certificate)
+  uint32_t ld2(uint32_t pos) const {
+    if (inside(pos, 2u)) return at(pos) & 0xffffu;
+    stray++;
+    return 0xffffu;
+  }
+  uint32_t wend() const { return have ? (uint32_t)(grel + wbytes) : 0x80000000u + wbytes; }
+};
+struct NoReachSimS : NoReachSimC {
+  mutable uint32_t deferred = 0;
+  uint32_t clamped(uint32_t pos, uint32_t need) const {
+    if (inside(pos, need)) return at(pos);
+    misses++;
+    return have ? at((uint32_t)(grel + wbytes - need)) : 0u;  // the window's last octets, or the zeros of no window
+  }
+  uint32_t ld4(uint32_t pos) const { return clamped(pos, 4u); }
+  uint32_t ld2c(uint32_t pos) const { return clamped(pos, 2u) & 0xffffu; }
+  struct KeyTail { bool valid; uint32_t at; uint32_t w[4]; };
+  KeyTail key_tail(uint32_t pos) const {  // the lane's own loads: they reach anywhere
+    KeyTail t{pos >= 12u && (uint64_t)pos + 4u <= size, pos - 12u, {0, 0, 0, 0}};
+    if (t.valid) memcpy(t.w, p + pos - 12u, 16);
+    return t;
+  }
+  void defer_exact() const { deferred++; }
+};
+static void put_walk(HarnessOut* out, bool ok, const ctmr::Walk& w) {
+  memset(out, 0, sizeof *out);
+  out->ok = ok;
+  if (!ok) return;
+  out->serial_off = w.serial_off; out->serial_len = w.serial_len;
+  out->not_before = w.not_before; out->not_after = w.not_after;
+  out->cn_off = w.cn_off; out->cn_len = w.cn_len;
+  out->bc_valid = w.bc_valid; out->is_ca = w.is_ca;
+  out->spki_off = w.spki_off; out->spki_len = w.spki_len;
+  memcpy(out->serial_w, w.serial_w, 20);
+  out->cn_match = w.cn_match;
+  out->nonfatal = (int32_t)w.nonfatal;
+}
+// returns 1 = the walk ended (out = its verdict and fields, as harness_walk_f gives them), 0 = DID NOT TERMINATE within
+// `cap` rounds; flavour 0 = C, 1 = S (a miss or a deferral: the verdict is the exact reader's, as in k_map_fused);
+// stats = {per-lane refills, misses, cooperative refills asked for in vain, defer_exact calls, exact rerun, window reads
+// outside the window}; fill = the octets behind the certificate
+extern "C" int harness_walk_window_noreach(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, int flavour,
+                                           int strings, int ext, uint64_t cap, uint8_t fill, HarnessOut* out, uint32_t* stats) {
+  std::vector<uint8_t> buf((size_t)len + 64, fill);
+  memcpy(buf.data(), der, len);
+  ctmr::Walk w;
+  memset(out, 0, sizeof *out);
+  for (int k = 0; k < 6; k++) stats[k] = 0;
+  try {
+    if (flavour == 0) {
+      NoReachSimC r{buf.data(), phase & 127u, wbytes, (uint32_t)buf.size(), cap};
+      const bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
+      stats[0] = r.refills; stats[2] = r.coop_asked; stats[5] = r.stray;
+      put_walk(out, ok, w);
+    } else {
+      NoReachSimS r{{buf.data(), phase & 127u, wbytes, (uint32_t)buf.size(), cap}};
+      bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
+      stats[0] = r.refills; stats[1] = r.misses; stats[2] = r.coop_asked; stats[3] = r.deferred; stats[5] = r.stray;
+      if (r.misses || r.deferred) {
+        PaddedReader g{buf.data()};
+        ok = ctmr::walk_cert(g, len, w, nullptr, true, strings != 0, ext != 0);
+        stats[4] = 1;
+      }
+      put_walk(out, ok, w);
+    }
+  } catch (const DidNotTerminate&) {
+    return 0;
+  }
+  return 1;
+}
+
 // k_ec_resolve's loader + equation on the host: the point whose X starts at BIT `xbit` of buf (RightAlign as a bit offset)
 extern "C" int harness_ec_point_bits(const uint8_t* buf, uint32_t len, uint64_t xbit, int curve) {
   std::vector<uint32_t> w((len + 3) / 4 + 40, 0xa5a5a5a5u);
