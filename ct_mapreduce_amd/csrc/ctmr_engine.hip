@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -318,6 +319,33 @@ int ensure(ctmr_engine* e, int which, size_t bytes) {
   return CTMR_OK;
 }
 
+// An owning device allocation, freed on destruction.  alloc() frees what it held and reports a failure as the HIP error,
+// which it also clears: a caller that falls back to a smaller size does not meet it again in hipGetLastError.
+struct DevMem {
+  void* p = nullptr;
+  DevMem() = default;
+  DevMem(const DevMem&) = delete;
+  DevMem& operator=(const DevMem&) = delete;
+  ~DevMem() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    const hipError_t r = hipMalloc(&p, bytes);
+    if (r != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+    }
+    return r;
+  }
+  uint8_t* u8() const { return (uint8_t*)p; }
+};
+
+// a positive integer from an environment variable (the test-only overrides); 0: unset, empty or zero
+uint64_t env_u64(const char* name) {
+  const char* v = getenv(name);
+  return v ? strtoull(v, nullptr, 10) : 0;
+}
+
 uint64_t pow2_at_least(uint64_t v) {
   uint64_t p = 1;
   while (p < v) p <<= 1;
@@ -527,30 +555,41 @@ int ensure_pairs(ctmr_engine* e) {
   return CTMR_OK;
 }
 
-// device pairs → list of (key, count)
-int dump_pairs(ctmr_engine* e, std::vector<std::pair<unsigned long long, unsigned long long>>* out) {
-  { int r0 = ensure_pairs(e); if (r0) return r0; }
-  HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
-  size_t cap = 1 << 16;
-  for (;;) {
-    int r = ensure(e, SC_MISC, cap * 16);
-    if (r) return r;
+// The non-empty (expDate, issuer) pairs of registered issuers, with the pair-table slot each lives in.
+struct PairRec { int32_t exp_hour; uint32_t canon; uint64_t count, slot; };
+int list_pairs(ctmr_engine* e, std::vector<PairRec>* out) {
+  int r;
+  if ((r = ensure_pairs(e))) return r;
+  for (size_t cap = 1 << 16;;) {
+    if ((r = ensure(e, SC_MISC, cap * 24))) return r;
     HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
-    hipLaunchKernelGGL(k_pairs, dim3((unsigned)((e->npairs + 255) / 256)), dim3(256), 0, e->stream,
-                       e->pairs, e->npairs, (unsigned long long*)e->d_scratch[SC_MISC],
-                       (uint64_t)cap, e->d_count);
+    hipLaunchKernelGGL(k_pairs_slots, dim3((unsigned)((e->npairs + 255) / 256)), dim3(256), 0, e->stream, e->pairs, e->npairs,
+                       (unsigned long long*)e->d_scratch[SC_MISC], (uint64_t)cap, e->d_count);
     unsigned long long cnt;
     HIPCHK(e, hipMemcpyAsync(&cnt, e->d_count, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (cnt <= cap) {
-      std::vector<unsigned long long> buf(cnt * 2);
-      if (cnt) HIPCHK(e, hipMemcpy(buf.data(), e->d_scratch[SC_MISC], cnt * 16, hipMemcpyDeviceToHost));
-      out->clear();
-      for (size_t i = 0; i < cnt; i++) out->push_back({buf[2 * i], buf[2 * i + 1]});
-      return CTMR_OK;
+    if (cnt > cap) {
+      cap = cnt + 1024;
+      continue;
     }
-    cap = cnt + 1024;
+    std::vector<unsigned long long> pr(cnt * 3);
+    if (cnt) HIPCHK(e, hipMemcpy(pr.data(), e->d_scratch[SC_MISC], cnt * 24, hipMemcpyDeviceToHost));
+    out->clear();
+    for (size_t i = 0; i < pr.size(); i += 3) {
+      const uint32_t canon = (uint32_t)(pr[i] >> 32) - 1;
+      if (canon < e->issuers.size()) out->push_back({(int32_t)(uint32_t)pr[i], canon, pr[i + 1], pr[i + 2]});
+    }
+    return CTMR_OK;
   }
+}
+
+// The canonical issuers in Issuer.ID order, and each one's rank in that order (indexed by canonical index).
+void issuers_by_id(const ctmr_engine* e, std::vector<uint32_t>* by_id, std::vector<uint32_t>* rank) {
+  by_id->clear();
+  for (uint32_t c = 0; c < e->issuers.size(); c++) if (e->issuers[c].canon == c) by_id->push_back(c);
+  std::sort(by_id->begin(), by_id->end(), [e](uint32_t a, uint32_t b) { return e->issuers[a].id < e->issuers[b].id; });
+  rank->assign(e->issuers.size(), 0);
+  for (uint32_t k = 0; k < by_id->size(); k++) (*rank)[(*by_id)[k]] = k;
 }
 
 int pair_count(ctmr_engine* e, int32_t exp_hour, uint32_t canon, uint64_t* n) {

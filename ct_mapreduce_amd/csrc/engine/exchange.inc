@@ -226,10 +226,10 @@ int ctmr_xchg_keys_device(ctmr_engine* e, void* d_keys32_out, void* d_keys64_out
 extern "C++" {
 namespace {
 template <class Rec>
-static void xchg_owner_pass1(ctmr_engine* e, const Rec* keys, uint64_t n, uint64_t recv_ref0, uint32_t* d_slot) {
+static void xchg_owner_pass1(ctmr_engine* e, const Rec* keys, uint64_t n, uint64_t round_ref0, uint64_t recv_ref0, uint32_t* d_slot) {
   if (!n) return;
   hipLaunchKernelGGL((k_keys_insert<Rec>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, keys, n, e->tbl(),
-                     (unsigned long long)e->rd.ref0, (unsigned long long)recv_ref0, d_slot);
+                     (unsigned long long)round_ref0, (unsigned long long)recv_ref0, d_slot);
 }
 template <class Rec>
 static void xchg_owner_pass2(ctmr_engine* e, const Rec* keys, uint64_t n, const InsertArgs& loc, uint64_t recv_ref0,
@@ -240,11 +240,26 @@ static void xchg_owner_pass2(ctmr_engine* e, const Rec* keys, uint64_t n, const 
 }
 template <class Rec>
 static void xchg_owner_resolve(ctmr_engine* e, const Rec* keys, uint64_t n, uint64_t recv_ref0, const uint32_t* d_slot,
-                               uint8_t* d_flags) {
+                               uint8_t* d_flags, DevStats* d_st) {
   if (!n) return;
   const uint64_t nb = (n + 1023) / 1024;
   hipLaunchKernelGGL((k_keys_resolve<Rec>), dim3((unsigned)(nb < 512 ? nb : 512)), dim3(1024), 0, e->stream, keys, n, nb,
-                     e->tbl(), (unsigned long long)recv_ref0, d_slot, d_flags, e->issuer_counts, e->d_stats + 1);
+                     e->tbl(), (unsigned long long)recv_ref0, d_slot, d_flags, e->issuer_counts, d_st);
+}
+
+// The owner's insert of n32 32-byte and n64 64-byte key records whose cells start at recv_ref0 (the 64-byte records'
+// behind the 32-byte ones): pass 1, pass 2 and the resolve, each over both arrays.  round_ref0: the first cell of the
+// round a word of which pass 2 settles by order (an owner-computes round: the shard's entry 0; outside a round: recv_ref0).
+// d_slot: n32 + n64 words; a "was unknown" byte per record goes to d_flags32 / d_flags64, the counts to d_st.
+static void xchg_owner_insert(ctmr_engine* e, const KeyRec32* k32, uint64_t n32, const KeyRec* k64, uint64_t n64,
+                              const InsertArgs& loc, uint64_t round_ref0, uint64_t recv_ref0, ctmr_record* rec_local,
+                              uint32_t* d_slot, uint8_t* d_flags32, uint8_t* d_flags64, DevStats* d_st) {
+  xchg_owner_pass1(e, k32, n32, round_ref0, recv_ref0, d_slot);
+  xchg_owner_pass1(e, k64, n64, round_ref0, recv_ref0 + n32, d_slot + n32);
+  xchg_owner_pass2(e, k32, n32, loc, recv_ref0, rec_local, d_slot);
+  xchg_owner_pass2(e, k64, n64, loc, recv_ref0 + n32, rec_local, d_slot + n32);
+  xchg_owner_resolve(e, k32, n32, recv_ref0, d_slot, d_flags32, d_st);
+  xchg_owner_resolve(e, k64, n64, recv_ref0 + n32, d_slot + n32, d_flags64, d_st);
 }
 }  // namespace
 }  // extern "C++"
@@ -278,14 +293,8 @@ int ctmr_xchg_insert_device(ctmr_engine* e, const void* d_keys32, uint64_t n32, 
   e->arena_used += N;
   InsertArgs loc;
   round_insert_args(e, rc, loc);  // after ensure_capacity: index and arena may be new ones
-  const KeyRec32* k32 = (const KeyRec32*)d_keys32;
-  const KeyRec* k64 = (const KeyRec*)d_keys64;
-  xchg_owner_pass1(e, k32, n32, rc.recv_ref0, d_slot);
-  xchg_owner_pass1(e, k64, n64, rc.recv_ref0 + n32, d_slot + n32);
-  xchg_owner_pass2(e, k32, n32, loc, rc.recv_ref0, rc.d_records, d_slot);
-  xchg_owner_pass2(e, k64, n64, loc, rc.recv_ref0 + n32, rc.d_records, d_slot + n32);
-  xchg_owner_resolve(e, k32, n32, rc.recv_ref0, d_slot, d_flags32);
-  xchg_owner_resolve(e, k64, n64, rc.recv_ref0 + n32, d_slot + n32, d_flags64);
+  xchg_owner_insert(e, (const KeyRec32*)d_keys32, n32, (const KeyRec*)d_keys64, n64, loc, rc.ref0, rc.recv_ref0,
+                    rc.d_records, d_slot, d_flags32, d_flags64, e->d_stats + 1);
   if (rc.n) {
     if ((r = round_resolve(e, rc, false))) return r;
     if ((r = round_collect(e, rc))) return r;

@@ -107,12 +107,15 @@ int known_parse_meta(ctmr_engine* e, const uint8_t* m, size_t len, bool whole, K
   return CTMR_OK;
 }
 
-// ctmr_set_insert's host half (the engine mutex is held): a member that is not a device-table member
-bool known_host_insert(ctmr_engine* e, const std::string& key, const std::string& m) {
-  const bool ins = e->hstore[key].insert(m).second;
-  int32_t eh; uint32_t canon;
-  if (ins && table_key(e, key.data(), key.size(), &eh, &canon)) e->host_issuer_counts[canon]++;
-  return ins;
+// What an entry point is given: the meta part parsed and, for the device variants (n_given: their record count), held
+// against the header.  `what` names the call in the message.
+int known_open(ctmr_engine* e, const uint8_t* m, size_t len, const uint64_t* n_given, const char* what, KnownMeta* km) {
+  int r;
+  if ((r = known_parse_meta(e, m, len, !n_given, km))) return r;
+  if (n_given && km->n_members != *n_given)
+    return fail(e, CTMR_E_INVAL, "%s: %llu member records given, the header says %llu", what, (unsigned long long)*n_given,
+                (unsigned long long)km->n_members);
+  return CTMR_OK;
 }
 
 // Export, host side: the sets in key order with their first members, the issuers they name, the host section.
@@ -121,53 +124,43 @@ struct KnownExport {
   std::vector<unsigned long long> cursor;   // per pair-table slot: the first member of its set
   std::vector<std::pair<uint64_t, uint64_t>> set_range;  // (first, count) in key order
   ctmr_known_image_info info{};
+  // the first record of set s, or info.members past the last set
+  uint64_t first(size_t s) const { return s < set_range.size() ? set_range[s].first : info.members; }
 };
+
+// The sets cut into runs of whole sets of at most `limit` records, a larger set standing alone: the set index at which
+// each run starts, then the number of sets.
+std::vector<size_t> known_cut_sets(const KnownExport& x, uint64_t limit) {
+  std::vector<size_t> cut{0};
+  for (size_t s = 0; s < x.set_range.size();) {
+    size_t t = s + 1;
+    while (t < x.set_range.size() && x.first(t + 1) - x.first(s) <= limit) t++;
+    cut.push_back(t);
+    s = t;
+  }
+  return cut;
+}
 
 int known_export_prepare(ctmr_engine* e, KnownExport* x) {
   int r;
-  if ((r = ensure_pairs(e))) return r;
-  std::vector<unsigned long long> pr;
-  for (size_t cap = 1 << 16;;) {
-    if ((r = ensure(e, SC_MISC, cap * 24))) return r;
-    HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
-    hipLaunchKernelGGL(k_pairs_slots, dim3((unsigned)((e->npairs + 255) / 256)), dim3(256), 0, e->stream, e->pairs, e->npairs,
-                       (unsigned long long*)e->d_scratch[SC_MISC], (uint64_t)cap, e->d_count);
-    unsigned long long cnt;
-    HIPCHK(e, hipMemcpyAsync(&cnt, e->d_count, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (cnt <= cap) {
-      pr.resize(cnt * 3);
-      if (cnt) HIPCHK(e, hipMemcpy(pr.data(), e->d_scratch[SC_MISC], cnt * 24, hipMemcpyDeviceToHost));
-      break;
-    }
-    cap = cnt + 1024;
-  }
-  struct S { uint32_t canon; int32_t eh; uint64_t count, slot; };
-  std::vector<S> sets;
-  for (size_t i = 0; i < pr.size(); i += 3) {
-    const uint32_t canon = (uint32_t)(pr[i] >> 32) - 1;
-    if (canon >= e->issuers.size()) continue;
-    sets.push_back({canon, (int32_t)(uint32_t)pr[i], pr[i + 1], pr[i + 2]});
-  }
+  std::vector<PairRec> sets;
+  if ((r = list_pairs(e, &sets))) return r;
   // key order: (hour, rank of the Issuer.ID) as one integer when every hour has a four-digit year, else the strings
-  std::vector<uint32_t> by_id;
-  for (uint32_t c = 0; c < e->issuers.size(); c++) if (e->issuers[c].canon == c) by_id.push_back(c);
-  std::sort(by_id.begin(), by_id.end(), [e](uint32_t a, uint32_t b) { return e->issuers[a].id < e->issuers[b].id; });
-  std::vector<uint32_t> id_rank(e->issuers.size(), 0);
-  for (uint32_t k = 0; k < by_id.size(); k++) id_rank[by_id[k]] = k;
+  std::vector<uint32_t> by_id, id_rank;
+  issuers_by_id(e, &by_id, &id_rank);
   bool fixed = true;
-  for (auto& s : sets) fixed = fixed && hour_fixed(s.eh);
+  for (auto& s : sets) fixed = fixed && hour_fixed(s.exp_hour);
   if (fixed) {
     std::vector<std::pair<uint64_t, uint32_t>> ord(sets.size());
     for (uint32_t k = 0; k < sets.size(); k++)
-      ord[k] = {((uint64_t)(sets[k].eh - KNOWN_HOUR_LO) << 24) | id_rank[sets[k].canon], k};
+      ord[k] = {((uint64_t)(sets[k].exp_hour - KNOWN_HOUR_LO) << 24) | id_rank[sets[k].canon], k};
     std::sort(ord.begin(), ord.end());
-    std::vector<S> sorted(sets.size());
+    std::vector<PairRec> sorted(sets.size());
     for (size_t k = 0; k < ord.size(); k++) sorted[k] = sets[ord[k].second];
     sets.swap(sorted);
   } else {
-    std::sort(sets.begin(), sets.end(), [e](const S& a, const S& b) {
-      return key_less(a.eh, e->issuers[a.canon].id, b.eh, e->issuers[b.canon].id);
+    std::sort(sets.begin(), sets.end(), [e](const PairRec& a, const PairRec& b) {
+      return key_less(a.exp_hour, e->issuers[a.canon].id, b.exp_hour, e->issuers[b.canon].id);
     });
   }
   // issuer ordinals: the referenced issuers in digest order (process-independent, like the digests themselves)
@@ -200,7 +193,7 @@ int known_export_prepare(ctmr_engine* e, KnownExport* x) {
   x->cursor.assign(e->npairs, 0ull);
   uint64_t first = 0;
   for (auto& s : sets) {
-    put32(o, (uint32_t)s.eh);
+    put32(o, (uint32_t)s.exp_hour);
     put32(o, ordinal[s.canon]);
     put64(o, first);
     put64(o, s.count);
@@ -231,8 +224,7 @@ int known_export_prepare(ctmr_engine* e, KnownExport* x) {
 
 // Export, device side: the member records of sets [s_lo, s_hi) into out (positions relative to the first of s_lo).
 int known_export_members(ctmr_engine* e, KnownExport& x, size_t s_lo, size_t s_hi, uint8_t* d_out) {
-  const uint64_t lo = s_lo < x.set_range.size() ? x.set_range[s_lo].first : x.info.members;
-  const uint64_t hi = s_hi < x.set_range.size() ? x.set_range[s_hi].first : x.info.members;
+  const uint64_t lo = x.first(s_lo), hi = x.first(s_hi);
   if (hi == lo) return CTMR_OK;
   // sets outside [lo, hi) get a cursor far above the chunk: their members are counted but not written (the slots of no
   // set are never reached by a live cell)
@@ -297,13 +289,12 @@ int known_sets_prepare(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_mem
 // The device side of the same: set_first[] and set_meta[], the per-block counts of a chunk of at most `chunk` records,
 // the error word and a DevStats, in one allocation; args(c) describes chunk c to the kernels of kernels/image.h.
 struct KnownDev {
-  void* tmp = nullptr;
+  DevMem tmp;
   size_t off_meta = 0, off_cnt = 0, off_err = 0, off_stats = 0;
   uint64_t n = 0, chunk = 0, nch = 0, nbmax = 0;
   const uint8_t* members = nullptr;
   uint32_t n_sets = 0, world = 1, rank = 0;
-  ~KnownDev() { if (tmp) (void)hipFree(tmp); }
-  uint8_t* t8() const { return (uint8_t*)tmp; }
+  uint8_t* t8() const { return tmp.u8(); }
   uint32_t* err() const { return (uint32_t*)(t8() + off_err); }
   DevStats* stats() const { return (DevStats*)(t8() + off_stats); }
   KnownImportArgs args(uint64_t c) const {
@@ -327,21 +318,26 @@ int known_dev_upload(ctmr_engine* e, const KnownMeta& km, const KnownSets& ks, c
   kd->off_err = kd->off_cnt + ((2 * kd->nbmax + 1) * 8 + 63) / 64 * 64;
   kd->off_stats = kd->off_err + 64;
   if (!N) return CTMR_OK;
-  HIPCHK(e, hipMalloc(&kd->tmp, kd->off_stats + sizeof(DevStats)));
+  HIPCHK(e, kd->tmp.alloc(kd->off_stats + sizeof(DevStats)));
   HIPCHK(e, hipMemcpyAsync(kd->t8(), km.set_first.data(), kd->off_meta, hipMemcpyHostToDevice, e->stream));
   if (km.n_sets) HIPCHK(e, hipMemcpyAsync(kd->t8() + kd->off_meta, ks.set_meta.data(), km.n_sets * 8, hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, hipMemsetAsync(kd->t8() + kd->off_err, 0, 64 + sizeof(DevStats), e->stream));
   return CTMR_OK;
 }
 
-// The count pass over chunk c (k_known_count: validates every record) and its scan; drains the stream.
+// The count pass over a chunk (k_known_count: validates every record) and its scan, queued on the stream.
+int known_count_launch(ctmr_engine* e, const KnownImportArgs& a) {
+  HIPCHK(e, hipMemsetAsync(a.cnt + 2 * a.nb, 0, 8, e->stream));
+  hipLaunchKernelGGL(k_known_count, dim3((unsigned)a.nb), dim3(256), 0, e->stream, a);
+  return scan_u64(e, (uint64_t*)a.cnt, 2 * a.nb + 1, false, SC_TMP);
+}
+
+// The same over chunk c, read back and checked; drains the stream.
 // → tot[0] = records of at most 20 octets taken, tot[1] = all records taken.
 int known_count_chunk(ctmr_engine* e, const KnownDev& kd, uint64_t c, const char* what, unsigned long long tot[2]) {
   const KnownImportArgs a = kd.args(c);
   int r;
-  HIPCHK(e, hipMemsetAsync(a.cnt + 2 * a.nb, 0, 8, e->stream));
-  hipLaunchKernelGGL(k_known_count, dim3((unsigned)a.nb), dim3(256), 0, e->stream, a);
-  if ((r = scan_u64(e, (uint64_t*)a.cnt, 2 * a.nb + 1, false, SC_TMP))) return r;
+  if ((r = known_count_launch(e, a))) return r;
   uint32_t err = 0;
   HIPCHK(e, hipMemcpyAsync(&tot[0], a.cnt + a.nb, 8, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipMemcpyAsync(&tot[1], a.cnt + 2 * a.nb, 8, hipMemcpyDeviceToHost, e->stream));
@@ -349,6 +345,20 @@ int known_count_chunk(ctmr_engine* e, const KnownDev& kd, uint64_t c, const char
   HIPCHK(e, hipStreamSynchronize(e->stream));
   HIPCHK(e, hipGetLastError());
   return known_record_error(e, err, what);
+}
+
+// Set s, of an issuer not registered here: its records copied down, f(key, member, index in the set) for each.
+template <class F>
+int known_unreg_walk(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, size_t s, F f) {
+  const uint64_t first = km.set_first[s], cnt = km.set_first[s + 1] - first;
+  std::vector<uint8_t> buf(cnt * KNOWN_REC_BYTES);
+  HIPCHK(e, hipMemcpy(buf.data(), d_members + first * KNOWN_REC_BYTES, buf.size(), hipMemcpyDeviceToHost));
+  const std::string key = "serials::" + exp_date_id(km.set_hour[s]) + "::" + km.ids[km.set_issuer[s]];
+  for (uint64_t i = 0; i < cnt; i++) {
+    const uint8_t* p = &buf[i * KNOWN_REC_BYTES];
+    f(key, std::string((const char*)p + 8, (size_t)rd64(p)), i);
+  }
+  return CTMR_OK;
 }
 
 // Import: owner round check, issuer remap, then the members on the device (d_members: km.n_members records).
@@ -364,7 +374,7 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
   if (rank == 0)
     for (auto& hm : km.host) {
       int32_t eh; uint32_t cn;
-      if (hm.second.size() <= CTMR_MAX_SERIAL && table_key(e, hm.first.data(), hm.first.size(), &eh, &cn)) host_point++;
+      host_point += set_point(e, hm.first.data(), hm.first.size(), hm.second.size(), &eh, &cn);
     }
   memset(st, 0, sizeof *st);
   st->members = km.n_members;
@@ -391,22 +401,17 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
     e->epoch++;
     e->pairs_dirty = true;
     DevStats* d_st = kd.stats();
-    struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } };
     for (uint64_t c = 0; c < nch; c++) {
       if (!n32[c] && !n64[c]) continue;
       const KnownImportArgs a = kd.args(c);
       const uint64_t nb = a.nb;
-      if (nch > 1) {  // cnt[] holds the counts of the last chunk counted: with several chunks, each counts again
-        HIPCHK(e, hipMemsetAsync(a.cnt + 2 * nb, 0, 8, e->stream));
-        hipLaunchKernelGGL(k_known_count, dim3((unsigned)nb), dim3(256), 0, e->stream, a);
-        if ((r = scan_u64(e, (uint64_t*)a.cnt, 2 * nb + 1, false, SC_TMP))) return r;
-      }
+      if (nch > 1)  // cnt[] holds the counts of the last chunk counted: with several chunks, each counts again
+        if ((r = known_count_launch(e, a))) return r;
       const uint64_t m32 = n32[c], m64 = n64[c], M = m32 + m64;
-      void* recs = nullptr;
+      DevMem recs;
       const size_t off64 = m32 * sizeof(KeyRec32), off_slot = off64 + m64 * sizeof(KeyRec), off_fl = off_slot + M * 4;
-      HIPCHK(e, hipMalloc(&recs, off_fl + M + 64));
-      Free free_recs{recs};
-      uint8_t* r8 = (uint8_t*)recs;
+      HIPCHK(e, recs.alloc(off_fl + M + 64));
+      uint8_t* r8 = recs.u8();
       KeyRec32* k32 = (KeyRec32*)r8;
       KeyRec* k64 = (KeyRec*)(r8 + off64);
       uint32_t* d_slot = (uint32_t*)(r8 + off_slot);
@@ -421,26 +426,7 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
       loc.ref0 = ref0;
       loc.n = 0;  // no entries of a batch to mark
       loc.ord_base = 0;
-      const Table t = e->tbl();
-      if (m32) hipLaunchKernelGGL((k_keys_insert<KeyRec32>), dim3((unsigned)((m32 + 255) / 256)), dim3(256), 0, e->stream,
-                                  (const KeyRec32*)k32, m32, t, ref0, ref0, d_slot);
-      if (m64) hipLaunchKernelGGL((k_keys_insert<KeyRec>), dim3((unsigned)((m64 + 255) / 256)), dim3(256), 0, e->stream,
-                                  (const KeyRec*)k64, m64, t, ref0, ref0 + m32, d_slot + m32);
-      if (m32) hipLaunchKernelGGL((k_keys_insert2<KeyRec32>), dim3((unsigned)((m32 + 255) / 256)), dim3(256), 0, e->stream,
-                                  (const KeyRec32*)k32, m32, loc, ref0, (ctmr_record*)nullptr, d_slot);
-      if (m64) hipLaunchKernelGGL((k_keys_insert2<KeyRec>), dim3((unsigned)((m64 + 255) / 256)), dim3(256), 0, e->stream,
-                                  (const KeyRec*)k64, m64, loc, ref0 + m32, (ctmr_record*)nullptr, d_slot + m32);
-      if (m32) {
-        const uint64_t nbr = (m32 + 1023) / 1024;
-        hipLaunchKernelGGL((k_keys_resolve<KeyRec32>), dim3((unsigned)(nbr < 512 ? nbr : 512)), dim3(1024), 0, e->stream,
-                           (const KeyRec32*)k32, m32, nbr, t, ref0, (const uint32_t*)d_slot, d_fl, e->issuer_counts, d_st);
-      }
-      if (m64) {
-        const uint64_t nbr = (m64 + 1023) / 1024;
-        hipLaunchKernelGGL((k_keys_resolve<KeyRec>), dim3((unsigned)(nbr < 512 ? nbr : 512)), dim3(1024), 0, e->stream,
-                           (const KeyRec*)k64, m64, nbr, t, ref0 + m32, (const uint32_t*)(d_slot + m32), d_fl + m32,
-                           e->issuer_counts, d_st);
-      }
+      xchg_owner_insert(e, k32, m32, k64, m64, loc, ref0, ref0, nullptr, d_slot, d_fl, d_fl + m32, d_st);
       if (e->d_bloom) {
         if (m32) hipLaunchKernelGGL((k_known_bloom<KeyRec32>), dim3((unsigned)((m32 + 255) / 256)), dim3(256), 0, e->stream,
                                     (const KeyRec32*)k32, m32, e->d_bloom, e->bloom_words - 1);
@@ -458,30 +444,20 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
     }
   }
   // ---- sets of issuers not registered here (world = 1): their members go where ctmr_set_insert puts them
-  for (size_t s : unreg) {
-    const uint64_t f = km.set_first[s], cnt = km.set_first[s + 1] - f;
-    std::vector<uint8_t> buf(cnt * KNOWN_REC_BYTES);
-    HIPCHK(e, hipMemcpy(buf.data(), d_members + f * KNOWN_REC_BYTES, buf.size(), hipMemcpyDeviceToHost));
-    const std::string key = "serials::" + exp_date_id(km.set_hour[s]) + "::" + km.ids[km.set_issuer[s]];
-    for (uint64_t i = 0; i < cnt; i++) {
-      const uint8_t* p = &buf[i * KNOWN_REC_BYTES];
-      inserted += known_host_insert(e, key, std::string((const char*)p + 8, (size_t)rd64(p)));
-    }
-  }
+  for (size_t s : unreg)
+    if ((r = known_unreg_walk(e, km, d_members, s, [&](const std::string& key, const std::string& m, uint64_t) {
+          inserted += host_insert(e, key, m);
+        })))
+      return r;
   st->inserted = inserted;
   st->known = st->taken - inserted;
   // ---- the host section (rank 0 alone): ctmr_set_insert, member by member
   if (rank == 0) {
     st->host_members = km.host.size();
     for (auto& hm : km.host) {
-      int32_t eh; uint32_t cn;
-      if (hm.second.size() <= CTMR_MAX_SERIAL && table_key(e, hm.first.data(), hm.first.size(), &eh, &cn)) {
-        int was_new = 0;
-        if ((r = point_op(e, 0, eh, cn, (const uint8_t*)hm.second.data(), hm.second.size(), &was_new))) return r;
-        st->host_inserted += was_new;
-      } else {
-        st->host_inserted += known_host_insert(e, hm.first, hm.second);
-      }
+      int was_new = 0;
+      if ((r = set_op(e, 0, hm.first, hm.second, &was_new))) return r;
+      st->host_inserted += was_new;
     }
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -491,38 +467,18 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
 // ---- bulk SetContains / SetRemove over an image's member records (include/ctmr.h ctmr_known_query* / ctmr_known_remove*,
 // DESIGN.md §14)
 
-// ctmr_set_remove's host half (the engine mutex is held)
-bool known_host_erase(ctmr_engine* e, const std::string& key, const std::string& m) {
-  auto it = e->hstore.find(key);
-  if (it == e->hstore.end() || !it->second.erase(m)) return false;
-  int32_t eh; uint32_t canon;
-  if (table_key(e, key.data(), key.size(), &eh, &canon)) e->host_issuer_counts[canon]--;
-  if (it->second.empty()) e->hstore.erase(it);
-  return true;
-}
-bool known_host_contains(ctmr_engine* e, const std::string& key, const std::string& m) {
-  auto it = e->hstore.find(key);
-  return it != e->hstore.end() && it->second.count(m) != 0;
-}
-
 // records per pass, as import's; CTMR_KNOWN_PROBE_CHUNK (tests only) forces small passes
 uint64_t known_probe_chunk() {
-  if (const char* ev = getenv("CTMR_KNOWN_PROBE_CHUNK")) {
-    const unsigned long long v = strtoull(ev, nullptr, 10);
-    if (v) return v < KNOWN_CHUNK ? v : KNOWN_CHUNK;
-  }
-  return KNOWN_CHUNK;
+  const uint64_t v = env_u64("CTMR_KNOWN_PROBE_CHUNK");
+  return v && v < KNOWN_CHUNK ? v : KNOWN_CHUNK;
 }
 
 // records per lane of k_known_query / k_known_remove: KNOWN_PROBE_RPL was the fastest of 1, 2, 4, 8 (DESIGN.md §14);
 // CTMR_KNOWN_PROBE_RPL selects another for scripts/bench_known_query.py's sweep and the tests of every instantiation
 constexpr uint32_t KNOWN_PROBE_RPL = 4;
 uint32_t known_probe_rpl() {
-  if (const char* ev = getenv("CTMR_KNOWN_PROBE_RPL")) {
-    const unsigned long v = strtoul(ev, nullptr, 10);
-    if (v == 1 || v == 2 || v == 4 || v == 8) return (uint32_t)v;
-  }
-  return KNOWN_PROBE_RPL;
+  const uint64_t v = env_u64("CTMR_KNOWN_PROBE_RPL");
+  return v == 1 || v == 2 || v == 4 || v == 8 ? (uint32_t)v : KNOWN_PROBE_RPL;
 }
 
 template <int R>
@@ -584,17 +540,13 @@ int known_probe_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_membe
   }
   // ---- sets of issuers not registered here (world = 1): where ctmr_set_insert puts their members, the host-side store
   for (size_t s : ks.unreg) {
-    const uint64_t f = km.set_first[s], cnt = km.set_first[s + 1] - f;
-    std::vector<uint8_t> buf(cnt * KNOWN_REC_BYTES), fl(cnt);
-    HIPCHK(e, hipMemcpy(buf.data(), d_members + f * KNOWN_REC_BYTES, buf.size(), hipMemcpyDeviceToHost));
-    const std::string key = "serials::" + exp_date_id(km.set_hour[s]) + "::" + km.ids[km.set_issuer[s]];
-    for (uint64_t i = 0; i < cnt; i++) {
-      const uint8_t* p = &buf[i * KNOWN_REC_BYTES];
-      const std::string m((const char*)p + 8, (size_t)rd64(p));
-      fl[i] = remove ? known_host_erase(e, key, m) : known_host_contains(e, key, m);
-      hits += fl[i];
-    }
-    if (!remove) HIPCHK(e, hipMemcpy(d_flags + f, fl.data(), cnt, hipMemcpyHostToDevice));
+    std::vector<uint8_t> fl(km.set_first[s + 1] - km.set_first[s]);
+    if ((r = known_unreg_walk(e, km, d_members, s, [&](const std::string& key, const std::string& m, uint64_t i) {
+          fl[i] = remove ? host_erase(e, key, m) : host_contains(e, key, m);
+          hits += fl[i];
+        })))
+      return r;
+    if (!remove) HIPCHK(e, hipMemcpy(d_flags + km.set_first[s], fl.data(), fl.size(), hipMemcpyHostToDevice));
   }
   memset(st, 0, sizeof *st);
   st->members = N;
@@ -605,14 +557,8 @@ int known_probe_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_membe
   if (rank == 0) {
     st->host_members = km.host.size();
     for (size_t i = 0; i < km.host.size(); i++) {
-      const auto& hm = km.host[i];
-      int32_t eh; uint32_t cn;
       int hit = 0;
-      if (hm.second.size() <= CTMR_MAX_SERIAL && table_key(e, hm.first.data(), hm.first.size(), &eh, &cn)) {
-        if ((r = point_op(e, remove ? 2 : 1, eh, cn, (const uint8_t*)hm.second.data(), hm.second.size(), &hit))) return r;
-      } else {
-        hit = remove ? known_host_erase(e, hm.first, hm.second) : known_host_contains(e, hm.first, hm.second);
-      }
+      if ((r = set_op(e, remove ? 2 : 1, km.host[i].first, km.host[i].second, &hit))) return r;
       if (!remove) host_flags[i] = (uint8_t)(hit != 0);
       st->host_hits += hit != 0;
     }
@@ -635,16 +581,12 @@ int known_query_room(ctmr_engine* e, const KnownMeta& km, uint32_t rank, const v
 }
 
 // the member records of a whole image, copied to the device (+ extra bytes behind them: a query's flags)
-int known_stage_members(ctmr_engine* e, const KnownMeta& km, const uint8_t* image, size_t extra, const char* what, void** d) {
-  *d = nullptr;
+int known_stage_members(ctmr_engine* e, const KnownMeta& km, const uint8_t* image, size_t extra, const char* what, DevMem* d) {
   const size_t bytes = km.n_members * KNOWN_REC_BYTES;
   if (!km.n_members) return CTMR_OK;
-  if (hipMalloc(d, bytes + extra) != hipSuccess) {
-    (void)hipGetLastError();
-    *d = nullptr;
+  if (d->alloc(bytes + extra) != hipSuccess)
     return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu member records", what, (unsigned long long)km.n_members);
-  }
-  HIPCHK(e, hipMemcpyAsync(*d, image + km.meta_bytes, bytes, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(d->p, image + km.meta_bytes, bytes, hipMemcpyHostToDevice, e->stream));
   return CTMR_OK;
 }
 
@@ -664,37 +606,20 @@ int ctmr_known_export(ctmr_engine* e, uint8_t* out, size_t cap, ctmr_known_image
   if (N) {
     // stage the member records on the device: all at once when that fits, else set range by set range
     uint64_t stage = N;
-    void* d = nullptr;
-    while (hipMalloc(&d, stage * KNOWN_REC_BYTES) != hipSuccess) {
-      (void)hipGetLastError();
-      d = nullptr;
+    DevMem d;
+    while (d.alloc(stage * KNOWN_REC_BYTES) != hipSuccess) {
       if (stage <= (1ull << 20)) return fail(e, CTMR_E_NOMEM, "known export: no device memory to stage the member records");
       stage /= 2;
     }
-    struct Free { void* p; ~Free() { (void)hipFree(p); } } free_d{d};
-    size_t s = 0;
-    while (s < x.set_range.size()) {
-      size_t t = s;
-      const uint64_t lo = x.set_range[s].first;
-      while (t < x.set_range.size() && x.set_range[t].first + x.set_range[t].second - lo <= stage) t++;
-      if (t == s) {  // one set larger than the staging buffer: stage it alone
-        void* big = nullptr;
-        if (hipMalloc(&big, x.set_range[s].second * KNOWN_REC_BYTES) != hipSuccess) {
-          (void)hipGetLastError();
-          return fail(e, CTMR_E_NOMEM, "known export: no device memory to stage a set of %llu members",
-                      (unsigned long long)x.set_range[s].second);
-        }
-        Free free_big{big};
-        if ((r = known_export_members(e, x, s, s + 1, (uint8_t*)big))) return r;
-        HIPCHK(e, hipMemcpy(out + x.info.meta_bytes + lo * KNOWN_REC_BYTES, big, x.set_range[s].second * KNOWN_REC_BYTES,
-                            hipMemcpyDeviceToHost));
-        s++;
-        continue;
-      }
-      const uint64_t hi = t < x.set_range.size() ? x.set_range[t].first : N;
-      if ((r = known_export_members(e, x, s, t, (uint8_t*)d))) return r;
-      HIPCHK(e, hipMemcpy(out + x.info.meta_bytes + lo * KNOWN_REC_BYTES, d, (hi - lo) * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
-      s = t;
+    const std::vector<size_t> cut = known_cut_sets(x, stage);
+    for (size_t c = 0; c + 1 < cut.size(); c++) {
+      const uint64_t lo = x.first(cut[c]), n = x.first(cut[c + 1]) - lo;
+      DevMem big;  // one set larger than the staging buffer: staged alone
+      if (n > stage && big.alloc(n * KNOWN_REC_BYTES) != hipSuccess)
+        return fail(e, CTMR_E_NOMEM, "known export: no device memory to stage a set of %llu members", (unsigned long long)n);
+      uint8_t* buf = n > stage ? big.u8() : d.u8();
+      if ((r = known_export_members(e, x, cut[c], cut[c + 1], buf))) return r;
+      HIPCHK(e, hipMemcpy(out + x.info.meta_bytes + lo * KNOWN_REC_BYTES, buf, n * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
     }
   }
   memcpy(out, x.meta.data(), x.meta.size());
@@ -725,19 +650,11 @@ int ctmr_known_import(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   KnownMeta km;
+  DevMem d;
   int r;
-  if ((r = known_parse_meta(e, image, len, true, &km))) return r;
-  void* d = nullptr;
-  if (km.n_members) {
-    if (hipMalloc(&d, km.n_members * KNOWN_REC_BYTES) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e, CTMR_E_NOMEM, "known import: no device memory for %llu member records", (unsigned long long)km.n_members);
-    }
-  }
-  struct Free { void* p; ~Free() { if (p) (void)hipFree(p); } } free_d{d};
-  if (km.n_members)
-    HIPCHK(e, hipMemcpyAsync(d, image + km.meta_bytes, km.n_members * KNOWN_REC_BYTES, hipMemcpyHostToDevice, e->stream));
-  return known_import_core(e, km, (const uint8_t*)d, world, rank, st);
+  if ((r = known_open(e, image, len, nullptr, "known import", &km))) return r;
+  if ((r = known_stage_members(e, km, image, 0, "known import", &d))) return r;
+  return known_import_core(e, km, d.u8(), world, rank, st);
 }
 
 int ctmr_known_import_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
@@ -747,9 +664,7 @@ int ctmr_known_import_device(ctmr_engine* e, const uint8_t* meta, size_t meta_le
   HIPCHK(e, hipSetDevice(e->device));
   KnownMeta km;
   int r;
-  if ((r = known_parse_meta(e, meta, meta_len, false, &km))) return r;
-  if (km.n_members != n_members) return fail(e, CTMR_E_INVAL, "known import: %llu member records given, the header says %llu",
-                                             (unsigned long long)n_members, (unsigned long long)km.n_members);
+  if ((r = known_open(e, meta, meta_len, &n_members, "known import", &km))) return r;
   return known_import_core(e, km, (const uint8_t*)d_members, world, rank, st);
 }
 
@@ -759,14 +674,13 @@ int ctmr_known_query(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t 
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   KnownMeta km;
+  DevMem d;
   int r;
-  if ((r = known_parse_meta(e, image, len, true, &km))) return r;
+  if ((r = known_open(e, image, len, nullptr, "known query", &km))) return r;
   if ((r = known_query_room(e, km, rank, flags, flags_cap, host_flags, host_flags_cap, st))) return r;
-  void* d = nullptr;
-  struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_d{d};
   if ((r = known_stage_members(e, km, image, km.n_members, "known query", &d))) return r;
-  uint8_t* d_flags = d ? (uint8_t*)d + km.n_members * KNOWN_REC_BYTES : nullptr;
-  if ((r = known_probe_core(e, km, (const uint8_t*)d, world, rank, false, d_flags, host_flags, st))) return r;
+  uint8_t* d_flags = d.p ? d.u8() + km.n_members * KNOWN_REC_BYTES : nullptr;
+  if ((r = known_probe_core(e, km, d.u8(), world, rank, false, d_flags, host_flags, st))) return r;
   if (km.n_members) HIPCHK(e, hipMemcpy(flags, d_flags, km.n_members, hipMemcpyDeviceToHost));
   return CTMR_OK;
 }
@@ -779,9 +693,7 @@ int ctmr_known_query_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len
   HIPCHK(e, hipSetDevice(e->device));
   KnownMeta km;
   int r;
-  if ((r = known_parse_meta(e, meta, meta_len, false, &km))) return r;
-  if (km.n_members != n_members) return fail(e, CTMR_E_INVAL, "known query: %llu member records given, the header says %llu",
-                                             (unsigned long long)n_members, (unsigned long long)km.n_members);
+  if ((r = known_open(e, meta, meta_len, &n_members, "known query", &km))) return r;
   if ((r = known_query_room(e, km, rank, d_flags, flags_cap, host_flags, host_flags_cap, st))) return r;
   return known_probe_core(e, km, (const uint8_t*)d_members, world, rank, false, (uint8_t*)d_flags, host_flags, st);
 }
@@ -792,12 +704,11 @@ int ctmr_known_remove(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   KnownMeta km;
+  DevMem d;
   int r;
-  if ((r = known_parse_meta(e, image, len, true, &km))) return r;
-  void* d = nullptr;
-  struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } free_d{d};
+  if ((r = known_open(e, image, len, nullptr, "known remove", &km))) return r;
   if ((r = known_stage_members(e, km, image, 0, "known remove", &d))) return r;
-  return known_probe_core(e, km, (const uint8_t*)d, world, rank, true, nullptr, nullptr, st);
+  return known_probe_core(e, km, d.u8(), world, rank, true, nullptr, nullptr, st);
 }
 
 int ctmr_known_remove_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
@@ -807,8 +718,6 @@ int ctmr_known_remove_device(ctmr_engine* e, const uint8_t* meta, size_t meta_le
   HIPCHK(e, hipSetDevice(e->device));
   KnownMeta km;
   int r;
-  if ((r = known_parse_meta(e, meta, meta_len, false, &km))) return r;
-  if (km.n_members != n_members) return fail(e, CTMR_E_INVAL, "known remove: %llu member records given, the header says %llu",
-                                             (unsigned long long)n_members, (unsigned long long)km.n_members);
+  if ((r = known_open(e, meta, meta_len, &n_members, "known remove", &km))) return r;
   return known_probe_core(e, km, (const uint8_t*)d_members, world, rank, true, nullptr, nullptr, st);
 }

@@ -72,37 +72,17 @@ int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
     by_id[parts[2]][{start, parts[1]}].host = &kv.second;
   }
   int r;
-  if ((r = ensure_pairs(e))) return r;
-  std::vector<unsigned long long> pr;
-  for (size_t cap = 1 << 16;;) {
-    if ((r = ensure(e, SC_MISC, cap * 24))) return r;
-    HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
-    hipLaunchKernelGGL(k_pairs_slots, dim3((unsigned)((e->npairs + 255) / 256)), dim3(256), 0, e->stream, e->pairs, e->npairs,
-                       (unsigned long long*)e->d_scratch[SC_MISC], (uint64_t)cap, e->d_count);
-    unsigned long long cnt;
-    HIPCHK(e, hipMemcpyAsync(&cnt, e->d_count, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (cnt <= cap) {
-      pr.resize(cnt * 3);
-      if (cnt) HIPCHK(e, hipMemcpy(pr.data(), e->d_scratch[SC_MISC], cnt * 24, hipMemcpyDeviceToHost));
-      break;
-    }
-    cap = cnt + 1024;
-  }
+  std::vector<PairRec> pr;
+  if ((r = list_pairs(e, &pr))) return r;
   // the device sets as integers: (rank of the issuer's ID, hour) — the per-set work of a table of many sets stays off
   // strings; an hour's ExpDate.ID is formatted only where a host-store key of the same issuer and second compares to it
-  std::vector<uint32_t> by_rank;
-  for (uint32_t c = 0; c < e->issuers.size(); c++) if (e->issuers[c].canon == c) by_rank.push_back(c);
-  std::sort(by_rank.begin(), by_rank.end(), [e](uint32_t p, uint32_t q) { return e->issuers[p].id < e->issuers[q].id; });
-  std::vector<uint32_t> rank_of(e->issuers.size(), 0);
-  for (uint32_t k = 0; k < by_rank.size(); k++) rank_of[by_rank[k]] = k;
+  std::vector<uint32_t> by_rank, rank_of;
+  issuers_by_id(e, &by_rank, &rank_of);
   struct Dev { uint64_t key, count, slot; };  // key = rank << 32 | (hour − KNOWN_HOUR_LO)
   std::vector<Dev> dev;
-  for (size_t i = 0; i < pr.size(); i += 3) {
-    const uint32_t canon = (uint32_t)(pr[i] >> 32) - 1;
-    const int32_t eh = (int32_t)(uint32_t)pr[i];
-    if (canon >= e->issuers.size() || !hour_fixed(eh) || now >= ((int64_t)eh + 1) * 3600) continue;
-    dev.push_back({((uint64_t)rank_of[canon] << 32) | (uint64_t)(eh - KNOWN_HOUR_LO), pr[i + 1], pr[i + 2]});
+  for (auto& p : pr) {
+    if (!hour_fixed(p.exp_hour) || now >= ((int64_t)p.exp_hour + 1) * 3600) continue;
+    dev.push_back({((uint64_t)rank_of[p.canon] << 32) | (uint64_t)(p.exp_hour - KNOWN_HOUR_LO), p.count, p.slot});
   }
   std::sort(dev.begin(), dev.end(), [](const Dev& p, const Dev& q) { return p.key < q.key; });
   KnownExport& x = L->x;
@@ -160,8 +140,7 @@ int known_lists_count(ctmr_engine* e, KnownLists& L, size_t s_lo, size_t s_hi, u
                       uint64_t* bytes) {
   int r;
   if ((r = known_export_members(e, L.x, s_lo, s_hi, d_rec))) return r;
-  const uint64_t lo = L.x.set_range[s_lo].first, hi = s_hi < L.x.set_range.size() ? L.x.set_range[s_hi].first : L.x.info.members;
-  const uint64_t n = hi - lo, nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
+  const uint64_t n = L.x.first(s_hi) - L.x.first(s_lo), nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
   HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
   hipLaunchKernelGGL(k_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec, n, cnt);
   if ((r = scan_u64(e, (uint64_t*)cnt, nb + 1, false, SC_MISC))) return r;
@@ -188,22 +167,8 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
   info->host_members = L.host_members;
   info->ids_bytes = ids_bytes;
   // chunks: runs of whole sets of at most `chunk` records (a larger set alone); the test-only override forces small ones
-  uint64_t chunk = LISTS_CHUNK;
-  if (const char* ev = getenv("CTMR_KNOWN_LISTS_CHUNK")) {
-    const unsigned long long v = strtoull(ev, nullptr, 10);
-    if (v) chunk = v;
-  }
-  std::vector<size_t> cut{0};  // set index at each chunk start, then the end
-  uint64_t max_n = 0;
-  for (size_t s = 0; s < L.x.set_range.size();) {
-    const uint64_t lo = L.x.set_range[s].first;
-    size_t t = s + 1;
-    while (t < L.x.set_range.size() && L.x.set_range[t].first + L.x.set_range[t].second - lo <= chunk) t++;
-    const uint64_t hi = t < L.x.set_range.size() ? L.x.set_range[t].first : N;
-    max_n = std::max(max_n, hi - lo);
-    cut.push_back(t);
-    s = t;
-  }
+  const uint64_t forced = env_u64("CTMR_KNOWN_LISTS_CHUNK");
+  const std::vector<size_t> cut = known_cut_sets(L.x, forced ? forced : LISTS_CHUNK);  // set index at each chunk start, then the end
   const size_t nch = cut.size() - 1;
   // points: the device record at which each list starts and each host-store piece goes in (ascending, unique)
   std::vector<uint64_t> pts;
@@ -215,21 +180,18 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
     }
   }
   size_t max_pts = 0;
+  uint64_t max_n = 0;
   for (size_t c = 0; c < nch; c++) {
-    const uint64_t lo = L.x.set_range[cut[c]].first, hi = cut[c + 1] < L.x.set_range.size() ? L.x.set_range[cut[c + 1]].first : N;
+    const uint64_t lo = L.x.first(cut[c]), hi = L.x.first(cut[c + 1]);
+    max_n = std::max(max_n, hi - lo);
     max_pts = std::max(max_pts, (size_t)(std::lower_bound(pts.begin(), pts.end(), hi) - std::lower_bound(pts.begin(), pts.end(), lo)));
   }
-  void *d_rec = nullptr, *tmp = nullptr, *d_text = nullptr;
-  struct Free { void*& p; ~Free() { if (p) (void)hipFree(p); } } f1{d_rec}, f2{tmp}, f3{d_text};
+  DevMem d_rec, tmp, d_text;
   const uint64_t nbmax = (max_n + LIST_BLOCK - 1) / LIST_BLOCK;
   const size_t off_pts = (nbmax + 1) * 8, off_po = off_pts + max_pts * 8;
-  if (N) {
-    if (hipMalloc(&d_rec, max_n * KNOWN_REC_BYTES) != hipSuccess || hipMalloc(&tmp, off_po + max_pts * 8 + 8) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e, CTMR_E_NOMEM, "known lists: no device memory to stage %llu member records", (unsigned long long)max_n);
-    }
-  }
-  unsigned long long* cnt = (unsigned long long*)tmp;
+  if (N && (d_rec.alloc(max_n * KNOWN_REC_BYTES) != hipSuccess || tmp.alloc(off_po + max_pts * 8 + 8) != hipSuccess))
+    return fail(e, CTMR_E_NOMEM, "known lists: no device memory to stage %llu member records", (unsigned long long)max_n);
+  unsigned long long* cnt = (unsigned long long*)tmp.p;
   std::vector<uint64_t> chunk_bytes(nch, ~0ull);
   // sizing: one count pass over every chunk, unless every buffer holds its bound (81 B per member for the text) and
   // the pass that writes can size as it goes; a single chunk is staged once either way
@@ -239,7 +201,7 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
   if (sized) {
     uint64_t dev_bytes = 0;
     for (size_t c = 0; c < nch; c++) {
-      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], (uint8_t*)d_rec, cnt, &chunk_bytes[c]))) return r;
+      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &chunk_bytes[c]))) return r;
       dev_bytes += chunk_bytes[c];
     }
     info->text_bytes = dev_bytes + L.host_bytes;
@@ -256,10 +218,10 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
     return k ? L.host[k - 1].hb + L.host[k - 1].text.size() : 0ull;
   };
   for (size_t c = 0; c < nch; c++) {
-    const uint64_t lo = L.x.set_range[cut[c]].first, hi = cut[c + 1] < L.x.set_range.size() ? L.x.set_range[cut[c + 1]].first : N;
+    const uint64_t lo = L.x.first(cut[c]), hi = L.x.first(cut[c + 1]);
     uint64_t bytes = chunk_bytes[c];
     if (nch > 1)  // (one chunk: still staged and scanned from the sizing pass)
-      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], (uint8_t*)d_rec, cnt, &bytes))) return r;
+      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &bytes))) return r;
     const size_t p0 = std::lower_bound(pts.begin(), pts.end(), lo) - pts.begin();
     const size_t p1 = std::lower_bound(pts.begin(), pts.end(), hi) - pts.begin();
     std::vector<uint64_t> rel(p1 - p0);
@@ -272,22 +234,17 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
       dest = text + base + hb_le(lo);
     } else {
       if (text_cap_dev < bytes) {
-        if (d_text) (void)hipFree(d_text);
-        d_text = nullptr;
-        text_cap_dev = 0;
-        if (hipMalloc(&d_text, bytes) != hipSuccess) {
-          (void)hipGetLastError();
+        if (d_text.alloc(bytes) != hipSuccess)
           return fail(e, CTMR_E_NOMEM, "known lists: no device memory to stage %llu text bytes", (unsigned long long)bytes);
-        }
         text_cap_dev = bytes;
       }
-      dest = (uint8_t*)d_text;
+      dest = d_text.u8();
     }
-    uint64_t* d_pts = (uint64_t*)((uint8_t*)tmp + off_pts);
-    unsigned long long* d_po = (unsigned long long*)((uint8_t*)tmp + off_po);
+    uint64_t* d_pts = (uint64_t*)(tmp.u8() + off_pts);
+    unsigned long long* d_po = (unsigned long long*)(tmp.u8() + off_po);
     if (!rel.empty()) HIPCHK(e, hipMemcpyAsync(d_pts, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, e->stream));
     const uint64_t n = hi - lo, nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
-    hipLaunchKernelGGL(k_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec, n,
+    hipLaunchKernelGGL(k_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec.p, n,
                        (const unsigned long long*)cnt, dest, (const uint64_t*)d_pts, (uint64_t)rel.size(), d_po);
     if (!rel.empty()) HIPCHK(e, hipMemcpyAsync(&D[p0], d_po, rel.size() * 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -306,7 +263,7 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
         };
         const uint64_t a = Dat(cuts[k]), b = Dat(cuts[k + 1]);
         if (b == a) continue;
-        HIPCHK(e, hipMemcpyAsync(text + a + hb_le(cuts[k]), (uint8_t*)d_text + (a - base), b - a,
+        HIPCHK(e, hipMemcpyAsync(text + a + hb_le(cuts[k]), d_text.u8() + (a - base), b - a,
                                  device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
       }
       HIPCHK(e, hipStreamSynchronize(e->stream));

@@ -3,45 +3,70 @@
 
 // ------------------------------------------------------------------ RemoteCache set methods
 
+extern "C++" {
+namespace {
+
+// The host-side store (the engine mutex is held): where a member lives that is not a device-table member.  A serials::
+// key of a registered issuer counts towards host_issuer_counts.
+bool host_insert(ctmr_engine* e, const std::string& key, const std::string& m) {
+  const bool ins = e->hstore[key].insert(m).second;
+  int32_t eh; uint32_t canon;
+  if (ins && table_key(e, key.data(), key.size(), &eh, &canon)) e->host_issuer_counts[canon]++;
+  return ins;
+}
+bool host_contains(ctmr_engine* e, const std::string& key, const std::string& m) {
+  auto it = e->hstore.find(key);
+  return it != e->hstore.end() && it->second.count(m) != 0;
+}
+bool host_erase(ctmr_engine* e, const std::string& key, const std::string& m) {
+  auto it = e->hstore.find(key);
+  if (it == e->hstore.end() || !it->second.erase(m)) return false;
+  int32_t eh; uint32_t canon;
+  if (table_key(e, key.data(), key.size(), &eh, &canon)) e->host_issuer_counts[canon]--;
+  if (it->second.empty()) e->hstore.erase(it);
+  return true;
+}
+
+// a device-table member: a serial that fits a key cell, under the serials:: key of a registered issuer
+bool set_point(ctmr_engine* e, const char* key, size_t kl, size_t ml, int32_t* eh, uint32_t* canon) {
+  return ml <= CTMR_MAX_SERIAL && table_key(e, key, kl, eh, canon);
+}
+
+// SetInsert (op 0), SetContains (1) or SetRemove (2) of one member, the engine mutex held: a device-table member goes
+// through point_op, anything else to the host-side store.  *out = 1: inserted / present / removed.
+int set_op(ctmr_engine* e, int op, const char* key, size_t kl, const uint8_t* m, size_t ml, int* out) {
+  int32_t eh; uint32_t canon;
+  if (set_point(e, key, kl, ml, &eh, &canon)) return point_op(e, op, eh, canon, m, ml, out);
+  const std::string k(key, kl), mem((const char*)m, ml);
+  *out = op == 0 ? host_insert(e, k, mem) : op == 1 ? host_contains(e, k, mem) : host_erase(e, k, mem);
+  return CTMR_OK;
+}
+int set_op(ctmr_engine* e, int op, const std::string& key, const std::string& m, int* out) {
+  return set_op(e, op, key.data(), key.size(), (const uint8_t*)m.data(), m.size(), out);
+}
+
+}  // namespace
+}  // extern "C++"
+
 int ctmr_set_insert(ctmr_engine* e, const char* key, size_t kl, const uint8_t* m, size_t ml, int* was_new) {
   if (!e || !key || (ml && !m) || !was_new) return CTMR_E_INVAL;
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
-  int32_t eh; uint32_t canon;
-  if (ml <= CTMR_MAX_SERIAL && table_key(e, key, kl, &eh, &canon)) return point_op(e, 0, eh, canon, m, ml, was_new);
-  std::string k(key, kl);
-  bool ins = e->hstore[k].insert(std::string((const char*)m, ml)).second;
-  if (ins && table_key(e, key, kl, &eh, &canon)) e->host_issuer_counts[canon]++;
-  *was_new = ins;
-  return CTMR_OK;
+  return set_op(e, 0, key, kl, m, ml, was_new);
 }
 
 int ctmr_set_contains(ctmr_engine* e, const char* key, size_t kl, const uint8_t* m, size_t ml, int* present) {
   if (!e || !key || (ml && !m) || !present) return CTMR_E_INVAL;
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
-  int32_t eh; uint32_t canon;
-  if (ml <= CTMR_MAX_SERIAL && table_key(e, key, kl, &eh, &canon)) return point_op(e, 1, eh, canon, m, ml, present);
-  auto it = e->hstore.find(std::string(key, kl));
-  *present = it != e->hstore.end() && it->second.count(std::string((const char*)m, ml));
-  return CTMR_OK;
+  return set_op(e, 1, key, kl, m, ml, present);
 }
 
 int ctmr_set_remove(ctmr_engine* e, const char* key, size_t kl, const uint8_t* m, size_t ml, int* removed) {
   if (!e || !key || (ml && !m) || !removed) return CTMR_E_INVAL;
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
-  int32_t eh; uint32_t canon;
-  if (ml <= CTMR_MAX_SERIAL && table_key(e, key, kl, &eh, &canon)) return point_op(e, 2, eh, canon, m, ml, removed);
-  std::string k(key, kl);
-  auto it = e->hstore.find(k);
-  *removed = 0;
-  if (it != e->hstore.end() && it->second.erase(std::string((const char*)m, ml))) {
-    *removed = 1;
-    if (table_key(e, key, kl, &eh, &canon)) e->host_issuer_counts[canon]--;
-    if (it->second.empty()) e->hstore.erase(it);
-  }
-  return CTMR_OK;
+  return set_op(e, 2, key, kl, m, ml, removed);
 }
 
 int ctmr_set_cardinality(ctmr_engine* e, const char* key, size_t kl, int64_t* n) {
@@ -114,13 +139,10 @@ int ctmr_keys(ctmr_engine* e, const char* pat, size_t pl, uint8_t* out, size_t c
   HIPCHK(e, hipSetDevice(e->device));
   std::set<std::string> keys;
   for (auto& kv : e->hstore) if (!kv.second.empty()) keys.insert(kv.first);
-  std::vector<std::pair<unsigned long long, unsigned long long>> pr;
-  int r = dump_pairs(e, &pr);
+  std::vector<PairRec> pr;
+  int r = list_pairs(e, &pr);
   if (r) return r;
-  for (auto& p : pr) {
-    const uint32_t canon = (uint32_t)(p.first >> 32) - 1;
-    if (canon < e->issuers.size()) keys.insert(make_key(e, (int32_t)(uint32_t)p.first, canon));
-  }
+  for (auto& p : pr) keys.insert(make_key(e, p.exp_hour, p.canon));
   std::vector<std::string> v;
   for (auto& k : keys) if (glob_match(pat, pl, k.data(), k.size())) v.push_back(k);
   int rc;
@@ -142,15 +164,13 @@ int ctmr_expire_sweep(ctmr_engine* e, int64_t now, uint64_t* removed) {
   uint64_t total = 0;
   // (1) every table key carries ExpireAt(expDate hour) (knowncertificates.go:98-104), unless
   //     overridden by an explicit later ExpireAt → handled in (2)
-  std::vector<std::pair<unsigned long long, unsigned long long>> pr;
-  int r = dump_pairs(e, &pr);
+  std::vector<PairRec> pr;
+  int r = list_pairs(e, &pr);
   if (r) return r;
   HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
   bool any_override = false;
-  for (auto& p : pr) {
-    const uint32_t canon = (uint32_t)(p.first >> 32) - 1;
-    if (canon < e->issuers.size() && e->expiry.count(make_key(e, (int32_t)(uint32_t)p.first, canon))) any_override = true;
-  }
+  for (auto& p : pr)
+    if (e->expiry.count(make_key(e, p.exp_hour, p.canon))) any_override = true;
   const unsigned blocks = (unsigned)((e->nslots + 255) / 256);
   e->pairs_dirty = true;
   if (!any_override) {
@@ -158,14 +178,11 @@ int ctmr_expire_sweep(ctmr_engine* e, int64_t now, uint64_t* removed) {
                        e->issuer_counts, e->pairs, e->npairs - 1, e->d_count);
   } else {
     for (auto& p : pr) {
-      const uint32_t canon = (uint32_t)(p.first >> 32) - 1;
-      const int32_t eh = (int32_t)(uint32_t)p.first;
-      if (canon >= e->issuers.size()) continue;
-      auto it = e->expiry.find(make_key(e, eh, canon));
-      const int64_t t = it != e->expiry.end() ? it->second : (int64_t)eh * 3600;
+      auto it = e->expiry.find(make_key(e, p.exp_hour, p.canon));
+      const int64_t t = it != e->expiry.end() ? it->second : (int64_t)p.exp_hour * 3600;
       if (t <= now)
-        hipLaunchKernelGGL(k_sweep, dim3(blocks), dim3(256), 0, e->stream, e->tbl(), 0, 0ll, (uint32_t)eh,
-                           canon, e->issuer_counts, e->pairs, e->npairs - 1, e->d_count);
+        hipLaunchKernelGGL(k_sweep, dim3(blocks), dim3(256), 0, e->stream, e->tbl(), 0, 0ll, (uint32_t)p.exp_hour,
+                           p.canon, e->issuer_counts, e->pairs, e->npairs - 1, e->d_count);
     }
   }
   unsigned long long cnt;

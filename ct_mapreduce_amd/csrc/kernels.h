@@ -15,9 +15,9 @@
 //   kernels/pem.h       k_pem_len, k_pem_encode
 //   kernels/entries.h   k_decode_match (decode + first Chain[0] match round), k_chain0_match, k_entry_decode (sweep builds)
 //   kernels/meta.h      k_meta_new
-//   kernels/misc.h      k_fingerprint, k_set_op / k_sweep / k_rehash / k_arena_compact / k_build_pairs / k_list / k_pairs,
+//   kernels/misc.h      k_fingerprint, k_set_op / k_sweep / k_rehash / k_arena_compact / k_build_pairs / k_list,
 //                       k_synth_*
-//   kernels/image.h     k_known_export / k_known_count / k_known_pack / k_known_bloom (the known-certificate image)
+//   kernels/image.h     k_pairs_slots / k_known_export / k_known_count / k_known_pack / k_known_bloom (the known-certificate image)
 //   kernels/lists.h     k_lists_count / k_lists_write (per-issuer known-serial lists as text)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once

@@ -10,7 +10,7 @@ namespace ctmr {
 // A member record of the image: u64 serial_len (0..40) | serial octets zero-padded to 40 — what k_list writes.
 constexpr uint32_t KNOWN_REC_BYTES = 48;
 
-// Export, step 1: the non-empty (expDate, issuer) pairs with the pair-table slot each lives in (k_pairs + the slot):
+// Export, step 1: the non-empty (expDate, issuer) pairs with the pair-table slot each lives in:
 // out[3k] = key, out[3k+1] = count, out[3k+2] = slot.
 __global__ void __launch_bounds__(256) k_pairs_slots(const PairSlot* pairs, uint64_t npairs, unsigned long long* out,
                                                      uint64_t cap, unsigned long long* count) {

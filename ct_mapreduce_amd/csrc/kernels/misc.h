@@ -222,20 +222,6 @@ __global__ void __launch_bounds__(256) k_list(Table t, uint32_t exp_hour_key,
   for (int q = 0; q < 5; q++) o[1 + q] = c->s[q];
 }
 
-// KeysToChan: dump the non-empty (expDate, issuer) pairs.
-__global__ void __launch_bounds__(256) k_pairs(const PairSlot* pairs, uint64_t npairs,
-                                               unsigned long long* out, uint64_t cap,
-                                               unsigned long long* count) {
-  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= npairs) return;
-  const unsigned long long k = pairs[j].key, c = pairs[j].count;
-  if (k == 0ull || c == 0ull) return;
-  const unsigned long long at = atomicAdd(count, 1ull);
-  if (at >= cap) return;
-  out[2 * at] = k;
-  out[2 * at + 1] = c;
-}
-
 // ------------------------------------------------------------------ synthetic generator
 __global__ void __launch_bounds__(256) k_synth_len(SynthCfg c, uint64_t first, uint64_t n,
                                                    uint64_t* offsets) {
