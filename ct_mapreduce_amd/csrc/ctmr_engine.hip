@@ -200,6 +200,7 @@ struct ctmr_engine {
   unsigned long long* issuer_counts = nullptr;
   uint32_t epoch = 0;
   bool pairs_dirty = false;  // pair table must be rebuilt before the next cardinality / keys query
+  int known_order = CTMR_KNOWN_ORDER_ANY;  // ctmr_set_known_order: the order inside a set of an export / a list
   // issuer table
   uint32_t max_issuers = 0;
   uint8_t* d_issuer_valid = nullptr;
@@ -685,5 +686,6 @@ extern "C" {
 #include "engine/synth.inc"
 #include "engine/image.inc"
 #include "engine/lists.inc"
+#include "engine/sort.inc"
 
 }  // extern "C"

@@ -222,8 +222,12 @@ int known_export_prepare(ctmr_engine* e, KnownExport* x) {
   return CTMR_OK;
 }
 
+int known_sort_sets(ctmr_engine* e, uint8_t* d_rec, const std::vector<uint64_t>& first);  // engine/sort.inc
+
 // Export, device side: the member records of sets [s_lo, s_hi) into out (positions relative to the first of s_lo).
-int known_export_members(ctmr_engine* e, KnownExport& x, size_t s_lo, size_t s_hi, uint8_t* d_out) {
+// ordered: under CTMR_KNOWN_ORDER_SORTED each set's records are sorted where they were staged (a caller that only
+// counts bytes passes false).
+int known_export_members(ctmr_engine* e, KnownExport& x, size_t s_lo, size_t s_hi, uint8_t* d_out, bool ordered = true) {
   const uint64_t lo = x.first(s_lo), hi = x.first(s_hi);
   if (hi == lo) return CTMR_OK;
   // sets outside [lo, hi) get a cursor far above the chunk: their members are counted but not written (the slots of no
@@ -238,6 +242,11 @@ int known_export_members(ctmr_engine* e, KnownExport& x, size_t s_lo, size_t s_h
                      (const PairSlot*)e->pairs, e->npairs - 1, (unsigned long long*)e->d_scratch[SC_TMP], d_out, hi - lo);
   HIPCHK(e, hipStreamSynchronize(e->stream));
   HIPCHK(e, hipGetLastError());
+  if (ordered && e->known_order == CTMR_KNOWN_ORDER_SORTED) {
+    std::vector<uint64_t> first(s_hi - s_lo + 1);
+    for (size_t s = s_lo; s <= s_hi; s++) first[s - s_lo] = x.first(s) - lo;
+    return known_sort_sets(e, d_out, first);
+  }
   return CTMR_OK;
 }
 

@@ -136,10 +136,11 @@ int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
 }
 
 // Device records [lo, hi) of the list order, staged and counted: *bytes = their text, cnt[] their block offsets.
+// ordered: as known_export_members takes it (the text's size does not depend on the order).
 int known_lists_count(ctmr_engine* e, KnownLists& L, size_t s_lo, size_t s_hi, uint8_t* d_rec, unsigned long long* cnt,
-                      uint64_t* bytes) {
+                      uint64_t* bytes, bool ordered) {
   int r;
-  if ((r = known_export_members(e, L.x, s_lo, s_hi, d_rec))) return r;
+  if ((r = known_export_members(e, L.x, s_lo, s_hi, d_rec, ordered))) return r;
   const uint64_t n = L.x.first(s_hi) - L.x.first(s_lo), nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
   HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
   hipLaunchKernelGGL(k_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec, n, cnt);
@@ -201,7 +202,7 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
   if (sized) {
     uint64_t dev_bytes = 0;
     for (size_t c = 0; c < nch; c++) {
-      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &chunk_bytes[c]))) return r;
+      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &chunk_bytes[c], nch <= 1))) return r;
       dev_bytes += chunk_bytes[c];
     }
     info->text_bytes = dev_bytes + L.host_bytes;
@@ -221,7 +222,7 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
     const uint64_t lo = L.x.first(cut[c]), hi = L.x.first(cut[c + 1]);
     uint64_t bytes = chunk_bytes[c];
     if (nch > 1)  // (one chunk: still staged and scanned from the sizing pass)
-      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &bytes))) return r;
+      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &bytes, true))) return r;
     const size_t p0 = std::lower_bound(pts.begin(), pts.end(), lo) - pts.begin();
     const size_t p1 = std::lower_bound(pts.begin(), pts.end(), hi) - pts.begin();
     std::vector<uint64_t> rel(p1 - p0);

@@ -19,6 +19,8 @@
 //                       k_synth_*
 //   kernels/image.h     k_pairs_slots / k_known_export / k_known_count / k_known_pack / k_known_bloom (the known-certificate image)
 //   kernels/lists.h     k_lists_count / k_lists_write (per-issuer known-serial lists as text)
+//   kernels/sort.h      k_sort_keys / k_sort_hist / k_sort_scatter / k_sort_heads / k_sort_regroup / k_sort_gather (the
+//                       order inside a known-certificate set: a segmented radix sort of member records)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once
 #include "kernels/readers.h"
@@ -36,3 +38,4 @@
 #include "kernels/misc.h"
 #include "kernels/image.h"
 #include "kernels/lists.h"
+#include "kernels/sort.h"

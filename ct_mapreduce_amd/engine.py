@@ -750,6 +750,27 @@ class Engine:
         writer.store_known_lists(ids, ioff, text, toff)
         return int(info.issuers)
 
+    # ---- the order inside a set (include/ctmr.h ctmr_known_sort* / ctmr_set_known_order; CPU twin:
+    # known_image.sort)
+    def set_known_order(self, order):
+        """N.KNOWN_ORDER_SORTED: known_export* and known_lists* write each set's members / each expDate's lines in
+        ascending byte-string order, so an export is a pure function of the sets held; N.KNOWN_ORDER_ANY (the default):
+        any order."""
+        self._ck(self._lib.ctmr_set_known_order(self._h, int(order)))
+
+    def known_sort(self, image) -> bytes:
+        """`image` with the member records of every set sorted on the GPU (repeats kept, meta unchanged)."""
+        buf = np.frombuffer(bytes(image), np.uint8).copy()
+        self._ck(self._lib.ctmr_known_sort(self._h, buf.ctypes.data if len(buf) else None, len(buf)))
+        return buf.tobytes()
+
+    def known_sort_device(self, meta, d_members):
+        """Sorts the member records (a torch uint8 tensor on this engine's device) of the image whose meta part is
+        `meta` in place, set by set."""
+        meta = bytes(meta)
+        n, ptr = self._members_ptr(d_members)
+        self._ck(self._lib.ctmr_known_sort_device(self._h, meta, len(meta), ptr, n))
+
     # ---- synthetic input (bench / tests)
     def synth_view_device(self, cfg: N.SynthConfig, first, n, align, d_starts, d_ends, d_payload, payload_cap,
                           d_issuer_idx, d_entry_type) -> int:

@@ -3,7 +3,8 @@ Redis protocol stream of remote_cache.redis_dump.
 
 An image is what `Engine.known_export` writes and `Engine.known_import` reads: every serials::<expDate>::<issuerID> set
 of the engine — what a restarted reference deployment still finds in its Redis.  `parse` checks exactly what the library
-checks before it applies an image; `build` is the canonical writer; `query` / `subtract` are the twins of
+checks before it applies an image; `build` is the canonical writer; `sort` is the twin of `Engine.known_sort`
+(every set's member records in ascending order, repeats kept); `query` / `subtract` are the twins of
 `Engine.known_query` / `Engine.known_remove` over a dict of sets; `to_resp` / `from_resp` turn an image into the
 SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start from a reference deployment's Redis
 contents).  Pure Python + numpy.
@@ -209,6 +210,26 @@ def build(sets) -> bytes:
         rec["len"][i] = len(m)
         rec["serial"][i, :len(m)] = np.frombuffer(m, np.uint8)
     return meta + rec.tobytes()
+
+
+def sort(image) -> bytes:
+    """The image with the member records of every set in ascending order of their serials as byte strings (a proper
+    prefix first) — Engine.known_sort without a GPU (include/ctmr.h).  Repeated records stay, the meta
+    part stays byte for byte; raises ImageError for what `parse` rejects."""
+    parse(image)
+    b = bytes(image)
+    _, _, _, n_iss, _, n_sets, n_mem, _, _, _ = _HEADER.unpack_from(b, 0)
+    at = len(b) - n_mem * MEMBER_BYTES
+    if n_mem < 2:
+        return b
+    rec = np.frombuffer(b, MEMBER_DTYPE, count=n_mem, offset=at)
+    so = HEADER_BYTES + 32 * n_iss
+    counts = [_SET.unpack_from(b, so + SET_BYTES * s)[3] for s in range(n_sets)]
+    set_of = np.repeat(np.arange(n_sets), counts)
+    # the 40 padded octets as five big-endian words, then serial_len: numpy compares them as unsigned integers
+    words = np.ascontiguousarray(rec["serial"]).view(">u8").astype(np.uint64)
+    order = np.lexsort((rec["len"],) + tuple(words[:, k] for k in (4, 3, 2, 1, 0)) + (set_of,))
+    return b[:at] + rec[order].tobytes()
 
 
 # ---- bulk SetContains / SetRemove with an image as the batch (include/ctmr.h ctmr_known_query / ctmr_known_remove;

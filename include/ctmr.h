@@ -263,7 +263,8 @@ int ctmr_table_info_get(ctmr_engine* e, ctmr_table_info* out);
  *   host section   host_bytes of {u32 key_len, key, u32 member_len, member} sorted by (key, member): the serials::
  *                  members of the host-side store (serials longer than CTMR_MAX_SERIAL; issuers not registered)
  *   members        at the next multiple of 64 B: n_members × 48 B {u64 serial_len (0..40), serial[40] zero-padded}
- *                  (k_list's record); the order inside a set is unspecified
+ *                  (k_list's record); the order inside a set is unspecified unless the writer sorted it (below:
+ *                  ctmr_set_known_order, ctmr_known_sort)
  * The bytes before the members ("meta") are small and live on the host; the device variants take meta and members as
  * separate buffers.  Exported members are the live members SetList / SetCardinality see (a Bloom-mode rank's SHADOW
  * keys are not: the union of a group's images holds each key once).  ExpireAt overrides, crl:: / issuer:: / log:: keys
@@ -370,7 +371,9 @@ int ctmr_known_remove_device(ctmr_engine* e, const uint8_t* meta, size_t meta_le
  * Lines.  hex.EncodeToString(serial) + "\n": lowercase, every raw octet, leading 00 kept; an empty serial is a line "\n".
  *   One line per set member, not deduplicated: a serial known under two expDates of one issuer is listed twice.  Within
  *   a list the lines of one expDate are contiguous and expDates ascend (by their first second, then bytewise as strings);
- *   the order inside an expDate is unspecified.  Lists are ordered by Issuer.ID bytewise.
+ *   the order inside an expDate is unspecified under CTMR_KNOWN_ORDER_ANY; under CTMR_KNOWN_ORDER_SORTED (below) the
+ *   lines of one expDate are in `LC_ALL=C sort` order ("\n" sorts before every hex digit, so a serial comes before
+ *   the serials it is a proper prefix of, as in the image).  Lists are ordered by Issuer.ID bytewise.
  * Left out.  A Bloom-mode rank's SHADOW keys, as in the image: the union of a group's ranks holds each key once, so the
  *   per-issuer concatenation of the ranks' lists is the group's list (up to the order inside an expDate).
  * Read-only: table, pair statistics, counters, host-side store and expiry records are as before.
@@ -394,6 +397,40 @@ int ctmr_known_lists(ctmr_engine* e, int64_t now_unix, uint8_t* text, size_t tex
 /* The same with text in device memory (of this engine's device); host-store lines are copied into it at their places. */
 int ctmr_known_lists_device(ctmr_engine* e, int64_t now_unix, void* d_text, size_t text_cap, uint8_t* ids, size_t ids_cap,
                             uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info);
+
+/* ---- the order inside a set: member records sorted on the GPU.  DESIGN.md §15.
+ *
+ * The order.  Within a set, member records ascend by serial as byte strings — octet by octet, unsigned, a proper prefix
+ *   before the longer string (what sorted() does to Python bytes).  On the 48-byte record this is the order of the 40
+ *   zero-padded octets compared big-endian, then serial_len: the serials "", 00, 00 00 have identical padding and
+ *   serial_len decides between them.  Equal records are indistinguishable, so the sorted bytes of a set are unique.
+ * ctmr_known_sort_device sorts the member records of an image v1 in place, set by set; the meta is read, not changed.
+ *   It validates as ctmr_known_import_device does — magic, version, sizes, set order / gaps / overlaps, issuer ordinals,
+ *   and on the device, before the first record moves, serial_len <= 40 and zero padding: CTMR_E_INVAL leaves the
+ *   buffer as it was.  The issuers the image names need not be registered here; nothing of the engine's state is read
+ *   or changed (table, pair statistics, counters, host-side store, Bloom filter, ctmr_table_info).  Repeated records
+ *   stay, next to each other.  The working buffers (about 82 B per record of a run: two 16-byte key buffers, the permuted
+ *   records aside, digit counts) are allocated before the first record moves: CTMR_E_NOMEM leaves the buffer as it was.
+ *   The records are sorted in runs of whole sets of at most 2^27 records (a larger set alone); a run's permuted records
+ *   are built aside and copied over it only when complete.  Returns after the engine's stream has drained.
+ * ctmr_known_sort does the same for an image in host memory (members staged on the device and copied back; the host
+ *   section is already ordered by (key, member) and stays).
+ * Cost.  A run is sorted in ROUNDS of a stable radix sort over (tie group, 8 serial octets): one round per 8 octets
+ *   while two records of a set still agree in every octet compared so far, the sixth and last on serial_len — AT MOST
+ *   SIX ROUNDS WHATEVER THE DATA HOLDS, and none for a run of one-member sets.  CT serials (16..20 random octets) take
+ *   one; a CA that starts every serial with the same 8 octets pays one more round, never a quadratic tie-break.
+ * ctmr_set_known_order: CTMR_KNOWN_ORDER_ANY (the default) leaves every call as it was.  Under
+ *   CTMR_KNOWN_ORDER_SORTED ctmr_known_export, ctmr_known_export_device, ctmr_known_lists and ctmr_known_lists_device
+ *   write each set's members / each expDate's lines in the order above, and nothing else about them changes (two-call
+ *   sizing, CTMR_E_RANGE writing nothing, the places of the host-store pieces — whose lines std::set already orders).
+ *   A sorted export is a pure function of the sets the engine holds: engines that reached the same sets by different
+ *   batch orders, by import, or under different issuer numberings export identical bytes (every issuer registered, no
+ *   serial above CTMR_MAX_SERIAL octets: exact; the host section is deterministic too).  Any other value: CTMR_E_INVAL. */
+#define CTMR_KNOWN_ORDER_ANY 0
+#define CTMR_KNOWN_ORDER_SORTED 1
+int ctmr_set_known_order(ctmr_engine* e, int order);
+int ctmr_known_sort(ctmr_engine* e, uint8_t* image, size_t len);
+int ctmr_known_sort_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, void* d_members, uint64_t n_members);
 
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
