@@ -486,13 +486,22 @@ int ensure_capacity(ctmr_engine* e, uint64_t incoming, bool round_start, uint64_
   int ar;
   if ((ar = ensure_arena(e, incoming_cells == ~0ull ? incoming : incoming_cells, round_start))) return ar;  // one cell per entry / received key / point insert
   if ((e->occupied + incoming) * 4 <= e->nslots * 3) return CTMR_OK;
-  // how many members are alive decides the new size: count them with the rebuild itself when tombstones may exist
-  uint64_t want = pow2_at_least((e->occupied + incoming) * 2);
+  // how many members are alive decides the new size, not how many slots are claimed: tombstones give their slots back in
+  // any rebuild, so a table whose members keep leaving is rebuilt at the size it has.  (Sized by `occupied`, every
+  // rebuild of an uncapped table at least doubled it, however few members were left: tests/test_gpu_table_lifecycle.py.)
+  unsigned long long alive = 0;
+  HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
+  hipLaunchKernelGGL(k_count_live, dim3((unsigned)((e->nslots + 255) / 256)), dim3(256), 0, e->stream,
+                     (const unsigned long long*)e->index, e->nslots, e->d_count);
+  HIPCHK(e, hipMemcpyAsync(&alive, e->d_count, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  uint64_t want = pow2_at_least((alive + incoming) * 2);
   if (want > e->max_slots) want = e->max_slots;
   if (want < e->nslots) want = e->nslots;
   // the smallest index that still keeps the 3/4 bound: what to fall back to when the comfortable size (load 1/2, old and
   // new index resident at once) does not fit the device
-  uint64_t least = pow2_at_least(((e->occupied + incoming) * 4 + 2) / 3);
+  uint64_t least = pow2_at_least(((alive + incoming) * 4 + 2) / 3);
   if (least < e->nslots) least = e->nslots;
   for (int attempt = 0; attempt < 3; attempt++) {
     unsigned long long* nt = nullptr;

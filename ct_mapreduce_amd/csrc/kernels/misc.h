@@ -132,6 +132,16 @@ __global__ void __launch_bounds__(256) k_sweep(Table t, int any_key,
   atomicAdd(removed, 1ull);
 }
 
+// The live words of the index (neither empty nor a tombstone): what a rebuild will carry over, counted before the new
+// index is sized.  One atomic per wave that holds any.
+__global__ void __launch_bounds__(256) k_count_live(const unsigned long long* index, uint64_t nslots,
+                                                    unsigned long long* live) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long w = j < nslots ? index[j] : 0ull;
+  const unsigned long long m = __ballot((w != 0ull) & (w != IDX_TOMB));
+  if (m && (threadIdx.x & 63) == 0) atomicAdd(live, (unsigned long long)__popcll(m));
+}
+
 // Table growth: every live word of the old index is re-inserted into the new (zeroed) one — the keys are distinct, so
 // one CAS claims the slot.  The word moves verbatim (tag and ref do not depend on the table size; the arena — copied
 // as it is when it grows too — keeps every cell where it was).  Tombstones stay behind, which is how their slots are
@@ -147,7 +157,7 @@ __global__ void __launch_bounds__(256) k_rehash(const unsigned long long* old_in
 #pragma unroll
   for (int k = 0; k < 5; k++) s[k] = c->s[k];
   uint64_t q = key_hash(c->meta & ~CELL_SHADOW, s) & t.mask;
-  for (uint64_t probes = 0;; probes++) {  // the new index holds at most half as many members as it has slots: this terminates
+  for (uint64_t probes = 0;; probes++) {  // the new index holds at most 3/4 as many members as it has slots: this terminates
     if (atomicCAS(&t.index[q], 0ull, w) == 0ull) break;
     q = probe_next(q, probes, t.mask);
   }
