@@ -120,8 +120,11 @@ int ctmr_meta_new(ctmr_engine* e, ctmr_meta_item* items, uint64_t items_cap, uin
         e->last_meta_items = got;
         break;
       }
-      if (r != CTMR_E_RANGE || attempt) return r;
-      cap = got + 1024;  // the memo was cleared: the second run re-reports everything into a buffer that fits
+      if (r != CTMR_E_RANGE || attempt == 2) return r;
+      // the memo was cleared: the next run re-reports everything into a buffer that fits.  `got` of the FIRST run counted
+      // against the memo earlier batches left — a cold memo reports those items again, and when they are more than the
+      // 1024 of slack the second run overflows too; its own count is the cold one, which the third run repeats.
+      cap = got + 1024;
     }
     e->last_meta_valid = true;
   }

@@ -16,62 +16,9 @@ from tests import storage_mirror as S
 from ct_mapreduce_amd.engine import Batch
 from oracle import oracle as orc
 from tests import der as D
+from tests.meta_corpus import dp, dp_ext, expected_first_sightings, got_first_sightings, uri
 
 NOW = synth.BASE_TIME
-
-
-def dp_ext(*points, critical=None):
-    return D.ext(0x1f, D.seq(*points), critical)
-
-
-def dp(*general_names, reasons=None, crl_issuer=None):
-    parts = []
-    if general_names:
-        parts.append(D.tlv(0xa0, D.tlv(0xa0, b"".join(general_names))))
-    if reasons:
-        parts.append(D.tlv(0x81, reasons))
-    if crl_issuer:
-        parts.append(D.tlv(0xa2, crl_issuer))
-    return D.seq(*parts)
-
-
-def uri(s):
-    return D.tlv(0x86, s)
-
-
-def expected_first_sightings(certs, issuer_canon, new_idx, exp_hours):
-    """The reference's memo semantics over the new certificates, in log order."""
-    seen, out = set(), set()
-    for i in new_idx:
-        meta = orc.cert_meta(certs[i])
-        assert meta is not None
-        name, uris, m = meta
-        c = issuer_canon[i]
-        host = (m.n_crl_ext > 1 or len(name) > 4096 or any(len(u) > 4096 for u in uris) or m.n_crl > 4
-                or len(certs[i]) > 0xfffe)
-        items = [(N.MK_EXPDATE, c, int(exp_hours[i]), b"")]
-        if host:
-            out.add((N.MK_HOST, i))
-        else:
-            items += [(N.MK_DN, c, 0, name)] + [(N.MK_CRL, c, 0, u) for u in uris]
-        for it in items:
-            if it not in seen:
-                seen.add(it)
-                out.add(it)
-    return out
-
-
-def got_first_sightings(eng, items):
-    out = set()
-    for kind, entry, idx, exp_hour, b in items:
-        c = eng.issuer_info(idx).canonical_idx
-        if kind == N.MK_HOST:
-            out.add((kind, entry))
-        elif kind == N.MK_EXPDATE:
-            out.add((kind, c, exp_hour, b""))
-        else:
-            out.add((kind, c, 0, b))
-    return out
 
 
 def test_first_sightings_on_synthetic_batches():
