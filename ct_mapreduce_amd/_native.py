@@ -23,6 +23,7 @@ PAYLOAD_PAD = 32
 MAX_SERIAL = 40
 E_INVAL, E_HIP, E_NOMEM, E_FULL, E_NOTFOUND, E_RANGE = -1, -2, -3, -4, -5, -6
 KNOWN_ORDER_ANY, KNOWN_ORDER_SORTED = 0, 1
+KNOWN_UNION, KNOWN_MINUS, KNOWN_INTERSECT = 0, 1, 2
 
 
 class Config(C.Structure):
@@ -171,6 +172,9 @@ SIGNATURES = {
     "ctmr_set_known_order": (C.c_int, [_P, C.c_int]),
     "ctmr_known_sort": (C.c_int, [_P, _P, C.c_size_t]),
     "ctmr_known_sort_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64]),
+    "ctmr_known_merge": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(KnownImageInfo)]),
+    "ctmr_known_merge_device": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64,
+                                          _P, C.c_size_t, _P, C.c_uint64, C.POINTER(KnownImageInfo)]),
     "ctmr_xchg_map_device": (C.c_int, [_P, C.POINTER(Shard), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]),
     "ctmr_xchg_map_chunk_device": (C.c_int, [_P, C.POINTER(Shard), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P,

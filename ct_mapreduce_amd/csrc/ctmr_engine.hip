@@ -13,6 +13,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <iterator>
 #include <system_error>
 #include <thread>
 #include <cmath>
@@ -696,5 +697,6 @@ extern "C" {
 #include "engine/image.inc"
 #include "engine/lists.inc"
 #include "engine/sort.inc"
+#include "engine/merge.inc"
 
 }  // extern "C"

@@ -21,6 +21,8 @@
 //   kernels/lists.h     k_lists_count / k_lists_write (per-issuer known-serial lists as text)
 //   kernels/sort.h      k_sort_keys / k_sort_hist / k_sort_scatter / k_sort_heads / k_sort_regroup / k_sort_gather (the
 //                       order inside a known-certificate set: a segmented radix sort of member records)
+//   kernels/merge.h     k_merge_ascending / k_merge_unique / k_merge_first / k_merge_rank / k_merge_sets / k_merge_place
+//                       (set algebra on known-certificate images: union, minus, intersect of canonical member records)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once
 #include "kernels/readers.h"
@@ -39,3 +41,4 @@
 #include "kernels/image.h"
 #include "kernels/lists.h"
 #include "kernels/sort.h"
+#include "kernels/merge.h"

@@ -116,6 +116,18 @@ class Group:
         from .known_image import merge_lists
         return merge_lists([e.known_lists(now) for e in self.engines])
 
+    def known_export(self) -> bytes:
+        """The group's known-certificate image: every local rank's sorted export folded with UNION on rank 0's engine
+        (Engine.known_merge) — byte for byte what ONE engine holding the group's sets exports under
+        N.KNOWN_ORDER_SORTED, whatever the world size, in owner and in Bloom mode (a Bloom-mode rank's SHADOW keys are
+        left out of its export already).  In-process groups only, like known_lists."""
+        out = None
+        for e in self.engines:
+            img = e.known_export()
+            out = self.engines[0].known_merge(N.KNOWN_UNION, img) if out is None else \
+                self.engines[0].known_merge(N.KNOWN_UNION, out, img)
+        return out
+
     def known_query(self, image):
         """SetContains over the group for every member of `image` → (flags, host_flags): numpy uint8, 1 where ANY local
         rank holds the member (every rank is asked about every record: a Bloom-mode rank keeps a key where it was first

@@ -771,6 +771,45 @@ class Engine:
         n, ptr = self._members_ptr(d_members)
         self._ck(self._lib.ctmr_known_sort_device(self._h, meta, len(meta), ptr, n))
 
+    # ---- set algebra on images (include/ctmr.h ctmr_known_merge*; CPU twins: known_image.union / minus /
+    # intersect)
+    def known_merge(self, op, a, b=None) -> bytes:
+        """The canonical image of a ∪ b (N.KNOWN_UNION), a \\ b (N.KNOWN_MINUS) or a ∩ b (N.KNOWN_INTERSECT), set by set,
+        on the GPU with no table behind it; b=None is the empty image (UNION then normalises a).  The engine's own sets
+        play no part.  Sized by the bounds (|a| + |b| members, the two metas), so one call."""
+        a = bytes(a)
+        b = None if b is None else bytes(b)
+        cap = len(a) + (len(b) if b is not None else 0) + 64
+        info = N.KnownImageInfo()
+        for _ in range(2):   # (a second call only when host-section pairs moved into sets and issuers of their own)
+            out = np.empty(cap, np.uint8)
+            rc = self._lib.ctmr_known_merge(self._h, int(op), a, len(a), b, len(b) if b is not None else 0,
+                                            out.ctypes.data, cap, C.byref(info))
+            if rc != N.E_RANGE:
+                break
+            cap = info.image_bytes
+        self._ck(rc)
+        return out[:info.image_bytes].tobytes()
+
+    def known_merge_device(self, op, a_meta, d_a, b_meta=None, d_b=None):
+        """known_merge with the member records in device memory (torch uint8 tensors on this engine's device)
+        → (meta bytes, torch uint8 tensor of the result's member records; a view)."""
+        import torch
+        a_meta = bytes(a_meta)
+        na, pa = self._members_ptr(d_a)
+        nb, pb = (0, None) if b_meta is None else self._members_ptr(d_b)
+        b_meta = None if b_meta is None else bytes(b_meta)
+        hosts = self._header_counts(a_meta)[1] + (self._header_counts(b_meta)[1] if b_meta is not None else 0)
+        meta_cap = len(a_meta) + (len(b_meta) if b_meta is not None else 0) + 64
+        cap = (na + nb if op == N.KNOWN_UNION else na) + hosts
+        meta = np.empty(meta_cap, np.uint8)
+        out = torch.empty(max(cap, 1) * 48, dtype=torch.uint8, device="cuda:%d" % self.device)
+        info = N.KnownImageInfo()
+        self._ck(self._lib.ctmr_known_merge_device(self._h, int(op), a_meta, len(a_meta), pa, na, b_meta,
+                                                   len(b_meta) if b_meta is not None else 0, pb, nb, meta.ctypes.data,
+                                                   meta_cap, C.c_void_p(out.data_ptr()), cap, C.byref(info)))
+        return meta[:info.meta_bytes].tobytes(), out[:info.members * 48]
+
     # ---- synthetic input (bench / tests)
     def synth_view_device(self, cfg: N.SynthConfig, first, n, align, d_starts, d_ends, d_payload, payload_cap,
                           d_issuer_idx, d_entry_type) -> int:

@@ -5,7 +5,8 @@ An image is what `Engine.known_export` writes and `Engine.known_import` reads: e
 of the engine — what a restarted reference deployment still finds in its Redis.  `parse` checks exactly what the library
 checks before it applies an image; `build` is the canonical writer; `sort` is the twin of `Engine.known_sort`
 (every set's member records in ascending order, repeats kept); `query` / `subtract` are the twins of
-`Engine.known_query` / `Engine.known_remove` over a dict of sets; `to_resp` / `from_resp` turn an image into the
+`Engine.known_query` / `Engine.known_remove` over a dict of sets; `union` / `minus` / `intersect` are the twins of
+`Engine.known_merge` (set algebra on images, key by key); `to_resp` / `from_resp` turn an image into the
 SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start from a reference deployment's Redis
 contents).  Pure Python + numpy.
 """
@@ -280,6 +281,45 @@ def subtract(sets, image) -> dict:
         if left:
             out[bytes(k)] = left
     return out
+
+
+# ---- set algebra on images (include/ctmr.h ctmr_known_merge*), without a GPU: `build` over the algebra
+# of the sets `parse` reads, key by key.  None stands for the empty image.
+
+KNOWN_UNION, KNOWN_MINUS, KNOWN_INTERSECT = 0, 1, 2
+
+
+def _sets_of(image) -> dict:
+    return {} if image is None else {k: set(v) for k, v in parse(image).sets.items()}
+
+
+def union(*images) -> bytes:
+    """The canonical image of the union of the images' sets; union(a) normalises a (members sorted, each once, the
+    host-section pairs the member section can carry moved there)."""
+    out = {}
+    for image in images:
+        for k, v in _sets_of(image).items():
+            out.setdefault(k, set()).update(v)
+    return build(out)
+
+
+def minus(a, b) -> bytes:
+    """The canonical image of a's sets without the members b's set of the same key holds."""
+    sb = _sets_of(b)
+    return build({k: v - sb.get(k, set()) for k, v in _sets_of(a).items()})
+
+
+def intersect(a, b) -> bytes:
+    """The canonical image of the members both images hold under the same key."""
+    sb = _sets_of(b)
+    return build({k: v & sb.get(k, set()) for k, v in _sets_of(a).items()})
+
+
+def merge(op, a, b=None) -> bytes:
+    """Engine.known_merge(op, a, b) without a GPU."""
+    if op not in (KNOWN_UNION, KNOWN_MINUS, KNOWN_INTERSECT):
+        raise ValueError("unknown op %r" % (op,))
+    return (union, minus, intersect)[op](a, b)
 
 
 class _SetsCache:

@@ -432,6 +432,44 @@ int ctmr_set_known_order(ctmr_engine* e, int order);
 int ctmr_known_sort(ctmr_engine* e, uint8_t* image, size_t len);
 int ctmr_known_sort_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, void* d_members, uint64_t n_members);
 
+/* ---- set algebra on images: union, minus and intersect of two images v1 on the GPU, with no table behind them.
+ *      DESIGN.md §16.
+ *
+ * Result.  The canonical image of the operation applied key by key to the sets the two images denote — byte for byte
+ *   what the canonical writer (known_image.build) makes of op(sets of A, sets of B): the issuers the surviving sets name
+ *   and no others, in digest order; the sets in key order, none empty; every set's members ascending in the order of
+ *   ctmr_known_sort, each member once; the host section's (key, member) pairs in order.
+ * Host-section pairs that belong in the member section.  The canonical writer puts a pair into the member section
+ *   whenever its key spells an (hour, issuer digest) as a set entry does and its member is at most CTMR_MAX_SERIAL octets.
+ *   An operand's exporter may have put such a pair into the host section (it had not registered the issuer): in the
+ *   result it is a member record, and it is compared with the other operand's member records as if it had been one.
+ * b == NULL with b_len == 0 (device variant: b_meta == NULL, b_meta_len == 0, b_members == 0) is the empty image:
+ *   CTMR_KNOWN_UNION then normalises A — sorts it, drops repeats and moves those host pairs.
+ * Operands.  Any image ctmr_known_import accepts, sorted or not, with repeated records or not.  Everything the import
+ *   rejects in either operand — magic, version, sizes, set order / gaps / overlaps, ordinals, and on the device a
+ *   serial_len above 40 or non-zero padding — and an unknown op are CTMR_E_INVAL with nothing written.  The issuers the
+ *   images name need not be registered here.
+ * Read-only.  Nothing of the engine's state is read or changed (table, pair statistics, counters, host-side store,
+ *   Bloom filter, ctmr_table_info), as for ctmr_known_sort; the operands are const and stay byte for byte as they were.
+ * Sizing.  The two-call convention of ctmr_known_export: a buffer that is too small gives CTMR_E_RANGE with *info filled
+ *   and nothing written.  A caller can size without a first call: at most |A| + |B| member records for CTMR_KNOWN_UNION
+ *   (host-section members counted in) and |A| for the other two; the meta is at most the two metas' bytes together.
+ * Memory.  Every working buffer is allocated before the first byte of the result is written: CTMR_E_NOMEM leaves the
+ *   output buffers as they were.  An operand whose sets are already ascending and free of repeats (a sorted export, an
+ *   earlier result) is used where it lies; any other is copied aside, sorted as ctmr_known_sort does and squeezed.
+ * Both return after the engine's stream has drained.  ctmr_known_merge takes and writes whole images in host memory
+ * (members staged on the device and copied back); ctmr_known_merge_device takes each operand's meta and member records
+ * (device memory of this engine's device, 16-byte aligned) apart and writes the result's the same way. */
+#define CTMR_KNOWN_UNION 0     /* A ∪ B */
+#define CTMR_KNOWN_MINUS 1     /* A \ B */
+#define CTMR_KNOWN_INTERSECT 2 /* A ∩ B */
+int ctmr_known_merge(ctmr_engine* e, int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, uint8_t* out,
+                     size_t cap, ctmr_known_image_info* info);
+int ctmr_known_merge_device(ctmr_engine* e, int op, const uint8_t* a_meta, size_t a_meta_len, const void* d_a, uint64_t a_members,
+                            const uint8_t* b_meta, size_t b_meta_len, const void* d_b, uint64_t b_members,
+                            uint8_t* out_meta, size_t out_meta_cap, void* d_out, uint64_t out_members_cap,
+                            ctmr_known_image_info* info);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner
