@@ -169,6 +169,10 @@ SIGNATURES = {
                                    C.POINTER(KnownListsInfo)]),
     "ctmr_known_lists_device": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t,
                                           C.POINTER(KnownListsInfo)]),
+    "ctmr_known_image_lists": (C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t,
+                                         C.POINTER(KnownListsInfo)]),
+    "ctmr_known_image_lists_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_int64, _P, C.c_size_t, _P, C.c_size_t,
+                                                _P, C.c_size_t, C.POINTER(KnownListsInfo)]),
     "ctmr_set_known_order": (C.c_int, [_P, C.c_int]),
     "ctmr_known_sort": (C.c_int, [_P, _P, C.c_size_t]),
     "ctmr_known_sort_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64]),

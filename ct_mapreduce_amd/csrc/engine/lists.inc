@@ -2,6 +2,8 @@
 // the serials of its sets that have not expired, as the text LocalDiskBackend.StoreKnownCertificateList writes
 // (storage/localdiskbackend.go).  The sets are chosen and ordered on the host (GetIssuerAndDatesFromCache, IsExpiredAt),
 // their members staged with k_known_export (engine/image.inc) and turned into text by k_lists_count / k_lists_write.
+// ctmr_known_image_lists* (DESIGN.md §17) chooses and orders the sets of an IMAGE by the same rules and runs the same
+// write loop over its member records where they lie (k_image_lists_count / k_image_lists_write): no table, no staging.
 // Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/image.inc.
 
 extern "C++" {
@@ -44,6 +46,7 @@ void lists_hex(const std::string& m, std::string* out) {
 
 struct KnownLists {
   KnownExport x;                         // the kept device sets in list order: cursors, record ranges, info.members
+  std::vector<uint64_t> set_slot;        // … and what each was given as: its pair-table slot, or its first record in an image
   std::vector<std::string> ids;          // Issuer.ID of each list, bytewise ascending
   std::vector<uint64_t> id_rec, id_hb;   // per list: device records before it, host-store bytes before it
   struct Host { uint64_t rec, hb; std::string text; };  // the lines of one host-store key: after device record rec - 1
@@ -51,12 +54,19 @@ struct KnownLists {
   uint64_t host_bytes = 0, host_members = 0, sets = 0;
 };
 
-// Which sets, grouped and ordered: the pair table's sets and the host store's serials:: keys, kept while
-// now < the end of their expDate; per Issuer.ID ascending, expDates ascending (by their first second, then as strings).
-int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
+// a device set as integers: key = (rank of its Issuer.ID among ids[]) << 32 | (hour − KNOWN_HOUR_LO) — the per-set work
+// of many sets stays off strings; an hour's ExpDate.ID is formatted only where a host key of the same issuer and second
+// compares to it
+struct ListDev { uint64_t key, count, slot; };
+
+// Which sets, grouped and ordered: the device sets `dev` (kept ones only; ids[rank] = the Issuer.ID of a rank, ascending)
+// and the serials:: keys of `store`, kept while now < the end of their expDate; per Issuer.ID ascending, expDates
+// ascending (by their first second, then as strings).
+int known_lists_arrange(ctmr_engine* e, const std::map<std::string, std::set<std::string>>& store, std::vector<ListDev>& dev,
+                        const std::vector<const std::string*>& ids, int64_t now, KnownLists* L) {
   struct Block { const std::set<std::string>* host = nullptr; };
   std::map<std::string, std::map<std::pair<int64_t, std::string>, Block>> by_id;  // the host-store keys
-  for (auto& kv : e->hstore) {
+  for (auto& kv : store) {
     const std::string& k = kv.first;
     if (k.compare(0, 9, "serials::") != 0 || kv.second.empty()) continue;
     std::vector<std::string> parts;  // strings.Split(key, "::")
@@ -71,22 +81,8 @@ int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
     if (!lists_parse_date(parts[1], &start, &end) || now >= end) continue;  // unparsable: skipped, as the reference does
     by_id[parts[2]][{start, parts[1]}].host = &kv.second;
   }
-  int r;
-  std::vector<PairRec> pr;
-  if ((r = list_pairs(e, &pr))) return r;
-  // the device sets as integers: (rank of the issuer's ID, hour) — the per-set work of a table of many sets stays off
-  // strings; an hour's ExpDate.ID is formatted only where a host-store key of the same issuer and second compares to it
-  std::vector<uint32_t> by_rank, rank_of;
-  issuers_by_id(e, &by_rank, &rank_of);
-  struct Dev { uint64_t key, count, slot; };  // key = rank << 32 | (hour − KNOWN_HOUR_LO)
-  std::vector<Dev> dev;
-  for (auto& p : pr) {
-    if (!hour_fixed(p.exp_hour) || now >= ((int64_t)p.exp_hour + 1) * 3600) continue;
-    dev.push_back({((uint64_t)rank_of[p.canon] << 32) | (uint64_t)(p.exp_hour - KNOWN_HOUR_LO), p.count, p.slot});
-  }
-  std::sort(dev.begin(), dev.end(), [](const Dev& p, const Dev& q) { return p.key < q.key; });
+  std::sort(dev.begin(), dev.end(), [](const ListDev& p, const ListDev& q) { return p.key < q.key; });
   KnownExport& x = L->x;
-  x.cursor.assign(e->npairs, KNOWN_CURSOR_OFF);  // sets not kept stay parked: their members are never written
   uint64_t rec = 0, hb = 0;
   auto put_host = [&](const std::set<std::string>* hs) {
     KnownLists::Host h{rec, hb, std::string()};
@@ -99,7 +95,7 @@ int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
   auto hi_it = by_id.begin();
   while (d < dev.size() || hi_it != by_id.end()) {
     // the next Issuer.ID: of the device sets, of the host-store keys, or of both
-    const std::string* dev_id = d < dev.size() ? &e->issuers[by_rank[dev[d].key >> 32]].id : nullptr;
+    const std::string* dev_id = d < dev.size() ? ids[dev[d].key >> 32] : nullptr;
     const bool take_dev = dev_id && (hi_it == by_id.end() || *dev_id <= hi_it->first);
     const bool take_host = hi_it != by_id.end() && (!dev_id || hi_it->first <= *dev_id);
     L->ids.push_back(take_dev ? *dev_id : hi_it->first);
@@ -118,7 +114,7 @@ int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
       else cmp = exp_date_id(eh).compare(hb_it->first.second);
       L->sets++;
       if (cmp <= 0) {
-        x.cursor[dev[d].slot] = rec;
+        L->set_slot.push_back(dev[d].slot);
         x.set_range.push_back({rec, dev[d].count});
         rec += dev[d].count;
         d++;
@@ -135,29 +131,104 @@ int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
   return CTMR_OK;
 }
 
-// Device records [lo, hi) of the list order, staged and counted: *bytes = their text, cnt[] their block offsets.
-// ordered: as known_export_members takes it (the text's size does not depend on the order).
-int known_lists_count(ctmr_engine* e, KnownLists& L, size_t s_lo, size_t s_hi, uint8_t* d_rec, unsigned long long* cnt,
-                      uint64_t* bytes, bool ordered) {
+// a device set of exp hour h is kept: its ExpDate.ID has four year digits and now < (h + 1) × 3600
+bool lists_hour_kept(int32_t h, int64_t now) { return hour_fixed(h) && now < ((int64_t)h + 1) * 3600; }
+
+// … of an engine: the pair table's sets and the host-side store
+int known_lists_prepare(ctmr_engine* e, int64_t now, KnownLists* L) {
   int r;
-  if ((r = known_export_members(e, L.x, s_lo, s_hi, d_rec, ordered))) return r;
-  const uint64_t n = L.x.first(s_hi) - L.x.first(s_lo), nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
-  HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
-  hipLaunchKernelGGL(k_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec, n, cnt);
-  if ((r = scan_u64(e, (uint64_t*)cnt, nb + 1, false, SC_MISC))) return r;
-  unsigned long long b;
-  HIPCHK(e, hipMemcpyAsync(&b, cnt + nb, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
-  *bytes = b;
+  std::vector<PairRec> pr;
+  if ((r = list_pairs(e, &pr))) return r;
+  std::vector<uint32_t> by_rank, rank_of;
+  issuers_by_id(e, &by_rank, &rank_of);
+  std::vector<const std::string*> ids(by_rank.size());
+  for (size_t k = 0; k < by_rank.size(); k++) ids[k] = &e->issuers[by_rank[k]].id;
+  std::vector<ListDev> dev;
+  for (auto& p : pr)
+    if (lists_hour_kept(p.exp_hour, now))
+      dev.push_back({((uint64_t)rank_of[p.canon] << 32) | (uint64_t)(p.exp_hour - KNOWN_HOUR_LO), p.count, p.slot});
+  if ((r = known_lists_arrange(e, e->hstore, dev, ids, now, L))) return r;
+  KnownExport& x = L->x;
+  x.cursor.assign(e->npairs, KNOWN_CURSOR_OFF);  // sets not kept stay parked: their members are never written
+  for (size_t k = 0; k < L->set_slot.size(); k++) x.cursor[L->set_slot[k]] = x.set_range[k].first;
   return CTMR_OK;
 }
 
-int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, size_t text_cap, uint8_t* ids, size_t ids_cap,
-                     uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info) {
-  KnownLists L;
+// … of an image: its set records (the ID of a set = the padded base64url of its digest in the image: km.ids) and the
+// keys of its host section.  host: the section's pairs as a store, which L points into.
+int image_lists_prepare(ctmr_engine* e, const KnownMeta& km, int64_t now, std::map<std::string, std::set<std::string>>* host,
+                        KnownLists* L) {
+  for (auto& hm : km.host) (*host)[hm.first].insert(hm.second);
+  std::vector<uint32_t> by_rank(km.n_issuers), rank_of(km.n_issuers);
+  for (uint32_t k = 0; k < km.n_issuers; k++) by_rank[k] = k;
+  std::sort(by_rank.begin(), by_rank.end(), [&](uint32_t a, uint32_t b) { return km.ids[a] != km.ids[b] ? km.ids[a] < km.ids[b] : a < b; });
+  std::vector<const std::string*> ids;
+  for (uint32_t k = 0; k < km.n_issuers; k++) {  // (a digest the image lists twice: one ID, one rank)
+    if (!k || km.ids[by_rank[k]] != km.ids[by_rank[k - 1]]) ids.push_back(&km.ids[by_rank[k]]);
+    rank_of[by_rank[k]] = (uint32_t)ids.size() - 1u;
+  }
+  std::vector<ListDev> dev;
+  for (uint64_t s = 0; s < km.n_sets; s++)
+    if (lists_hour_kept(km.set_hour[s], now))
+      dev.push_back({((uint64_t)rank_of[km.set_issuer[s]] << 32) | (uint64_t)(km.set_hour[s] - KNOWN_HOUR_LO),
+                     km.set_first[s + 1] - km.set_first[s], km.set_first[s]});
+  return known_lists_arrange(e, *host, dev, ids, now, L);
+}
+
+// Where the write loop's records come from: staged by k_known_export into a buffer of the loop's (an engine's lists), or
+// the segments of an image — the kept sets in list order, set k the records [seg_src[k], …) of `image`.
+struct ListSource {
+  bool segments = false;           // false: stage with k_known_export
+  const uint8_t* image = nullptr;  // segments: the image's member records on the device
+  DevMem seg;                      // seg_dst[K + 1], seg_src[K], then the error word
+  size_t K = 0;
+  const char* what = "known lists";
+  const uint64_t* dst() const { return (const uint64_t*)seg.p; }
+  const uint64_t* src() const { return dst() + K + 1; }
+  uint32_t* err() const { return (uint32_t*)(dst() + 2 * K + 1); }
+  ListSegs segs(size_t s_lo, size_t s_hi) const { return ListSegs{image, dst() + s_lo, src() + s_lo, (uint32_t)(s_hi - s_lo)}; }
+};
+
+int image_lists_upload(ctmr_engine* e, const KnownLists& L, ListSource* src) {
+  const size_t K = L.x.set_range.size();
+  src->K = K;
+  if (!K) return CTMR_OK;
+  if (K > 0xffffffffull) return fail(e, CTMR_E_NOMEM, "%s: %zu sets", src->what, K);
+  std::vector<uint64_t> t(2 * K + 2, 0ull);
+  for (size_t k = 0; k <= K; k++) t[k] = L.x.first(k);
+  for (size_t k = 0; k < K; k++) t[K + 1 + k] = L.set_slot[k];
+  if (src->seg.alloc(t.size() * 8) != hipSuccess) return fail(e, CTMR_E_NOMEM, "%s: no device memory for %zu segments", src->what, K);
+  HIPCHK(e, hipMemcpyAsync(src->seg.p, t.data(), t.size() * 8, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));  // (t goes out of scope)
+  return CTMR_OK;
+}
+
+// Device records [lo, hi) of the list order, staged and counted: *bytes = their text, cnt[] their block offsets.
+// ordered: as known_export_members takes it (the text's size does not depend on the order).
+// An image's segments are counted where they lie, and every record read is validated.
+int known_lists_count(ctmr_engine* e, KnownLists& L, const ListSource& src, size_t s_lo, size_t s_hi, uint8_t* d_rec,
+                      unsigned long long* cnt, uint64_t* bytes, bool ordered) {
   int r;
-  if ((r = known_lists_prepare(e, now, &L))) return r;
+  if (!src.segments && (r = known_export_members(e, L.x, s_lo, s_hi, d_rec, ordered))) return r;
+  const uint64_t n = L.x.first(s_hi) - L.x.first(s_lo), nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
+  HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
+  if (!src.segments) hipLaunchKernelGGL(k_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec, n, cnt);
+  else if (n) hipLaunchKernelGGL(k_image_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, src.segs(s_lo, s_hi), n, cnt, src.err());
+  if ((r = scan_u64(e, (uint64_t*)cnt, nb + 1, false, SC_MISC))) return r;
+  unsigned long long b;
+  uint32_t err = 0;
+  HIPCHK(e, hipMemcpyAsync(&b, cnt + nb, 8, hipMemcpyDeviceToHost, e->stream));
+  if (src.segments && n) HIPCHK(e, hipMemcpyAsync(&err, src.err(), 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  *bytes = b;
+  return known_record_error(e, err, src.what);
+}
+
+// The sizing and the write loop over the sets L arranged, their records from src.
+int known_lists_emit(ctmr_engine* e, KnownLists& L, const ListSource& src, bool device, uint8_t* text, size_t text_cap,
+                     uint8_t* ids, size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info) {
+  int r;
   const uint64_t N = L.x.info.members, G = L.ids.size();
   uint64_t ids_bytes = 0;
   for (auto& s : L.ids) ids_bytes += s.size();
@@ -190,30 +261,40 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
   DevMem d_rec, tmp, d_text;
   const uint64_t nbmax = (max_n + LIST_BLOCK - 1) / LIST_BLOCK;
   const size_t off_pts = (nbmax + 1) * 8, off_po = off_pts + max_pts * 8;
-  if (N && (d_rec.alloc(max_n * KNOWN_REC_BYTES) != hipSuccess || tmp.alloc(off_po + max_pts * 8 + 8) != hipSuccess))
-    return fail(e, CTMR_E_NOMEM, "known lists: no device memory to stage %llu member records", (unsigned long long)max_n);
+  if (N && ((!src.segments && d_rec.alloc(max_n * KNOWN_REC_BYTES) != hipSuccess) || tmp.alloc(off_po + max_pts * 8 + 8) != hipSuccess))
+    return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu member records", src.what, (unsigned long long)max_n);
   unsigned long long* cnt = (unsigned long long*)tmp.p;
   std::vector<uint64_t> chunk_bytes(nch, ~0ull);
   // sizing: one count pass over every chunk, unless every buffer holds its bound (81 B per member for the text) and
   // the pass that writes can size as it goes; a single chunk is staged once either way
   const bool caps_ok = (!G || (ids && ids_cap >= ids_bytes)) && offs && offs_cap >= 2 * (G + 1);
   const bool roomy = caps_ok && text && text_cap >= (uint64_t)LIST_LINE_MAX * N + L.host_bytes;
-  const bool sized = nch <= 1 || !roomy;
+  const bool sized = nch <= 1 || !roomy || src.segments;  // (an image's records are validated before the first text byte)
   if (sized) {
     uint64_t dev_bytes = 0;
     for (size_t c = 0; c < nch; c++) {
-      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &chunk_bytes[c], nch <= 1))) return r;
+      if ((r = known_lists_count(e, L, src, cut[c], cut[c + 1], d_rec.u8(), cnt, &chunk_bytes[c], nch <= 1))) return r;
       dev_bytes += chunk_bytes[c];
     }
     info->text_bytes = dev_bytes + L.host_bytes;
     if (!caps_ok || (info->text_bytes && (!text || text_cap < info->text_bytes)))
-      return fail(e, CTMR_E_RANGE, "known lists: %llu text bytes, %llu ID bytes and %llu offsets needed",
+      return fail(e, CTMR_E_RANGE, "%s: %llu text bytes, %llu ID bytes and %llu offsets needed", src.what,
                   (unsigned long long)info->text_bytes, (unsigned long long)ids_bytes, (unsigned long long)(2 * (G + 1)));
   }
   // ---- write: chunk by chunk, each at its place among the host-store pieces
   std::vector<uint64_t> D(pts.size(), 0);  // the device text offset at each point
   size_t text_cap_dev = 0;
   uint64_t base = 0;
+  auto splits = [&](uint64_t lo, uint64_t hi) {  // host pieces strictly inside records [lo, hi)
+    const auto h = std::upper_bound(L.host.begin(), L.host.end(), lo, [](uint64_t v, const KnownLists::Host& x) { return v < x.rec; });
+    return h != L.host.end() && h->rec < hi;
+  };
+  if (src.segments) {  // every buffer before the first text byte: the largest chunk that is staged as text
+    for (size_t c = 0; c < nch; c++)
+      if (!device || splits(L.x.first(cut[c]), L.x.first(cut[c + 1]))) text_cap_dev = std::max<size_t>(text_cap_dev, chunk_bytes[c]);
+    if (text_cap_dev && d_text.alloc(text_cap_dev) != hipSuccess)
+      return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu text bytes", src.what, (unsigned long long)text_cap_dev);
+  }
   auto hb_le = [&](uint64_t rec) {  // host-store bytes of the pieces that go in at or before device record rec
     size_t k = std::upper_bound(L.host.begin(), L.host.end(), rec, [](uint64_t v, const KnownLists::Host& h) { return v < h.rec; }) - L.host.begin();
     return k ? L.host[k - 1].hb + L.host[k - 1].text.size() : 0ull;
@@ -222,21 +303,21 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
     const uint64_t lo = L.x.first(cut[c]), hi = L.x.first(cut[c + 1]);
     uint64_t bytes = chunk_bytes[c];
     if (nch > 1)  // (one chunk: still staged and scanned from the sizing pass)
-      if ((r = known_lists_count(e, L, cut[c], cut[c + 1], d_rec.u8(), cnt, &bytes, true))) return r;
+      if ((r = known_lists_count(e, L, src, cut[c], cut[c + 1], d_rec.u8(), cnt, &bytes, true))) return r;
     const size_t p0 = std::lower_bound(pts.begin(), pts.end(), lo) - pts.begin();
     const size_t p1 = std::lower_bound(pts.begin(), pts.end(), hi) - pts.begin();
     std::vector<uint64_t> rel(p1 - p0);
     for (size_t k = p0; k < p1; k++) rel[k - p0] = pts[k] - lo;
     // host pieces strictly inside the chunk split its text: then it is staged and copied piece by piece
     const auto h0 = std::upper_bound(L.host.begin(), L.host.end(), lo, [](uint64_t v, const KnownLists::Host& h) { return v < h.rec; });
-    const bool split = h0 != L.host.end() && h0->rec < hi;
+    const bool split = splits(lo, hi);
     uint8_t* dest;
     if (device && !split) {
       dest = text + base + hb_le(lo);
     } else {
       if (text_cap_dev < bytes) {
         if (d_text.alloc(bytes) != hipSuccess)
-          return fail(e, CTMR_E_NOMEM, "known lists: no device memory to stage %llu text bytes", (unsigned long long)bytes);
+          return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu text bytes", src.what, (unsigned long long)bytes);
         text_cap_dev = bytes;
       }
       dest = d_text.u8();
@@ -245,8 +326,12 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
     unsigned long long* d_po = (unsigned long long*)(tmp.u8() + off_po);
     if (!rel.empty()) HIPCHK(e, hipMemcpyAsync(d_pts, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, e->stream));
     const uint64_t n = hi - lo, nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
-    hipLaunchKernelGGL(k_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec.p, n,
-                       (const unsigned long long*)cnt, dest, (const uint64_t*)d_pts, (uint64_t)rel.size(), d_po);
+    if (!src.segments)
+      hipLaunchKernelGGL(k_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec.p, n,
+                         (const unsigned long long*)cnt, dest, (const uint64_t*)d_pts, (uint64_t)rel.size(), d_po);
+    else if (n)
+      hipLaunchKernelGGL(k_image_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, src.segs(cut[c], cut[c + 1]), n,
+                         (const unsigned long long*)cnt, dest, (const uint64_t*)d_pts, (uint64_t)rel.size(), d_po);
     if (!rel.empty()) HIPCHK(e, hipMemcpyAsync(&D[p0], d_po, rel.size() * 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipGetLastError());
@@ -294,6 +379,30 @@ int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, si
   return CTMR_OK;
 }
 
+int known_lists_core(ctmr_engine* e, int64_t now, bool device, uint8_t* text, size_t text_cap, uint8_t* ids, size_t ids_cap,
+                     uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info) {
+  KnownLists L;
+  int r;
+  if ((r = known_lists_prepare(e, now, &L))) return r;
+  return known_lists_emit(e, L, ListSource(), device, text, text_cap, ids, ids_cap, offs, offs_cap, info);
+}
+
+// The lists of an image whose meta is parsed and whose member records are on the device.
+int image_lists_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, int64_t now, bool device, uint8_t* text,
+                     size_t text_cap, uint8_t* ids, size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info) {
+  ListSource src;
+  src.what = "known image lists";
+  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "%s: null member records", src.what);
+  std::map<std::string, std::set<std::string>> host;
+  KnownLists L;
+  int r;
+  if ((r = image_lists_prepare(e, km, now, &host, &L))) return r;
+  src.segments = true;
+  src.image = d_members;
+  if ((r = image_lists_upload(e, L, &src))) return r;
+  return known_lists_emit(e, L, src, device, text, text_cap, ids, ids_cap, offs, offs_cap, info);
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -311,4 +420,30 @@ int ctmr_known_lists_device(ctmr_engine* e, int64_t now_unix, void* d_text, size
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   return known_lists_core(e, now_unix, true, (uint8_t*)d_text, text_cap, ids, ids_cap, offs, offs_cap, info);
+}
+
+int ctmr_known_image_lists(ctmr_engine* e, const uint8_t* image, size_t len, int64_t now_unix, uint8_t* text, size_t text_cap,
+                           uint8_t* ids, size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info) {
+  if (!e || !image || !info) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  DevMem d;
+  int r;
+  if ((r = known_open(e, image, len, nullptr, "known image lists", &km))) return r;
+  if ((r = known_stage_members(e, km, image, 0, "known image lists", &d))) return r;
+  return image_lists_core(e, km, d.u8(), now_unix, false, text, text_cap, ids, ids_cap, offs, offs_cap, info);
+}
+
+int ctmr_known_image_lists_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members, uint64_t n_members,
+                                  int64_t now_unix, void* d_text, size_t text_cap, uint8_t* ids, size_t ids_cap,
+                                  uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info) {
+  if (!e || !meta || !info) return CTMR_E_INVAL;
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  KnownMeta km;
+  int r;
+  if ((r = known_open(e, meta, meta_len, &n_members, "known image lists", &km))) return r;
+  return image_lists_core(e, km, (const uint8_t*)d_members, now_unix, true, (uint8_t*)d_text, text_cap, ids, ids_cap, offs,
+                          offs_cap, info);
 }

@@ -2,6 +2,9 @@
 // records k_known_export stages (image.h) turned into the text LocalDiskBackend.StoreKnownCertificateList writes, one
 // line hex(serial) "\n" per record.  A count pass (per-block byte totals, then scan_u64) and a write pass that stages
 // each block's text in LDS and stores it with 16-byte stores between two ragged ends.
+// ctmr_known_image_lists*  runs the same two passes over the member records of an image where they lie:
+// the kept sets are SEGMENTS of a virtual record sequence in list order (ListSegs), and virtual record v is read at
+// seg_src[s] + v − seg_dst[s].  Its count pass (k_image_lists_count) also validates every record it reads.
 // gfx950 (CDNA4, wave64) only; part of kernels.h, which includes the pieces in dependency order.
 #pragma once
 #include "image.h"
@@ -36,19 +39,20 @@ __device__ __forceinline__ uint8_t list_hex(uint32_t v) { return (uint8_t)(v < 1
 // phase of its first global byte, so that every 16-byte aligned global chunk is one aligned 16-byte LDS word.
 // pts[0..npts) (ascending record indices of the chunk): pt_off[k] = the text offset of record pts[k] — where the host
 // needs the text position of a record (an issuer's first line, host-store lines that go in between).
-__global__ void __launch_bounds__(LIST_BLOCK) k_lists_write(const uint8_t* recs, uint64_t n, const unsigned long long* base,
-                                                           uint8_t* out, const uint64_t* pts, uint64_t npts,
-                                                           unsigned long long* pt_off) {
+// src(i, n): where record i of the n the launch covers lies (called with i < n by every such lane of a wave).
+template <class Src>
+__device__ __forceinline__ void lists_write_body(const Src& src, uint64_t n, const unsigned long long* base, uint8_t* out,
+                                                 const uint64_t* pts, uint64_t npts, unsigned long long* pt_off) {
   __shared__ __attribute__((aligned(16))) uint8_t text[LIST_BLOCK * LIST_LINE_MAX + 16];
   __shared__ uint32_t ws[LIST_BLOCK / 64];
   const uint64_t i = (uint64_t)blockIdx.x * LIST_BLOCK + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   uint4 c0 = make_uint4(0u, 0u, 0u, 0u), c1 = c0, c2 = c0;
   if (i < n) {
-    const uint4* src = (const uint4*)(recs + i * KNOWN_REC_BYTES);
-    c0 = src[0];
-    c1 = src[1];
-    c2 = src[2];
+    const uint4* rec = src(i, n);
+    c0 = rec[0];
+    c1 = rec[1];
+    c2 = rec[2];
   }
   const uint32_t len = i < n ? (c0.x < (uint32_t)CTMR_MAX_SERIAL ? c0.x : (uint32_t)CTMR_MAX_SERIAL) : 0u;
   const uint32_t bytes = i < n ? 2u * len + 1u : 0u;
@@ -115,6 +119,84 @@ __global__ void __launch_bounds__(LIST_BLOCK) k_lists_write(const uint8_t* recs,
     const uint32_t x = head + 16u * nvec + threadIdx.x;
     gstart[x] = text[phase + x];
   }
+}
+
+// the records where they were staged: record i is the i-th of recs
+struct ListStaged {
+  const uint8_t* recs;
+  __device__ __forceinline__ const uint4* operator()(uint64_t i, uint64_t) const { return (const uint4*)(recs + i * KNOWN_REC_BYTES); }
+};
+
+__global__ void __launch_bounds__(LIST_BLOCK) k_lists_write(const uint8_t* recs, uint64_t n, const unsigned long long* base,
+                                                           uint8_t* out, const uint64_t* pts, uint64_t npts,
+                                                           unsigned long long* pt_off) {
+  lists_write_body(ListStaged{recs}, n, base, out, pts, npts, pt_off);
+}
+
+// ---- the lists of an image (ctmr_known_image_lists*).  A launch covers n virtual records of k whole segments: segment s
+// holds the virtual records [dst[s], dst[s + 1]) (dst ascending, every segment non-empty, dst[0] = the launch's first
+// virtual record, dst[k] = dst[0] + n) and lies at records [src[s], src[s] + dst[s + 1] − dst[s]) of the image.  Record i
+// of the launch is virtual record dst[0] + i; its segment comes from known_set_of over dst, narrowed first to the
+// segments of its wave's first and last record (k_sort_keys, k_merge_rank).
+struct ListSegs {
+  const uint8_t* recs;  // the image's member records
+  const uint64_t* dst;  // k + 1
+  const uint64_t* src;  // k
+  uint32_t k;
+  __device__ __forceinline__ const uint4* operator()(uint64_t i, uint64_t n) const {
+    const uint64_t v0 = dst[0], wi = i - (threadIdx.x & 63u);
+    const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
+    const uint32_t s_lo = known_set_of(dst, 0u, k - 1u, wfirst);
+    const uint32_t s_hi = known_set_of(dst, s_lo, k - 1u, wlast);
+    const uint32_t s = known_set_of(dst, s_lo, s_hi, v);
+    return (const uint4*)(recs + (src[s] + (v - dst[s])) * KNOWN_REC_BYTES);
+  }
+};
+
+// Count pass over the segments: cnt[blk] = the text bytes of the launch's records [256 blk, 256 blk + 256), and every
+// record read is validated as k_known_count validates — *err |= 1 for a serial_len above 40, |= 2 for padding octets
+// that are not zero, one atomicOr per wave that saw one.
+__global__ void __launch_bounds__(LIST_BLOCK) k_image_lists_count(ListSegs g, uint64_t n, unsigned long long* cnt, uint32_t* err) {
+  __shared__ uint32_t ws[LIST_BLOCK / 64];
+  const uint64_t i = (uint64_t)blockIdx.x * LIST_BLOCK + threadIdx.x;
+  uint32_t b = 0u, bad = 0u;
+  if (i < n) {
+    const uint4* rec = g(i, n);
+    const uint4 v0 = rec[0], v1 = rec[1], v2 = rec[2];
+    const unsigned long long len = (unsigned long long)v0.x | ((unsigned long long)v0.y << 32);
+    const unsigned long long s[5] = {(unsigned long long)v0.z | ((unsigned long long)v0.w << 32),
+                                     (unsigned long long)v1.x | ((unsigned long long)v1.y << 32),
+                                     (unsigned long long)v1.z | ((unsigned long long)v1.w << 32),
+                                     (unsigned long long)v2.x | ((unsigned long long)v2.y << 32),
+                                     (unsigned long long)v2.z | ((unsigned long long)v2.w << 32)};
+    if (len > CTMR_MAX_SERIAL) {
+      bad = 1u;
+    } else {
+#pragma unroll
+      for (uint32_t q = 0; q < 5; q++) {  // octets behind serial_len are zero
+        const uint64_t lo = 8ull * q;
+        const unsigned long long pad = len <= lo ? ~0ull : (len >= lo + 8 ? 0ull : (~0ull << (8ull * (len - lo))));
+        if (s[q] & pad) bad = 2u;
+      }
+    }
+    b = 2u * (uint32_t)(len < (unsigned long long)CTMR_MAX_SERIAL ? len : (unsigned long long)CTMR_MAX_SERIAL) + 1u;
+  }
+  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d);
+  if ((threadIdx.x & 63u) == 0) {
+    ws[threadIdx.x >> 6] = b;
+    if (mb1 | mb2) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
+}
+
+// Write pass over the segments: k_lists_write with the indirect source (pts / pt_off in the launch's record indices).
+__global__ void __launch_bounds__(LIST_BLOCK) k_image_lists_write(ListSegs g, uint64_t n, const unsigned long long* base,
+                                                                 uint8_t* out, const uint64_t* pts, uint64_t npts,
+                                                                 unsigned long long* pt_off) {
+  lists_write_body(g, n, base, out, pts, npts, pt_off);
 }
 
 }  // namespace ctmr

@@ -110,9 +110,14 @@ class Group:
         self._check(self._lib.ctmr_group_issuer_counts(self._h, out.ctypes.data, n))
         return out[:n]
 
-    def known_lists(self, now) -> list:
-        """The group's per-issuer known-serial lists: every local rank's Engine.known_lists(now), merged per Issuer.ID
-        (known_image.merge_lists).  In-process groups only: an RCCL group gathers its ranks' lists itself."""
+    def known_lists(self, now, canonical=False) -> list:
+        """The group's per-issuer known-serial lists.  By default every local rank's Engine.known_lists(now)
+        concatenated per Issuer.ID in rank order (known_image.merge_lists): each key once, but an issuer's expDates
+        repeat rank by rank.  canonical=True: the lists of the group's image (known_export) written by rank 0's engine
+        (Engine.known_image_lists) — byte for byte what ONE engine holding the group's sets writes under
+        N.KNOWN_ORDER_SORTED.  In-process groups only: an RCCL group gathers its ranks' lists itself."""
+        if canonical:
+            return self.engines[0].known_image_lists(self.known_export(), now)
         from .known_image import merge_lists
         return merge_lists([e.known_lists(now) for e in self.engines])
 

@@ -750,6 +750,64 @@ class Engine:
         writer.store_known_lists(ids, ioff, text, toff)
         return int(info.issuers)
 
+    # ---- the same lists straight from an image, with no table behind them (include/ctmr.h ctmr_known_image_lists*,
+    # DESIGN.md §17; CPU twin: known_image.image_lists)
+    def _known_image_lists_call(self, fn, alloc, n, host_bytes):
+        """One call sized by the bound — 81 B per member record, the host section's lines at most 2 B per octet of the
+        section — and a second, exact one only for IDs or offsets beyond the guess (CTMR_E_RANGE fills `info`)."""
+        info = N.KnownListsInfo()
+        text_cap, ids_cap, n_offs = 81 * n + 2 * host_bytes + 1, 1 << 12, 256
+        for _ in range(2):
+            text = alloc(text_cap)
+            ids, offs = np.empty(max(ids_cap, 1), np.uint8), np.empty(max(n_offs, 2), np.uint64)
+            rc = fn(text, text_cap, ids.ctypes.data, ids_cap, offs.ctypes.data, n_offs, C.byref(info))
+            if rc != N.E_RANGE:
+                break
+            text_cap, ids_cap, n_offs = info.text_bytes, info.ids_bytes, 2 * (info.issuers + 1)
+        self._ck(rc)
+        g = info.issuers
+        return text, ids[:info.ids_bytes].tobytes(), offs[:g + 1].copy(), offs[g + 1:2 * g + 2].copy(), info
+
+    @staticmethod
+    def _host_bytes(buf):
+        """The host section's bytes as the header of an image or its meta part has them, held to what `buf` could carry."""
+        from .known_image import _HEADER
+        return min(_HEADER.unpack_from(buf, 0)[7], len(buf)) if len(buf) >= 64 else 0
+
+    def known_image_lists_raw(self, image, now):
+        """known_lists_raw of the sets `image` holds, read where they lie: one line per member record in the image's
+        order (a canonical image gives sorted lists).  The engine's own sets and issuers play no part.
+        → (text: numpy uint8, ids: bytes, text offsets, ID offsets (u64, issuers + 1 each), info)."""
+        image = bytes(image)
+        text, ids, toff, ioff, info = self._known_image_lists_call(
+            lambda t, tc, *rest: self._lib.ctmr_known_image_lists(self._h, image, len(image), int(now), t.ctypes.data, tc, *rest),
+            lambda cap: np.empty(max(cap, 1), np.uint8), self._header_counts(image)[0], self._host_bytes(image))
+        return text[:info.text_bytes], ids, toff, ioff, info
+
+    def known_image_lists(self, image, now) -> list:
+        """[(Issuer.ID bytes, list text bytes)] in ID order of the sets `image` holds that are not expired at `now`."""
+        text, ids, toff, ioff, info = self.known_image_lists_raw(image, now)
+        return [(ids[ioff[k]:ioff[k + 1]], text[toff[k]:toff[k + 1]].tobytes()) for k in range(info.issuers)]
+
+    def known_image_lists_device(self, meta, d_members, now):
+        """known_image_lists with the member records in device memory (a torch uint8 tensor) → ([Issuer.ID bytes], text
+        offsets (numpy u64, issuers + 1), torch uint8 tensor of the text on this engine's device; a view)."""
+        import torch
+        meta = bytes(meta)
+        n, ptr = self._members_ptr(d_members)
+        dev = "cuda:%d" % self.device
+        text, ids, toff, ioff, info = self._known_image_lists_call(
+            lambda t, tc, *rest: self._lib.ctmr_known_image_lists_device(self._h, meta, len(meta), ptr, n, int(now),
+                                                                         C.c_void_p(t.data_ptr()), tc, *rest),
+            lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), n, self._host_bytes(meta))
+        return [ids[ioff[k]:ioff[k + 1]] for k in range(info.issuers)], toff, text[:info.text_bytes]
+
+    def store_image_lists(self, writer, image, now) -> int:
+        """store_known_lists for the lists of `image` at `now`.  → the lists handed to the backend."""
+        text, ids, toff, ioff, info = self.known_image_lists_raw(image, now)
+        writer.store_known_lists(ids, ioff, text, toff)
+        return int(info.issuers)
+
     # ---- the order inside a set (include/ctmr.h ctmr_known_sort* / ctmr_set_known_order, DESIGN.md §15; CPU twin:
     # known_image.sort)
     def set_known_order(self, order):

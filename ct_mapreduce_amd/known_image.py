@@ -6,7 +6,8 @@ of the engine — what a restarted reference deployment still finds in its Redis
 checks before it applies an image; `build` is the canonical writer; `sort` is the twin of `Engine.known_sort`
 (every set's member records in ascending order, repeats kept); `query` / `subtract` are the twins of
 `Engine.known_query` / `Engine.known_remove` over a dict of sets; `union` / `minus` / `intersect` are the twins of
-`Engine.known_merge` (set algebra on images, key by key); `to_resp` / `from_resp` turn an image into the
+`Engine.known_merge` (set algebra on images, key by key); `image_lists` is the twin of `Engine.known_image_lists`
+(per-issuer lists straight from an image, in the image's order); `to_resp` / `from_resp` turn an image into the
 SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start from a reference deployment's Redis
 contents).  Pure Python + numpy.
 """
@@ -50,7 +51,7 @@ class KnownImage:
 # ExpDate.ID() "2006-01-02-15" of an hour count (storage/types.go:339-384), as the library formats it
 def _civil_from_days(z):
     z += 719468
-    era = (z if z >= 0 else z - 146096) // 146097
+    era = z // 146097          # (// floors: no adjustment for negative z, unlike C)
     doe = z - era * 146097
     yoe = (doe - doe // 1460 + doe // 36524 - doe // 146096) // 365
     doy = doe - (365 * yoe + yoe // 4 - yoe // 100)
@@ -77,7 +78,7 @@ def set_key(exp_hour: int, digest: bytes) -> bytes:
 
 def _days_from_civil(y, m, d):
     y -= m <= 2
-    era = (y if y >= 0 else y - 399) // 400
+    era = y // 400
     yoe = y - era * 400
     doy = (153 * (m - 3 if m > 2 else m + 9) + 2) // 5 + d - 1
     doe = yoe * 365 + yoe // 4 - yoe // 100 + doy
@@ -424,6 +425,40 @@ def lists_of_sets(sets, now) -> list:
 def known_lists(image, now) -> list:
     """The per-issuer known-serial lists of an image at `now`: Engine.known_lists of the engine that exported it."""
     return lists_of_sets(parse(image).sets, now)
+
+
+# the hours whose ExpDate.ID has four year digits: the library lists no set record of another hour
+_HOUR_LO, _HOUR_HI = _days_from_civil(0, 1, 1) * 24, _days_from_civil(10000, 1, 1) * 24
+
+
+def image_lists(image, now) -> list:
+    """[(Issuer.ID, text)] of an image at `now` as Engine.known_image_lists writes it (include/ctmr.h
+    ctmr_known_image_lists): one line per member record in the image's order inside its set, repeats
+    kept; the host-section members of a key behind the member records of the same key; expiry, grouping and order as
+    in `list_blocks`.  Raises ImageError for what `parse` rejects and ListsError for a host key that does not split
+    into three "::" parts."""
+    parse(image)
+    b = bytes(image)
+    _, _, _, n_iss, _, n_sets, n_mem, _, _, _ = _HEADER.unpack_from(b, 0)
+    so = HEADER_BYTES + 32 * n_iss
+    rec = np.frombuffer(b, MEMBER_DTYPE, count=n_mem, offset=len(b) - n_mem * MEMBER_BYTES)
+    by_id = {}
+    for s in range(n_sets):
+        eh, ordinal, first, count = _SET.unpack_from(b, so + SET_BYTES * s)
+        if not _HOUR_LO <= eh < _HOUR_HI or now >= (eh + 1) * 3600:
+            continue
+        ident = issuer_id(b[HEADER_BYTES + 32 * ordinal:HEADER_BYTES + 32 * (ordinal + 1)])
+        r = rec[first:first + count]
+        by_id.setdefault(ident, {})[(eh * 3600, exp_date_id(eh))] = [bytes(m[:int(l)]) for l, m in zip(r["len"], r["serial"])]
+    for key, member in records(image)[1]:
+        parts = key.split(b"::")
+        if len(parts) != 3:
+            raise ListsError("unexpected key format: %r" % key)
+        span = exp_date_span(parts[1])
+        if span is None or now >= span[1]:
+            continue
+        by_id.setdefault(parts[2], {}).setdefault((span[0], parts[1]), []).append(member)
+    return [(i, b"".join(line(m) for k in sorted(by_id[i]) for m in by_id[i][k])) for i in sorted(by_id)]
 
 
 def merge_lists(per_rank) -> list:

@@ -470,6 +470,43 @@ int ctmr_known_merge_device(ctmr_engine* e, int op, const uint8_t* a_meta, size_
                             uint8_t* out_meta, size_t out_meta_cap, void* d_out, uint64_t out_members_cap,
                             ctmr_known_image_info* info);
 
+/* ---- per-issuer known-serial lists straight from an image v1, with no table behind them.  DESIGN.md §17.
+ *
+ * Output.  text, ids, offs and *info are exactly those of ctmr_known_lists (info.members = lines from member records,
+ *   info.host_members = lines from the host section), with the same two-call convention — a buffer that is too small
+ *   gives CTMR_E_RANGE with *info filled and nothing written — and the same bound to size in one call: 81 B × member
+ *   records plus the host section's lines (2 × octets + 1 each).
+ * Which sets.  Every set record of the image and every key of its host section, under the expiry rules of
+ *   ctmr_known_lists: a set of exp hour h is kept iff now_unix < (h + 1) × 3600, and hours outside the years 0000..9999
+ *   are skipped; a host key's date is parsed as NewExpDate parses it (hour or day resolution) and a key it cannot parse
+ *   is skipped; a host key that does not split into exactly three "::" parts fails the call with CTMR_E_INVAL.
+ * Grouping.  One list per Issuer.ID string.  A set record's ID is the padded base64url of its digest in the image: the
+ *   engine's issuer registry plays no part and the issuers need not be registered here.  A host key gives its own issuer
+ *   string.  Lists ascend bytewise by ID; inside a list expDates ascend by their first second, then bytewise as strings.
+ *   A set record and a host key of the same expDate string and issuer form ONE block: the member records first, then
+ *   the host members — where ctmr_known_lists puts the host-side store's members of a key the table holds too.
+ * Lines.  One line per member record, in the image's order inside its set; repeated records stay: the call neither sorts
+ *   nor deduplicates.  A canonical image (a sorted export, any ctmr_known_merge result) therefore gives every expDate's
+ *   lines in `LC_ALL=C sort` order, and for an image an engine exported under CTMR_KNOWN_ORDER_SORTED the text is byte
+ *   for byte what that engine's ctmr_known_lists writes under CTMR_KNOWN_ORDER_SORTED at the same now_unix.  A caller
+ *   with an unsorted image normalises it first: ctmr_known_merge(CTMR_KNOWN_UNION, image, NULL).
+ * Validation.  The meta is checked as ctmr_known_import checks it (magic, version, sizes, set order / gaps / overlaps,
+ *   ordinals).  On the device, before the first text byte is written, every record of a KEPT set is checked for
+ *   serial_len <= 40 and zero padding; the records of sets that are not kept are not read.  CTMR_E_INVAL and
+ *   CTMR_E_NOMEM leave every output buffer as it was.
+ * Read-only.  Nothing of the engine's state is read or changed (table, pair statistics, counters, host-side store,
+ *   Bloom filter, ctmr_table_info), as for ctmr_known_sort; the operand is const and stays as it was.
+ * The member records are read where they lie, twice (a count pass, then the pass that writes), in runs of whole kept
+ * sets of at most 2^27 records.  ctmr_known_image_lists takes a whole image in host memory (its member section staged
+ * on the device once); ctmr_known_image_lists_device takes the meta and the member records (device memory of this
+ * engine's device, 16-byte aligned) apart and writes the text to device memory, the host section's lines copied into it
+ * at their places.  Both return after the engine's stream has drained. */
+int ctmr_known_image_lists(ctmr_engine* e, const uint8_t* image, size_t len, int64_t now_unix, uint8_t* text, size_t text_cap,
+                           uint8_t* ids, size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info);
+int ctmr_known_image_lists_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                                  uint64_t n_members, int64_t now_unix, void* d_text, size_t text_cap, uint8_t* ids,
+                                  size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner
