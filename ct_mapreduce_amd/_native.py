@@ -102,6 +102,11 @@ class KnownImportStats(C.Structure):
                 ("host_members", C.c_uint64), ("host_inserted", C.c_uint64)]
 
 
+class KnownRespInfo(C.Structure):
+    _fields_ = [("sets", C.c_uint64), ("members", C.c_uint64), ("host_members", C.c_uint64), ("commands", C.c_uint64),
+                ("text_bytes", C.c_uint64)]
+
+
 class KnownListsInfo(C.Structure):
     _fields_ = [("issuers", C.c_uint64), ("sets", C.c_uint64), ("members", C.c_uint64), ("host_members", C.c_uint64),
                 ("text_bytes", C.c_uint64), ("ids_bytes", C.c_uint64)]
@@ -173,6 +178,9 @@ SIGNATURES = {
                                          C.POINTER(KnownListsInfo)]),
     "ctmr_known_image_lists_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_int64, _P, C.c_size_t, _P, C.c_size_t,
                                                 _P, C.c_size_t, C.POINTER(KnownListsInfo)]),
+    "ctmr_known_image_resp": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t, C.POINTER(KnownRespInfo)]),
+    "ctmr_known_image_resp_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, _P, C.c_size_t,
+                                               C.POINTER(KnownRespInfo)]),
     "ctmr_set_known_order": (C.c_int, [_P, C.c_int]),
     "ctmr_known_sort": (C.c_int, [_P, _P, C.c_size_t]),
     "ctmr_known_sort_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64]),

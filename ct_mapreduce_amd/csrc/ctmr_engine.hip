@@ -696,6 +696,7 @@ extern "C" {
 #include "engine/synth.inc"
 #include "engine/image.inc"
 #include "engine/lists.inc"
+#include "engine/resp.inc"
 #include "engine/sort.inc"
 #include "engine/merge.inc"
 

@@ -20,6 +20,8 @@
 //   kernels/image.h     k_pairs_slots / k_known_export / k_known_count / k_known_pack / k_known_bloom (the known-certificate image)
 //   kernels/lists.h     k_lists_count / k_lists_write (per-issuer known-serial lists as text), k_image_lists_count /
 //                       k_image_lists_write (the same straight from an image's member records)
+//   kernels/resp.h      k_image_resp_count / k_image_resp_write (an image's member records as the Redis protocol stream of SADD
+//                       and EXPIREAT commands)
 //   kernels/sort.h      k_sort_keys / k_sort_hist / k_sort_scatter / k_sort_heads / k_sort_regroup / k_sort_gather (the
 //                       order inside a known-certificate set: a segmented radix sort of member records)
 //   kernels/merge.h     k_merge_ascending / k_merge_unique / k_merge_first / k_merge_rank / k_merge_sets / k_merge_place
@@ -41,5 +43,6 @@
 #include "kernels/misc.h"
 #include "kernels/image.h"
 #include "kernels/lists.h"
+#include "kernels/resp.h"
 #include "kernels/sort.h"
 #include "kernels/merge.h"

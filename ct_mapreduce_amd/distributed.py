@@ -121,6 +121,11 @@ class Group:
         from .known_image import merge_lists
         return merge_lists([e.known_lists(now) for e in self.engines])
 
+    def known_resp(self, members_per_command=512) -> bytes:
+        """The group's sets as a Redis protocol stream of SADD and EXPIREAT commands: the stream of the group's image
+        (known_export) written by rank 0's engine (Engine.known_image_resp).  In-process groups only, like known_lists."""
+        return self.engines[0].known_image_resp(self.known_export(), members_per_command)
+
     def known_export(self) -> bytes:
         """The group's known-certificate image: every local rank's sorted export folded with UNION on rank 0's engine
         (Engine.known_merge) — byte for byte what ONE engine holding the group's sets exports under

@@ -808,13 +808,76 @@ class Engine:
         writer.store_known_lists(ids, ioff, text, toff)
         return int(info.issuers)
 
+    # ---- the Redis protocol stream of an image (include/ctmr.h ctmr_known_image_resp*; CPU twin:
+    # known_image.image_resp)
+    def _known_resp_call(self, fn, alloc, buf, n):
+        """One call sized by the header's bound (include/ctmr.h) and a second, exact one only when the header understated
+        the image (CTMR_E_RANGE fills `info`)."""
+        from .known_image import _HEADER, resp_bound
+        h = _HEADER.unpack_from(buf, 0) if len(buf) >= 64 else (0,) * 10
+        per = min(max(int(fn.per), 1), 1 << 20)
+        text_cap = resp_bound(n, min(h[5], len(buf) // 24), min(h[7], len(buf)), min(h[8], len(buf) // 8), per)
+        info = N.KnownRespInfo()
+        for _ in range(2):
+            text = alloc(text_cap)
+            rc = fn(text, text_cap, C.byref(info))
+            if rc != N.E_RANGE:
+                break
+            text_cap = info.text_bytes
+        self._ck(rc)
+        return text, info
+
+    def known_image_resp(self, image, members_per_command=512) -> bytes:
+        """The SADD + EXPIREAT stream of the sets `image` holds, as `redis-cli --pipe` loads it: the keys in order, the
+        member records in the image's order, at most `members_per_command` members per SADD.  The engine's own sets and
+        issuers play no part."""
+        image = bytes(image)
+
+        def fn(t, tc, info):
+            return self._lib.ctmr_known_image_resp(self._h, image, len(image), fn.per, t.ctypes.data, tc, info)
+        fn.per = int(members_per_command)
+        if not 0 <= fn.per < 1 << 32:
+            raise ValueError("members_per_command %r" % (members_per_command,))
+        text, info = self._known_resp_call(fn, lambda cap: np.empty(max(cap, 1), np.uint8), image, self._header_counts(image)[0])
+        return text[:info.text_bytes].tobytes()
+
+    def known_image_resp_device(self, meta, d_members, members_per_command=512):
+        """known_image_resp with the member records in device memory (a torch uint8 tensor) → torch uint8 tensor of the
+        stream on this engine's device; a view."""
+        import torch
+        meta = bytes(meta)
+        n, ptr = self._members_ptr(d_members)
+        dev = "cuda:%d" % self.device
+
+        def fn(t, tc, info):
+            return self._lib.ctmr_known_image_resp_device(self._h, meta, len(meta), ptr, n, fn.per, C.c_void_p(t.data_ptr()), tc, info)
+        fn.per = int(members_per_command)
+        if not 0 <= fn.per < 1 << 32:
+            raise ValueError("members_per_command %r" % (members_per_command,))
+        text, info = self._known_resp_call(fn, lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), meta, n)
+        return text[:info.text_bytes]
+
+    def known_resp(self, members_per_command=512) -> bytes:
+        """The stream of the engine's own sets: known_image_resp of its sorted export.  The order setting
+        (set_known_order) is left as it was found."""
+        was = self._known_order
+        self.set_known_order(N.KNOWN_ORDER_SORTED)
+        try:
+            image = self.known_export()
+        finally:
+            self.set_known_order(was)
+        return self.known_image_resp(image, members_per_command)
+
     # ---- the order inside a set (include/ctmr.h ctmr_known_sort* / ctmr_set_known_order, DESIGN.md §15; CPU twin:
     # known_image.sort)
+    _known_order = N.KNOWN_ORDER_ANY   # what set_known_order last set
+
     def set_known_order(self, order):
         """N.KNOWN_ORDER_SORTED: known_export* and known_lists* write each set's members / each expDate's lines in
         ascending byte-string order, so an export is a pure function of the sets held; N.KNOWN_ORDER_ANY (the default):
         any order."""
         self._ck(self._lib.ctmr_set_known_order(self._h, int(order)))
+        self._known_order = int(order)
 
     def known_sort(self, image) -> bytes:
         """`image` with the member records of every set sorted on the GPU (repeats kept, meta unchanged)."""

@@ -7,7 +7,8 @@ checks before it applies an image; `build` is the canonical writer; `sort` is th
 (every set's member records in ascending order, repeats kept); `query` / `subtract` are the twins of
 `Engine.known_query` / `Engine.known_remove` over a dict of sets; `union` / `minus` / `intersect` are the twins of
 `Engine.known_merge` (set algebra on images, key by key); `image_lists` is the twin of `Engine.known_image_lists`
-(per-issuer lists straight from an image, in the image's order); `to_resp` / `from_resp` turn an image into the
+(per-issuer lists straight from an image, in the image's order); `image_resp` is the twin of `Engine.known_image_resp`
+(the SADD + EXPIREAT stream of an image as it lies, key by key); `to_resp` / `from_resp` turn an image into the
 SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start from a reference deployment's Redis
 contents).  Pure Python + numpy.
 """
@@ -470,3 +471,73 @@ def merge_lists(per_rank) -> list:
         for i, text in lists:
             out.setdefault(bytes(i), []).append(bytes(text))
     return [(i, b"".join(out[i])) for i in sorted(out)]
+
+
+# ---- the Redis protocol stream of an image as it lies (include/ctmr.h ctmr_known_image_resp), without a GPU
+
+RESP_MAX_PER_COMMAND = 1 << 20
+
+
+def image_resp(image, members_per_command=512) -> bytes:
+    """The SADD + EXPIREAT stream of an image as Engine.known_image_resp writes it: the keys of the set records and of
+    the host section in ascending bytewise order, a key of both sections once.  Per key: its member records in image
+    order in SADD commands of at most `members_per_command` members, its host-section members in section order in SADD
+    commands of their own, then one EXPIREAT key <first second of its expDate> (none for a host key without a second
+    "::" or with a date `exp_date_span` cannot parse).  Neither sorts nor deduplicates.  Raises ImageError for what
+    `parse` rejects and for a set record whose hour lies outside the years 0000..9999."""
+    from .remote_cache import _resp
+    per = int(members_per_command)
+    if not 1 <= per <= RESP_MAX_PER_COMMAND:
+        raise ValueError("members_per_command %r outside 1..2^20" % (members_per_command,))
+    parse(image)
+    b = bytes(image)
+    _, _, _, n_iss, _, n_sets, n_mem, _, _, _ = _HEADER.unpack_from(b, 0)
+    so = HEADER_BYTES + 32 * n_iss
+    rec = np.frombuffer(b, MEMBER_DTYPE, count=n_mem, offset=len(b) - n_mem * MEMBER_BYTES)
+    dev, expire = {}, {}
+    for s in range(n_sets):
+        eh, ordinal, first, count = _SET.unpack_from(b, so + SET_BYTES * s)
+        if not _HOUR_LO <= eh < _HOUR_HI:
+            raise ImageError("set %d: hour %d lies outside the years 0000..9999" % (s, eh))
+        key = set_key(eh, b[HEADER_BYTES + 32 * ordinal:HEADER_BYTES + 32 * (ordinal + 1)])
+        r = rec[first:first + count]
+        dev[key] = [bytes(m[:int(l)]) for l, m in zip(r["len"], r["serial"])]
+        expire[key] = eh * 3600
+    host = {}
+    for key, member in records(image)[1]:
+        host.setdefault(key, []).append(member)
+    for key in host:
+        if key not in expire:
+            date, sep, _ = key[len(PREFIX):].partition(b"::")
+            span = exp_date_span(date) if sep else None
+            expire[key] = None if span is None else span[0]
+    out = []
+    for key in sorted(expire):
+        for members in (dev.get(key, ()), host.get(key, ())):
+            for i in range(0, len(members), per):
+                out.append(_resp(b"SADD", key, *members[i:i + per]))
+        if expire[key] is not None:
+            out.append(_resp(b"EXPIREAT", key, b"%d" % expire[key]))
+    return b"".join(out)
+
+
+def _digits(v):
+    return len(b"%d" % v)
+
+
+def resp_record_bytes(p, c, serial_len, hour, per, host_members=False) -> int:
+    """The stream bytes of the member record at position p of a set of c records: its bulk string, the
+    SADD header in front of it when it opens a command, and the EXPIREAT behind it when it is the set's last and the key
+    has no host-section members.  The key of a set record is always 68 octets."""
+    n = 5 + _digits(serial_len) + serial_len
+    if p % per == 0:
+        n += 13 + _digits(min(per, c - p) + 2) + 75
+    if p == c - 1 and not host_members:
+        t = _digits(hour * 3600)
+        n += 98 + _digits(t) + t
+    return n
+
+
+def resp_bound(n_members, n_sets, host_bytes, n_host_members, per) -> int:
+    """The size a caller can give the text buffer without a first call (include/ctmr.h ctmr_known_image_resp)."""
+    return 47 * n_members + 95 * (n_members // per + n_sets) + 112 * n_sets + 2 * host_bytes + 208 * n_host_members

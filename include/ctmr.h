@@ -507,6 +507,50 @@ int ctmr_known_image_lists_device(ctmr_engine* e, const uint8_t* meta, size_t me
                                   uint64_t n_members, int64_t now_unix, void* d_text, size_t text_cap, uint8_t* ids,
                                   size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info);
 
+/* ---- the Redis protocol stream of an image v1: the SADD commands of every serials:: key and the EXPIREAT
+ *      KnownCertificates.setExpiryFlag puts on it (storage/knowncertificates.go:98-104), as `redis-cli --pipe` loads them
+ *      into the Redis of a reference deployment.  DESIGN.md §18.
+ *
+ * Keys.  Those of the image's set records and those of its host section, in ascending bytewise key order; a key that
+ *   occurs in both sections is one key.  info.sets counts keys.
+ * Per key, in this order: its member records in the image's order, in SADD commands of at most members_per_command
+ *   members each; its host-section members in section order, in SADD commands of their own under the same cap; one
+ *   EXPIREAT key <seconds>.  The call neither sorts nor deduplicates: a caller with an unsorted image normalises it
+ *   first with ctmr_known_merge(CTMR_KNOWN_UNION, image, NULL).
+ * Encoding.  A command is a RESP array of bulk strings: "*<argc>\r\n", then "$<len>\r\n<octets>\r\n" per argument
+ *   (SADD, the key, the members; EXPIREAT, the key, the seconds in decimal).  Members are raw octets; an empty serial is
+ *   "$0\r\n\r\n".
+ * EXPIREAT seconds.  For a set record: hour × 3600, negative before 1970.  For a key of the host section alone: the
+ *   first second of the date between "serials::" and the next "::", parsed as NewExpDate parses it (hour or day
+ *   resolution); a key without a second "::", or with a date that does not parse, gets its SADD commands and no
+ *   EXPIREAT — the reference would never have put a TTL on it.
+ * members_per_command is 1..2^20; anything else is CTMR_E_INVAL.
+ * Validation.  The meta is checked as ctmr_known_import checks it.  A set record whose hour lies outside the years
+ *   0000..9999 cannot be spelled as a key: CTMR_E_INVAL.  On the device every record is checked for serial_len <= 40 and
+ *   zero padding before the first text byte is written, and every working buffer is allocated before it too:
+ *   CTMR_E_INVAL and CTMR_E_NOMEM leave the output as it was.
+ * Sizing.  The two-call convention: a buffer that is too small gives CTMR_E_RANGE with *info filled and nothing
+ *   written.  A caller can size without a first call: with n member records, `sets` set records, host_bytes octets of
+ *   host section holding host_members members (all four in the image's header) the text is at most
+ *     47 n + 95 (n / members_per_command + sets) + 112 sets + 2 host_bytes + 208 host_members   octets
+ *   (n / members_per_command rounded down).
+ * Read-only.  Nothing of the engine's state is read or changed (table, pair statistics, counters, host-side store,
+ *   Bloom filter, ctmr_table_info), as for ctmr_known_sort; the issuers need not be registered; the operand is const
+ *   and stays as it was.
+ * The member records are read where they lie, twice (a count pass, then the pass that writes), in runs of whole sets of
+ * at most 2^27 records.  ctmr_known_image_resp takes a whole image in host memory (its member section staged on the
+ * device once); ctmr_known_image_resp_device takes the meta and the member records (device memory of this engine's
+ * device, 16-byte aligned) apart and writes the text to device memory, the host section's commands copied into it at
+ * their places.  Both return after the engine's stream has drained. */
+typedef struct {
+  uint64_t sets, members, host_members, commands, text_bytes;  /* keys; member records; host-section members; SADD + EXPIREAT */
+} ctmr_known_resp_info;
+int ctmr_known_image_resp(ctmr_engine* e, const uint8_t* image, size_t len, uint32_t members_per_command, uint8_t* text,
+                          size_t text_cap, ctmr_known_resp_info* info);
+int ctmr_known_image_resp_device(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const void* d_members,
+                                 uint64_t n_members, uint32_t members_per_command, void* d_text, size_t text_cap,
+                                 ctmr_known_resp_info* info);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner
