@@ -107,6 +107,10 @@ class KnownRespInfo(C.Structure):
                 ("text_bytes", C.c_uint64)]
 
 
+class KnownRespImageInfo(C.Structure):
+    _fields_ = KnownImageInfo._fields_ + [("commands", C.c_uint64), ("skipped_members", C.c_uint64)]
+
+
 class KnownListsInfo(C.Structure):
     _fields_ = [("issuers", C.c_uint64), ("sets", C.c_uint64), ("members", C.c_uint64), ("host_members", C.c_uint64),
                 ("text_bytes", C.c_uint64), ("ids_bytes", C.c_uint64)]
@@ -181,6 +185,9 @@ SIGNATURES = {
     "ctmr_known_image_resp": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t, C.POINTER(KnownRespInfo)]),
     "ctmr_known_image_resp_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, _P, C.c_size_t,
                                                C.POINTER(KnownRespInfo)]),
+    "ctmr_known_resp_image": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(KnownRespImageInfo)]),
+    "ctmr_known_resp_image_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_uint64,
+                                               C.POINTER(KnownRespImageInfo)]),
     "ctmr_set_known_order": (C.c_int, [_P, C.c_int]),
     "ctmr_known_sort": (C.c_int, [_P, _P, C.c_size_t]),
     "ctmr_known_sort_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64]),

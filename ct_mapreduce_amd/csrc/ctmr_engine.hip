@@ -9,6 +9,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -699,5 +700,6 @@ extern "C" {
 #include "engine/resp.inc"
 #include "engine/sort.inc"
 #include "engine/merge.inc"
+#include "engine/resp_parse.inc"
 
 }  // extern "C"

@@ -22,6 +22,8 @@
 //                       k_image_lists_write (the same straight from an image's member records)
 //   kernels/resp.h      k_image_resp_count / k_image_resp_write (an image's member records as the Redis protocol stream of SADD
 //                       and EXPIREAT commands)
+//   kernels/resp_parse.h k_resp_mark / k_resp_cuts / k_resp_resolve / k_resp_chain / k_resp_commands / k_resp_place (a Redis
+//                       protocol stream of SADD and EXPIREAT commands as it lies → an image's member records)
 //   kernels/sort.h      k_sort_keys / k_sort_hist / k_sort_scatter / k_sort_heads / k_sort_regroup / k_sort_gather (the
 //                       order inside a known-certificate set: a segmented radix sort of member records)
 //   kernels/merge.h     k_merge_ascending / k_merge_unique / k_merge_first / k_merge_rank / k_merge_sets / k_merge_place
@@ -44,5 +46,6 @@
 #include "kernels/image.h"
 #include "kernels/lists.h"
 #include "kernels/resp.h"
+#include "kernels/resp_parse.h"
 #include "kernels/sort.h"
 #include "kernels/merge.h"

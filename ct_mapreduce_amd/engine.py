@@ -868,6 +868,60 @@ class Engine:
             self.set_known_order(was)
         return self.known_image_resp(image, members_per_command)
 
+    # ---- a Redis protocol stream as it lies → an image (include/ctmr.h ctmr_known_resp_image*; CPU twin:
+    # known_image.resp_image)
+    def known_resp_image(self, stream) -> bytes:
+        """The image of a stream of SADD / EXPIREAT commands (what `redis-cli --pipe` loads, what known_image_resp
+        writes): member records in stream order, neither sorted nor deduplicated — known_merge(N.KNOWN_UNION, image)
+        does that.  The engine's own sets and issuers play no part."""
+        stream = bytes(stream)
+        info = N.KnownRespImageInfo()
+        cap = 1 << 16
+        for _ in range(2):
+            out = np.empty(cap, np.uint8)
+            rc = self._lib.ctmr_known_resp_image(self._h, stream, len(stream), out.ctypes.data, cap, C.byref(info))
+            if rc != N.E_RANGE:
+                break
+            cap = info.image_bytes
+        self._ck(rc)
+        return out[:info.image_bytes].tobytes()
+
+    def known_resp_image_device(self, d_stream, n=None):
+        """known_resp_image of the first n bytes of a torch uint8 tensor on this engine's device (all of it by default;
+        any alignment) → (meta bytes, torch uint8 tensor of the member records on the device; a view).  The records are
+        sized by their bound (n / 6), the meta by a second call when 64 KiB were short."""
+        import torch
+        if not hasattr(d_stream, "data_ptr"):
+            raise TypeError("d_stream: a torch tensor on this engine's device")
+        n = d_stream.numel() if n is None else int(n)
+        if not 0 <= n <= d_stream.numel():
+            raise ValueError("n = %r of %d bytes" % (n, d_stream.numel()))
+        ptr = C.c_void_p(d_stream.data_ptr()) if n else None
+        info = N.KnownRespImageInfo()
+        meta_cap, members_cap = getattr(self, "_resp_meta_cap", 1 << 16), max(n // 6, 1)
+        out = torch.empty(members_cap * 48, dtype=torch.uint8, device="cuda:%d" % self.device)
+        for _ in range(2):
+            meta = np.empty(meta_cap, np.uint8)
+            rc = self._lib.ctmr_known_resp_image_device(self._h, ptr, n, meta.ctypes.data, meta_cap, C.c_void_p(out.data_ptr()),
+                                                        members_cap, C.byref(info))
+            if rc != N.E_RANGE:
+                break
+            meta_cap = info.meta_bytes
+        self._ck(rc)
+        self._resp_meta_cap = max(meta_cap, info.meta_bytes)
+        return meta[:info.meta_bytes].tobytes(), out[:info.members * 48]
+
+    def known_import_resp(self, stream, world=1, rank=0) -> dict:
+        """The warm start from a reference deployment's Redis contents: every serials:: member of the stream (bytes, or
+        a torch uint8 tensor on this engine's device) this rank takes, as SetInsert would add it.  Stream → member
+        records on the device → known_import_device: no image in host memory."""
+        import torch
+        if not hasattr(stream, "data_ptr"):
+            raw = np.frombuffer(bytes(stream), np.uint8)
+            stream = torch.from_numpy(raw.copy()).to("cuda:%d" % self.device)
+        meta, d_members = self.known_resp_image_device(stream)
+        return self.known_import_device(meta, d_members, world, rank)
+
     # ---- the order inside a set (include/ctmr.h ctmr_known_sort* / ctmr_set_known_order, DESIGN.md §15; CPU twin:
     # known_image.sort)
     _known_order = N.KNOWN_ORDER_ANY   # what set_known_order last set

@@ -8,9 +8,10 @@ checks before it applies an image; `build` is the canonical writer; `sort` is th
 `Engine.known_query` / `Engine.known_remove` over a dict of sets; `union` / `minus` / `intersect` are the twins of
 `Engine.known_merge` (set algebra on images, key by key); `image_lists` is the twin of `Engine.known_image_lists`
 (per-issuer lists straight from an image, in the image's order); `image_resp` is the twin of `Engine.known_image_resp`
-(the SADD + EXPIREAT stream of an image as it lies, key by key); `to_resp` / `from_resp` turn an image into the
-SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start from a reference deployment's Redis
-contents).  Pure Python + numpy.
+(the SADD + EXPIREAT stream of an image as it lies, key by key) and `resp_image` its inverse, the twin of
+`Engine.known_resp_image` (a SADD / EXPIREAT stream as it lies → an image, members in stream order); `to_resp` /
+`from_resp` turn an image into the SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start
+from a reference deployment's Redis contents).  Pure Python + numpy.
 """
 import base64
 import io
@@ -354,7 +355,9 @@ def to_resp(image, out) -> dict:
 
 def from_resp(stream) -> bytes:
     """An image of the serials:: sets of a redis_dump / redis-cli style stream of SADD (and EXPIREAT) commands.  Other
-    keys are skipped."""
+    keys are skipped.  One member at a time through redis_load; `resp_image` is the strict twin of the GPU path
+    (Engine.known_resp_image / known_import_resp), and union(resp_image(s)) == from_resp(s) for every stream both
+    accept."""
     from .remote_cache import redis_load
     if isinstance(stream, (bytes, bytearray, memoryview)):
         stream = io.BytesIO(bytes(stream))
@@ -541,3 +544,107 @@ def resp_record_bytes(p, c, serial_len, hour, per, host_members=False) -> int:
 def resp_bound(n_members, n_sets, host_bytes, n_host_members, per) -> int:
     """The size a caller can give the text buffer without a first call (include/ctmr.h ctmr_known_image_resp)."""
     return 47 * n_members + 95 * (n_members // per + n_sets) + 112 * n_sets + 2 * host_bytes + 208 * n_host_members
+
+
+# ---- a Redis protocol stream as it lies → an image (include/ctmr.h ctmr_known_resp_image; DESIGN.md §19), without a GPU
+
+class RespError(ValueError):
+    """The stream is not a sequence of the commands ctmr_known_resp_image takes: the library fails with CTMR_E_INVAL."""
+
+
+def resp_commands(stream) -> list:
+    """The commands of a stream, each a list of its arguments.  Grammar: zero or more `*<N>\r\n` (N >= 1) followed by N
+    bulk strings `$<L>\r\n<L octets>\r\n`; N and L are 1..10 decimal digits without sign or leading zero ("0" itself
+    is allowed); nothing else — no inline commands, no null bulk strings, no trailing bytes."""
+    b = bytes(stream)
+    n, p, out = len(b), 0, []
+
+    def number(p, lead):
+        if p >= n or b[p] != lead:
+            raise RespError("offset %d: %r expected" % (p, chr(lead)))
+        q = p + 1
+        while q < n and q - p <= 10 and 0x30 <= b[q] <= 0x39:
+            q += 1
+        d = b[p + 1:q]
+        if not d or (len(d) > 1 and d[0] == 0x30) or b[q:q + 2] != b"\r\n":
+            raise RespError("offset %d: 1..10 digits without a leading zero and CRLF expected" % p)
+        return int(d), q + 2
+
+    while p < n:
+        at = p
+        argc, p = number(p, 0x2a)
+        if argc < 1:
+            raise RespError("offset %d: a command of no arguments" % at)
+        args = []
+        for _ in range(argc):
+            ln, q = number(p, 0x24)
+            if q + ln + 2 > n or b[q + ln:q + ln + 2] != b"\r\n":
+                raise RespError("offset %d: a bulk string of %d octets does not end in CRLF inside the stream" % (p, ln))
+            args.append(b[q:q + ln])
+            p = q + ln + 2
+        out.append(args)
+    return out
+
+
+def resp_image_parts(stream):
+    """→ (image, info dict) of a stream: `resp_image` and the counts ctmr_known_resp_image_info carries besides the
+    image's own (commands; skipped_members: members of SADD commands under keys outside serials::)."""
+    dev, host, commands, skipped = {}, set(), 0, 0
+    for args in resp_commands(stream):
+        commands += 1
+        name = args[0].upper()
+        if name == b"SADD":
+            if len(args) < 3:
+                raise RespError("SADD with %d arguments" % len(args))
+            key = args[1]
+            if not key.startswith(PREFIX):
+                skipped += len(args) - 2
+                continue
+            pk = parse_key(key)
+            for m in args[2:]:
+                if pk is not None and len(m) <= MAX_SERIAL:
+                    dev.setdefault(key, (pk, []))[1].append(m)
+                else:
+                    host.add((key, m))
+        elif name in (b"EXPIREAT", b"PEXPIREAT"):
+            if len(args) != 3:
+                raise RespError("%s with %d arguments" % (name.decode(), len(args)))
+        elif name == b"SELECT":
+            if len(args) != 2:
+                raise RespError("SELECT with %d arguments" % len(args))
+        else:
+            raise RespError("command %r" % args[0][:32])
+    host = sorted(host)
+    keys = sorted(dev)
+    digests = sorted({dev[k][0][1] for k in keys})
+    ordinal = {d: i for i, d in enumerate(digests)}
+    set_part, members, first = [], [], 0
+    for k in keys:
+        (eh, dg), ms = dev[k]
+        set_part.append(_SET.pack(eh, ordinal[dg], first, len(ms)))
+        members += ms
+        first += len(ms)
+    host_part = b"".join(struct.pack("<I", len(k)) + k + struct.pack("<I", len(m)) + m for k, m in host)
+    meta = _HEADER.pack(MAGIC, VERSION, HEADER_BYTES, len(digests), 0, len(keys), first, len(host_part), len(host), 0)
+    meta += b"".join(digests) + b"".join(set_part) + host_part
+    meta += b"\0" * (-len(meta) % 64)
+    rec = np.zeros(first, MEMBER_DTYPE)
+    if first:
+        rec["len"] = np.fromiter((len(m) for m in members), np.uint64, first)
+        rec["serial"] = np.frombuffer(b"".join(m.ljust(MAX_SERIAL, b"\0") for m in members), np.uint8).reshape(first, MAX_SERIAL)
+    info = dict(members=first, sets=len(keys), host_members=len(host), meta_bytes=len(meta),
+                image_bytes=len(meta) + MEMBER_BYTES * first, issuers=len(digests), commands=commands, skipped_members=skipped)
+    return meta + rec.tobytes(), info
+
+
+def resp_image(stream) -> bytes:
+    """The image of a SADD / EXPIREAT stream as Engine.known_resp_image writes it — the inverse of `image_resp`.  The
+    commands: SADD key member… (at least one member), EXPIREAT / PEXPIREAT key time and SELECT db (accepted and ignored:
+    the image implies the expiry), names in any case; anything else raises RespError, as does every violation of the
+    grammar of `resp_commands`.  A SADD under a key outside serials:: is skipped.  Under a serials:: key a member of at
+    most 40 octets whose key `parse_key` takes becomes a member record, every other (key, member) pair goes to the host
+    section.  The image is valid for `parse` but not necessarily canonical: issuers in digest order, one set per key
+    with member records in key order, the records of a set in stream order across all its commands with repeats kept,
+    the host pairs sorted and each once.  resp_image(image_resp(build(sets), per)) == build(sets), and
+    union(resp_image(s)) == from_resp(s)."""
+    return resp_image_parts(stream)[0]

@@ -551,6 +551,60 @@ int ctmr_known_image_resp_device(ctmr_engine* e, const uint8_t* meta, size_t met
                                  uint64_t n_members, uint32_t members_per_command, void* d_text, size_t text_cap,
                                  ctmr_known_resp_info* info);
 
+/* ---- a Redis protocol stream as it lies → an image v1: the inverse of ctmr_known_image_resp*.  What a reference
+ *      deployment holds in its Redis (`redis-cli --rdb` replayed, a rewritten AOF without an RDB preamble, the stream
+ *      ctmr_known_image_resp wrote) becomes member records on the device without one Python or host step per member.
+ *      DESIGN.md §19.
+ *
+ * Grammar.  Zero or more commands back to back and nothing else.  A command is "*<N>\r\n" followed by N >= 1 bulk
+ *   strings "$<L>\r\n<L octets>\r\n"; <N> and <L> are 1..10 decimal digits without sign or leading zero ("0" itself is
+ *   allowed).  Argument 0 is the command's name in any ASCII case: SADD key member… (N >= 3), EXPIREAT / PEXPIREAT key time
+ *   (N = 3) and SELECT db (N = 2); the last three are accepted and ignored — the image implies the expiry.  Everything
+ *   else is CTMR_E_INVAL: another command, an inline command, a null bulk string, a missing CRLF, a truncated tail,
+ *   trailing bytes; ctmr_last_error() names the byte offset where the device knows it.  Members are raw octets and may
+ *   hold anything, "\r\n$3\r\n" included.
+ * Which members.  A SADD whose key does not start with "serials::" is skipped (info.skipped_members counts its
+ *   members).  Under a serials:: key a member of at most CTMR_MAX_SERIAL octets becomes a member record when the key
+ *   spells an (hour, issuer digest) exactly as a set entry does — 68 octets, "YYYY-MM-DD-HH" of a real calendar date and an
+ *   hour 00..23, the padded base64url of a 32-byte digest; every other (key, member) pair goes to the host section.
+ * Result.  An image ctmr_known_import accepts, not necessarily canonical (the contract of ctmr_known_image_resp's
+ *   operand): the issuers of the keys that have a member record, in digest order; one set per such key, in key order;
+ *   the member records of a set in STREAM ORDER across all commands of its key, adjacent or not, repeats kept; the host
+ *   section's pairs sorted, each once.  The call neither sorts nor deduplicates: ctmr_known_merge(CTMR_KNOWN_UNION,
+ *   image, NULL) does.  An empty stream gives the empty image (64 B of meta).
+ * Sizing.  The two-call convention: a buffer that is too small gives CTMR_E_RANGE with *info filled and nothing
+ *   written.  A caller can bound the member records without a first call: at most len / 6, the shortest member being
+ *   "$0\r\n\r\n".  The meta has NO linear bound in len — every host-section pair repeats its key —, so a caller sizes
+ *   it by a first call (or generously: a stream written from an image has the meta of that image).
+ * Length.  len >= 2^32 − 64 is CTMR_E_INVAL, decided before the first byte is read: a longer stream is split by the
+ *   caller at a command start and the images joined with CTMR_KNOWN_UNION.
+ * CTMR_E_INVAL and CTMR_E_NOMEM leave every output buffer as it was: all working memory is allocated, and the whole
+ *   stream validated, before the first output byte.
+ * Read-only.  Nothing of the engine's state is read or changed (table, pair statistics, counters, host-side store,
+ *   Bloom filter, ctmr_table_info), as for ctmr_known_sort; the stream is const and no byte beyond len is read.
+ * Cost.  The stream is read where it lies; token starts are found in parallel (a candidate test per byte, then the
+ *   candidates no earlier one spans).  A member that contains a well-formed fake header which lands on a CRLF opens a
+ *   conflict region that one lane resolves by walking it; the region is as long as the span the fake header claims,
+ *   which a hostile stream can make the whole stream — slow then, not wrong.
+ * ctmr_known_resp_image takes the stream in host memory (staged on the device once) and writes the whole image to host
+ * memory; ctmr_known_resp_image_device takes it in device memory of this engine's device at ANY alignment, writes the
+ * meta to host memory and the member records to device memory (16-byte aligned).  Both return after the engine's
+ * stream has drained. */
+typedef struct {
+  uint64_t members;        /* member records (device section) */
+  uint64_t sets;
+  uint64_t host_members;   /* members of the host section */
+  uint64_t meta_bytes;     /* header + issuers + sets + host section, padded to 64 */
+  uint64_t image_bytes;    /* meta_bytes + 48 × members */
+  uint32_t issuers, reserved;
+  uint64_t commands;       /* commands of the stream, the ignored ones counted in */
+  uint64_t skipped_members;  /* members of SADD commands under keys outside serials:: */
+} ctmr_known_resp_image_info;
+int ctmr_known_resp_image(ctmr_engine* e, const uint8_t* stream, size_t len, uint8_t* out, size_t cap,
+                          ctmr_known_resp_image_info* info);
+int ctmr_known_resp_image_device(ctmr_engine* e, const void* d_stream, size_t len, uint8_t* out_meta, size_t out_meta_cap,
+                                 void* d_out, uint64_t out_members_cap, ctmr_known_resp_image_info* info);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner
