@@ -284,7 +284,22 @@ static int round_collect(ctmr_engine* e, RoundCtx& rc) {
   rc.payload_bytes = ends[1] - ends[0];  // entry view: the whole blob (leaf_input + extra_data)
   // one claimed slot per key that was new HERE (a key that left for its owner claims its slot there; long serials live in
   // the host-side set)
-  e->occupied += (rc.own_counted ? 0ull : rc.hs.n_new - rc.hs.n_remote) + rc.remote_new;
+  if (!rc.own_counted) {
+    e->occupied += rc.hs.n_new - rc.hs.n_remote + rc.remote_new;
+  } else {
+    // The table was rebuilt behind the shard's own claims (ctmr_xchg_insert_device): the rebuild's live count holds them,
+    // and a received record that took such a slot over by its lower order (settle_order) is new without claiming a slot —
+    // live + remote_new counted those twice (tests/test_gpu_xchg_corpus.py).  No member has left since the rebuild, so
+    // the claimed slots are the live ones: counted, on this rare path, as the rebuild counted them.
+    unsigned long long alive = 0;
+    HIPCHK(e, hipMemsetAsync(e->d_count, 0, 8, e->stream));
+    hipLaunchKernelGGL(k_count_live, dim3((unsigned)((e->nslots + 255) / 256)), dim3(256), 0, e->stream,
+                       (const unsigned long long*)e->index, e->nslots, e->d_count);
+    HIPCHK(e, hipMemcpyAsync(&alive, e->d_count, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipGetLastError());
+    e->occupied = alive;
+  }
   if (rc.hs.n_full || both[1].n_full)  // cannot happen after ensure_capacity; kept as the kernels' own guard
     return fail(e, CTMR_E_FULL, "known-certificate table full (%llu slots): %llu entries dropped",
                 (unsigned long long)e->nslots, rc.hs.n_full + both[1].n_full);

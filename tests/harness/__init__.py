@@ -266,6 +266,28 @@ def host_keys_lib():
     return _hk
 
 
+_hash = None
+
+
+def hash_lib():
+    """Host build of the key hashing (csrc/ctmr_dev.h key_meta / mixk / key_hash / key_tag, csrc/kernels/keyrec.h
+    key_owner_h / bloom_pos): what the port in tests/xchg_corpus.py is held against."""
+    global _hash
+    if _hash is None:
+        _hash = C.CDLL(_lib("hash"))
+        _hash.harness_key_meta.argtypes = [C.c_int32, C.c_uint32, C.c_uint32]
+        _hash.harness_mixk.argtypes = [C.c_uint64]
+        _hash.harness_key_hash.argtypes = [C.c_uint64, C.POINTER(C.c_uint64)]
+        _hash.harness_key_tag.argtypes = [C.c_uint64]
+        _hash.harness_key_owner_h.argtypes = [C.c_uint64, C.c_uint32]
+        _hash.harness_bloom_pos.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        for f in (_hash.harness_key_meta, _hash.harness_mixk, _hash.harness_key_hash):
+            f.restype = C.c_uint64
+        _hash.harness_key_tag.restype = _hash.harness_key_owner_h.restype = C.c_uint32
+        _hash.harness_bloom_pos.restype = None
+    return _hash
+
+
 def build_fake_rccl() -> str:
     """The stand-in for librccl (fake_rccl.cpp: ranks as threads or processes on ONE GPU, bytes through POSIX shared
     memory), built on demand; hand the path to the library through CTMR_RCCL_LIB."""
@@ -281,6 +303,10 @@ LIBS = {
     "ossl": ("ossl_extract.c", "libossl_extract.so", ["gcc", "-O2", "-shared", "-fPIC"], {"libs": ["-lcrypto"]}),
     "host_keys": ("host_keys_harness.cpp", "libhost_keys_harness.so", ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall"],
                   {"deps": [os.path.join(CSRC, "host_keys.h")]}),
+    # (the device headers as the host sees them: the flags of fake_rccl)
+    "hash": ("hash_harness.cpp", "libhash_harness.so",
+             ["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"],
+             {"deps": WALK_DEPS + [os.path.join(CSRC, "ctmr_dev.h"), os.path.join(CSRC, "kernels", "keyrec.h")]}),
     "fake_rccl": ("fake_rccl.cpp", "libfake_rccl.so",
                   ["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"],
                   {"libs": ["-L/opt/rocm/lib", "-lamdhip64", "-pthread", "-lrt"]}),

@@ -260,7 +260,7 @@ def test_raw_shards_with_synchronised_issuer_registration():
 
 
 @pytest.mark.parametrize("mode", ["owner", "bloom"])
-@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("world", [2, 4, 8, 16])
 def test_serials_of_every_length_across_ranks(world, mode):
     """Serial numbers of 1..45 octets, duplicated across shards.  The owner-computes exchange sends keys with serials of
     up to 20 octets as 32-byte records and the rare 21..40-octet ones as 64-byte records on a path of their own; serials
@@ -273,9 +273,13 @@ def test_serials_of_every_length_across_ranks(world, mode):
     rng = random.Random(4242 + world)
     issuer = synth.issuer(synth.config(n_issuers=1), 0)
     name = D.name(D.rdn(3, b"Synth Issuer 000"))
-    uniq = []
+    uniq, drawn = [], set()
     for ln in list(range(1, 46)) * 6:                                # six keys of every length 1..45
-        s = bytes([rng.randrange(1, 0x7f)] + [rng.randrange(256) for _ in range(ln - 1)])
+        while True:                                                  # (six of the 126 one-octet serials may repeat: drawn again)
+            s = bytes([rng.randrange(1, 0x7f)] + [rng.randrange(256) for _ in range(ln - 1)])
+            if s not in drawn:
+                break
+        drawn.add(s)
         uniq.append(D.cert(serial=s, issuer=name, not_after=D.utctime("270101000000Z")))
     certs = list(uniq)
     certs += [uniq[rng.randrange(len(uniq))] for _ in range(len(uniq))]          # every key about once more, anywhere
