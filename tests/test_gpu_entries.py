@@ -327,27 +327,15 @@ def test_trusted_log_compares_bytes_when_two_registered_certificates_share_tag_a
     certificates of one length whose hashes agree in the upper 32 bits and in the table's home slot — found here by
     search, with a numpy port of cert_quick_hash over the signature's last 16 bytes — must still be told apart: every
     entry's Chain[0] is the SECOND one, the first one sits in front of it in the probe run."""
+    from tests.chain0_corpus import quick_hash_tails               # the numpy port of cert_quick_hash
     U = np.uint64
-
-    def qh_mix(z):
-        z = (z ^ (z >> U(30))) * U(0xbf58476d1ce4e5b9)
-        z = (z ^ (z >> U(27))) * U(0x94d049bb133111eb)
-        return z ^ (z >> U(31))
-
     cfg = synth.config(seed=79, n_issuers=1)
     iss = synth.issuer(cfg, 0)
     L = len(iss)
     rng = np.random.default_rng(20260923)
     n = 1 << 22
     tails = rng.integers(0, 1 << 32, (n, 4), dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        h = qh_mix(U(0x9e3779b97f4a7c15) + U(L))
-        hd = np.frombuffer(iss[:16], "<u4").astype(np.uint64)
-        for k in range(4):
-            h = qh_mix(h ^ (hd[k] << U(1) | U(1)))
-        h = np.full(n, h, np.uint64)
-        for k in range(4):
-            h = qh_mix(h ^ (tails[:, k] << U(1)))
+    h = quick_hash_tails(L, iss[:16], tails)
     slots = 1024                                                   # idb_ht_size of an engine with max_issuers <= 256
     sig = ((h >> U(32)) << U(10)) | (h & U(slots - 1))
     order = np.argsort(sig, kind="stable")
