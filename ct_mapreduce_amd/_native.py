@@ -111,6 +111,11 @@ class KnownRespImageInfo(C.Structure):
     _fields_ = KnownImageInfo._fields_ + [("commands", C.c_uint64), ("skipped_members", C.c_uint64)]
 
 
+class EntriesJsonInfo(C.Structure):
+    _fields_ = [("responses", C.c_uint64), ("entries", C.c_uint64), ("text_bytes", C.c_uint64), ("blob_bytes", C.c_uint64),
+                ("bad_response", C.c_uint64), ("bad_offset", C.c_uint64)]
+
+
 class KnownListsInfo(C.Structure):
     _fields_ = [("issuers", C.c_uint64), ("sets", C.c_uint64), ("members", C.c_uint64), ("host_members", C.c_uint64),
                 ("text_bytes", C.c_uint64), ("ids_bytes", C.c_uint64)]
@@ -240,6 +245,9 @@ SIGNATURES = {
                                           C.POINTER(BatchStats)]),
     "ctmr_map_entries": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(DecodeStats),
                                    C.POINTER(BatchStats)]),
+    "ctmr_entries_json": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(EntriesJsonInfo)]),
+    "ctmr_entries_json_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P,
+                                           C.POINTER(EntriesJsonInfo)]),
     "ctmr_meta_new_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ctmr_meta_new": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
     "ctmr_meta_reset": (C.c_int, [_P]),

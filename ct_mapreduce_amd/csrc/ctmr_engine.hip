@@ -701,5 +701,6 @@ extern "C" {
 #include "engine/sort.inc"
 #include "engine/merge.inc"
 #include "engine/resp_parse.inc"
+#include "engine/entries_json.inc"
 
 }  // extern "C"

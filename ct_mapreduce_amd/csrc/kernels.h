@@ -24,6 +24,8 @@
 //                       and EXPIREAT commands)
 //   kernels/resp_parse.h k_resp_mark / k_resp_cuts / k_resp_resolve / k_resp_chain / k_resp_commands / k_resp_place (a Redis
 //                       protocol stream of SADD and EXPIREAT commands as it lies → an image's member records)
+//   kernels/entries_json.h k_ej_quotes / k_ej_mark / k_ej_resp / k_ej_check / k_ej_decode (get-entries JSON bodies as they
+//                       lie → the raw-entry batch: tokens by quote parity, the grammar by position, base64 → bytes)
 //   kernels/sort.h      k_sort_keys / k_sort_hist / k_sort_scatter / k_sort_heads / k_sort_regroup / k_sort_gather (the
 //                       order inside a known-certificate set: a segmented radix sort of member records)
 //   kernels/merge.h     k_merge_ascending / k_merge_unique / k_merge_first / k_merge_rank / k_merge_sets / k_merge_place
@@ -47,5 +49,6 @@
 #include "kernels/lists.h"
 #include "kernels/resp.h"
 #include "kernels/resp_parse.h"
+#include "kernels/entries_json.h"
 #include "kernels/sort.h"
 #include "kernels/merge.h"

@@ -24,6 +24,15 @@ class CtmrError(RuntimeError):
         self.code = code
 
 
+class EntriesJsonError(CtmrError):
+    """A get-entries response outside the grammar of ctmr_entries_json*: the host decodes that one itself."""
+
+    def __init__(self, code, msg, bad_response, bad_offset):
+        super().__init__(code, msg)
+        self.bad_response = bad_response
+        self.bad_offset = bad_offset
+
+
 @dataclass
 class Batch:
     """Packed CT-entry batch (SURVEY.md §8(d) layout), host side."""
@@ -54,6 +63,7 @@ class RawEntries:
     """Raw get-entries batch: blob = leaf_input_0 ‖ extra_data_0 ‖ leaf_input_1 ‖ …, bounds u64[2n+1] (include/ctmr.h)."""
     blob: np.ndarray         # u8
     bounds: np.ndarray       # u64[2n+1]
+    resp_first: np.ndarray = None   # u64[R+1] when the batch came from R get-entries bodies: each body's first entry
 
     @property
     def n(self):
@@ -293,6 +303,75 @@ class Engine:
             C.c_void_p(d_new_idx) if d_new_idx else None, C.c_void_p(d_timestamp) if d_timestamp else None,
             C.byref(ds), C.byref(st)))
         return st, ds
+
+    # ---- get-entries HTTP bodies as they lie (include/ctmr.h ctmr_entries_json*; CPU twin: get_entries.parse)
+    def _ej_ck(self, rc, info):
+        if rc == N.E_INVAL and info.bad_response != 2**64 - 1:
+            raise EntriesJsonError(rc, self._lib.ctmr_last_error(self._h).decode(errors="replace"), info.bad_response,
+                                   info.bad_offset)
+        self._ck(rc)
+
+    def entries_json(self, bodies) -> RawEntries:
+        """The raw entries of get-entries bodies (a list of bytes, in log order): JSON and base64 decoded on the GPU,
+        text and result in host memory; the blob keeps the PAYLOAD_PAD zero bytes behind bounds[2n], as
+        synth.host_entries' does.  A body outside the grammar raises EntriesJsonError with its number."""
+        from . import get_entries
+        text, rb = get_entries.join(bodies)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        info = N.EntriesJsonInfo()
+        blob_cap, entries_cap = len(text) * 3 // 4 + N.PAYLOAD_PAD, len(text) // 34
+        blob = np.empty(blob_cap, np.uint8)
+        bounds = np.empty(2 * entries_cap + 1, np.uint64)
+        first = np.empty(len(bodies) + 1, np.uint64)
+        self._ej_ck(self._lib.ctmr_entries_json(self._h, buf.ctypes.data, rb.ctypes.data, len(bodies), blob.ctypes.data, blob_cap,
+                                                bounds.ctypes.data, entries_cap, first.ctypes.data, C.byref(info)), info)
+        return RawEntries(blob[:info.blob_bytes + N.PAYLOAD_PAD], bounds[:2 * info.entries + 1], first)
+
+    def entries_json_device(self, d_text, resp_bounds):
+        """entries_json of a torch uint8 tensor on this engine's device (any alignment; body r at
+        d_text[resp_bounds[r]:resp_bounds[r + 1]]) → (d_blob, d_bounds, resp_first, info): torch tensors on the device —
+        blob_bytes + PAYLOAD_PAD bytes and u64[2n + 1] as int64, views of buffers sized in one call by the bounds
+        3/4 text_bytes and text_bytes / 34 — and the host array u64[R + 1]."""
+        import torch
+        if not hasattr(d_text, "data_ptr"):
+            raise TypeError("d_text: a torch tensor on this engine's device")
+        rb = np.ascontiguousarray(resp_bounds, dtype=np.uint64)
+        R = len(rb) - 1
+        if R < 0 or (R and ((rb[1:] < rb[:-1]).any() or int(rb[R]) > d_text.numel())):
+            raise ValueError("resp_bounds do not ascend or reach beyond the text")
+        text_bytes = int(rb[R] - rb[0]) if R else 0
+        blob_cap, entries_cap = text_bytes * 3 // 4 + N.PAYLOAD_PAD, text_bytes // 34
+        dev = "cuda:%d" % self.device
+        d_blob = torch.empty(blob_cap, dtype=torch.uint8, device=dev)
+        d_bounds = torch.empty(2 * entries_cap + 1, dtype=torch.int64, device=dev)
+        first = np.empty(R + 1, np.uint64)
+        info = N.EntriesJsonInfo()
+        self._ej_ck(self._lib.ctmr_entries_json_device(self._h, C.c_void_p(d_text.data_ptr()) if text_bytes else None, rb.ctypes.data, R,
+                                                       C.c_void_p(d_blob.data_ptr()), blob_cap, C.c_void_p(d_bounds.data_ptr()),
+                                                       entries_cap, first.ctypes.data, C.byref(info)), info)
+        return d_blob[:info.blob_bytes + N.PAYLOAD_PAD], d_bounds[:2 * info.entries + 1], first, info
+
+    def map_entries_json(self, bodies) -> EntriesResult:
+        """map_entries over get-entries bodies (a list of bytes): text → raw entries on the device → map_entries_device,
+        no blob in host memory."""
+        import torch
+        from . import get_entries
+        text, rb = get_entries.join(bodies)
+        dev = "cuda:%d" % self.device
+        d_text = torch.from_numpy(np.frombuffer(text, np.uint8).copy() if text else np.zeros(1, np.uint8)).to(dev)
+        d_blob, d_bounds, _, info = self.entries_json_device(d_text, rb)
+        n = int(info.entries)
+        if not n:   # nothing to map
+            return EntriesResult(np.zeros(0, RECORD_DTYPE), np.zeros(0, np.uint64), np.zeros(0, np.uint64), N.BatchStats(),
+                                 N.DecodeStats())
+        d_rec = torch.zeros(max(n, 1) * RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_new = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        d_ts = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        st, ds = self.map_entries_device(d_blob.data_ptr(), d_bounds.data_ptr(), n, d_rec.data_ptr() if n else 0,
+                                         d_new.data_ptr() if n else 0, d_ts.data_ptr() if n else 0)
+        records = d_rec.cpu().numpy().view(RECORD_DTYPE)[:n].copy()
+        return EntriesResult(records, d_new.cpu().numpy().view(np.uint64)[:st.n_new].copy(),
+                             d_ts.cpu().numpy().view(np.uint64)[:n].copy(), st, ds)
 
     def synth_entries_device(self, cfg: N.SynthConfig, first, n, d_bounds, d_blob, blob_cap) -> int:
         out = C.c_uint64()

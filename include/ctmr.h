@@ -851,6 +851,60 @@ int ctmr_map_entries_device(ctmr_engine* e, const uint8_t* d_blob, const uint64_
                             ctmr_decode_stats* dstats, ctmr_batch_stats* stats);
 int ctmr_map_entries(ctmr_engine* e, const uint8_t* blob, const uint64_t* bounds, uint64_t n, ctmr_record* records,
                      uint64_t* new_idx, uint64_t* timestamp, ctmr_decode_stats* dstats, ctmr_batch_stats* stats);
+
+/* ---- get-entries HTTP bodies as they lie → a raw-entry batch: what the reference's downloader holds before CT-go's
+ *      GetRawEntries has run encoding/json and encoding/base64 over it, one entry at a time (ct-fetch.go:424-452).
+ *      The JSON is tokenised, checked and its base64 decoded on the device.  DESIGN.md §20.
+ *
+ * Input.  Response r is text[resp_bounds[r], resp_bounds[r + 1]); resp_bounds is a HOST array u64[n_responses + 1],
+ *   ascending: several bodies lie in one buffer, as a downloader collects them.  No byte outside the bounds decides
+ *   anything.  n_responses = 0 gives the empty batch.
+ * Grammar of one response (ws: any run of the bytes 0x20 0x09 0x0A 0x0D):
+ *       ws { ws "entries" ws : ws [ ws ( entry ( ws , ws entry )* )? ws ] ws } ws
+ *       entry = { ws K ws : ws V ws , ws K' ws : ws V ws }
+ *   {K, K'} = {"leaf_input", "extra_data"} in either order, each exactly once, spelled exactly.  V = '"' b64 '"': zero or
+ *   more characters of A-Z a-z 0-9 + /, the total length a multiple of 4, the last quantum may end in "=" or "==";
+ *   the bits left over in a padded quantum may hold any value and are dropped (as Go's non-strict StdEncoding and
+ *   Python's b64decode do).  {"entries":[]} is a valid response of no entries.  The string state starts afresh at
+ *   every response boundary: a body that ends inside a string is invalid whatever the next body begins with.
+ *   EVERYTHING ELSE is outside the grammar and fails the call with CTMR_E_INVAL, info.bad_response naming the lowest
+ *   such response: a backslash anywhere (so the escapes \/ and \u0041, which JSON allows); any other key, a repeated key, a key
+ *   in another letter case; a value that is not such a string; a trailing comma; bytes behind the closing brace other
+ *   than ws; a byte-order mark; an empty or all-ws body; an unpadded or URL-safe alphabet.
+ *   This is the language CT log servers emit, NOT all of what encoding/json would accept into ct.GetEntriesResponse:
+ *   Go's decoder matches keys case-insensitively, ignores unknown keys and resolves escapes.  The host keeps its own
+ *   decoder for a response named in bad_response.  Like the rest of the CT-go boundary this is recalled, not pinned
+ *   (DESIGN.md §2).
+ * Output.  blob = leaf_input_0 ‖ extra_data_0 ‖ leaf_input_1 ‖ … and bounds u64[2n + 1], exactly ctmr_map_entries*'
+ *   input: always leaf first, then extra, whatever their order in the text, back to back, bounds[0] = 0; the
+ *   CTMR_PAYLOAD_PAD bytes behind bounds[2n] are zeroed, so the output is a valid raw-entry batch as it stands.
+ *   resp_first is a HOST array u64[n_responses + 1] or NULL: the index of each response's first entry
+ *   (resp_first[n_responses] = n), which is how the host maps entries back to log indices.
+ * Sizing.  The two-call convention: a blob_cap below blob_bytes + CTMR_PAYLOAD_PAD or an entries_cap below entries
+ *   gives CTMR_E_RANGE with *info filled and nothing written.  Bounds a caller may use without a first call:
+ *   blob_bytes <= 3/4 text_bytes, entries <= text_bytes / 34.
+ * CTMR_E_INVAL and CTMR_E_NOMEM leave every output buffer as it was: all working memory is allocated, and the whole
+ *   text validated, before the first output byte.  Every position is 64-bit: a text of 2^32 bytes and more is one call
+ *   (the working tables are about 6 % of a text of 4 KB entries, so no run-splitting is imposed on the caller).
+ * Read-only.  Nothing of the engine's state is read or changed; the text is const.
+ * ctmr_entries_json takes the text in host memory (the bytes inside the bounds staged on the device once) and writes
+ * blob and bounds to host memory; ctmr_entries_json_device takes the text in device memory of this engine's device at
+ * ANY alignment and writes d_blob (16-byte aligned) and d_bounds on the device.  Both return after the engine's stream
+ * has drained. */
+typedef struct {
+  uint64_t responses, entries;
+  uint64_t text_bytes;      /* resp_bounds[R] - resp_bounds[0] */
+  uint64_t blob_bytes;      /* bounds[2n]; the call needs blob_bytes + CTMR_PAYLOAD_PAD of capacity */
+  uint64_t bad_response;    /* on CTMR_E_INVAL: the LOWEST-numbered response outside the grammar; else UINT64_MAX */
+  uint64_t bad_offset;      /* on CTMR_E_INVAL: a byte offset inside that response's bounds (advisory) */
+} ctmr_entries_json_info;
+int ctmr_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses,
+                      uint8_t* blob, size_t blob_cap, uint64_t* bounds, uint64_t entries_cap, uint64_t* resp_first,
+                      ctmr_entries_json_info* info);
+int ctmr_entries_json_device(ctmr_engine* e, const void* d_text, const uint64_t* resp_bounds, uint64_t n_responses,
+                             void* d_blob, size_t blob_cap, uint64_t* d_bounds, uint64_t entries_cap,
+                             uint64_t* resp_first, ctmr_entries_json_info* info);
+
 /* Asynchronous ingestion (ctmr_submit_batch above) for RAW get-entries responses — what the reference's downloader actually holds (ct-fetch.go:446-462):
  * blob = leaf_input_0 ‖ extra_data_0 ‖ leaf_input_1 ‖ …, bounds u64[2n+1] (ctmr_map_entries' input).  Submits of
  * either form share the pipeline and its ordering; a super-batch holds one form (a change of form closes the open one).
