@@ -1,8 +1,11 @@
-"""-m gpu: 32-bit TAG collisions in the known-certificate table.  Two different keys with the same tag and the same
-home slot make pass 1 remember a candidate slot whose key is NOT theirs; pass 2 (k_insert2) must notice and fall back
-to the fully synchronised upsert.  At 2^-32 per probe this never shows up in random data, so the colliding serials are
-searched for here with a numpy port of key_meta/key_hash (ct_mapreduce_amd/csrc/ctmr_dev.h) and fed through the
-real path; everything must still equal the oracle."""
+"""-m gpu: TAG collisions in the known-certificate table.  An index word carries a 24-bit tag (key_tag of
+ct_mapreduce_amd/csrc/ctmr_dev.h: the top 24 bits of key_hash, above the 40-bit arena reference).  Two different keys
+with the same tag and the same home slot make pass 1 remember a candidate slot whose key is NOT theirs; pass 2
+(k_insert2) must notice and fall back to the fully synchronised upsert.  At 2^-24 per probe this hardly shows up in
+random data, so the colliding serials are searched for here with a numpy port of key_meta/key_hash and fed through the
+real path; everything must still equal the oracle.  (The search below matches the top 32 bits of the hash and the home
+slot — more than the tag asks for; tests/reduce_corpus.py searches for the 24-bit tag itself and adds triples, runs
+that wrap the index and known-and-new mixtures.)"""
 import numpy as np
 import pytest
 
