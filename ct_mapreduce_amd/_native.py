@@ -116,6 +116,11 @@ class EntriesJsonInfo(C.Structure):
                 ("bad_response", C.c_uint64), ("bad_offset", C.c_uint64)]
 
 
+class PemDecodeInfo(C.Structure):
+    _fields_ = [("files", C.c_uint64), ("certificates", C.c_uint64), ("text_bytes", C.c_uint64), ("payload_bytes", C.c_uint64),
+                ("regular", C.c_uint64), ("irregular", C.c_uint64), ("bad_file", C.c_uint64), ("bad_offset", C.c_uint64)]
+
+
 class KnownListsInfo(C.Structure):
     _fields_ = [("issuers", C.c_uint64), ("sets", C.c_uint64), ("members", C.c_uint64), ("host_members", C.c_uint64),
                 ("text_bytes", C.c_uint64), ("ids_bytes", C.c_uint64)]
@@ -248,6 +253,8 @@ SIGNATURES = {
     "ctmr_entries_json": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(EntriesJsonInfo)]),
     "ctmr_entries_json_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P,
                                            C.POINTER(EntriesJsonInfo)]),
+    "ctmr_pem_decode": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(PemDecodeInfo)]),
+    "ctmr_pem_decode_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(PemDecodeInfo)]),
     "ctmr_meta_new_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ctmr_meta_new": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
     "ctmr_meta_reset": (C.c_int, [_P]),

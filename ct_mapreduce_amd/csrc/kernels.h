@@ -26,6 +26,8 @@
 //                       protocol stream of SADD and EXPIREAT commands as it lies → an image's member records)
 //   kernels/entries_json.h k_ej_quotes / k_ej_mark / k_ej_resp / k_ej_check / k_ej_decode (get-entries JSON bodies as they
 //                       lie → the raw-entry batch: tokens by quote parity, the grammar by position, base64 → bytes)
+//   kernels/pem_decode.h k_pd_mark / k_pd_fstart / k_pd_files / k_pd_check / k_pd_squeeze / k_pd_decode (PEM certificate files
+//                       as they lie → a packed batch: armor lines by their dashes, the grammar by counts, base64 → bytes)
 //   kernels/sort.h      k_sort_keys / k_sort_hist / k_sort_scatter / k_sort_heads / k_sort_regroup / k_sort_gather (the
 //                       order inside a known-certificate set: a segmented radix sort of member records)
 //   kernels/merge.h     k_merge_ascending / k_merge_unique / k_merge_first / k_merge_rank / k_merge_sets / k_merge_place
@@ -50,5 +52,6 @@
 #include "kernels/resp.h"
 #include "kernels/resp_parse.h"
 #include "kernels/entries_json.h"
+#include "kernels/pem_decode.h"
 #include "kernels/sort.h"
 #include "kernels/merge.h"

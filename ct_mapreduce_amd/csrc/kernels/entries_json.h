@@ -361,6 +361,24 @@ __device__ __forceinline__ uint32_t ej_sextet(uint32_t c) {
   return v & 63u;
 }
 
+// A staged tile leaves: stage[phase, phase + total) → [gstart, gstart + total), LDS byte x ↔ global byte gstart - phase + x
+// (k_lists_write): 16-byte non-temporal stores for the body, byte stores for the ragged ends, so that neighbouring tiles
+// never share a store.  phase = the 16-byte phase of gstart; every thread of the block calls, behind the barrier.
+__device__ __forceinline__ void ej_store_tile(const uint8_t* stage, uint32_t phase, uint32_t total, uint8_t* gstart) {
+  const uint32_t head = (16u - phase) & 15u;
+  if (head >= total) {
+    if (threadIdx.x < total) gstart[threadIdx.x] = stage[phase + threadIdx.x];
+    return;
+  }
+  const uint32_t nvec = (total - head) >> 4, tail = (total - head) & 15u;
+  if (threadIdx.x < head) gstart[threadIdx.x] = stage[phase + threadIdx.x];
+  if (threadIdx.x < nvec) st_stream16((uint4*)(gstart + head) + threadIdx.x, ((const uint4*)(stage + phase + head))[threadIdx.x]);
+  if (threadIdx.x < tail) {
+    const uint32_t x = head + 16u * nvec + threadIdx.x;
+    gstart[x] = stage[phase + x];
+  }
+}
+
 // decode: block = tile t of string i = tile_str[t]: its characters [EJ_DTILE k, …) → blob[bounds[i] + EJ_DOUT k, …)
 __global__ void __launch_bounds__(EJ_DBLOCK) k_ej_decode(const uint8_t* s, uint64_t b0, const unsigned long long* tile_str, const unsigned long long* tile_first,
                                                          const unsigned long long* bounds, const unsigned long long* src, uint8_t* blob) {
@@ -385,20 +403,7 @@ __global__ void __launch_bounds__(EJ_DBLOCK) k_ej_decode(const uint8_t* s, uint6
     o[2] = (uint8_t)x;
   }
   __syncthreads();
-  // out: [gstart, gstart + total); LDS byte x ↔ global byte gstart - phase + x (k_lists_write)
-  uint8_t* gstart = blob + dst;
-  const uint32_t head = (16u - phase) & 15u;
-  if (head >= total) {
-    if (threadIdx.x < total) gstart[threadIdx.x] = stage[phase + threadIdx.x];
-    return;
-  }
-  const uint32_t nvec = (total - head) >> 4, tail = (total - head) & 15u;
-  if (threadIdx.x < head) gstart[threadIdx.x] = stage[phase + threadIdx.x];
-  if (threadIdx.x < nvec) st_stream16((uint4*)(gstart + head) + threadIdx.x, ((const uint4*)(stage + phase + head))[threadIdx.x]);
-  if (threadIdx.x < tail) {
-    const uint32_t x = head + 16u * nvec + threadIdx.x;
-    gstart[x] = stage[phase + x];
-  }
+  ej_store_tile(stage, phase, total, blob + dst);
 }
 
 }  // namespace ctmr

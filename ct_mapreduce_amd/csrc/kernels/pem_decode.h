@@ -1,0 +1,468 @@
+// kernels/pem_decode.h — files of concatenated "-----BEGIN CERTIFICATE-----" blocks as they lie → the payload and offsets
+// of a packed batch (include/ctmr.h ctmr_pem_decode*).  The inverse of kernels/pem.h.
+// '-' is not in the base64 alphabet, so every dash of a valid file belongs to an armor line, and the armor lines of a
+// file alternate BEGIN, END: that does here what quote parity does in kernels/entries_json.h.  The passes, each a launch:
+//   mark      one wave per EJ_TILE bytes.  Per byte a class: dash, LF, blank, alphabet, '=', other.  Counted per block —
+//             armor tokens, body characters (alphabet and '='), '=' — scanned, then written: the token list
+//             (position << 1 | kind) with the characters and the '=' in front of each.  Found here: an "other" byte; a
+//             dash outside an armor line (a run of dashes starts a line and spells a literal, or closes one; no run is
+//             longer than 5); and, through a summary byte per block that says what the block's last non-ws byte was, a
+//             character behind a '=' and a character behind dashes with no LF between.
+//   fstart    the characters in front of every file boundary (a wave each).
+//   files     per file: its first token (a binary search), its token count (even), its certificates.
+//   check     a lane per token: kinds alternate from BEGIN; no character lies between an END and the next BEGIN, before
+//             the first BEGIN or behind the last END; between BEGIN and END C % 4 == 0 and at most two '='.  The END's
+//             lane writes the decoded length and decides the block's layout: regular (L, e) — lines of L characters,
+//             each ended by the same eol of e bytes, nothing else — or irregular.
+//   squeeze   irregular blocks only: their characters copied contiguously into a working buffer.
+//   decode    the hot path: one tile of EJ_DTILE characters of one certificate per block → EJ_DOUT bytes.  A lane finds
+//             its quantum at body + (r / L)(L + e) + r % L, straight in the text, and packs 4 → 3.
+// The text lies at any alignment (EjText, ej_chunk).  gfx950 (CDNA4, wave64) only; part of kernels.h.
+#pragma once
+#include "entries_json.h"
+
+namespace ctmr {
+
+constexpr uint32_t PD_BEGIN = 0, PD_END = 1;
+constexpr uint32_t PD_BEGIN_LEN = 27, PD_END_LEN = 25;      // the armor lines without their eol
+constexpr uint32_t PD_BEGIN_CHARS = 16, PD_END_CHARS = 14;  // the letters in them: what the character count sees of them
+constexpr uint32_t PD_LMAX = 1024;  // a regular block of two lines and more has lines of at most this; so has BEGIN's blank run
+constexpr uint32_t PD_OWN = 32;     // the eols a lane checks itself; what a block has beyond them the whole wave checks
+constexpr uint32_t PD_IRREGULAR = 3;  // lay[i] & 3: 1, 2 = the eol bytes of a regular block, 0 = a single line without need of one
+constexpr uint32_t PD_S_ANY = 1, PD_S_EQ = 2, PD_S_DASH = 4, PD_S_LF = 8;  // the summary byte of a block
+
+__device__ __forceinline__ bool pd_is_blank(uint32_t c) { return c == 0x20u || c == 0x09u || c == 0x0du; }
+__device__ __forceinline__ bool pd_is_ws(uint32_t c) { return pd_is_blank(c) || c == 0x0au; }
+
+template <uint32_t N>
+__device__ __forceinline__ bool pd_spells(const uint8_t* s, uint64_t at, const char (&lit)[N]) {
+  uint32_t diff = 0u;  // (no branch per byte: the caller has checked that all of them lie in the file)
+#pragma unroll
+  for (uint32_t k = 0; k + 1u < N; k++) diff |= (uint32_t)s[at + k] ^ (uint32_t)(uint8_t)lit[k];
+  return diff == 0u;
+}
+
+// the offset from s of the first byte of mark block blk (below lo, even negative, for block 0)
+__device__ __forceinline__ int64_t pd_block_pos(const EjText& T, uint64_t blk) {
+  return (int64_t)(T.a0 + blk * EJ_TILE - (uint64_t)(uintptr_t)T.s);
+}
+
+// What precedes the byte at p, ws skipped, inside its file [fs, …): *lf = an LF lies between.  → 0 nothing (the file's
+// start), else PD_S_ANY | PD_S_EQ or PD_S_DASH when it is one.  Bytes of p's own block are read; the blocks before it
+// answer with their summary, unless the file starts inside one.
+__device__ __forceinline__ uint32_t pd_before(const EjText& T, const uint8_t* sum, uint64_t blk, uint64_t p, uint64_t fs, bool* lf) {
+  bool seen = false;
+  uint32_t cls = 0u;
+  int64_t q = (int64_t)p, start = pd_block_pos(T, blk);
+  for (;;) {  // bytes down to `low`, then the summaries of the blocks in front
+    const int64_t low = start > (int64_t)fs ? start : (int64_t)fs;
+    while (q > low && !cls) {
+      const uint32_t c = T.s[--q];
+      if (c == 0x0au) seen = true;
+      else if (!pd_is_blank(c)) cls = PD_S_ANY | (c == 0x3du ? PD_S_EQ : 0u) | (c == 0x2du ? PD_S_DASH : 0u);
+    }
+    if (cls || low == (int64_t)fs) break;
+    for (;;) {  // q = start, the first byte of block blk, behind fs: blk >= 1
+      start = pd_block_pos(T, --blk);
+      if (start < (int64_t)fs) break;  // (the file starts inside this one: its bytes)
+      const uint32_t m = sum[blk];
+      q = start;
+      if (m & PD_S_LF) seen = true;
+      if (m & PD_S_ANY) cls = m & (PD_S_ANY | PD_S_EQ | PD_S_DASH);
+      if (cls || start == (int64_t)fs) break;
+    }
+    if (cls || start == (int64_t)fs) break;
+  }
+  *lf = seen;
+  return cls;
+}
+
+// mark.  WRITE = false: cnt_t / cnt_c / cnt_e[blk] = the armor tokens / body characters / '=' of block blk, sum[blk] its
+// summary, and what a block can know alone is reported.  WRITE = true, behind the exclusive scans: tok[] = position << 1
+// | kind of every armor line, ctok[] / etok[] = the characters / '=' of the text in front of it; what needs the
+// summaries is reported.
+template <bool WRITE>
+__global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, unsigned long long* cnt_t, unsigned long long* cnt_c,
+                                                      unsigned long long* cnt_e, uint8_t* sum, unsigned long long* tok,
+                                                      unsigned long long* ctok, unsigned long long* etok, unsigned long long* err) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t blk = b0 + blockIdx.x;
+  int64_t p0;
+  uint32_t valid;
+  const uint4 v = ej_chunk(T, blk, lane, &p0, &valid);
+  uint32_t dash = 0u, lf = 0u, blank = 0u, alpha = 0u, eq = 0u;
+#pragma unroll
+  for (uint32_t q = 0; q < EJ_PER; q++) {
+    const uint32_t c = ej_byte(v, q);
+    dash |= (c == 0x2du ? 1u : 0u) << q;
+    lf |= (c == 0x0au ? 1u : 0u) << q;
+    blank |= (pd_is_blank(c) ? 1u : 0u) << q;
+    alpha |= ((((c | 0x20u) - 0x61u) < 26u || (c - 0x30u) < 10u || c == 0x2bu || c == 0x2fu) ? 1u : 0u) << q;
+    eq |= (c == 0x3du ? 1u : 0u) << q;
+  }
+  dash &= valid;
+  lf &= valid;
+  alpha &= valid;
+  eq &= valid;
+  const uint32_t chars = alpha | eq;
+  const uint32_t other = valid & ~(dash | lf | blank | chars);
+  // the block's file, when it has one only (k_ej_mark)
+  const uint64_t s0 = (uint64_t)(uintptr_t)T.s;
+  const uint64_t blk_lo = T.a0 + blk * EJ_TILE - s0 + (blk == 0 ? T.lo - (T.a0 - s0) : 0ull);
+  const uint64_t blk_end = T.a0 + (blk + 1ull) * EJ_TILE - s0;
+  const uint64_t r_lo = ej_resp_of(T.rb, T.R, blk_lo);
+  const bool uniform = T.rb[r_lo + 1] >= (blk_end < T.hi ? blk_end : T.hi);
+  // runs of dashes.  A dash with a dash in front of it: some byte of the four before that is none (or the file's start).
+  // A run's first dash at a line start is a token and spells a literal; elsewhere it closes one.
+  const uint32_t prev_alpha = __shfl_up(alpha >> 15, 1);  // the byte in front of the lane's first (lane 0: unknown)
+  uint32_t tokm = 0u, kinds = 0u;
+  bool bad = other != 0u;
+  uint64_t bad_at = bad ? (uint64_t)(p0 + (int64_t)(__ffs(other) - 1)) : 0ull;
+  {
+    uint32_t m = dash;
+    while (m) {
+      const uint32_t q = (uint32_t)__ffs(m) - 1u;
+      m &= m - 1u;
+      const uint64_t p = (uint64_t)(p0 + (int64_t)q);
+      const uint64_t f = uniform ? r_lo : ej_resp_of(T.rb, T.R, p);
+      const uint64_t fs = T.rb[f], fe = T.rb[f + 1];
+      const bool run = p > fs && T.s[p - 1] == 0x2du, line = !run && (p == fs || T.s[p - 1] == 0x0au);
+      if (line) {  // a token, spelled right or not: BEGIN unless an E follows its dashes
+        tokm |= 1u << q;
+        if (p + 5u < fe && T.s[p + 5] == 0x45u) kinds |= 1u << q;
+      }
+      if (WRITE) continue;
+      bool ok;
+      if (run) {
+        ok = false;
+#pragma unroll 1
+        for (uint32_t k = 2; k <= 5u && !ok; k++) ok = p - fs < k || T.s[p - k] != 0x2du;
+      } else if (line) {
+        ok = (p + PD_BEGIN_LEN <= fe && pd_spells(T.s, p, "-----BEGIN CERTIFICATE-----")) || (p + PD_END_LEN <= fe && pd_spells(T.s, p, "-----END CERTIFICATE-----"));
+      } else {
+        ok = (p - fs >= 22u && pd_spells(T.s, p - 22u, "-----BEGIN CERTIFICATE")) || (p - fs >= 20u && pd_spells(T.s, p - 20u, "-----END CERTIFICATE"));
+      }
+      if (!ok && !bad) {
+        bad = true;
+        bad_at = p;
+      }
+    }
+  }
+  if (!WRITE) {
+    uint64_t vr = 0;
+    if (bad) vr = uniform ? r_lo : ej_resp_of(T.rb, T.R, bad_at);
+    ej_report(err, bad, vr, bad_at);
+  }
+  // counts: tokens and characters in one scan (each at most EJ_TILE), the '=' in another
+  uint32_t total, total_e;
+  const uint32_t packed = ej_wave_scan((uint32_t)__popc(tokm) | ((uint32_t)__popc(chars) << 16), &total);
+  const uint32_t eq_before = ej_wave_scan((uint32_t)__popc(eq), &total_e);
+  if (!WRITE) {
+    // the summary: the block's last non-ws byte and whether an LF lies behind it
+    const uint32_t nonws = valid & ~(lf | blank);
+    const unsigned long long has = __ballot(nonws != 0u), haslf = __ballot(lf != 0u);
+    uint32_t m = 0u;
+    if (has) {
+      const uint32_t top = 63u - (uint32_t)__clzll(has);
+      const uint32_t tq = 31u - (uint32_t)__clz(__shfl(nonws, top));
+      const uint32_t td = __shfl(dash, top), te = __shfl(eq, top), tl = __shfl(lf, top);
+      m = PD_S_ANY | (((td >> tq) & 1u) ? PD_S_DASH : 0u) | (((te >> tq) & 1u) ? PD_S_EQ : 0u);
+      if ((tl >> tq) > 1u || (top < 63u && (haslf >> (top + 1u)))) m |= PD_S_LF;
+    } else if (haslf) {
+      m = PD_S_LF;
+    }
+    if (lane == 0) {
+      cnt_t[blk] = total & 0xffffu;
+      cnt_c[blk] = total >> 16;
+      cnt_e[blk] = total_e;
+      sum[blk] = (uint8_t)m;
+    }
+    return;
+  }
+  // a character with no alphabet character right in front of it: what precedes it, ws skipped, decides
+  {
+    uint32_t m = chars & ~((alpha << 1) | ((lane != 0u && prev_alpha) ? 1u : 0u));
+    bool bad2 = false;
+    uint64_t at2 = 0, f2 = 0;
+    while (m) {
+      const uint32_t q = (uint32_t)__ffs(m) - 1u;
+      m &= m - 1u;
+      const uint64_t p = (uint64_t)(p0 + (int64_t)q);
+      const uint64_t f = uniform ? r_lo : ej_resp_of(T.rb, T.R, p);
+      const uint64_t fs = T.rb[f];
+      const bool is_eq = (eq >> q) & 1u;
+      bool seen_lf = false, ok;
+      const uint32_t cls = pd_before(T, sum, blk, p, fs, &seen_lf);
+      if (!cls) ok = false;  // (a character at a file's start)
+      else if (cls & PD_S_EQ) ok = is_eq;
+      else if (cls & PD_S_DASH) {
+        if (T.s[p - 1] == 0x2du) ok = !is_eq && p - fs >= 5u && (p - fs == 5u || T.s[p - 6] == 0x0au);  // the letter behind a line's first dashes
+        else ok = seen_lf;
+      } else ok = true;
+      if (!ok && !bad2) {
+        bad2 = true;
+        at2 = p;
+        f2 = f;
+      }
+    }
+    ej_report(err, bad2, f2, at2);
+  }
+  unsigned long long at = cnt_t[blk] + (packed & 0xffffu);
+  const unsigned long long c_lane = cnt_c[blk] + (packed >> 16), e_lane = cnt_e[blk] + eq_before;
+  uint32_t m = tokm;
+  while (m) {
+    const uint32_t q = (uint32_t)__ffs(m) - 1u;
+    m &= m - 1u;
+    tok[at] = ((unsigned long long)(p0 + (int64_t)q) << 1) | ((kinds >> q) & 1u);
+    ctok[at] = c_lane + (uint32_t)__popc(chars & ((1u << q) - 1u));
+    etok[at] = e_lane + (uint32_t)__popc(eq & ((1u << q) - 1u));
+    at++;
+  }
+}
+
+// fstart: cfile[r] = the characters of [lo, rb[r]) (r <= R): the scanned block count plus the characters of rb[r]'s block
+// before it; a wave per boundary (k_ej_qstart)
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_fstart(EjText T, uint64_t b0, const unsigned long long* cnt_c, uint64_t nb, unsigned long long* cfile) {
+  const uint64_t r = (b0 + blockIdx.x) * (RP_BLOCK / 64) + (threadIdx.x >> 6);
+  if (r > T.R) return;  // (whole waves leave)
+  const uint64_t at = T.rb[r];
+  const uint64_t blk = ((uint64_t)(uintptr_t)T.s + at - T.a0) / EJ_TILE;
+  if (blk >= nb) {  // (hi at a block's edge)
+    if ((threadIdx.x & 63u) == 0) cfile[r] = cnt_c[nb];
+    return;
+  }
+  int64_t p0;
+  uint32_t valid, total;
+  const uint4 v = ej_chunk(T, blk, threadIdx.x & 63u, &p0, &valid);
+  uint32_t chars = 0u, before = 0u;
+#pragma unroll
+  for (uint32_t q = 0; q < EJ_PER; q++) {
+    const uint32_t c = ej_byte(v, q);
+    chars |= ((((c | 0x20u) - 0x61u) < 26u || (c - 0x30u) < 10u || c == 0x2bu || c == 0x2fu || c == 0x3du) ? 1u : 0u) << q;
+  }
+  const int64_t d = (int64_t)at - p0;
+  if (d >= 16) before = 0xffffu;
+  else if (d > 0) before = 0xffffu >> (16u - (uint32_t)d);
+  (void)ej_wave_scan((uint32_t)__popc(chars & valid & before), &total);
+  if ((threadIdx.x & 63u) == 0) cfile[r] = cnt_c[blk] + total;
+}
+
+// files: tfirst[r] = the tokens before rb[r] (r <= R); ccnt[r] = the certificates of file r, half its tokens — an odd
+// count is reported; ccnt[R] = 0 (the scan's total)
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_files(EjText T, uint64_t b0, const unsigned long long* tok, uint64_t ntok,
+                                                       unsigned long long* tfirst, unsigned long long* ccnt, unsigned long long* err) {
+  const uint64_t r = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
+  bool bad = false;
+  uint64_t off = 0;
+  if (r <= T.R) {
+    uint64_t first[2];
+#pragma unroll
+    for (uint32_t k = 0; k < 2; k++) {
+      const uint64_t at = T.rb[r + k < T.R ? r + k : T.R];
+      uint64_t l = 0, h = ntok;
+      while (l < h) {
+        const uint64_t mid = (l + h) >> 1;
+        if ((tok[mid] >> 1) < at) l = mid + 1;
+        else h = mid;
+      }
+      first[k] = l;
+    }
+    tfirst[r] = first[0];
+    uint64_t n = 0;
+    if (r < T.R) {
+      n = (first[1] - first[0]) >> 1;
+      bad = (first[1] - first[0]) & 1ull;
+      off = bad ? tok[first[1] - 1] >> 1 : 0ull;  // the armor line left alone
+    }
+    ccnt[r] = n;
+  }
+  ej_report(err, bad, r, off);
+}
+
+// the tables the check reads and writes
+struct PdCheck {
+  const unsigned long long* tok;
+  const unsigned long long* ctok;
+  const unsigned long long* etok;
+  uint64_t ntok;
+  const unsigned long long* tfirst;  // R + 1
+  const unsigned long long* ffirst;  // R + 1: the certificates before file r
+  const unsigned long long* cfile;   // R + 1: the characters before file r
+  unsigned long long* len;           // n + 1: the decoded length
+  unsigned long long* src;           // n: regular: where the body starts (from s); irregular: the BEGIN's token
+  unsigned long long* lay;           // n: L << 2 | e, L = 0: one line; PD_IRREGULAR
+  unsigned long long* sqlen;         // n + 1: the characters of an irregular block, else 0
+  unsigned long long* sqtiles;       // n + 1: the mark blocks its body touches, else 0
+};
+
+// check: one lane per token.  f_limit: the lowest file the passes before have reported, or none (~0).  The check relies on
+// armor lines that are spelled right and come in pairs, so it looks at the files below that one only: a violation of its
+// own in one of them is the lower one.
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_check(EjText T, uint64_t b0, PdCheck C, uint64_t f_limit, unsigned long long* err) {
+  const uint64_t t = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
+  bool bad = false, irregular = false, is_end = false;
+  uint64_t f = 0, pos = 0, i = 0, cc = 0, ne = 0, p0 = 0, b = 0;
+  uint32_t L = 0, e = 0;
+  unsigned long long w_nl = 0;  // the eols of a long regular block: what lies beyond the first PD_OWN the wave checks together
+  if (t < C.ntok) {
+    const unsigned long long tk = C.tok[t];
+    pos = tk >> 1;
+    const uint32_t kind = (uint32_t)(tk & 1ull);
+    f = ej_resp_of(T.rb, T.R, pos);
+    const uint64_t j = t - C.tfirst[f], nt = C.tfirst[f + 1] - C.tfirst[f];
+    if (f < f_limit && !(nt & 1ull)) {  // (else the file has been reported, or lies behind one that has)
+      bad = kind != (uint32_t)(j & 1ull);
+      if (!(j & 1ull)) {
+        bad = bad || C.ctok[t] != (j == 0 ? C.cfile[f] : C.ctok[t - 1] + PD_END_CHARS);
+      } else {
+        is_end = true;
+        cc = C.ctok[t] - C.ctok[t - 1] - PD_BEGIN_CHARS;
+        ne = C.etok[t] - C.etok[t - 1];
+        bad = bad || (cc & 3ull) || ne > 2 || (C.tok[t - 1] & 1ull) != PD_BEGIN;
+        if (j + 1 == nt) bad = bad || C.cfile[f + 1] != C.ctok[t] + PD_END_CHARS;
+        i = C.ffirst[f] + (j >> 1);
+        p0 = C.tok[t - 1] >> 1;
+        const uint64_t p1 = pos;
+        if (!bad && cc) {
+          // the body starts behind BEGIN's blank* LF
+          uint64_t q = p0 + PD_BEGIN_LEN;
+          for (uint32_t k = 0; k < PD_LMAX && q < p1 && pd_is_blank(T.s[q]); k++) q++;
+          if (q >= p1 || T.s[q] != 0x0au) irregular = true;
+          else {
+            b = q + 1;
+            const uint64_t ws = p1 - b - cc;  // >= 1: an LF lies in front of END
+            if (ws == 1) e = 1;               // one line, ended by that LF
+            else if (ws == 2 && T.s[p1 - 2] == 0x0du) e = 2;
+            else {
+              uint32_t l0 = 0;
+              while (l0 <= PD_LMAX && b + l0 < p1 && !pd_is_ws(T.s[b + l0])) l0++;  // (stops at that LF at the latest)
+              const uint32_t c = T.s[b + l0];
+              e = c == 0x0au ? 1u : (c == 0x0du && T.s[b + l0 + 1] == 0x0au) ? 2u : 0u;
+              L = l0;
+              if (l0 == 0 || l0 > PD_LMAX || (l0 & 3u) || !e || ws % e) irregular = true;
+              else {
+                const uint64_t nl = ws / e;
+                if (nl < 2 || (nl - 1) * L >= cc || cc > nl * L) irregular = true;
+                else {  // with every eol at its arithmetic place no other ws is left: ws = e nl
+                  const uint64_t own = nl - 1 < PD_OWN ? nl - 1 : PD_OWN;
+                  for (uint64_t k = 1; k <= own && !irregular; k++) {
+                    const uint64_t at = k + 1 < nl ? b + k * (L + e) + L : p1 - e;
+                    irregular = T.s[at + e - 1] != 0x0au || (e == 2 && T.s[at] != 0x0du);
+                  }
+                  if (!irregular && nl - 1 > PD_OWN) w_nl = nl;
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  // the long ones, one after the other, by the whole wave
+  unsigned long long big = __ballot(w_nl != 0);
+  while (big) {  // (wave-uniform)
+    const int l = __ffsll(big) - 1;
+    big &= big - 1ull;
+    const unsigned long long xb = __shfl((unsigned long long)b, l), xp1 = __shfl((unsigned long long)pos, l), xnl = __shfl(w_nl, l);
+    const uint32_t xL = __shfl(L, l), xe = __shfl(e, l);
+    bool miss = false;
+    for (unsigned long long k = PD_OWN + 1 + (threadIdx.x & 63u); k < xnl && !miss; k += 64ull) {
+      const uint64_t at = k + 1 < xnl ? xb + k * (xL + xe) + xL : xp1 - xe;
+      miss = T.s[at + xe - 1] != 0x0au || (xe == 2 && T.s[at] != 0x0du);
+    }
+    if (__ballot(miss) && (int)(threadIdx.x & 63u) == l) irregular = true;
+  }
+  if (is_end) {
+    C.len[i] = bad ? 0ull : cc / 4 * 3 - ne;
+    C.src[i] = irregular ? t - 1 : b;
+    C.lay[i] = irregular ? PD_IRREGULAR : ((unsigned long long)L << 2) | e;
+    C.sqlen[i] = irregular ? cc : 0ull;
+    const uint64_t s0 = (uint64_t)(uintptr_t)T.s;
+    C.sqtiles[i] = irregular ? (s0 + pos - 1 - T.a0) / EJ_TILE - (s0 + p0 + PD_BEGIN_LEN - T.a0) / EJ_TILE + 1 : 0ull;
+  }
+  const unsigned long long irr = __ballot(irregular);
+  if ((threadIdx.x & 63u) == 0 && irr) atomicAdd(err + 2, (unsigned long long)__popcll(irr));
+  ej_report(err, bad, f, pos);
+}
+
+// squeeze: block = tile t of irregular certificate i = tile_cert[t]: the characters of one mark block between the
+// certificate's armor lines → sq[sqoff[i] + their rank in the body]
+__global__ void __launch_bounds__(EJ_BLOCK) k_pd_squeeze(EjText T, uint64_t b0, const unsigned long long* tile_cert, const unsigned long long* tile_first,
+                                                         const unsigned long long* src, const unsigned long long* tok, const unsigned long long* ctok,
+                                                         const unsigned long long* cnt_c, const unsigned long long* sqoff, uint8_t* sq) {
+  const uint64_t t = b0 + blockIdx.x, i = tile_cert[t], k = t - tile_first[i];
+  const uint64_t tb = src[i];
+  const uint64_t from = (tok[tb] >> 1) + PD_BEGIN_LEN, to = tok[tb + 1] >> 1;
+  const uint64_t blk = ((uint64_t)(uintptr_t)T.s + from - T.a0) / EJ_TILE + k;
+  int64_t p0;
+  uint32_t valid, total;
+  const uint4 v = ej_chunk(T, blk, threadIdx.x, &p0, &valid);
+  uint32_t chars = 0u;
+#pragma unroll
+  for (uint32_t q = 0; q < EJ_PER; q++) {
+    const uint32_t c = ej_byte(v, q);
+    chars |= ((((c | 0x20u) - 0x61u) < 26u || (c - 0x30u) < 10u || c == 0x2bu || c == 0x2fu || c == 0x3du) ? 1u : 0u) << q;
+  }
+  chars &= valid;
+  const unsigned long long rank = cnt_c[blk] + ej_wave_scan((uint32_t)__popc(chars), &total) - (ctok[tb] + PD_BEGIN_CHARS);
+  uint8_t* out = sq + sqoff[i];
+  uint32_t m = chars;
+  while (m) {
+    const uint32_t q = (uint32_t)__ffs(m) - 1u;
+    m &= m - 1u;
+    const int64_t p = p0 + (int64_t)q;
+    if (p >= (int64_t)from && p < (int64_t)to) out[rank + (uint32_t)__popc(chars & ((1u << q) - 1u))] = (uint8_t)ej_byte(v, q);
+  }
+}
+
+// the tables of the decode
+struct PdDecode {
+  const unsigned long long* tile_cert;
+  const unsigned long long* tile_first;
+  const unsigned long long* offsets;  // n + 1: the scanned lengths
+  const unsigned long long* src;
+  const unsigned long long* lay;
+  const unsigned long long* sqoff;
+  const uint8_t* sq;
+};
+
+// decode: block = tile t of certificate i: its characters [EJ_DTILE k, …) → payload[offsets[i] + EJ_DOUT k, …)
+__global__ void __launch_bounds__(EJ_DBLOCK) k_pd_decode(const uint8_t* s, uint64_t b0, PdDecode D, uint8_t* payload) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[EJ_DOUT + 16];
+  const uint64_t t = b0 + blockIdx.x, i = D.tile_cert[t], k = t - D.tile_first[i];
+  const uint64_t at0 = D.offsets[i], dec = D.offsets[i + 1] - at0;
+  const uint64_t left = dec - k * EJ_DOUT;
+  const uint32_t total = left < EJ_DOUT ? (uint32_t)left : EJ_DOUT;  // 1 … EJ_DOUT
+  const uint64_t dst = at0 + k * EJ_DOUT;
+  const uint32_t phase = (uint32_t)(dst & 15ull);
+  const unsigned long long lay = D.lay[i];
+  const bool squeezed = (lay & 3ull) == PD_IRREGULAR;
+  const uint32_t L = squeezed ? 0u : (uint32_t)(lay >> 2), e = squeezed ? 0u : (uint32_t)(lay & 3ull);
+  const uint64_t base = squeezed ? (uint64_t)(uintptr_t)D.sq + D.sqoff[i] : (uint64_t)(uintptr_t)s + D.src[i];
+  const uint64_t r0 = k * EJ_DTILE;  // the tile's first character; the line it lies in and where (block-uniform)
+  const uint64_t line0 = L ? r0 / L : 0ull;
+  const uint64_t in0 = L ? r0 % L : r0;
+  if (3u * threadIdx.x < total) {
+    uint64_t a;
+    if (L) {  // a quantum never straddles a line: L % 4 == 0
+      const uint32_t m = (uint32_t)in0 + 4u * threadIdx.x;
+      a = base + (line0 + m / L) * (uint64_t)(L + e) + m % L;
+    } else {
+      a = base + in0 + 4ull * threadIdx.x;
+    }
+    const uint32_t sh = 8u * (uint32_t)(a & 3ull);
+    const uint32_t* w = (const uint32_t*)(uintptr_t)(a & ~3ull);
+    uint32_t ch = __builtin_nontemporal_load(w);
+    if (sh) ch = (ch >> sh) | (__builtin_nontemporal_load(w + 1) << (32u - sh));  // (the quantum reaches into w[1])
+    const uint32_t x = (ej_sextet(ch & 0xffu) << 18) | (ej_sextet((ch >> 8) & 0xffu) << 12) | (ej_sextet((ch >> 16) & 0xffu) << 6) |
+                       ej_sextet(ch >> 24);
+    uint8_t* o = stage + phase + 3u * threadIdx.x;
+    o[0] = (uint8_t)(x >> 16);
+    o[1] = (uint8_t)(x >> 8);
+    o[2] = (uint8_t)x;
+  }
+  __syncthreads();
+  ej_store_tile(stage, phase, total, payload + dst);
+}
+
+}  // namespace ctmr

@@ -33,6 +33,15 @@ class EntriesJsonError(CtmrError):
         self.bad_offset = bad_offset
 
 
+class PemDecodeError(CtmrError):
+    """A PEM file outside the grammar of ctmr_pem_decode*: the host decodes that one itself."""
+
+    def __init__(self, code, msg, bad_file, bad_offset):
+        super().__init__(code, msg)
+        self.bad_file = bad_file
+        self.bad_offset = bad_offset
+
+
 @dataclass
 class Batch:
     """Packed CT-entry batch (SURVEY.md §8(d) layout), host side."""
@@ -372,6 +381,87 @@ class Engine:
         records = d_rec.cpu().numpy().view(RECORD_DTYPE)[:n].copy()
         return EntriesResult(records, d_new.cpu().numpy().view(np.uint64)[:st.n_new].copy(),
                              d_ts.cpu().numpy().view(np.uint64)[:n].copy(), st, ds)
+
+    # ---- PEM certificate files as they lie (include/ctmr.h ctmr_pem_decode*; CPU twin: pem_text.parse)
+    def _pd_call(self, fn, alloc):
+        """The two calls of the sizing convention: one without buffers for the sizes (CTMR_E_RANGE fills `info`), one
+        into buffers of exactly that size.  A file outside the grammar raises PemDecodeError with its number."""
+        info = N.PemDecodeInfo()
+        rc = fn(None, 0, None, 0, None, info)
+        bufs = None
+        if rc == N.E_RANGE:
+            bufs = alloc(info.payload_bytes + N.PAYLOAD_PAD, info.certificates + 1, info.files + 1)
+            rc = fn(bufs[0], info.payload_bytes + N.PAYLOAD_PAD, bufs[1], info.certificates, bufs[2], info)
+        if rc == N.E_INVAL and info.bad_file != 2**64 - 1:
+            raise PemDecodeError(rc, self._lib.ctmr_last_error(self._h).decode(errors="replace"), info.bad_file, info.bad_offset)
+        self._ck(rc)
+        return bufs, info
+
+    def pem_decode(self, files):
+        """The certificates of PEM files (a list of bytes: concatenated CERTIFICATE blocks each), armor and base64
+        decoded on the GPU, text and result in host memory → (payload: numpy uint8 of payload_bytes + PAYLOAD_PAD, the
+        padding zeroed; offsets u64[n + 1]; file_first u64[F + 1]; info).  With issuer indices and entry types this is a
+        Batch."""
+        from . import pem_text
+        text, fb = pem_text.join(files)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        addr = lambda a: a.ctypes.data if a is not None else None
+        (payload, offsets, first), info = self._pd_call(
+            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode(self._h, buf.ctypes.data, fb.ctypes.data, len(files), addr(p), pc,
+                                                                     addr(o), oc, addr(ff), C.byref(info)),
+            lambda pb, no, nf: (np.empty(pb, np.uint8), np.empty(no, np.uint64), np.empty(nf, np.uint64)))
+        return payload, offsets, first, info
+
+    def pem_decode_device(self, d_text, file_bounds):
+        """pem_decode of a torch uint8 tensor on this engine's device (any alignment; file f at
+        d_text[file_bounds[f]:file_bounds[f + 1]]) → (d_payload, d_offsets, file_first, info): torch tensors on the
+        device — payload_bytes + PAYLOAD_PAD bytes and u64[n + 1] as int64 — and the host array u64[F + 1]."""
+        import torch
+        if not hasattr(d_text, "data_ptr"):
+            raise TypeError("d_text: a torch tensor on this engine's device")
+        fb = np.ascontiguousarray(file_bounds, dtype=np.uint64)
+        F = len(fb) - 1
+        if F < 0 or (F and ((fb[1:] < fb[:-1]).any() or int(fb[F]) > d_text.numel())):
+            raise ValueError("file_bounds do not ascend or reach beyond the text")
+        dev = "cuda:%d" % self.device
+        torch.cuda.synchronize(self.device)     # the engine runs on a stream of its own: what was queued to write d_text is done first
+        text = C.c_void_p(d_text.data_ptr()) if F and fb[F] > fb[0] else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        (d_payload, d_offsets, first), info = self._pd_call(
+            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_device(self._h, text, fb.ctypes.data, F, ptr(p), pc, ptr(o), oc,
+                                                                            ff.ctypes.data if ff is not None else None, C.byref(info)),
+            lambda pb, no, nf: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(no, dtype=torch.int64, device=dev),
+                                np.empty(nf, np.uint64)))
+        return d_payload, d_offsets, first, info
+
+    def map_pem(self, files, issuer_idx, want_records=True, want_new=True) -> BatchResult:
+        """map_batch over PEM files (a list of bytes): text → packed batch on the device → map_batch_device, no DER in
+        host memory.  issuer_idx: one issuer table index per FILE, or NO_ISSUER — under the reference's layout a file
+        lies below its issuer's directory — expanded to one per certificate on the device.  entry_type is 0
+        throughout: a certificate on disk was accepted once, and as an X509 entry it is accepted again, findings or not."""
+        import torch
+        from . import pem_text
+        text, fb = pem_text.join(files)
+        iss = np.ascontiguousarray(issuer_idx, dtype=np.uint32)
+        if iss.shape != (len(files),):
+            raise ValueError("issuer_idx: one per file")
+        dev = "cuda:%d" % self.device
+        d_text = torch.from_numpy(np.frombuffer(text, np.uint8).copy() if text else np.zeros(1, np.uint8)).to(dev)
+        d_payload, d_offsets, first, info = self.pem_decode_device(d_text, fb)
+        n = int(info.certificates)
+        if not n:   # nothing to map
+            return BatchResult(np.zeros(0, RECORD_DTYPE), np.zeros(0, np.uint64), N.BatchStats())
+        counts = torch.from_numpy(np.diff(first.astype(np.int64))).to(dev)
+        d_iss = torch.repeat_interleave(torch.from_numpy(iss.view(np.int32).copy()).to(dev), counts).contiguous()
+        d_et = torch.zeros(n, dtype=torch.uint8, device=dev)
+        d_rec = torch.zeros(n * RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_new = torch.zeros(n, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(self.device)     # (the issuer indices and the zeroed outputs are whole before the engine's stream starts)
+        st = self.map_batch_device(d_payload.data_ptr(), d_offsets.data_ptr(), d_iss.data_ptr(), d_et.data_ptr(), n,
+                                   d_rec.data_ptr() if want_records else 0, d_new.data_ptr() if want_new else 0)
+        records = d_rec.cpu().numpy().view(RECORD_DTYPE)[:n].copy() if want_records else np.zeros(n, RECORD_DTYPE)
+        new_idx = d_new.cpu().numpy().view(np.uint64)[:st.n_new].copy() if want_new else np.zeros(0, np.uint64)
+        return BatchResult(records, new_idx, st)
 
     def synth_entries_device(self, cfg: N.SynthConfig, first, n, d_bounds, d_blob, blob_cap) -> int:
         out = C.c_uint64()

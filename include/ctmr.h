@@ -905,6 +905,73 @@ int ctmr_entries_json_device(ctmr_engine* e, const void* d_text, const uint64_t*
                              void* d_blob, size_t blob_cap, uint64_t* d_bounds, uint64_t entries_cap,
                              uint64_t* resp_first, ctmr_entries_json_info* info);
 
+/* ---- PEM certificate files as they lie → a packed batch: what LocalDiskBackend.StoreCertificatePEM wrote
+ *      (storage/filesystemdatabase.go:167-201, storage/localdiskbackend.go:194-199) read back without encoding/pem and
+ *      encoding/base64 on a host core: the inverse of ctmr_pem_new / ctmr_pem_encode_device.  The armor lines are found,
+ *      the grammar checked and the base64 decoded on the device.  DESIGN.md §21.
+ *
+ * Input.  File f is text[file_bounds[f], file_bounds[f + 1]); file_bounds is a HOST array u64[n_files + 1], ascending.
+ *   No byte outside the bounds decides anything, and the state starts afresh at every file boundary.  n_files = 0 gives
+ *   the empty batch.  ws = 0x20 0x09 0x0D 0x0A; blank = 0x20 0x09 0x0D.
+ *       file  = gap ( block gap )*              gap = zero or more ws bytes
+ *       block = BEGIN body END
+ *       BEGIN = "-----BEGIN CERTIFICATE-----" blank* LF    its first dash is the file's first byte or follows an LF
+ *       body  = any run of ws and of the characters A-Z a-z 0-9 + / =
+ *       END   = "-----END CERTIFICATE-----" blank* ( LF | end of file )    its first dash follows an LF
+ *   The body's non-ws characters are its base64 text: their count is a multiple of 4; '=' occurs only as the last one or
+ *   the last two of them; ws may lie anywhere between them, inside a quantum and between the two pads included; the
+ *   spare bits of a padded quantum may hold any value and are dropped (the rule of ctmr_entries_json).  A body with no
+ *   characters is a certificate of 0 bytes: the map will call it a parse error, the decoder does not.  A file of ws
+ *   only, or of 0 bytes, holds no certificates and is valid.
+ *   EVERYTHING ELSE is outside the grammar and fails the call with CTMR_E_INVAL, info.bad_file naming the LOWEST such
+ *   file and info.bad_offset an advisory byte offset inside it: a '-' that is not part of such an armor line (4 or 6
+ *   dashes, a dash inside a body, the URL-safe alphabet); any other block type (X509 CRL, TRUSTED CERTIFICATE, another
+ *   letter case); a "Key: value" header line; any byte that is neither ws nor part of a block (a "# Label:" comment,
+ *   OpenSSL's "subject=" lines, a byte-order mark, NUL, a byte >= 0x80); a BEGIN without END, an END without BEGIN, two
+ *   BEGINs; a non-blank byte behind the closing dashes; a BEGIN not at a line start; a character count that is not a
+ *   multiple of 4, a '=' followed by an alphabet character, three '=', an unpadded last quantum.
+ *   This is a subset of what encoding/pem takes: Go's  for { block, rest = pem.Decode(rest) }  skips text between blocks
+ *   and blocks that fail, and parses headers.  For every file inside this grammar it yields the same blocks — Type
+ *   CERTIFICATE, no headers, the same bytes.  The host keeps its own decoder for a file named in bad_file.  Like the
+ *   rest of the Go boundary this is recalled, not pinned.
+ * Output.  payload = DER_0 ‖ DER_1 ‖ … back to back in text order and offsets u64[n + 1], offsets[0] = 0: exactly
+ *   ctmr_map_batch*' input; the CTMR_PAYLOAD_PAD bytes behind offsets[n] are zeroed, so the output is a valid packed
+ *   payload as it stands.  file_first is a HOST array u64[n_files + 1] or NULL: the index of each file's first
+ *   certificate, file_first[n_files] = n.
+ * Sizing.  The two-call convention: a payload_cap below payload_bytes + CTMR_PAYLOAD_PAD or a certs_cap below
+ *   certificates gives CTMR_E_RANGE with *info filled and nothing written.  Bounds a caller may use without a first
+ *   call: payload_bytes <= 3/4 text_bytes, and certificates <= (text_bytes + n_files) / 54 — a block takes its two
+ *   armor lines, 27 + 25 bytes, the LF behind BEGIN and the LF in front of the next BEGIN, 54 in all; only the last
+ *   block of a file may end with the file and save that LF, one byte per file.
+ * CTMR_E_INVAL and CTMR_E_NOMEM leave every output buffer as it was: all working memory is allocated, and the whole
+ *   text validated, before the first output byte.  Every position is 64-bit: a text of 2^32 bytes and more is one call.
+ * info.regular / info.irregular say how the blocks were read.  A block is regular when its body is lines of one length
+ *   L (a multiple of 4, at most 1024 when there are two lines or more; the last line may be shorter), every line ended
+ *   by the same eol, LF or CR LF, with no other ws in the body, and at most 1024 blanks stand behind BEGIN's dashes:
+ *   what pem.EncodeToMemory, ctmr_pem_new and OpenSSL write.  Its base64 is decoded from the text where it lies.  A
+ *   body of no characters is regular.  Every other block of the grammar is irregular: its characters are first copied
+ *   together into working memory.  The result is the same.
+ * Read-only.  Nothing of the engine's state is read or changed; the text is const.
+ * ctmr_pem_decode takes the text in host memory (the bytes inside the bounds staged on the device once) and writes
+ * payload, offsets to host memory; ctmr_pem_decode_device takes the text in device memory of this engine's device at
+ * ANY alignment and writes d_payload (16-byte aligned) and d_offsets on the device.  Both return after the engine's
+ * stream has drained. */
+typedef struct {
+  uint64_t files, certificates;
+  uint64_t text_bytes;      /* file_bounds[F] - file_bounds[0] */
+  uint64_t payload_bytes;   /* offsets[n]; the call needs payload_bytes + CTMR_PAYLOAD_PAD of capacity */
+  uint64_t regular;         /* blocks decoded from the text where it lies */
+  uint64_t irregular;       /* blocks decoded through the squeezed copy */
+  uint64_t bad_file;        /* on CTMR_E_INVAL: the LOWEST-numbered file outside the grammar; else UINT64_MAX */
+  uint64_t bad_offset;      /* on CTMR_E_INVAL: a byte offset inside that file's bounds (advisory); else UINT64_MAX */
+} ctmr_pem_decode_info;
+int ctmr_pem_decode(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files,
+                    uint8_t* payload, size_t payload_cap, uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first,
+                    ctmr_pem_decode_info* info);
+int ctmr_pem_decode_device(ctmr_engine* e, const void* d_text, const uint64_t* file_bounds, uint64_t n_files,
+                           void* d_payload, size_t payload_cap, uint64_t* d_offsets, uint64_t certs_cap,
+                           uint64_t* file_first, ctmr_pem_decode_info* info);
+
 /* Asynchronous ingestion (ctmr_submit_batch above) for RAW get-entries responses — what the reference's downloader actually holds (ct-fetch.go:446-462):
  * blob = leaf_input_0 ‖ extra_data_0 ‖ leaf_input_1 ‖ …, bounds u64[2n+1] (ctmr_map_entries' input).  Submits of
  * either form share the pipeline and its ordering; a super-batch holds one form (a change of form closes the open one).
