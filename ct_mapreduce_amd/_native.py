@@ -253,6 +253,12 @@ SIGNATURES = {
     "ctmr_entries_json": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(EntriesJsonInfo)]),
     "ctmr_entries_json_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P,
                                            C.POINTER(EntriesJsonInfo)]),
+    "ctmr_entries_json_each": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, _P, C.POINTER(EntriesJsonInfo)]),
+    "ctmr_entries_json_each_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, _P,
+                                                C.POINTER(EntriesJsonInfo)]),
+    "ctmr_submit_entries_json": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ctmr_wait_entries_json": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(EntriesJsonInfo),
+                                         C.POINTER(DecodeStats), C.POINTER(BatchStats)]),
     "ctmr_pem_decode": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(PemDecodeInfo)]),
     "ctmr_pem_decode_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(PemDecodeInfo)]),
     "ctmr_meta_new_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -702,6 +702,7 @@ extern "C" {
 #include "engine/merge.inc"
 #include "engine/resp_parse.inc"
 #include "engine/entries_json.inc"
+#include "engine/pipeline_json.inc"
 #include "engine/pem_decode.inc"
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // engine/entries_json.inc — get-entries HTTP bodies as they lie → a raw-entry batch (include/ctmr.h ctmr_entries_json*,
-// DESIGN.md §20).  The text stays where it lies; the kernels of kernels/entries_json.h find its tokens, check the
+// DESIGN.md §20; ctmr_entries_json_each*, every body judged alone, §22).  The text stays where it lies; the kernels of kernels/entries_json.h find its tokens, check the
 // grammar and decode the base64.  The host sees counts only: tokens, entries, decoded bytes, tiles.
 // Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/resp_parse.inc.
 
@@ -11,6 +11,8 @@ struct EntriesJson {
   EjText text{};
   uint64_t n = 0, ntiles = 0;
   ctmr_entries_json_info info{};
+  std::vector<uint64_t> bad;  // each: the verdict of every response, UINT64_MAX or an offset inside it
+  bool no_text = false;       // each: no body holds a byte, nothing was launched: efirst is not there, all of it is zero
 };
 
 const char* const ENTRIES_JSON = "entries json";
@@ -49,10 +51,19 @@ int ej_scan(ctmr_engine* e, DevMem& data, uint64_t n, uint64_t* total) {
 
 // Everything but the blob: the text (device memory, any alignment; response r at s[rb[r], rb[r + 1])) validated, J->info
 // made, the tables of the decode left on the device.  Drains the stream.
-int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint64_t R, EntriesJson* J) {
+// each: a response outside the grammar fails nothing: J->bad[r] gets its offset, J->info names the lowest, and efirst,
+// bounds, src are those of the responses inside the grammar alone, the others holding no entries.
+int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint64_t R, EntriesJson* J, bool each = false) {
   int r;
   ctmr_entries_json_info& info = J->info;
   ej_info_none(&info, R);
+  if (each) {
+    try {
+      J->bad.assign(R, ~0ull);
+    } catch (const std::bad_alloc&) {
+      return fail(e, CTMR_E_NOMEM, "%s: no host memory for %llu verdicts", ENTRIES_JSON, (unsigned long long)R);
+    }
+  }
   for (uint64_t i = 0; i < R; i++)
     if (rb[i] > rb[i + 1]) return fail(e, CTMR_E_INVAL, "%s: resp_bounds[%llu] lies behind its successor", ENTRIES_JSON, (unsigned long long)i);
   if ((r = ej_alloc(e, &J->bounds, 1))) return r;
@@ -63,6 +74,14 @@ int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint
   }
   const uint64_t lo = rb[0], hi = rb[R];
   info.text_bytes = hi - lo;
+  if (lo == hi && each) {  // empty bodies only: each has its verdict, and no kernel runs over an empty range
+    std::copy(rb, rb + R, J->bad.begin());
+    J->no_text = true;
+    info.bad_response = 0;
+    info.bad_offset = lo;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return CTMR_OK;
+  }
   if (lo == hi) {
     info.bad_response = 0;
     info.bad_offset = lo;
@@ -80,13 +99,13 @@ int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint
   const uint64_t nb = ((uint64_t)(uintptr_t)s + hi - T.a0 + EJ_TILE - 1) / EJ_TILE;
   DevMem qblk_m, cnt_t_m, cnt_o_m, err_m, qstart_m, tfirst_m, tok_m, oddb_m;
   if ((r = ej_alloc(e, &qblk_m, nb + 1)) || (r = ej_alloc(e, &cnt_t_m, nb + 1)) || (r = ej_alloc(e, &cnt_o_m, nb + 1)) ||
-      (r = ej_alloc(e, &err_m, 2)) || (r = ej_alloc(e, &qstart_m, R)) || (r = ej_alloc(e, &tfirst_m, R + 1)) || (r = ej_alloc(e, &J->efirst, R + 1)))
+      (r = ej_alloc(e, &err_m, each ? R : 2)) || (r = ej_alloc(e, &qstart_m, R)) || (r = ej_alloc(e, &tfirst_m, R + 1)) || (r = ej_alloc(e, &J->efirst, R + 1)))
     return r;
   unsigned long long* err = (unsigned long long*)err_m.p;
   unsigned long long* qblk = (unsigned long long*)qblk_m.p;
   unsigned long long* cnt_t = (unsigned long long*)cnt_t_m.p;
   unsigned long long* cnt_o = (unsigned long long*)cnt_o_m.p;
-  HIPCHK(e, hipMemsetAsync(err, 0xff, 16, e->stream));
+  HIPCHK(e, hipMemsetAsync(err, 0xff, (each ? R : 2) * 8, e->stream));
   // ---- string state
   ej_turns(nb, [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_ej_quotes, g, dim3(EJ_BLOCK), 0, e->stream, T, b0, qblk); });
   if ((r = ej_scan(e, qblk_m, nb, nullptr))) return r;
@@ -95,8 +114,12 @@ int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint
   });
   // ---- tokens
   ej_turns(nb, [&](uint64_t b0, dim3 g) {
-    hipLaunchKernelGGL((k_ej_mark<false>), g, dim3(EJ_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)qblk,
-                       (const unsigned long long*)qstart_m.p, cnt_t, cnt_o, (unsigned long long*)nullptr, (unsigned long long*)nullptr, err);
+    if (each)
+      hipLaunchKernelGGL((k_ej_mark<false, true>), g, dim3(EJ_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)qblk,
+                         (const unsigned long long*)qstart_m.p, cnt_t, cnt_o, (unsigned long long*)nullptr, (unsigned long long*)nullptr, err);
+    else
+      hipLaunchKernelGGL((k_ej_mark<false>), g, dim3(EJ_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)qblk,
+                         (const unsigned long long*)qstart_m.p, cnt_t, cnt_o, (unsigned long long*)nullptr, (unsigned long long*)nullptr, err);
   });
   uint64_t ntok = 0;
   if ((r = ej_scan(e, cnt_o_m, nb, nullptr)) || (r = ej_scan(e, cnt_t_m, nb, &ntok))) return r;
@@ -107,8 +130,12 @@ int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint
   });
   // ---- responses, entries
   ej_turns(ej_blocks(R + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
-    hipLaunchKernelGGL(k_ej_resp, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)tok_m.p, ntok, (unsigned long long*)tfirst_m.p,
-                       (unsigned long long*)J->efirst.p, err);
+    if (each)
+      hipLaunchKernelGGL(k_ej_resp<true>, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)tok_m.p, ntok,
+                         (unsigned long long*)tfirst_m.p, (unsigned long long*)J->efirst.p, err);
+    else
+      hipLaunchKernelGGL(k_ej_resp<false>, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)tok_m.p, ntok,
+                         (unsigned long long*)tfirst_m.p, (unsigned long long*)J->efirst.p, err);
   });
   uint64_t n = 0;
   if ((r = scan_u64(e, (uint64_t*)J->efirst.p, R + 1, false, SC_MISC))) return r;
@@ -119,12 +146,56 @@ int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint
   if (ntok) {
     const EjCheck C{(const unsigned long long*)tok_m.p,    (const unsigned long long*)oddb_m.p,     ntok, (const unsigned long long*)tfirst_m.p,
                     (const unsigned long long*)J->efirst.p, (unsigned long long*)J->bounds.p, (unsigned long long*)J->src.p};
-    ej_turns(ej_blocks(ntok, RP_BLOCK), [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_ej_check, g, dim3(RP_BLOCK), 0, e->stream, T, b0, C, err); });
+    ej_turns(ej_blocks(ntok, RP_BLOCK), [&](uint64_t b0, dim3 g) {
+      if (each) hipLaunchKernelGGL(k_ej_check<true>, g, dim3(RP_BLOCK), 0, e->stream, T, b0, C, err);
+      else hipLaunchKernelGGL(k_ej_check<false>, g, dim3(RP_BLOCK), 0, e->stream, T, b0, C, err);
+    });
   }
-  unsigned long long h_err[2] = {0, 0};
-  HIPCHK(e, hipMemcpyAsync(h_err, err, 16, hipMemcpyDeviceToHost, e->stream));
+  unsigned long long h_err[2] = {~0ull, ~0ull};
+  if (each) {
+    HIPCHK(e, hipMemcpyAsync(J->bad.data(), err, R * 8, hipMemcpyDeviceToHost, e->stream));
+  } else {
+    HIPCHK(e, hipMemcpyAsync(h_err, err, 16, hipMemcpyDeviceToHost, e->stream));
+  }
   HIPCHK(e, hipStreamSynchronize(e->stream));
   HIPCHK(e, hipGetLastError());
+  if (each) {
+    uint64_t n_bad = 0;
+    for (uint64_t i = R; i-- > 0;)
+      if (J->bad[i] != ~0ull) {
+        n_bad++;
+        info.bad_response = i;
+        info.bad_offset = J->bad[i];
+      }
+    if (n_bad) {
+      // the responses with a verdict leave: their counts to zero, efirst scanned again, and the lengths and sources the
+      // check wrote under the old numbering gathered under the new one (entry-sized; a second check would be token-sized
+      // and read the keys and pads from the text again)
+      const uint64_t n0 = n;
+      DevMem efirst2, len2, src2;
+      if ((r = ej_alloc(e, &efirst2, R + 1))) return r;
+      ej_turns(ej_blocks(R + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
+        hipLaunchKernelGGL(k_ej_drop, g, dim3(RP_BLOCK), 0, e->stream, b0, R, (const unsigned long long*)err, (const unsigned long long*)J->efirst.p,
+                           (unsigned long long*)efirst2.p);
+      });
+      if ((r = scan_u64(e, (uint64_t*)efirst2.p, R + 1, false, SC_MISC))) return r;
+      HIPCHK(e, hipMemcpyAsync(&n, (uint64_t*)efirst2.p + R, 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipStreamSynchronize(e->stream));
+      HIPCHK(e, hipGetLastError());
+      if ((r = ej_alloc(e, &len2, 2 * n + 1)) || (r = ej_alloc(e, &src2, 2 * n))) return r;
+      if (n)
+        ej_turns(ej_blocks(n0, RP_BLOCK), [&](uint64_t b0, dim3 g) {
+          hipLaunchKernelGGL(k_ej_gather, g, dim3(RP_BLOCK), 0, e->stream, b0, R, n0, (const unsigned long long*)err,
+                             (const unsigned long long*)J->efirst.p, (const unsigned long long*)efirst2.p, (const unsigned long long*)J->bounds.p,
+                             (const unsigned long long*)J->src.p, (unsigned long long*)len2.p, (unsigned long long*)src2.p);
+        });
+      HIPCHK(e, hipStreamSynchronize(e->stream));  // (the old tables are freed when this block ends)
+      HIPCHK(e, hipGetLastError());
+      std::swap(J->efirst.p, efirst2.p);
+      std::swap(J->bounds.p, len2.p);
+      std::swap(J->src.p, src2.p);
+    }
+  }
   if (h_err[0] != ~0ull) {
     info.bad_response = h_err[0];
     info.bad_offset = h_err[1];
@@ -175,7 +246,7 @@ int entries_json_decode(ctmr_engine* e, const EntriesJson& J, uint8_t* d_blob) {
 
 int entries_json_resp_first(ctmr_engine* e, const EntriesJson& J, uint64_t R, uint64_t* resp_first) {
   if (!resp_first) return CTMR_OK;
-  if (!R) resp_first[0] = 0;
+  if (!R || J.no_text) memset(resp_first, 0, (R + 1) * 8);
   else HIPCHK(e, hipMemcpy(resp_first, J.efirst.p, (R + 1) * 8, hipMemcpyDeviceToHost));
   return CTMR_OK;
 }
@@ -183,32 +254,42 @@ int entries_json_resp_first(ctmr_engine* e, const EntriesJson& J, uint64_t R, ui
 }  // namespace
 }  // extern "C++"
 
-int ctmr_entries_json_device(ctmr_engine* e, const void* d_text, const uint64_t* resp_bounds, uint64_t n_responses, void* d_blob,
-                             size_t blob_cap, uint64_t* d_bounds, uint64_t entries_cap, uint64_t* resp_first, ctmr_entries_json_info* info) {
+extern "C++" {
+namespace {
+
+// ctmr_entries_json_device and, with resp_bad, ctmr_entries_json_each_device
+int entries_json_device_call(ctmr_engine* e, const void* d_text, const uint64_t* resp_bounds, uint64_t n_responses, void* d_blob, size_t blob_cap,
+                             uint64_t* d_bounds, uint64_t entries_cap, uint64_t* resp_first, uint64_t* resp_bad, bool each,
+                             ctmr_entries_json_info* info) {
   if (!e || !info) return CTMR_E_INVAL;
   ej_info_none(info, n_responses);  // (a bad argument names no response)
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (!resp_bounds) return fail(e, CTMR_E_INVAL, "%s: null resp_bounds", ENTRIES_JSON);
+  if (each && !resp_bad) return fail(e, CTMR_E_INVAL, "%s: null resp_bad", ENTRIES_JSON);
   if (n_responses && resp_bounds[n_responses] > resp_bounds[0] && !d_text) return fail(e, CTMR_E_INVAL, "%s: null text", ENTRIES_JSON);
   if ((uintptr_t)d_blob & 15u) return fail(e, CTMR_E_INVAL, "%s: the blob is not 16-byte aligned", ENTRIES_JSON);
   EntriesJson J;
-  int r = entries_json_core(e, (const uint8_t*)d_text, resp_bounds, n_responses, &J);
+  int r = entries_json_core(e, (const uint8_t*)d_text, resp_bounds, n_responses, &J, each);
   *info = J.info;
   if (r) return r;
   if ((r = entries_json_fits(e, J, d_blob, blob_cap, d_bounds, entries_cap))) return r;
   if ((r = entries_json_decode(e, J, (uint8_t*)d_blob))) return r;
   HIPCHK(e, hipMemcpy(d_bounds, J.bounds.p, (2 * J.n + 1) * 8, hipMemcpyDeviceToDevice));
+  if (each && n_responses) memcpy(resp_bad, J.bad.data(), n_responses * 8);
   return entries_json_resp_first(e, J, n_responses, resp_first);
 }
 
-int ctmr_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses, uint8_t* blob, size_t blob_cap,
-                      uint64_t* bounds, uint64_t entries_cap, uint64_t* resp_first, ctmr_entries_json_info* info) {
+// ctmr_entries_json and, with resp_bad, ctmr_entries_json_each
+int entries_json_host_call(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses, uint8_t* blob, size_t blob_cap,
+                           uint64_t* bounds, uint64_t entries_cap, uint64_t* resp_first, uint64_t* resp_bad, bool each,
+                           ctmr_entries_json_info* info) {
   if (!e || !info) return CTMR_E_INVAL;
   ej_info_none(info, n_responses);  // (a bad argument names no response)
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (!resp_bounds) return fail(e, CTMR_E_INVAL, "%s: null resp_bounds", ENTRIES_JSON);
+  if (each && !resp_bad) return fail(e, CTMR_E_INVAL, "%s: null resp_bad", ENTRIES_JSON);
   const uint64_t lo = n_responses ? resp_bounds[0] : 0, hi = n_responses ? resp_bounds[n_responses] : 0;
   if (hi > lo && !text) return fail(e, CTMR_E_INVAL, "%s: null text", ENTRIES_JSON);
   DevMem d_text, d_blob;
@@ -217,7 +298,7 @@ int ctmr_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_
     HIPCHK(e, hipMemcpyAsync(d_text.p, text + lo, hi - lo, hipMemcpyHostToDevice, e->stream));
   }
   EntriesJson J;
-  int r = entries_json_core(e, (const uint8_t*)((uintptr_t)d_text.p - lo), resp_bounds, n_responses, &J);
+  int r = entries_json_core(e, (const uint8_t*)((uintptr_t)d_text.p - lo), resp_bounds, n_responses, &J, each);
   *info = J.info;
   if (r) return r;
   if ((r = entries_json_fits(e, J, blob, blob_cap, bounds, entries_cap))) return r;
@@ -226,5 +307,30 @@ int ctmr_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_
   if ((r = entries_json_decode(e, J, d_blob.u8()))) return r;
   HIPCHK(e, hipMemcpy(blob, d_blob.p, J.info.blob_bytes + CTMR_PAYLOAD_PAD, hipMemcpyDeviceToHost));
   HIPCHK(e, hipMemcpy(bounds, J.bounds.p, (2 * J.n + 1) * 8, hipMemcpyDeviceToHost));
+  if (each && n_responses) memcpy(resp_bad, J.bad.data(), n_responses * 8);
   return entries_json_resp_first(e, J, n_responses, resp_first);
+}
+
+}  // namespace
+}  // extern "C++"
+
+int ctmr_entries_json_device(ctmr_engine* e, const void* d_text, const uint64_t* resp_bounds, uint64_t n_responses, void* d_blob,
+                             size_t blob_cap, uint64_t* d_bounds, uint64_t entries_cap, uint64_t* resp_first, ctmr_entries_json_info* info) {
+  return entries_json_device_call(e, d_text, resp_bounds, n_responses, d_blob, blob_cap, d_bounds, entries_cap, resp_first, nullptr, false, info);
+}
+
+int ctmr_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses, uint8_t* blob, size_t blob_cap,
+                      uint64_t* bounds, uint64_t entries_cap, uint64_t* resp_first, ctmr_entries_json_info* info) {
+  return entries_json_host_call(e, text, resp_bounds, n_responses, blob, blob_cap, bounds, entries_cap, resp_first, nullptr, false, info);
+}
+
+int ctmr_entries_json_each_device(ctmr_engine* e, const void* d_text, const uint64_t* resp_bounds, uint64_t n_responses, void* d_blob,
+                                  size_t blob_cap, uint64_t* d_bounds, uint64_t entries_cap, uint64_t* resp_first, uint64_t* resp_bad,
+                                  ctmr_entries_json_info* info) {
+  return entries_json_device_call(e, d_text, resp_bounds, n_responses, d_blob, blob_cap, d_bounds, entries_cap, resp_first, resp_bad, true, info);
+}
+
+int ctmr_entries_json_each(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses, uint8_t* blob, size_t blob_cap,
+                           uint64_t* bounds, uint64_t entries_cap, uint64_t* resp_first, uint64_t* resp_bad, ctmr_entries_json_info* info) {
+  return entries_json_host_call(e, text, resp_bounds, n_responses, blob, blob_cap, bounds, entries_cap, resp_first, resp_bad, true, info);
 }

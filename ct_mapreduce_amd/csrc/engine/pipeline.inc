@@ -1,5 +1,7 @@
-// engine/pipeline.inc — asynchronous host ingestion: ctmr_submit_batch / ctmr_wait / ctmr_flush.
-// Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/map.inc.
+// engine/pipeline.inc — asynchronous host ingestion: ctmr_submit_batch / ctmr_wait / ctmr_flush, and the raw-entry and
+// get-entries JSON forms of both (ctmr_submit_entries*, ctmr_wait_entries*).
+// Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/map.inc; the
+// worker's step for the JSON form is engine/pipeline_json.inc, behind engine/entries_json.inc.
 //
 // The reference's downloader hands insertCTWorker one get-entries response at a time — at most 1 001 entries
 // (cmd/ct-fetch/ct-fetch.go:417-424) — through a 16 384-entry channel (:132), and the workers drain it concurrently
@@ -24,10 +26,18 @@ namespace {
 constexpr uint32_t PIPE_SLOTS = 4;
 constexpr uint32_t PIPE_MAX_STREAMS = 4;  // copy streams: consecutive submits' DMA transfers overlap their set-up
 constexpr uint64_t PIPE_CLOSE_ENTRIES = 65536, PIPE_CLOSE_BYTES = 96ull << 20;
+constexpr uint64_t PIPE_CLOSE_BODIES = 4096;  // JSON super-batches: the entries are not known before the worker has run
+
+// What a super-batch holds: the packed form (ctmr_submit_batch), blob + bounds u64[2n+1] (ctmr_submit_entries), or
+// get-entries bodies as text (ctmr_submit_entries_json).  One form per super-batch.
+enum PipeForm : uint8_t { PF_PACKED = 0, PF_RAW, PF_JSON };
 
 struct PipeTicket {
-  uint64_t first, n;
+  uint64_t first, n;  // its entries in the super-batch (JSON: known when the worker is done)
   bool consumed;
+  uint64_t body0 = 0, nbody = 0;  // JSON: its bodies in the super-batch,
+  uint64_t text_at = 0;           //   where its text starts in the slot's,
+  uint64_t text_base = 0;         //   and resp_bounds[0] of the submit: offsets go back to the caller's text pointer
 };
 
 enum PipeState { PS_FREE = 0, PS_OPEN, PS_QUEUED, PS_DONE };
@@ -52,7 +62,12 @@ struct PipeSlot {
   // fill state
   uint64_t n = 0, bytes = 0;
   bool any_type = false;
-  bool raw = false;                                     // blob + bounds u64[2n+1] (ctmr_submit_entries) instead of the packed form
+  PipeForm form = PF_PACKED;
+  // JSON super-batches: d_payload holds the text.  The bodies' bounds in it live here, not in the meta buffers, which
+  // pipe_slot_reserve frees when the worker sizes the slot by the entries found.
+  std::vector<uint64_t> body_rb;                        // bodies + 1
+  std::vector<uint64_t> body_first, body_bad;           // the worker's: each body's first entry (bodies + 1), its verdict
+  uint8_t* d_blob = nullptr; size_t blob_cap = 0;       // the decoded entries; h_meta: their bounds u64[2n+1]
   ctmr_decode_stats dstats{};
   std::vector<PipeTicket> tickets;
   hipEvent_t ev_h2d[PIPE_MAX_STREAMS] = {};
@@ -130,7 +145,9 @@ int pipe_close_locked(ctmr_engine* e, ctmr_pipeline* p) {
   if (p->open < 0) return CTMR_OK;
   PipeSlot& s = p->slots[p->open];
   HIPCHK(e, hipSetDevice(e->device));
-  if (s.raw) {
+  if (s.form == PF_JSON) {
+    // (the bodies' bounds go to the device with the worker's call)
+  } else if (s.form == PF_RAW) {
     slot_h_offsets(s)[2 * s.n] = s.bytes;
     HIPCHK(e, hipMemcpyAsync(s.d_meta, s.h_meta, (2 * s.n + 1) * 8, hipMemcpyHostToDevice, p->copy_stream[0]));
   } else {
@@ -146,6 +163,8 @@ int pipe_close_locked(ctmr_engine* e, ctmr_pipeline* p) {
   p->cv.notify_all();
   return CTMR_OK;
 }
+
+int pipe_run_json(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view);  // engine/pipeline_json.inc
 
 void pipe_worker(ctmr_engine* e) {
   ctmr_pipeline* p = e->pipe.load(std::memory_order_acquire);
@@ -168,7 +187,9 @@ void pipe_worker(ctmr_engine* e) {
       for (uint32_t q = 0; q < p->n_streams; q++)
         if (hipStreamWaitEvent(e->stream, s.ev_h2d[q], 0) != hipSuccess) rc = CTMR_E_HIP;
       ctmr_entry_view view{};
-      if (rc == CTMR_OK && s.raw)  // decode + Chain[0] match (issuers registered on the way) + map/reduce, as ctmr_map_entries_device
+      if (rc == CTMR_OK && s.form == PF_JSON)  // every body judged, the good ones decoded into s.d_blob, then as a raw super-batch
+        rc = pipe_run_json(e, s, &view);
+      else if (rc == CTMR_OK && s.form == PF_RAW)  // decode + Chain[0] match (issuers registered on the way) + map/reduce, as ctmr_map_entries_device
         rc = s.n ? map_entries_locked(e, s.d_payload, (const uint64_t*)s.d_meta, s.n, s.d_records, s.d_new, s.d_ts, &s.dstats,
                                       &s.stats, &view)
                  : CTMR_OK;
@@ -178,7 +199,7 @@ void pipe_worker(ctmr_engine* e) {
                                &s.stats, nullptr, 0, s.bytes);
       if (rc == CTMR_OK) {
         hipError_t h = hipMemcpyAsync(s.h_records, s.d_records, s.n * sizeof(ctmr_record), hipMemcpyDeviceToHost, e->stream);
-        if (h == hipSuccess && s.raw && s.n) {
+        if (h == hipSuccess && s.form != PF_PACKED && s.n) {
           h = hipMemcpyAsync(s.h_ts, s.d_ts, s.n * 8, hipMemcpyDeviceToHost, e->stream);
           if (h == hipSuccess) h = hipMemcpyAsync(s.h_etype, view.entry_type, s.n, hipMemcpyDeviceToHost, e->stream);
           if (h == hipSuccess) h = hipMemcpyAsync(s.h_c0len, view.chain0_len, s.n * 4, hipMemcpyDeviceToHost, e->stream);
@@ -195,6 +216,11 @@ void pipe_worker(ctmr_engine* e) {
     }
     {
       std::lock_guard<std::mutex> lk(p->mu);
+      if (s.form == PF_JSON && rc == CTMR_OK)  // now the tickets' entries are known
+        for (auto& t : s.tickets) {
+          t.first = s.body_first[t.body0];
+          t.n = s.body_first[t.body0 + t.nbody] - t.first;
+        }
       s.rc = rc;
       s.err = err;
       s.state = PS_DONE;
@@ -241,6 +267,7 @@ void pipe_shutdown(ctmr_engine* e) {
   (void)hipSetDevice(e->device);
   for (auto& s : p->slots) {
     (void)hipFree(s.d_payload); (void)hipFree(s.d_meta); (void)hipFree(s.d_records); (void)hipFree(s.d_new); (void)hipFree(s.d_ts);
+    (void)hipFree(s.d_blob);
     (void)hipHostFree(s.h_meta); (void)hipHostFree(s.h_records); (void)hipHostFree(s.h_new); (void)hipHostFree(s.h_ts);
     (void)hipHostFree(s.h_etype); (void)hipHostFree(s.h_c0len);
     for (auto ev : s.ev_h2d)
@@ -259,7 +286,7 @@ extern "C++" {
 namespace {
 
 // Make sure a super-batch of the wanted form is open and has room for n entries / `bytes` bytes (p->mu held through lk).
-int pipe_open_for(ctmr_engine* e, ctmr_pipeline* p, std::unique_lock<std::mutex>& lk, bool raw, uint64_t n, uint64_t bytes) {
+int pipe_open_for(ctmr_engine* e, ctmr_pipeline* p, std::unique_lock<std::mutex>& lk, PipeForm form, uint64_t n, uint64_t bytes) {
   int r;
   int k = -1;
   // Everything is decided again after every wait: while this submitter slept (the wait releases p->mu) another one may
@@ -268,7 +295,7 @@ int pipe_open_for(ctmr_engine* e, ctmr_pipeline* p, std::unique_lock<std::mutex>
   for (;;) {
     if (p->open >= 0) {
       PipeSlot& s = p->slots[p->open];
-      if (s.raw != raw || s.n + n > s.ent_cap || s.bytes + bytes + CTMR_PAYLOAD_PAD + 16 > s.payload_cap)
+      if (s.form != form || s.n + n > s.ent_cap || s.bytes + bytes + CTMR_PAYLOAD_PAD + 16 > s.payload_cap)
         if ((r = pipe_close_locked(e, p))) return r;
     }
     if (p->open >= 0) return CTMR_OK;
@@ -291,8 +318,11 @@ int pipe_open_for(ctmr_engine* e, ctmr_pipeline* p, std::unique_lock<std::mutex>
   s.seq = p->next_seq++;
   s.n = s.bytes = 0;
   s.any_type = false;
-  s.raw = raw;
+  s.form = form;
   s.tickets.clear();
+  s.body_rb.assign(1, 0);
+  s.body_first.clear();
+  s.body_bad.clear();
   s.rc = CTMR_OK;
   s.err.clear();
   memset(&s.stats, 0, sizeof s.stats);
@@ -312,7 +342,7 @@ int pipe_append(ctmr_engine* e, ctmr_pipeline* p, const uint8_t* src, uint64_t b
   *ticket = (s.seq << 20) | (uint64_t)(s.tickets.size() - 1);  // ≤ 2^20 tickets per super-batch (it closes at 65 536 entries; empty batches: see below)
   s.n += n;
   s.bytes += bytes;
-  if (s.n >= PIPE_CLOSE_ENTRIES || s.bytes >= PIPE_CLOSE_BYTES || s.tickets.size() >= (1u << 20) - 1)
+  if (s.n >= PIPE_CLOSE_ENTRIES || s.bytes >= PIPE_CLOSE_BYTES || s.tickets.size() >= (1u << 20) - 1 || s.body_rb.size() > PIPE_CLOSE_BODIES)
     return pipe_close_locked(e, p);
   return CTMR_OK;
 }
@@ -333,7 +363,7 @@ int ctmr_submit_batch(ctmr_engine* e, const uint8_t* payload, const uint64_t* of
   std::unique_lock<std::mutex> lk(p->mu);
   HIPCHK(e, hipSetDevice(e->device));
   // (a batch larger than a whole slot gets a slot of its own, grown to fit)
-  if ((r = pipe_open_for(e, p, lk, false, n, bytes))) return r;
+  if ((r = pipe_open_for(e, p, lk, PF_PACKED, n, bytes))) return r;
   PipeSlot& s = p->slots[p->open];
   uint64_t* ho = slot_h_offsets(s) + s.n;
   for (uint64_t i = 0; i < n; i++) ho[i] = s.bytes + (offsets[i] - base);
@@ -354,11 +384,46 @@ int ctmr_submit_entries(ctmr_engine* e, const uint8_t* blob, const uint64_t* bou
   if (n >= (1ull << 30)) return fail(e, CTMR_E_INVAL, "batch too large");
   std::unique_lock<std::mutex> lk(p->mu);
   HIPCHK(e, hipSetDevice(e->device));
-  if ((r = pipe_open_for(e, p, lk, true, n, bytes))) return r;
+  if ((r = pipe_open_for(e, p, lk, PF_RAW, n, bytes))) return r;
   PipeSlot& s = p->slots[p->open];
   uint64_t* hb = slot_h_offsets(s) + 2 * s.n;  // bounds of the super-batch: this batch's, moved behind the bytes already there
   for (uint64_t i = 0; i < 2 * n; i++) hb[i] = s.bytes + (bounds[i] - base);
   return pipe_append(e, p, blob + base, bytes, n, ticket);
+}
+
+int ctmr_submit_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses, ctmr_ticket* ticket) {
+  if (!e || !ticket || (n_responses && !resp_bounds)) return CTMR_E_INVAL;
+  for (uint64_t i = 0; i < n_responses; i++)
+    if (resp_bounds[i + 1] < resp_bounds[i]) return fail(e, CTMR_E_INVAL, "resp_bounds not monotone at %llu", (unsigned long long)i);
+  const uint64_t base = n_responses ? resp_bounds[0] : 0, bytes = n_responses ? resp_bounds[n_responses] - base : 0;
+  if (bytes && !text) return fail(e, CTMR_E_INVAL, "null text");
+  if (n_responses >= (1ull << 30)) return fail(e, CTMR_E_INVAL, "batch too large");
+  ctmr_pipeline* p;
+  int r;
+  if ((r = pipe_get(e, &p))) return r;
+  std::unique_lock<std::mutex> lk(p->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((r = pipe_open_for(e, p, lk, PF_JSON, 0, bytes))) return r;
+  PipeSlot& s = p->slots[p->open];
+  const uint64_t body0 = s.body_rb.size() - 1, at = s.bytes;
+  try {
+    for (uint64_t i = 1; i <= n_responses; i++) s.body_rb.push_back(at + (resp_bounds[i] - base));
+  } catch (const std::bad_alloc&) {
+    s.body_rb.resize(body0 + 1);
+    return fail(e, CTMR_E_NOMEM, "no host memory for the bounds of %llu bodies", (unsigned long long)n_responses);
+  }
+  const size_t had = s.tickets.size();
+  r = pipe_append(e, p, bytes ? text + base : nullptr, bytes, 0, ticket);
+  if (s.tickets.size() == had) {  // the copy failed: no ticket, no bodies
+    s.body_rb.resize(body0 + 1);
+    return r;
+  }
+  PipeTicket& t = s.tickets[had];  // (p->mu is held: the worker has not seen the slot, closed or not)
+  t.body0 = body0;
+  t.nbody = n_responses;
+  t.text_at = at;
+  t.text_base = base;
+  return r;
 }
 
 int ctmr_flush(ctmr_engine* e) {
@@ -370,8 +435,11 @@ int ctmr_flush(ctmr_engine* e) {
   return pipe_close_locked(e, p);
 }
 
+// json: the call is ctmr_wait_entries_json, which alone collects a ticket of the JSON form (the others have no capacity
+// argument) and collects no other; entries_cap, resp_first, resp_bad and info are its arguments.
 static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
-                     ctmr_decode_stats* dstats, ctmr_batch_stats* stats) {
+                     ctmr_decode_stats* dstats, ctmr_batch_stats* stats, bool json = false, uint64_t entries_cap = 0,
+                     uint64_t* resp_first = nullptr, uint64_t* resp_bad = nullptr, ctmr_entries_json_info* info = nullptr) {
   if (!e) return CTMR_E_INVAL;
   ctmr_pipeline* p;
   int r;
@@ -383,10 +451,41 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
     if (c.state != PS_FREE && c.seq == seq) s = &c;
   if (!s || tix >= s->tickets.size() || s->tickets[tix].consumed)
     return fail(e, CTMR_E_NOTFOUND, "unknown or already collected ticket");
+  if ((s->form == PF_JSON) != json)  // (the ticket stays collectable)
+    return fail(e, CTMR_E_INVAL, json ? "not a ticket of ctmr_submit_entries_json" : "a ticket of ctmr_submit_entries_json: ctmr_wait_entries_json collects it");
   if (s->state == PS_OPEN && (r = pipe_close_locked(e, p))) return r;  // nobody else will launch it
   p->cv.wait(lk, [&] { return s->state == PS_DONE; });
   PipeTicket& t = s->tickets[tix];
   int rc = s->rc;
+  if (rc != CTMR_OK && json && info) {  // the super-batch failed: no body was judged
+    memset(info, 0, sizeof *info);
+    info->responses = t.nbody;
+    info->bad_response = info->bad_offset = ~0ull;
+  }
+  if (rc == CTMR_OK && json) {
+    const uint64_t* rb = s->body_rb.data() + t.body0;
+    const uint64_t* bad = s->body_bad.data() + t.body0;
+    const uint64_t back = t.text_base - t.text_at;  // an offset in the slot's text → one from the submit's text pointer
+    if (info) {
+      memset(info, 0, sizeof *info);
+      info->responses = t.nbody;
+      info->entries = t.n;
+      info->text_bytes = rb[t.nbody] - rb[0];
+      info->blob_bytes = slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first];
+      info->bad_response = info->bad_offset = ~0ull;
+      for (uint64_t i = t.nbody; i-- > 0;)
+        if (bad[i] != ~0ull) {
+          info->bad_response = i;
+          info->bad_offset = bad[i] + back;
+        }
+    }
+    if (entries_cap < t.n)
+      return fail(e, CTMR_E_RANGE, "the ticket holds %llu entries", (unsigned long long)t.n);
+    if (resp_first)
+      for (uint64_t i = 0; i <= t.nbody; i++) resp_first[i] = s->body_first[t.body0 + i] - t.first;
+    if (resp_bad)
+      for (uint64_t i = 0; i < t.nbody; i++) resp_bad[i] = bad[i] == ~0ull ? ~0ull : bad[i] + back;
+  }
   if (rc == CTMR_OK) {
     if (records && t.n) memcpy(records, s->h_records + t.first, t.n * sizeof(ctmr_record));
     // this batch's slice of the super-batch's NEW list (ascending), rebased to the batch
@@ -408,7 +507,7 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
       stats->n_new = (uint64_t)(hi - lo);
       stats->n_dup = stats->by_status[CTMR_ST_PASS] - stats->n_new;
       stats->n_host_set = host_set;
-      stats->payload_bytes = s->raw ? slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first]
+      stats->payload_bytes = s->form != PF_PACKED ? slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first]
                                     : slot_h_offsets(*s)[t.first + t.n] - slot_h_offsets(*s)[t.first];
       stats->map_launches = 1;
       stats->ms_map = s->stats.ms_map; stats->ms_insert = s->stats.ms_insert; stats->ms_resolve = s->stats.ms_resolve;
@@ -416,12 +515,12 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
       (void)new_flag;
     }
     if (timestamp) {
-      if (s->raw) memcpy(timestamp, s->h_ts + t.first, t.n * 8);
+      if (s->form != PF_PACKED) memcpy(timestamp, s->h_ts + t.first, t.n * 8);
       else memset(timestamp, 0, t.n * 8);  // a packed batch carries no timestamps
     }
     if (dstats) {
       memset(dstats, 0, sizeof *dstats);
-      if (s->raw) {
+      if (s->form != PF_PACKED) {
         dstats->n = t.n;
         for (uint64_t i = 0; i < t.n; i++) {
           const uint8_t et = s->h_etype[t.first + i];
@@ -455,4 +554,10 @@ int ctmr_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, uint64_t
 int ctmr_wait_entries(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
                       ctmr_decode_stats* dstats, ctmr_batch_stats* stats) {
   return pipe_wait(e, ticket, records, new_idx, timestamp, dstats, stats);
+}
+
+int ctmr_wait_entries_json(ctmr_engine* e, ctmr_ticket ticket, uint64_t entries_cap, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
+                           uint64_t* resp_first, uint64_t* resp_bad, ctmr_entries_json_info* info, ctmr_decode_stats* dstats,
+                           ctmr_batch_stats* stats) {
+  return pipe_wait(e, ticket, records, new_idx, timestamp, dstats, stats, true, entries_cap, resp_first, resp_bad, info);
 }

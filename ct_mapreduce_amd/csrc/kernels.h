@@ -25,7 +25,8 @@
 //   kernels/resp_parse.h k_resp_mark / k_resp_cuts / k_resp_resolve / k_resp_chain / k_resp_commands / k_resp_place (a Redis
 //                       protocol stream of SADD and EXPIREAT commands as it lies → an image's member records)
 //   kernels/entries_json.h k_ej_quotes / k_ej_mark / k_ej_resp / k_ej_check / k_ej_decode (get-entries JSON bodies as they
-//                       lie → the raw-entry batch: tokens by quote parity, the grammar by position, base64 → bytes)
+//                       lie → the raw-entry batch: tokens by quote parity, the grammar by position, base64 → bytes;
+//                       k_ej_drop / k_ej_gather: every body judged on its own, the bad ones left out)
 //   kernels/pem_decode.h k_pd_mark / k_pd_fstart / k_pd_files / k_pd_check / k_pd_squeeze / k_pd_decode (PEM certificate files
 //                       as they lie → a packed batch: armor lines by their dashes, the grammar by counts, base64 → bytes)
 //   kernels/sort.h      k_sort_keys / k_sort_hist / k_sort_scatter / k_sort_heads / k_sort_regroup / k_sort_gather (the

@@ -14,6 +14,10 @@
 //             '=' at the end) and writes the decoded lengths, leaf first whatever the order in the text.
 //   decode    the hot path: one tile of EJ_DTILE characters of one string per block → EJ_DOUT bytes, staged in LDS at the
 //             16-byte phase of the first global byte and stored as k_lists_write stores (16-byte body, byte-wide ends).
+// Every body judged on its own (ctmr_entries_json_each*): mark, resp and check take EACH = true and report
+// to a table of one word per response (ej_verdict) instead of the call's one pair; behind check, k_ej_drop zeroes the
+// entry count of every response with a verdict and k_ej_gather moves the good entries' lengths and sources to their
+// places under the new numbering.  EACH = false compiles to what the strict call has always run.
 // The text lies at any alignment: quotes and mark read the aligned 16-byte chunks that cover it and mask what is outside
 // the bounds, decode reads aligned dwords that hold at least one character of its string.  Non-temporal loads: the text
 // is read and never needed again.  gfx950 (CDNA4, wave64) only; part of kernels.h.
@@ -105,6 +109,19 @@ __device__ __forceinline__ void ej_report(unsigned long long* err, bool bad, uin
   }
 }
 
+// EACH = false: err is the call's pair (lowest response, lowest offset) and the wave reduces first (ej_report).
+// EACH = true (ctmr_entries_json_each*): err is a table of one word per response, ~0 = inside the grammar so
+// far, and a lane with a finding does its own atomicMin on its response's word — a wave holds lanes of any number of
+// responses, so nothing is reduced over it; findings are rare.  r < R wherever bad is set.
+template <bool EACH>
+__device__ __forceinline__ void ej_verdict(unsigned long long* err, bool bad, uint64_t r, uint64_t off) {
+  if (EACH) {
+    if (bad) atomicMin(err + r, (unsigned long long)off);
+  } else {
+    ej_report(err, bad, r, off);
+  }
+}
+
 // quotes: cnt[blk] = the quotes among the text's bytes of block blk
 __global__ void __launch_bounds__(EJ_BLOCK) k_ej_quotes(EjText T, uint64_t b0, unsigned long long* cnt) {
   const uint64_t blk = b0 + blockIdx.x;
@@ -135,7 +152,8 @@ __global__ void __launch_bounds__(RP_BLOCK) k_ej_qstart(EjText T, uint64_t b0, c
 
 // mark.  WRITE = false: cnt_t[blk] / cnt_o[blk] = the tokens / odd bytes of block blk, and every violation is reported.
 // WRITE = true, behind the exclusive scans: tok[] = position << 3 | kind of every token, oddb[] = the odd bytes before it.
-template <bool WRITE>
+// EACH (ej_verdict): a lane reports its first violation in every response its 16 bytes touch.
+template <bool WRITE, bool EACH = false>
 __global__ void __launch_bounds__(EJ_BLOCK) k_ej_mark(EjText T, uint64_t b0, const unsigned long long* qblk, const unsigned long long* qstart,
                                                       unsigned long long* cnt_t, unsigned long long* cnt_o, unsigned long long* tok,
                                                       unsigned long long* oddb, unsigned long long* err) {
@@ -188,7 +206,18 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_ej_mark(EjText T, uint64_t b0, con
       voff = (uint64_t)(p0 + (int64_t)(__ffs(viol) - 1));
       vr = uniform ? r_lo : ej_resp_of(T.rb, T.R, voff);
     }
-    ej_report(err, viol != 0u, vr, voff);
+    ej_verdict<EACH>(err, viol != 0u, vr, voff);
+    if (EACH && viol && !uniform) {  // the lane's later violations may lie in later responses
+      uint32_t m = viol & (viol - 1u);
+#pragma unroll 1
+      while (m) {
+        const uint64_t off = (uint64_t)(p0 + (int64_t)(__ffs(m) - 1));
+        m &= m - 1u;
+        const uint64_t r2 = ej_resp_of(T.rb, T.R, off);
+        if (r2 != vr) ej_verdict<true>(err, true, r2, off);
+        vr = r2;
+      }
+    }
   }
   const uint32_t packed = ej_wave_scan((uint32_t)__popc(tokm) | ((uint32_t)__popc(odd) << 16), &total);
   if (!WRITE) {
@@ -221,6 +250,7 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_ej_mark(EjText T, uint64_t b0, con
 
 // resp: tfirst[r] = the tokens before rb[r] (r <= R); ecnt[r] = the entries the token count of response r stands for,
 // 0 and a report when it stands for none; ecnt[R] = 0 (the scan's total)
+template <bool EACH = false>
 __global__ void __launch_bounds__(RP_BLOCK) k_ej_resp(EjText T, uint64_t b0, const unsigned long long* tok, uint64_t ntok,
                                                       unsigned long long* tfirst, unsigned long long* ecnt, unsigned long long* err) {
   const uint64_t r = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
@@ -249,7 +279,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_ej_resp(EjText T, uint64_t b0, con
     }
     ecnt[r] = n;
   }
-  ej_report(err, bad, r, off);
+  ej_verdict<EACH>(err, bad, r, off);
 }
 
 template <uint32_t N>
@@ -283,6 +313,7 @@ __device__ __forceinline__ bool ej_value(const EjText& T, const EjCheck& C, uint
 }
 
 // check: one lane per token
+template <bool EACH = false>
 __global__ void __launch_bounds__(RP_BLOCK) k_ej_check(EjText T, uint64_t b0, EjCheck C, unsigned long long* err) {
   const uint64_t t = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
   bool bad = false;
@@ -325,7 +356,36 @@ __global__ void __launch_bounds__(RP_BLOCK) k_ej_check(EjText T, uint64_t b0, Ej
       bad = bad || kind != want;
     }
   }
-  ej_report(err, bad, r, pos);
+  ej_verdict<EACH>(err, bad, r, pos);
+}
+
+// each, behind check: the entry count of a response with a verdict, from whichever pass, goes to zero.  cnt[r] = the
+// entries of response r when bad_at[r] says none, else 0; cnt[R] = 0 (the scan's total).  efirst0: the scan of k_ej_resp's
+// counts, which k_ej_check numbered its entries by.
+__global__ void __launch_bounds__(RP_BLOCK) k_ej_drop(uint64_t b0, uint64_t R, const unsigned long long* bad_at, const unsigned long long* efirst0,
+                                                      unsigned long long* cnt) {
+  const uint64_t r = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
+  if (r > R) return;
+  cnt[r] = (r < R && bad_at[r] == ~0ull) ? efirst0[r + 1] - efirst0[r] : 0ull;
+}
+
+// each, behind the scan of k_ej_drop's counts (efirst): the lengths and sources k_ej_check wrote, compacted over the good
+// responses.  One lane per entry e0 of the old numbering (n0 = efirst0[R] > 0); its response is the last r with
+// efirst0[r] <= e0, which has entries, so it is that one and no empty neighbour.
+__global__ void __launch_bounds__(RP_BLOCK) k_ej_gather(uint64_t b0, uint64_t R, uint64_t n0, const unsigned long long* bad_at,
+                                                        const unsigned long long* efirst0, const unsigned long long* efirst,
+                                                        const unsigned long long* len0, const unsigned long long* src0, unsigned long long* len,
+                                                        unsigned long long* src) {
+  const uint64_t e0 = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
+  if (e0 >= n0) return;
+  const uint64_t r = ej_resp_of((const uint64_t*)efirst0, R, e0);
+  if (bad_at[r] != ~0ull) return;
+  const uint64_t e = efirst[r] + (e0 - efirst0[r]);
+#pragma unroll
+  for (uint32_t k = 0; k < 2; k++) {
+    len[2 * e + k] = len0[2 * e0 + k];
+    src[2 * e + k] = src0[2 * e0 + k];
+  }
 }
 
 // tiles[i] = the decode tiles of string i (bounds: the scanned lengths)

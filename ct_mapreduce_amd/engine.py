@@ -73,6 +73,7 @@ class RawEntries:
     blob: np.ndarray         # u8
     bounds: np.ndarray       # u64[2n+1]
     resp_first: np.ndarray = None   # u64[R+1] when the batch came from R get-entries bodies: each body's first entry
+    bad: list = None                # entries_json_each: per body None, or the offset that puts it outside the grammar
 
     @property
     def n(self):
@@ -104,6 +105,9 @@ class EntriesResult:
     timestamp: np.ndarray    # u64[n], ms
     stats: N.BatchStats
     decode: N.DecodeStats
+    resp_first: np.ndarray = None   # wait_entries_json: u64[R+1], each body's first entry in this ticket
+    bad: list = None                # wait_entries_json: per body None, or the offset (from the submit's first byte) that
+                                    # puts it outside the grammar; such a body has no entries
 
 
 @dataclass
@@ -130,6 +134,7 @@ class Engine:
         self._h = h
         self.device = device
         self.collect_meta = bool(collect_meta)
+        self._json_bodies = {}   # ticket of submit_entries_json → its bodies: wait_entries_json sizes resp_first and bad by it
 
     # ---- lifecycle
     def close(self):
@@ -263,6 +268,47 @@ class Engine:
                                              C.byref(ds), C.byref(st)))
         return EntriesResult(records, new_idx[:st.n_new], ts[:n], st, ds)
 
+    def submit_entries_json(self, bodies) -> int:
+        """get-entries HTTP bodies as they lie (a list of bytes — a downloader submits one; or (text, resp_bounds) with
+        text an array or an address, e.g. a pinned buffer of pinned_array kept untouched until the wait).  Returns the
+        ticket (ctmr_submit_entries_json)."""
+        from . import get_entries
+        if isinstance(bodies, tuple):
+            text, rb = bodies
+            rb = np.ascontiguousarray(rb, dtype=np.uint64)
+            addr = text.ctypes.data if hasattr(text, "ctypes") else text
+        else:
+            text, rb = get_entries.join(bodies)
+            addr = np.frombuffer(text, np.uint8).ctypes.data if text else None   # pageable: staged before the call returns
+        t = C.c_uint64(0)
+        self._ck(self._lib.ctmr_submit_entries_json(self._h, addr, rb.ctypes.data, len(rb) - 1, C.byref(t)))
+        self._json_bodies[t.value] = len(rb) - 1
+        return t.value
+
+    def wait_entries_json(self, ticket: int) -> EntriesResult:
+        """The ticket's result (ctmr_wait_entries_json; the size query is done here): EntriesResult with resp_first and
+        bad.  A body outside the grammar has no entries and its offset in bad; the call does not fail for it."""
+        R = self._json_bodies.get(ticket)
+        if R is None:
+            raise CtmrError(N.E_NOTFOUND, "not a ticket of submit_entries_json, or already collected")
+        info, st, ds = N.EntriesJsonInfo(), N.BatchStats(), N.DecodeStats()
+        first = np.zeros(R + 1, np.uint64)
+        bad = np.zeros(max(R, 1), np.uint64)
+        # the size query; a ticket without entries is collected by it, so the verdicts are asked for here too
+        rc = self._lib.ctmr_wait_entries_json(self._h, ticket, 0, None, None, None, first.ctypes.data, bad.ctypes.data, C.byref(info),
+                                              C.byref(ds), C.byref(st))
+        n = int(info.entries) if rc == N.E_RANGE else 0
+        records = np.zeros(n, dtype=RECORD_DTYPE)
+        new_idx = np.zeros(max(n, 1), dtype=np.uint64)
+        ts = np.zeros(max(n, 1), dtype=np.uint64)
+        if rc == N.E_RANGE:
+            rc = self._lib.ctmr_wait_entries_json(self._h, ticket, n, records.ctypes.data, new_idx.ctypes.data, ts.ctypes.data,
+                                                  first.ctypes.data, bad.ctypes.data, C.byref(info), C.byref(ds), C.byref(st))
+        del self._json_bodies[ticket]   # collected, or failed with its super-batch: either way it is gone
+        self._ck(rc)
+        return EntriesResult(records, new_idx[:st.n_new], ts[:n], st, ds, first,
+                             [None if int(b) == 2**64 - 1 else int(b) for b in bad[:R]])
+
     def map_batch_device(self, d_payload, d_offsets, d_issuer_idx, d_entry_type, n, d_records=0,
                          d_new_idx=0) -> N.BatchStats:
         """All pointers are device addresses (ints), e.g. torch tensors' data_ptr()."""
@@ -359,6 +405,48 @@ class Engine:
                                                        C.c_void_p(d_blob.data_ptr()), blob_cap, C.c_void_p(d_bounds.data_ptr()),
                                                        entries_cap, first.ctypes.data, C.byref(info)), info)
         return d_blob[:info.blob_bytes + N.PAYLOAD_PAD], d_bounds[:2 * info.entries + 1], first, info
+
+    def entries_json_each(self, bodies) -> RawEntries:
+        """entries_json with every body judged on its own (ctmr_entries_json_each; CPU twin:
+        get_entries.parse_each): nothing is raised for a body outside the grammar — it has no entries, and .bad[r] holds
+        its offset (None for the others)."""
+        from . import get_entries
+        text, rb = get_entries.join(bodies)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        info = N.EntriesJsonInfo()
+        blob_cap, entries_cap = len(text) * 3 // 4 + N.PAYLOAD_PAD, len(text) // 34
+        blob = np.empty(blob_cap, np.uint8)
+        bounds = np.empty(2 * entries_cap + 1, np.uint64)
+        first = np.empty(len(bodies) + 1, np.uint64)
+        bad = np.empty(max(len(bodies), 1), np.uint64)
+        self._ck(self._lib.ctmr_entries_json_each(self._h, buf.ctypes.data, rb.ctypes.data, len(bodies), blob.ctypes.data, blob_cap,
+                                                  bounds.ctypes.data, entries_cap, first.ctypes.data, bad.ctypes.data, C.byref(info)))
+        return RawEntries(blob[:info.blob_bytes + N.PAYLOAD_PAD], bounds[:2 * info.entries + 1], first,
+                          [None if int(b) == 2**64 - 1 else int(b) for b in bad[:len(bodies)]])
+
+    def entries_json_each_device(self, d_text, resp_bounds):
+        """entries_json_device with every body judged on its own → (d_blob, d_bounds, resp_first, bad, info); bad as in
+        entries_json_each, offsets counted as resp_bounds counts."""
+        import torch
+        if not hasattr(d_text, "data_ptr"):
+            raise TypeError("d_text: a torch tensor on this engine's device")
+        rb = np.ascontiguousarray(resp_bounds, dtype=np.uint64)
+        R = len(rb) - 1
+        if R < 0 or (R and ((rb[1:] < rb[:-1]).any() or int(rb[R]) > d_text.numel())):
+            raise ValueError("resp_bounds do not ascend or reach beyond the text")
+        text_bytes = int(rb[R] - rb[0]) if R else 0
+        blob_cap, entries_cap = text_bytes * 3 // 4 + N.PAYLOAD_PAD, text_bytes // 34
+        dev = "cuda:%d" % self.device
+        d_blob = torch.empty(blob_cap, dtype=torch.uint8, device=dev)
+        d_bounds = torch.empty(2 * entries_cap + 1, dtype=torch.int64, device=dev)
+        first = np.empty(R + 1, np.uint64)
+        bad = np.empty(max(R, 1), np.uint64)
+        info = N.EntriesJsonInfo()
+        self._ck(self._lib.ctmr_entries_json_each_device(self._h, C.c_void_p(d_text.data_ptr()) if text_bytes else None, rb.ctypes.data, R,
+                                                         C.c_void_p(d_blob.data_ptr()), blob_cap, C.c_void_p(d_bounds.data_ptr()),
+                                                         entries_cap, first.ctypes.data, bad.ctypes.data, C.byref(info)))
+        return (d_blob[:info.blob_bytes + N.PAYLOAD_PAD], d_bounds[:2 * info.entries + 1], first,
+                [None if int(b) == 2**64 - 1 else int(b) for b in bad[:R]], info)
 
     def map_entries_json(self, bodies) -> EntriesResult:
         """map_entries over get-entries bodies (a list of bytes): text → raw entries on the device → map_entries_device,

@@ -137,6 +137,29 @@ def parse(bodies):
     return b"".join(parts), np.asarray(bounds, np.uint64), np.asarray(resp_first, np.uint64)
 
 
+def parse_each(bodies):
+    """Every body judged on its own, the twin of ctmr_entries_json_each* (DESIGN.md §22): (blob bytes, bounds u64[2n+1],
+    resp_first u64[R+1], bad).  bad[r] is None, or an offset inside body r (counted from the first body's first byte) when
+    that body is outside the grammar: it contributes no entries, resp_first[r + 1] == resp_first[r], and blob and
+    bounds are those of `parse` over the other bodies."""
+    parts, bounds, resp_first, bad, at, base = [], [0], [0], [], 0, 0
+    for body in bodies:
+        try:
+            entries = parse_one(body)
+            bad.append(None)
+        except _Bad as b:
+            entries = []
+            bad.append(base + max(b.at, 0))
+        for pair in entries:
+            for x in pair:
+                parts.append(x)
+                at += len(x)
+                bounds.append(at)
+        resp_first.append((len(bounds) - 1) // 2)
+        base += len(body)
+    return b"".join(parts), np.asarray(bounds, np.uint64), np.asarray(resp_first, np.uint64), bad
+
+
 def b64_encode(b):
     """The writer's encoder: nothing is judged here, so the standard library serves."""
     return binascii.b2a_base64(bytes(b), newline=False)

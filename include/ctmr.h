@@ -196,7 +196,9 @@ int ctmr_submit_batch(ctmr_engine* e, const uint8_t* payload, const uint64_t* of
                       const uint8_t* entry_type, uint64_t n, ctmr_ticket* ticket);
 int ctmr_flush(ctmr_engine* e);
 int ctmr_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, uint64_t* new_idx, ctmr_batch_stats* stats);
-/* (raw get-entries responses: ctmr_submit_entries / ctmr_wait_entries, with the raw-entry calls below) */
+/* (raw get-entries responses: ctmr_submit_entries / ctmr_wait_entries, and get-entries bodies as text:
+ * ctmr_submit_entries_json / ctmr_wait_entries_json, with the raw-entry calls below; ctmr_wait refuses a ticket of the
+ * text form with CTMR_E_INVAL and leaves it collectable) */
 
 /* ---- storage.RemoteCache set methods on byte strings (storage/types.go:83-102;
  *      Redis impl storage/rediscache.go:57-120,153-169; mock storage/mockcache.go:38-166).
@@ -905,6 +907,28 @@ int ctmr_entries_json_device(ctmr_engine* e, const void* d_text, const uint64_t*
                              void* d_blob, size_t blob_cap, uint64_t* d_bounds, uint64_t entries_cap,
                              uint64_t* resp_first, ctmr_entries_json_info* info);
 
+/* Every body judged on its own: ctmr_entries_json* with a verdict per response instead of one for the call.  DESIGN.md §22.
+ * Arguments as above, and resp_bad, a HOST array u64[n_responses], required (NULL: CTMR_E_INVAL).  The grammar is
+ * exactly the one above, not a byte wider.
+ *   resp_bad[r] = UINT64_MAX: body r is inside the grammar.  Any other value: it is outside, and the value is an
+ *   advisory byte offset in [resp_bounds[r], max(resp_bounds[r + 1], resp_bounds[r] + 1)).
+ * A body outside the grammar fails nothing and contributes no entries: resp_first[r + 1] == resp_first[r] for it, the
+ *   call returns CTMR_OK, info.bad_response / info.bad_offset name the LOWEST such body (UINT64_MAX: none), and
+ *   info.entries / info.blob_bytes count the other bodies only.  blob, bounds, entries and blob_bytes are byte for byte
+ *   what ctmr_entries_json* returns for the sub-sequence of good bodies; with no bad body every output of
+ *   ctmr_entries_json* is reproduced bit for bit.  The host decodes the bodies named in resp_bad itself and nothing is
+ *   handed over twice.
+ * n_responses = 0, bodies that are all empty and a single empty body give CTMR_OK, the verdicts (an empty body is
+ *   outside the grammar, its offset resp_bounds[r]) and the empty batch.
+ * Sizing is by the good bodies: CTMR_E_RANGE as above, with *info filled.  CTMR_E_RANGE, CTMR_E_NOMEM and argument
+ *   errors leave every output buffer, resp_bad included, as it was. */
+int ctmr_entries_json_each(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses,
+                           uint8_t* blob, size_t blob_cap, uint64_t* bounds, uint64_t entries_cap, uint64_t* resp_first,
+                           uint64_t* resp_bad, ctmr_entries_json_info* info);
+int ctmr_entries_json_each_device(ctmr_engine* e, const void* d_text, const uint64_t* resp_bounds, uint64_t n_responses,
+                                  void* d_blob, size_t blob_cap, uint64_t* d_bounds, uint64_t entries_cap,
+                                  uint64_t* resp_first, uint64_t* resp_bad, ctmr_entries_json_info* info);
+
 /* ---- PEM certificate files as they lie → a packed batch: what LocalDiskBackend.StoreCertificatePEM wrote
  *      (storage/filesystemdatabase.go:167-201, storage/localdiskbackend.go:194-199) read back without encoding/pem and
  *      encoding/base64 on a host core: the inverse of ctmr_pem_new / ctmr_pem_encode_device.  The armor lines are found,
@@ -983,6 +1007,34 @@ int ctmr_pem_decode_device(ctmr_engine* e, const void* d_text, const uint64_t* f
 int ctmr_submit_entries(ctmr_engine* e, const uint8_t* blob, const uint64_t* bounds, uint64_t n, ctmr_ticket* ticket);
 int ctmr_wait_entries(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
                       ctmr_decode_stats* dstats, ctmr_batch_stats* stats);
+/* The third form: get-entries HTTP bodies as they lie (the text ctmr_entries_json_each takes), one or more per submit; a
+ * downloader submits the one resp.Body it holds (ct-fetch.go:417-424).  DESIGN.md §22.
+ * ctmr_submit_entries_json returns at once: the bytes inside the bounds go to HBM behind the previous submit's on the
+ *   copy streams — straight DMA when text came from ctmr_alloc_pinned (keep it untouched until the wait), otherwise
+ *   staged before the call returns — and the bodies' bounds are kept with the ticket.  Submits coalesce into a
+ *   super-batch of this form; it closes at 96 MB of text, at 4 096 bodies, on ctmr_flush, when one of its tickets is
+ *   waited for, and when a submit of another form arrives (the number of entries is not known before it runs).
+ * The worker judges every body alone (ctmr_entries_json_each_device), then decodes, matches and maps the good bodies'
+ *   entries as ONE batch, like a raw super-batch.  A body outside the grammar costs its own ticket its entries and no
+ *   other ticket anything.  Failures of the whole super-batch (CTMR_E_NOTFOUND under ctmr_set_issuer_autoregister(e, 0),
+ *   CTMR_E_FULL, CTMR_E_HIP) reach every ticket of it, as for the raw form.
+ * ctmr_wait_entries_json blocks until the ticket's super-batch is done.  info: responses, text_bytes, entries = n and
+ *   blob_bytes of THIS ticket, bad_response the lowest bad body of the ticket (UINT64_MAX: none), bad_offset its offset.
+ *   entries_cap < n: CTMR_E_RANGE with *info filled, nothing written and the ticket NOT consumed — a first call with
+ *   entries_cap = 0 is the size query.  Otherwise records[n], new_idx (relative to the ticket, ascending), timestamp[n],
+ *   dstats and stats as ctmr_wait_entries slices them, resp_first u64[R + 1] relative to the ticket, resp_bad u64[R]
+ *   with offsets relative to the text pointer the submit was given; any output pointer may be NULL.  A ticket with bad
+ *   bodies still returns CTMR_OK.
+ * ctmr_wait and ctmr_wait_entries have no capacity argument: they refuse a ticket of this form with CTMR_E_INVAL and
+ *   leave it collectable.
+ * Ordering: bodies keep submission order, entries body order, super-batches run in order with the other forms: records,
+ *   NEW lists, timestamps, issuer indices and the engine's sets are those of one synchronous call per submit over its
+ *   good bodies, in submission order. */
+int ctmr_submit_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses,
+                             ctmr_ticket* ticket);
+int ctmr_wait_entries_json(ctmr_engine* e, ctmr_ticket ticket, uint64_t entries_cap, ctmr_record* records,
+                           uint64_t* new_idx, uint64_t* timestamp, uint64_t* resp_first, uint64_t* resp_bad,
+                           ctmr_entries_json_info* info, ctmr_decode_stats* dstats, ctmr_batch_stats* stats);
 /* Issuer registration policy of the raw-entry calls.  on = 1 (default): a Chain[0] certificate met for the first time
  * is registered by the call.  on = 0: nothing is registered; when a batch contains unregistered Chain[0]
  * certificates the decode fails with CTMR_E_NOTFOUND and ctmr_pending_issuers lists them (distinct, [u32 len][DER]…,
