@@ -701,6 +701,7 @@ extern "C" {
 #include "engine/sort.inc"
 #include "engine/merge.inc"
 #include "engine/resp_parse.inc"
+#include "engine/text_decode.inc"
 #include "engine/entries_json.inc"
 #include "engine/pipeline_json.inc"
 #include "engine/pem_decode.inc"

@@ -2,8 +2,8 @@
 // (include/ctmr.h ctmr_pem_decode*, DESIGN.md §21).  The text stays where it lies; the kernels of kernels/pem_decode.h
 // find its armor lines, check the grammar and decode the base64.  The host sees counts only: tokens, certificates,
 // decoded bytes, tiles.
-// Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/entries_json.inc,
-// whose helpers (ej_turns, ej_blocks, ej_alloc, ej_scan) it uses.
+// Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/text_decode.inc,
+// which has the host steps this decoder shares with engine/entries_json.inc.
 
 extern "C++" {
 namespace {
@@ -11,7 +11,7 @@ namespace {
 struct PemDecode {
   DevMem rb, tok, ctok, cnt_c, ffirst;         // what the squeeze and the results need
   DevMem offsets, src, lay, sqoff, sqtiles;    // per certificate
-  EjText text{};
+  TxText text{};
   uint64_t n = 0, sq_bytes = 0;
   ctmr_pem_decode_info info{};
 };
@@ -24,37 +24,30 @@ void pd_info_none(ctmr_pem_decode_info* info, uint64_t F) {
   info->bad_file = info->bad_offset = ~0ull;
 }
 
+int pd_alloc(ctmr_engine* e, DevMem* m, uint64_t words) { return tx_alloc(e, PEM_DECODE, m, words); }
+
 // Everything but the payload: the text (device memory, any alignment; file f at s[fb[f], fb[f + 1])) validated, P->info
 // made, the tables of the decode left on the device.  Drains the stream.
 int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64_t F, PemDecode* P) {
   int r;
   ctmr_pem_decode_info& info = P->info;
   pd_info_none(&info, F);
-  for (uint64_t i = 0; i < F; i++)
-    if (fb[i] > fb[i + 1]) return fail(e, CTMR_E_INVAL, "%s: file_bounds[%llu] lies behind its successor", PEM_DECODE, (unsigned long long)i);
-  if ((r = ej_alloc(e, &P->offsets, 1)) || (r = ej_alloc(e, &P->ffirst, F + 1))) return r;
+  TxText& T = P->text;
+  uint64_t nb = 0;
+  if ((r = tx_open(e, PEM_DECODE, "file_bounds", s, fb, F, &P->rb, &T, &nb)) || (r = pd_alloc(e, &P->offsets, 1)) ||
+      (r = pd_alloc(e, &P->ffirst, F + 1)))
+    return r;
   HIPCHK(e, hipMemsetAsync(P->offsets.p, 0, 8, e->stream));
   HIPCHK(e, hipMemsetAsync(P->ffirst.p, 0, (F + 1) * 8, e->stream));
-  const uint64_t lo = F ? fb[0] : 0, hi = F ? fb[F] : 0;
-  info.text_bytes = hi - lo;
-  if (lo == hi) {  // no files, or empty ones only
+  info.text_bytes = T.hi - T.lo;
+  if (!nb) {  // no files, or empty ones only
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return CTMR_OK;
   }
-  if ((r = ej_alloc(e, &P->rb, F + 1))) return r;
-  HIPCHK(e, hipMemcpyAsync(P->rb.p, fb, (F + 1) * 8, hipMemcpyHostToDevice, e->stream));
-  EjText& T = P->text;
-  T.s = s;
-  T.rb = (const uint64_t*)P->rb.p;
-  T.R = F;
-  T.lo = lo;
-  T.hi = hi;
-  T.a0 = ((uint64_t)(uintptr_t)s + lo) & ~15ull;
-  const uint64_t nb = ((uint64_t)(uintptr_t)s + hi - T.a0 + EJ_TILE - 1) / EJ_TILE;
   DevMem cnt_t_m, cnt_e_m, sum_m, err_m, cfile_m, tfirst_m, etok_m;
-  if ((r = ej_alloc(e, &cnt_t_m, nb + 1)) || (r = ej_alloc(e, &P->cnt_c, nb + 1)) || (r = ej_alloc(e, &cnt_e_m, nb + 1)) ||
-      (r = ej_alloc(e, &sum_m, (nb + 7) / 8)) || (r = ej_alloc(e, &err_m, 3)) || (r = ej_alloc(e, &cfile_m, F + 1)) ||
-      (r = ej_alloc(e, &tfirst_m, F + 1)))
+  if ((r = pd_alloc(e, &cnt_t_m, nb + 1)) || (r = pd_alloc(e, &P->cnt_c, nb + 1)) || (r = pd_alloc(e, &cnt_e_m, nb + 1)) ||
+      (r = pd_alloc(e, &sum_m, (nb + 7) / 8)) || (r = pd_alloc(e, &err_m, 3)) || (r = pd_alloc(e, &cfile_m, F + 1)) ||
+      (r = pd_alloc(e, &tfirst_m, F + 1)))
     return r;
   unsigned long long* err = (unsigned long long*)err_m.p;
   unsigned long long* cnt_t = (unsigned long long*)cnt_t_m.p;
@@ -63,79 +56,57 @@ int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64
   HIPCHK(e, hipMemsetAsync(err, 0xff, 16, e->stream));
   HIPCHK(e, hipMemsetAsync(err + 2, 0, 8, e->stream));  // the irregular blocks
   // ---- armor lines
-  ej_turns(nb, [&](uint64_t b0, dim3 g) {
-    hipLaunchKernelGGL((k_pd_mark<false>), g, dim3(EJ_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)nullptr,
+  tx_turns(nb, [&](uint64_t b0, dim3 g) {
+    hipLaunchKernelGGL((k_pd_mark<false>), g, dim3(TX_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)nullptr,
                        (unsigned long long*)nullptr, (unsigned long long*)nullptr, err);
   });
   uint64_t ntok = 0;
-  if ((r = ej_scan(e, P->cnt_c, nb, nullptr)) || (r = ej_scan(e, cnt_e_m, nb, nullptr)) || (r = ej_scan(e, cnt_t_m, nb, &ntok))) return r;
-  if ((r = ej_alloc(e, &P->tok, ntok)) || (r = ej_alloc(e, &P->ctok, ntok)) || (r = ej_alloc(e, &etok_m, ntok))) return r;
-  ej_turns(nb, [&](uint64_t b0, dim3 g) {
-    hipLaunchKernelGGL((k_pd_mark<true>), g, dim3(EJ_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)P->tok.p,
+  if ((r = tx_scan(e, P->cnt_c, nb, nullptr)) || (r = tx_scan(e, cnt_e_m, nb, nullptr)) || (r = tx_scan(e, cnt_t_m, nb, &ntok))) return r;
+  if ((r = pd_alloc(e, &P->tok, ntok)) || (r = pd_alloc(e, &P->ctok, ntok)) || (r = pd_alloc(e, &etok_m, ntok))) return r;
+  tx_turns(nb, [&](uint64_t b0, dim3 g) {
+    hipLaunchKernelGGL((k_pd_mark<true>), g, dim3(TX_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)P->tok.p,
                        (unsigned long long*)P->ctok.p, (unsigned long long*)etok_m.p, err);
   });
   // ---- files, certificates
-  ej_turns(ej_blocks(F + 1, RP_BLOCK / 64), [&](uint64_t b0, dim3 g) {
+  tx_turns(tx_blocks(F + 1, RP_BLOCK / 64), [&](uint64_t b0, dim3 g) {
     hipLaunchKernelGGL(k_pd_fstart, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)cnt_c, nb, (unsigned long long*)cfile_m.p);
   });
-  ej_turns(ej_blocks(F + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
+  tx_turns(tx_blocks(F + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
     hipLaunchKernelGGL(k_pd_files, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)P->tok.p, ntok, (unsigned long long*)tfirst_m.p,
                        (unsigned long long*)P->ffirst.p, err);
   });
   uint64_t n = 0;
   if ((r = scan_u64(e, (uint64_t*)P->ffirst.p, F + 1, false, SC_MISC))) return r;
   unsigned long long h_err[3] = {0, 0, 0};
-  auto outside = [&]() {
-    info.bad_file = h_err[0];
-    info.bad_offset = h_err[1];
-    return fail(e, CTMR_E_INVAL, "%s: file %llu is outside the grammar near offset %llu", PEM_DECODE, h_err[0], h_err[1]);
-  };
   HIPCHK(e, hipMemcpyAsync(&n, (uint64_t*)P->ffirst.p + F, 8, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipMemcpyAsync(h_err, err, 24, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
+  if ((r = tx_drain(e))) return r;
   const uint64_t f_limit = h_err[0];  // the files from this one on are outside the grammar or need no verdict: the check skips them
-  if ((r = ej_alloc(e, &P->offsets, n + 1)) || (r = ej_alloc(e, &P->src, n)) || (r = ej_alloc(e, &P->lay, n)) || (r = ej_alloc(e, &P->sqoff, n + 1)) ||
-      (r = ej_alloc(e, &P->sqtiles, n + 1)))
+  if ((r = pd_alloc(e, &P->offsets, n + 1)) || (r = pd_alloc(e, &P->src, n)) || (r = pd_alloc(e, &P->lay, n)) || (r = pd_alloc(e, &P->sqoff, n + 1)) ||
+      (r = pd_alloc(e, &P->sqtiles, n + 1)))
     return r;
   if (ntok) {
     const PdCheck C{(const unsigned long long*)P->tok.p,    (const unsigned long long*)P->ctok.p,    (const unsigned long long*)etok_m.p, ntok,
                     (const unsigned long long*)tfirst_m.p,  (const unsigned long long*)P->ffirst.p,  (const unsigned long long*)cfile_m.p,
                     (unsigned long long*)P->offsets.p,      (unsigned long long*)P->src.p,           (unsigned long long*)P->lay.p,
                     (unsigned long long*)P->sqoff.p,        (unsigned long long*)P->sqtiles.p};
-    ej_turns(ej_blocks(ntok, RP_BLOCK), [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_pd_check, g, dim3(RP_BLOCK), 0, e->stream, T, b0, C, f_limit, err); });
+    tx_turns(tx_blocks(ntok, RP_BLOCK), [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_pd_check, g, dim3(RP_BLOCK), 0, e->stream, T, b0, C, f_limit, err); });
   }
   HIPCHK(e, hipMemcpyAsync(h_err, err, 24, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
-  if (h_err[0] != ~0ull) return outside();
+  if ((r = tx_drain(e))) return r;
+  if (h_err[0] != ~0ull) {
+    info.bad_file = h_err[0];
+    info.bad_offset = h_err[1];
+    return fail(e, CTMR_E_INVAL, "%s: file %llu is outside the grammar near offset %llu", PEM_DECODE, h_err[0], h_err[1]);
+  }
   // ---- offsets, and where the characters of the irregular blocks go
   uint64_t payload_bytes = 0;
-  if ((r = ej_scan(e, P->offsets, n, &payload_bytes)) || (r = ej_scan(e, P->sqoff, n, &P->sq_bytes))) return r;
+  if ((r = tx_scan(e, P->offsets, n, &payload_bytes)) || (r = tx_scan(e, P->sqoff, n, &P->sq_bytes))) return r;
   P->n = n;
   info.certificates = n;
   info.payload_bytes = payload_bytes;
   info.irregular = h_err[2];
   info.regular = n - h_err[2];
-  return CTMR_OK;
-}
-
-// CTMR_E_RANGE unless the caller's buffers hold the result
-int pem_decode_fits(ctmr_engine* e, const PemDecode& P, const void* payload, size_t payload_cap, const void* offsets, uint64_t certs_cap) {
-  if (!payload || !offsets || payload_cap < P.info.payload_bytes + CTMR_PAYLOAD_PAD || certs_cap < P.info.certificates)
-    return fail(e, CTMR_E_RANGE, "%s: %llu certificates and %llu + %d payload bytes needed", PEM_DECODE, (unsigned long long)P.info.certificates,
-                (unsigned long long)P.info.payload_bytes, CTMR_PAYLOAD_PAD);
-  return CTMR_OK;
-}
-
-// tile_first[0, n): the tiles of each item, scanned in place to the tiles before it; tile_item[t] = the item of tile t.  Drains.
-int pd_tile_list(ctmr_engine* e, DevMem& tile_first, uint64_t n, DevMem* tile_item, uint64_t* ntiles) {
-  int r;
-  if ((r = ej_scan(e, tile_first, n, ntiles)) || (r = ej_alloc(e, tile_item, *ntiles))) return r;
-  if (*ntiles)
-    ej_turns(ej_blocks(n, RP_BLOCK), [&](uint64_t b0, dim3 g) {
-      hipLaunchKernelGGL(k_ej_tile_list, g, dim3(RP_BLOCK), 0, e->stream, b0, (const unsigned long long*)tile_first.p, n, (unsigned long long*)tile_item->p);
-    });
   return CTMR_OK;
 }
 
@@ -147,17 +118,13 @@ int pem_decode_decode(ctmr_engine* e, PemDecode& P, uint8_t* d_payload) {
   int r;
   const uint64_t n = P.n;
   if (n) {
-    if ((r = ej_alloc(e, &tile_first, n + 1))) return r;
-    ej_turns(ej_blocks(n, RP_BLOCK), [&](uint64_t b0, dim3 g) {
-      hipLaunchKernelGGL(k_ej_tiles, g, dim3(RP_BLOCK), 0, e->stream, b0, (const unsigned long long*)P.offsets.p, n, (unsigned long long*)tile_first.p);
-    });
-    if ((r = pd_tile_list(e, tile_first, n, &tile_cert, &ntiles))) return r;
+    if ((r = tx_tile_list(e, PEM_DECODE, &P.offsets, n, &tile_first, &tile_cert, &ntiles))) return r;
     if (P.sq_bytes) {
       if (sq.alloc(P.sq_bytes + 16) != hipSuccess)
         return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu squeezed characters", PEM_DECODE, (unsigned long long)P.sq_bytes);
-      if ((r = pd_tile_list(e, P.sqtiles, n, &sq_cert, &nsq))) return r;
-      ej_turns(nsq, [&](uint64_t b0, dim3 g) {
-        hipLaunchKernelGGL(k_pd_squeeze, g, dim3(EJ_BLOCK), 0, e->stream, P.text, b0, (const unsigned long long*)sq_cert.p,
+      if ((r = tx_tile_list(e, PEM_DECODE, nullptr, n, &P.sqtiles, &sq_cert, &nsq))) return r;
+      tx_turns(nsq, [&](uint64_t b0, dim3 g) {
+        hipLaunchKernelGGL(k_pd_squeeze, g, dim3(TX_BLOCK), 0, e->stream, P.text, b0, (const unsigned long long*)sq_cert.p,
                            (const unsigned long long*)P.sqtiles.p, (const unsigned long long*)P.src.p, (const unsigned long long*)P.tok.p,
                            (const unsigned long long*)P.ctok.p, (const unsigned long long*)P.cnt_c.p, (const unsigned long long*)P.sqoff.p, sq.u8());
       });
@@ -166,13 +133,10 @@ int pem_decode_decode(ctmr_engine* e, PemDecode& P, uint8_t* d_payload) {
       const PdDecode D{(const unsigned long long*)tile_cert.p, (const unsigned long long*)tile_first.p, (const unsigned long long*)P.offsets.p,
                        (const unsigned long long*)P.src.p,     (const unsigned long long*)P.lay.p,      (const unsigned long long*)P.sqoff.p,
                        sq.u8()};
-      ej_turns(ntiles, [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_pd_decode, g, dim3(EJ_DBLOCK), 0, e->stream, P.text.s, b0, D, d_payload); });
+      tx_turns(ntiles, [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_pd_decode, g, dim3(TX_DBLOCK), 0, e->stream, P.text.s, b0, D, d_payload); });
     }
   }
-  HIPCHK(e, hipMemsetAsync(d_payload + P.info.payload_bytes, 0, CTMR_PAYLOAD_PAD, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
-  return CTMR_OK;
+  return tx_finish(e, d_payload, P.info.payload_bytes);
 }
 
 int pem_decode_file_first(ctmr_engine* e, const PemDecode& P, uint64_t F, uint64_t* file_first) {
@@ -180,51 +144,42 @@ int pem_decode_file_first(ctmr_engine* e, const PemDecode& P, uint64_t F, uint64
   return CTMR_OK;
 }
 
-}  // namespace
-}  // extern "C++"
-
-int ctmr_pem_decode_device(ctmr_engine* e, const void* d_text, const uint64_t* file_bounds, uint64_t n_files, void* d_payload, size_t payload_cap,
-                           uint64_t* d_offsets, uint64_t certs_cap, uint64_t* file_first, ctmr_pem_decode_info* info) {
-  if (!e || !info) return CTMR_E_INVAL;
-  pd_info_none(info, n_files);  // (a bad argument names no file)
-  std::lock_guard<std::mutex> g(e->mu);
-  HIPCHK(e, hipSetDevice(e->device));
-  if (n_files && !file_bounds) return fail(e, CTMR_E_INVAL, "%s: null file_bounds", PEM_DECODE);
-  if (n_files && file_bounds[n_files] > file_bounds[0] && !d_text) return fail(e, CTMR_E_INVAL, "%s: null text", PEM_DECODE);
-  if ((uintptr_t)d_payload & 15u) return fail(e, CTMR_E_INVAL, "%s: the payload is not 16-byte aligned", PEM_DECODE);
-  PemDecode P;
-  int r = pem_decode_core(e, (const uint8_t*)d_text, file_bounds, n_files, &P);
-  *info = P.info;
-  if (r) return r;
-  if ((r = pem_decode_fits(e, P, d_payload, payload_cap, d_offsets, certs_cap))) return r;
-  if ((r = pem_decode_decode(e, P, (uint8_t*)d_payload))) return r;
-  HIPCHK(e, hipMemcpy(d_offsets, P.offsets.p, (P.n + 1) * 8, hipMemcpyDeviceToDevice));
-  return pem_decode_file_first(e, P, n_files, file_first);
-}
-
-int ctmr_pem_decode(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files, uint8_t* payload, size_t payload_cap,
+// ctmr_pem_decode (host: text, payload and offsets are host memory, staged here) and ctmr_pem_decode_device
+int pem_decode_call(ctmr_engine* e, bool host, const void* text, const uint64_t* file_bounds, uint64_t n_files, void* payload, size_t payload_cap,
                     uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first, ctmr_pem_decode_info* info) {
   if (!e || !info) return CTMR_E_INVAL;
   pd_info_none(info, n_files);  // (a bad argument names no file)
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (n_files && !file_bounds) return fail(e, CTMR_E_INVAL, "%s: null file_bounds", PEM_DECODE);
-  const uint64_t lo = n_files ? file_bounds[0] : 0, hi = n_files ? file_bounds[n_files] : 0;
-  if (hi > lo && !text) return fail(e, CTMR_E_INVAL, "%s: null text", PEM_DECODE);
   DevMem d_text, d_payload;
-  if (hi > lo) {  // the bytes inside the bounds, staged once
-    if (d_text.alloc(hi - lo) != hipSuccess) return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu bytes", PEM_DECODE, (unsigned long long)(hi - lo));
-    HIPCHK(e, hipMemcpyAsync(d_text.p, text + lo, hi - lo, hipMemcpyHostToDevice, e->stream));
-  }
+  const uint8_t* s;
+  int r;
+  if ((r = tx_stage(e, PEM_DECODE, (const uint8_t*)text, file_bounds, n_files, host ? &d_text : nullptr, &s))) return r;
+  if (!host && ((uintptr_t)payload & 15u)) return fail(e, CTMR_E_INVAL, "%s: the payload is not 16-byte aligned", PEM_DECODE);
   PemDecode P;
-  int r = pem_decode_core(e, (const uint8_t*)((uintptr_t)d_text.p - lo), file_bounds, n_files, &P);
+  r = pem_decode_core(e, s, file_bounds, n_files, &P);
   *info = P.info;
   if (r) return r;
-  if ((r = pem_decode_fits(e, P, payload, payload_cap, offsets, certs_cap))) return r;
-  if (d_payload.alloc(P.info.payload_bytes + CTMR_PAYLOAD_PAD) != hipSuccess)
+  if ((r = tx_fits(e, PEM_DECODE, P.n, "certificates", P.info.payload_bytes, "payload", payload, payload_cap, offsets, certs_cap))) return r;
+  if (host && d_payload.alloc(P.info.payload_bytes + CTMR_PAYLOAD_PAD) != hipSuccess)
     return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu decoded bytes", PEM_DECODE, (unsigned long long)P.info.payload_bytes);
-  if ((r = pem_decode_decode(e, P, d_payload.u8()))) return r;
-  HIPCHK(e, hipMemcpy(payload, d_payload.p, P.info.payload_bytes + CTMR_PAYLOAD_PAD, hipMemcpyDeviceToHost));
-  HIPCHK(e, hipMemcpy(offsets, P.offsets.p, (P.n + 1) * 8, hipMemcpyDeviceToHost));
+  if ((r = pem_decode_decode(e, P, host ? d_payload.u8() : (uint8_t*)payload))) return r;
+  if (host) HIPCHK(e, hipMemcpy(payload, d_payload.p, P.info.payload_bytes + CTMR_PAYLOAD_PAD, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(offsets, P.offsets.p, (P.n + 1) * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
   return pem_decode_file_first(e, P, n_files, file_first);
 }
+
+}  // namespace
+}  // extern "C++"
+
+int ctmr_pem_decode_device(ctmr_engine* e, const void* d_text, const uint64_t* file_bounds, uint64_t n_files, void* d_payload, size_t payload_cap,
+                           uint64_t* d_offsets, uint64_t certs_cap, uint64_t* file_first, ctmr_pem_decode_info* info) {
+  return pem_decode_call(e, false, d_text, file_bounds, n_files, d_payload, payload_cap, d_offsets, certs_cap, file_first, info);
+}
+
+int ctmr_pem_decode(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files, uint8_t* payload, size_t payload_cap,
+                    uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first, ctmr_pem_decode_info* info) {
+  return pem_decode_call(e, true, text, file_bounds, n_files, payload, payload_cap, offsets, certs_cap, file_first, info);
+}
+

@@ -2,7 +2,7 @@
 // of a packed batch (include/ctmr.h ctmr_pem_decode*).  The inverse of kernels/pem.h.
 // '-' is not in the base64 alphabet, so every dash of a valid file belongs to an armor line, and the armor lines of a
 // file alternate BEGIN, END: that does here what quote parity does in kernels/entries_json.h.  The passes, each a launch:
-//   mark      one wave per EJ_TILE bytes.  Per byte a class: dash, LF, blank, alphabet, '=', other.  Counted per block —
+//   mark      one wave per TX_TILE bytes.  Per byte a class: dash, LF, blank, alphabet, '=', other.  Counted per block —
 //             armor tokens, body characters (alphabet and '='), '=' — scanned, then written: the token list
 //             (position << 1 | kind) with the characters and the '=' in front of each.  Found here: an "other" byte; a
 //             dash outside an armor line (a run of dashes starts a line and spells a literal, or closes one; no run is
@@ -15,11 +15,12 @@
 //             lane writes the decoded length and decides the block's layout: regular (L, e) — lines of L characters,
 //             each ended by the same eol of e bytes, nothing else — or irregular.
 //   squeeze   irregular blocks only: their characters copied contiguously into a working buffer.
-//   decode    the hot path: one tile of EJ_DTILE characters of one certificate per block → EJ_DOUT bytes.  A lane finds
-//             its quantum at body + (r / L)(L + e) + r % L, straight in the text, and packs 4 → 3.
-// The text lies at any alignment (EjText, ej_chunk).  gfx950 (CDNA4, wave64) only; part of kernels.h.
+//   decode    the hot path: one tile of TX_DTILE characters of one certificate per block → TX_DOUT bytes.  A lane finds
+//             its quantum at body + (r / L)(L + e) + r % L, straight in the text, and packs 4 → 3 (tx_decode_tile).
+// The text, its segments (here: the files), the chunks and tiles it is read in, the wave's scan and report and the decode
+// of a tile are those of kernels/text_scan.h; what is here is PEM.  gfx950 (CDNA4, wave64) only; part of kernels.h.
 #pragma once
-#include "entries_json.h"
+#include "text_scan.h"
 
 namespace ctmr {
 
@@ -43,14 +44,14 @@ __device__ __forceinline__ bool pd_spells(const uint8_t* s, uint64_t at, const c
 }
 
 // the offset from s of the first byte of mark block blk (below lo, even negative, for block 0)
-__device__ __forceinline__ int64_t pd_block_pos(const EjText& T, uint64_t blk) {
-  return (int64_t)(T.a0 + blk * EJ_TILE - (uint64_t)(uintptr_t)T.s);
+__device__ __forceinline__ int64_t pd_block_pos(const TxText& T, uint64_t blk) {
+  return (int64_t)(T.a0 + blk * TX_TILE - (uint64_t)(uintptr_t)T.s);
 }
 
 // What precedes the byte at p, ws skipped, inside its file [fs, …): *lf = an LF lies between.  → 0 nothing (the file's
 // start), else PD_S_ANY | PD_S_EQ or PD_S_DASH when it is one.  Bytes of p's own block are read; the blocks before it
 // answer with their summary, unless the file starts inside one.
-__device__ __forceinline__ uint32_t pd_before(const EjText& T, const uint8_t* sum, uint64_t blk, uint64_t p, uint64_t fs, bool* lf) {
+__device__ __forceinline__ uint32_t pd_before(const TxText& T, const uint8_t* sum, uint64_t blk, uint64_t p, uint64_t fs, bool* lf) {
   bool seen = false;
   uint32_t cls = 0u;
   int64_t q = (int64_t)p, start = pd_block_pos(T, blk);
@@ -82,22 +83,22 @@ __device__ __forceinline__ uint32_t pd_before(const EjText& T, const uint8_t* su
 // | kind of every armor line, ctok[] / etok[] = the characters / '=' of the text in front of it; what needs the
 // summaries is reported.
 template <bool WRITE>
-__global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, unsigned long long* cnt_t, unsigned long long* cnt_c,
+__global__ void __launch_bounds__(TX_BLOCK) k_pd_mark(TxText T, uint64_t b0, unsigned long long* cnt_t, unsigned long long* cnt_c,
                                                       unsigned long long* cnt_e, uint8_t* sum, unsigned long long* tok,
                                                       unsigned long long* ctok, unsigned long long* etok, unsigned long long* err) {
   const uint32_t lane = threadIdx.x;
   const uint64_t blk = b0 + blockIdx.x;
   int64_t p0;
   uint32_t valid;
-  const uint4 v = ej_chunk(T, blk, lane, &p0, &valid);
+  const uint4 v = tx_chunk(T, blk, lane, &p0, &valid);
   uint32_t dash = 0u, lf = 0u, blank = 0u, alpha = 0u, eq = 0u;
 #pragma unroll
-  for (uint32_t q = 0; q < EJ_PER; q++) {
-    const uint32_t c = ej_byte(v, q);
+  for (uint32_t q = 0; q < TX_PER; q++) {
+    const uint32_t c = tx_byte(v, q);
     dash |= (c == 0x2du ? 1u : 0u) << q;
     lf |= (c == 0x0au ? 1u : 0u) << q;
     blank |= (pd_is_blank(c) ? 1u : 0u) << q;
-    alpha |= ((((c | 0x20u) - 0x61u) < 26u || (c - 0x30u) < 10u || c == 0x2bu || c == 0x2fu) ? 1u : 0u) << q;
+    alpha |= TX_ALPHABET_BIT(c) << q;
     eq |= (c == 0x3du ? 1u : 0u) << q;
   }
   dash &= valid;
@@ -106,12 +107,8 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, uns
   eq &= valid;
   const uint32_t chars = alpha | eq;
   const uint32_t other = valid & ~(dash | lf | blank | chars);
-  // the block's file, when it has one only (k_ej_mark)
-  const uint64_t s0 = (uint64_t)(uintptr_t)T.s;
-  const uint64_t blk_lo = T.a0 + blk * EJ_TILE - s0 + (blk == 0 ? T.lo - (T.a0 - s0) : 0ull);
-  const uint64_t blk_end = T.a0 + (blk + 1ull) * EJ_TILE - s0;
-  const uint64_t r_lo = ej_resp_of(T.rb, T.R, blk_lo);
-  const bool uniform = T.rb[r_lo + 1] >= (blk_end < T.hi ? blk_end : T.hi);
+  bool uniform;  // the block lies in one file, r_lo
+  const uint64_t r_lo = tx_block_segment(T, blk, &uniform);
   // runs of dashes.  A dash with a dash in front of it: some byte of the four before that is none (or the file's start).
   // A run's first dash at a line start is a token and spells a literal; elsewhere it closes one.
   const uint32_t prev_alpha = __shfl_up(alpha >> 15, 1);  // the byte in front of the lane's first (lane 0: unknown)
@@ -124,8 +121,8 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, uns
       const uint32_t q = (uint32_t)__ffs(m) - 1u;
       m &= m - 1u;
       const uint64_t p = (uint64_t)(p0 + (int64_t)q);
-      const uint64_t f = uniform ? r_lo : ej_resp_of(T.rb, T.R, p);
-      const uint64_t fs = T.rb[f], fe = T.rb[f + 1];
+      const uint64_t f = uniform ? r_lo : tx_segment_of(T.sb, T.S, p);
+      const uint64_t fs = T.sb[f], fe = T.sb[f + 1];
       const bool run = p > fs && T.s[p - 1] == 0x2du, line = !run && (p == fs || T.s[p - 1] == 0x0au);
       if (line) {  // a token, spelled right or not: BEGIN unless an E follows its dashes
         tokm |= 1u << q;
@@ -150,13 +147,13 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, uns
   }
   if (!WRITE) {
     uint64_t vr = 0;
-    if (bad) vr = uniform ? r_lo : ej_resp_of(T.rb, T.R, bad_at);
-    ej_report(err, bad, vr, bad_at);
+    if (bad) vr = uniform ? r_lo : tx_segment_of(T.sb, T.S, bad_at);
+    tx_report(err, bad, vr, bad_at);
   }
-  // counts: tokens and characters in one scan (each at most EJ_TILE), the '=' in another
+  // counts: tokens and characters in one scan (each at most TX_TILE), the '=' in another
   uint32_t total, total_e;
-  const uint32_t packed = ej_wave_scan((uint32_t)__popc(tokm) | ((uint32_t)__popc(chars) << 16), &total);
-  const uint32_t eq_before = ej_wave_scan((uint32_t)__popc(eq), &total_e);
+  const uint32_t packed = tx_wave_scan((uint32_t)__popc(tokm) | ((uint32_t)__popc(chars) << 16), &total);
+  const uint32_t eq_before = tx_wave_scan((uint32_t)__popc(eq), &total_e);
   if (!WRITE) {
     // the summary: the block's last non-ws byte and whether an LF lies behind it
     const uint32_t nonws = valid & ~(lf | blank);
@@ -188,8 +185,8 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, uns
       const uint32_t q = (uint32_t)__ffs(m) - 1u;
       m &= m - 1u;
       const uint64_t p = (uint64_t)(p0 + (int64_t)q);
-      const uint64_t f = uniform ? r_lo : ej_resp_of(T.rb, T.R, p);
-      const uint64_t fs = T.rb[f];
+      const uint64_t f = uniform ? r_lo : tx_segment_of(T.sb, T.S, p);
+      const uint64_t fs = T.sb[f];
       const bool is_eq = (eq >> q) & 1u;
       bool seen_lf = false, ok;
       const uint32_t cls = pd_before(T, sum, blk, p, fs, &seen_lf);
@@ -205,7 +202,7 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, uns
         f2 = f;
       }
     }
-    ej_report(err, bad2, f2, at2);
+    tx_report(err, bad2, f2, at2);
   }
   unsigned long long at = cnt_t[blk] + (packed & 0xffffu);
   const unsigned long long c_lane = cnt_c[blk] + (packed >> 16), e_lane = cnt_e[blk] + eq_before;
@@ -220,63 +217,40 @@ __global__ void __launch_bounds__(EJ_BLOCK) k_pd_mark(EjText T, uint64_t b0, uns
   }
 }
 
-// fstart: cfile[r] = the characters of [lo, rb[r]) (r <= R): the scanned block count plus the characters of rb[r]'s block
-// before it; a wave per boundary (k_ej_qstart)
-__global__ void __launch_bounds__(RP_BLOCK) k_pd_fstart(EjText T, uint64_t b0, const unsigned long long* cnt_c, uint64_t nb, unsigned long long* cfile) {
+// fstart: cfile[r] = the characters of [lo, sb[r]) (r <= R); a wave per boundary
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_fstart(TxText T, uint64_t b0, const unsigned long long* cnt_c, uint64_t nb, unsigned long long* cfile) {
   const uint64_t r = (b0 + blockIdx.x) * (RP_BLOCK / 64) + (threadIdx.x >> 6);
-  if (r > T.R) return;  // (whole waves leave)
-  const uint64_t at = T.rb[r];
-  const uint64_t blk = ((uint64_t)(uintptr_t)T.s + at - T.a0) / EJ_TILE;
+  if (r > T.S) return;  // (whole waves leave)
+  const uint64_t at = T.sb[r];
+  const uint64_t blk = tx_block_of(T, at);
   if (blk >= nb) {  // (hi at a block's edge)
     if ((threadIdx.x & 63u) == 0) cfile[r] = cnt_c[nb];
     return;
   }
-  int64_t p0;
-  uint32_t valid, total;
-  const uint4 v = ej_chunk(T, blk, threadIdx.x & 63u, &p0, &valid);
-  uint32_t chars = 0u, before = 0u;
-#pragma unroll
-  for (uint32_t q = 0; q < EJ_PER; q++) {
-    const uint32_t c = ej_byte(v, q);
-    chars |= ((((c | 0x20u) - 0x61u) < 26u || (c - 0x30u) < 10u || c == 0x2bu || c == 0x2fu || c == 0x3du) ? 1u : 0u) << q;
-  }
-  const int64_t d = (int64_t)at - p0;
-  if (d >= 16) before = 0xffffu;
-  else if (d > 0) before = 0xffffu >> (16u - (uint32_t)d);
-  (void)ej_wave_scan((uint32_t)__popc(chars & valid & before), &total);
-  if ((threadIdx.x & 63u) == 0) cfile[r] = cnt_c[blk] + total;
+  const unsigned long long c = tx_boundary_prefix<tx_alphabet_mask<true>>(T, blk, at, cnt_c);
+  if ((threadIdx.x & 63u) == 0) cfile[r] = c;
 }
 
-// files: tfirst[r] = the tokens before rb[r] (r <= R); ccnt[r] = the certificates of file r, half its tokens — an odd
+// files: tfirst[r] = the tokens before sb[r] (r <= R); ccnt[r] = the certificates of file r, half its tokens — an odd
 // count is reported; ccnt[R] = 0 (the scan's total)
-__global__ void __launch_bounds__(RP_BLOCK) k_pd_files(EjText T, uint64_t b0, const unsigned long long* tok, uint64_t ntok,
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_files(TxText T, uint64_t b0, const unsigned long long* tok, uint64_t ntok,
                                                        unsigned long long* tfirst, unsigned long long* ccnt, unsigned long long* err) {
   const uint64_t r = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
   bool bad = false;
   uint64_t off = 0;
-  if (r <= T.R) {
+  if (r <= T.S) {
     uint64_t first[2];
-#pragma unroll
-    for (uint32_t k = 0; k < 2; k++) {
-      const uint64_t at = T.rb[r + k < T.R ? r + k : T.R];
-      uint64_t l = 0, h = ntok;
-      while (l < h) {
-        const uint64_t mid = (l + h) >> 1;
-        if ((tok[mid] >> 1) < at) l = mid + 1;
-        else h = mid;
-      }
-      first[k] = l;
-    }
+    tx_first_tokens(T, r, tok, ntok, 1u, first);
     tfirst[r] = first[0];
     uint64_t n = 0;
-    if (r < T.R) {
+    if (r < T.S) {
       n = (first[1] - first[0]) >> 1;
       bad = (first[1] - first[0]) & 1ull;
       off = bad ? tok[first[1] - 1] >> 1 : 0ull;  // the armor line left alone
     }
     ccnt[r] = n;
   }
-  ej_report(err, bad, r, off);
+  tx_report(err, bad, r, off);
 }
 
 // the tables the check reads and writes
@@ -298,7 +272,7 @@ struct PdCheck {
 // check: one lane per token.  f_limit: the lowest file the passes before have reported, or none (~0).  The check relies on
 // armor lines that are spelled right and come in pairs, so it looks at the files below that one only: a violation of its
 // own in one of them is the lower one.
-__global__ void __launch_bounds__(RP_BLOCK) k_pd_check(EjText T, uint64_t b0, PdCheck C, uint64_t f_limit, unsigned long long* err) {
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_check(TxText T, uint64_t b0, PdCheck C, uint64_t f_limit, unsigned long long* err) {
   const uint64_t t = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
   bool bad = false, irregular = false, is_end = false;
   uint64_t f = 0, pos = 0, i = 0, cc = 0, ne = 0, p0 = 0, b = 0;
@@ -308,7 +282,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_pd_check(EjText T, uint64_t b0, Pd
     const unsigned long long tk = C.tok[t];
     pos = tk >> 1;
     const uint32_t kind = (uint32_t)(tk & 1ull);
-    f = ej_resp_of(T.rb, T.R, pos);
+    f = tx_segment_of(T.sb, T.S, pos);
     const uint64_t j = t - C.tfirst[f], nt = C.tfirst[f + 1] - C.tfirst[f];
     if (f < f_limit && !(nt & 1ull)) {  // (else the file has been reported, or lies behind one that has)
       bad = kind != (uint32_t)(j & 1ull);
@@ -378,40 +352,34 @@ __global__ void __launch_bounds__(RP_BLOCK) k_pd_check(EjText T, uint64_t b0, Pd
     C.lay[i] = irregular ? PD_IRREGULAR : ((unsigned long long)L << 2) | e;
     C.sqlen[i] = irregular ? cc : 0ull;
     const uint64_t s0 = (uint64_t)(uintptr_t)T.s;
-    C.sqtiles[i] = irregular ? (s0 + pos - 1 - T.a0) / EJ_TILE - (s0 + p0 + PD_BEGIN_LEN - T.a0) / EJ_TILE + 1 : 0ull;
+    C.sqtiles[i] = irregular ? (s0 + pos - 1 - T.a0) / TX_TILE - (s0 + p0 + PD_BEGIN_LEN - T.a0) / TX_TILE + 1 : 0ull;
   }
   const unsigned long long irr = __ballot(irregular);
   if ((threadIdx.x & 63u) == 0 && irr) atomicAdd(err + 2, (unsigned long long)__popcll(irr));
-  ej_report(err, bad, f, pos);
+  tx_report(err, bad, f, pos);
 }
 
 // squeeze: block = tile t of irregular certificate i = tile_cert[t]: the characters of one mark block between the
 // certificate's armor lines → sq[sqoff[i] + their rank in the body]
-__global__ void __launch_bounds__(EJ_BLOCK) k_pd_squeeze(EjText T, uint64_t b0, const unsigned long long* tile_cert, const unsigned long long* tile_first,
+__global__ void __launch_bounds__(TX_BLOCK) k_pd_squeeze(TxText T, uint64_t b0, const unsigned long long* tile_cert, const unsigned long long* tile_first,
                                                          const unsigned long long* src, const unsigned long long* tok, const unsigned long long* ctok,
                                                          const unsigned long long* cnt_c, const unsigned long long* sqoff, uint8_t* sq) {
   const uint64_t t = b0 + blockIdx.x, i = tile_cert[t], k = t - tile_first[i];
   const uint64_t tb = src[i];
   const uint64_t from = (tok[tb] >> 1) + PD_BEGIN_LEN, to = tok[tb + 1] >> 1;
-  const uint64_t blk = ((uint64_t)(uintptr_t)T.s + from - T.a0) / EJ_TILE + k;
+  const uint64_t blk = tx_block_of(T, from) + k;
   int64_t p0;
   uint32_t valid, total;
-  const uint4 v = ej_chunk(T, blk, threadIdx.x, &p0, &valid);
-  uint32_t chars = 0u;
-#pragma unroll
-  for (uint32_t q = 0; q < EJ_PER; q++) {
-    const uint32_t c = ej_byte(v, q);
-    chars |= ((((c | 0x20u) - 0x61u) < 26u || (c - 0x30u) < 10u || c == 0x2bu || c == 0x2fu || c == 0x3du) ? 1u : 0u) << q;
-  }
-  chars &= valid;
-  const unsigned long long rank = cnt_c[blk] + ej_wave_scan((uint32_t)__popc(chars), &total) - (ctok[tb] + PD_BEGIN_CHARS);
+  const uint4 v = tx_chunk(T, blk, threadIdx.x, &p0, &valid);
+  const uint32_t chars = tx_alphabet_mask<true>(v) & valid;
+  const unsigned long long rank = cnt_c[blk] + tx_wave_scan((uint32_t)__popc(chars), &total) - (ctok[tb] + PD_BEGIN_CHARS);
   uint8_t* out = sq + sqoff[i];
   uint32_t m = chars;
   while (m) {
     const uint32_t q = (uint32_t)__ffs(m) - 1u;
     m &= m - 1u;
     const int64_t p = p0 + (int64_t)q;
-    if (p >= (int64_t)from && p < (int64_t)to) out[rank + (uint32_t)__popc(chars & ((1u << q) - 1u))] = (uint8_t)ej_byte(v, q);
+    if (p >= (int64_t)from && p < (int64_t)to) out[rank + (uint32_t)__popc(chars & ((1u << q) - 1u))] = (uint8_t)tx_byte(v, q);
   }
 }
 
@@ -426,23 +394,18 @@ struct PdDecode {
   const uint8_t* sq;
 };
 
-// decode: block = tile t of certificate i: its characters [EJ_DTILE k, …) → payload[offsets[i] + EJ_DOUT k, …)
-__global__ void __launch_bounds__(EJ_DBLOCK) k_pd_decode(const uint8_t* s, uint64_t b0, PdDecode D, uint8_t* payload) {
-  __shared__ __attribute__((aligned(16))) uint8_t stage[EJ_DOUT + 16];
-  const uint64_t t = b0 + blockIdx.x, i = D.tile_cert[t], k = t - D.tile_first[i];
-  const uint64_t at0 = D.offsets[i], dec = D.offsets[i + 1] - at0;
-  const uint64_t left = dec - k * EJ_DOUT;
-  const uint32_t total = left < EJ_DOUT ? (uint32_t)left : EJ_DOUT;  // 1 … EJ_DOUT
-  const uint64_t dst = at0 + k * EJ_DOUT;
-  const uint32_t phase = (uint32_t)(dst & 15ull);
-  const unsigned long long lay = D.lay[i];
+// decode: block = tile t of certificate i: its characters [TX_DTILE k, …) → payload[offsets[i] + TX_DOUT k, …)
+__global__ void __launch_bounds__(TX_DBLOCK) k_pd_decode(const uint8_t* s, uint64_t b0, PdDecode D, uint8_t* payload) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[TX_DOUT + 16];
+  const TxTile w = tx_tile(b0 + blockIdx.x, D.tile_cert, D.tile_first, D.offsets);
+  const unsigned long long lay = D.lay[w.i];
   const bool squeezed = (lay & 3ull) == PD_IRREGULAR;
   const uint32_t L = squeezed ? 0u : (uint32_t)(lay >> 2), e = squeezed ? 0u : (uint32_t)(lay & 3ull);
-  const uint64_t base = squeezed ? (uint64_t)(uintptr_t)D.sq + D.sqoff[i] : (uint64_t)(uintptr_t)s + D.src[i];
-  const uint64_t r0 = k * EJ_DTILE;  // the tile's first character; the line it lies in and where (block-uniform)
+  const uint64_t base = squeezed ? (uint64_t)(uintptr_t)D.sq + D.sqoff[w.i] : (uint64_t)(uintptr_t)s + D.src[w.i];
+  const uint64_t r0 = w.k * TX_DTILE;  // the tile's first character; the line it lies in and where (block-uniform)
   const uint64_t line0 = L ? r0 / L : 0ull;
   const uint64_t in0 = L ? r0 % L : r0;
-  if (3u * threadIdx.x < total) {
+  if (tx_has_quantum(w)) {
     uint64_t a;
     if (L) {  // a quantum never straddles a line: L % 4 == 0
       const uint32_t m = (uint32_t)in0 + 4u * threadIdx.x;
@@ -450,19 +413,9 @@ __global__ void __launch_bounds__(EJ_DBLOCK) k_pd_decode(const uint8_t* s, uint6
     } else {
       a = base + in0 + 4ull * threadIdx.x;
     }
-    const uint32_t sh = 8u * (uint32_t)(a & 3ull);
-    const uint32_t* w = (const uint32_t*)(uintptr_t)(a & ~3ull);
-    uint32_t ch = __builtin_nontemporal_load(w);
-    if (sh) ch = (ch >> sh) | (__builtin_nontemporal_load(w + 1) << (32u - sh));  // (the quantum reaches into w[1])
-    const uint32_t x = (ej_sextet(ch & 0xffu) << 18) | (ej_sextet((ch >> 8) & 0xffu) << 12) | (ej_sextet((ch >> 16) & 0xffu) << 6) |
-                       ej_sextet(ch >> 24);
-    uint8_t* o = stage + phase + 3u * threadIdx.x;
-    o[0] = (uint8_t)(x >> 16);
-    o[1] = (uint8_t)(x >> 8);
-    o[2] = (uint8_t)x;
+    tx_stage_quantum(stage, w, a);
   }
-  __syncthreads();
-  ej_store_tile(stage, phase, total, payload + dst);
+  tx_tile_leaves(stage, w, payload);
 }
 
 }  // namespace ctmr

@@ -7,8 +7,8 @@ import random
 
 from ct_mapreduce_amd import get_entries as ge
 
-MARK_BLOCK = 1024    # the bytes of a mark block (kernels/entries_json.h EJ_TILE): one wave, 16 bytes a lane
-DECODE_TILE = 1024   # the characters of a decode tile (EJ_DTILE) → 768 bytes
+MARK_BLOCK = 1024    # the bytes of a mark block (kernels/text_scan.h TX_TILE): one wave, 16 bytes a lane
+DECODE_TILE = 1024   # the characters of a decode tile (TX_DTILE) → 768 bytes
 TILE_OUT = DECODE_TILE * 3 // 4
 
 
