@@ -261,6 +261,10 @@ SIGNATURES = {
                                          C.POINTER(DecodeStats), C.POINTER(BatchStats)]),
     "ctmr_pem_decode": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(PemDecodeInfo)]),
     "ctmr_pem_decode_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, C.POINTER(PemDecodeInfo)]),
+    "ctmr_pem_decode_each": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, _P, C.POINTER(PemDecodeInfo)]),
+    "ctmr_pem_decode_each_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, _P, _P, C.POINTER(PemDecodeInfo)]),
+    "ctmr_submit_pem": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "ctmr_wait_pem": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P, _P, C.POINTER(PemDecodeInfo), C.POINTER(BatchStats)]),
     "ctmr_meta_new_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ctmr_meta_new": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
     "ctmr_meta_reset": (C.c_int, [_P]),

@@ -705,5 +705,6 @@ extern "C" {
 #include "engine/entries_json.inc"
 #include "engine/pipeline_json.inc"
 #include "engine/pem_decode.inc"
+#include "engine/pipeline_pem.inc"
 
 }  // extern "C"

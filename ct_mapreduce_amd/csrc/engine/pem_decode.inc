@@ -14,6 +14,8 @@ struct PemDecode {
   TxText text{};
   uint64_t n = 0, sq_bytes = 0;
   ctmr_pem_decode_info info{};
+  DevMem bad;            // each: the verdict of every file, UINT64_MAX or an offset inside it — fetched only when any_bad
+  bool any_bad = false;  // each: some file is outside the grammar (info names the lowest)
 };
 
 const char* const PEM_DECODE = "pem decode";
@@ -28,7 +30,9 @@ int pd_alloc(ctmr_engine* e, DevMem* m, uint64_t words) { return tx_alloc(e, PEM
 
 // Everything but the payload: the text (device memory, any alignment; file f at s[fb[f], fb[f + 1])) validated, P->info
 // made, the tables of the decode left on the device.  Drains the stream.
-int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64_t F, PemDecode* P) {
+// each: a file outside the grammar fails nothing: P->bad[f] (device) gets its offset, P->info names the lowest, and ffirst
+// and the tables of the decode are those of the files inside the grammar alone, the others holding no certificates.
+int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64_t F, PemDecode* P, bool each = false) {
   int r;
   ctmr_pem_decode_info& info = P->info;
   pd_info_none(&info, F);
@@ -44,27 +48,33 @@ int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return CTMR_OK;
   }
-  DevMem cnt_t_m, cnt_e_m, sum_m, err_m, cfile_m, tfirst_m, etok_m;
+  // each: the table of verdicts, F words and the lowest file with one behind them (pd_verdict); gate: its copy for the check
+  DevMem cnt_t_m, cnt_e_m, sum_m, err_m, gate_m, cfile_m, tfirst_m, etok_m;
   if ((r = pd_alloc(e, &cnt_t_m, nb + 1)) || (r = pd_alloc(e, &P->cnt_c, nb + 1)) || (r = pd_alloc(e, &cnt_e_m, nb + 1)) ||
       (r = pd_alloc(e, &sum_m, (nb + 7) / 8)) || (r = pd_alloc(e, &err_m, 3)) || (r = pd_alloc(e, &cfile_m, F + 1)) ||
-      (r = pd_alloc(e, &tfirst_m, F + 1)))
+      (r = pd_alloc(e, &tfirst_m, F + 1)) || (each && ((r = pd_alloc(e, &P->bad, F + 1)) || (r = pd_alloc(e, &gate_m, F)))))
     return r;
-  unsigned long long* err = (unsigned long long*)err_m.p;
+  unsigned long long* err = (unsigned long long*)(each ? P->bad.p : err_m.p);
+  unsigned long long* irr = (unsigned long long*)err_m.p + 2;
   unsigned long long* cnt_t = (unsigned long long*)cnt_t_m.p;
   unsigned long long* cnt_c = (unsigned long long*)P->cnt_c.p;
   unsigned long long* cnt_e = (unsigned long long*)cnt_e_m.p;
-  HIPCHK(e, hipMemsetAsync(err, 0xff, 16, e->stream));
-  HIPCHK(e, hipMemsetAsync(err + 2, 0, 8, e->stream));  // the irregular blocks
+  HIPCHK(e, hipMemsetAsync(err, 0xff, each ? (F + 1) * 8 : 16, e->stream));
+  HIPCHK(e, hipMemsetAsync(irr, 0, 8, e->stream));  // the irregular blocks
+  const auto k_count = each ? k_pd_mark<false, true> : k_pd_mark<false, false>;  // (each: the kernels that fill the table of verdicts)
+  const auto k_write = each ? k_pd_mark<true, true> : k_pd_mark<true, false>;
+  const auto k_files = each ? k_pd_files<true> : k_pd_files<false>;
+  const auto k_check = each ? k_pd_check<true> : k_pd_check<false>;
   // ---- armor lines
   tx_turns(nb, [&](uint64_t b0, dim3 g) {
-    hipLaunchKernelGGL((k_pd_mark<false>), g, dim3(TX_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)nullptr,
+    hipLaunchKernelGGL(k_count, g, dim3(TX_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)nullptr,
                        (unsigned long long*)nullptr, (unsigned long long*)nullptr, err);
   });
   uint64_t ntok = 0;
   if ((r = tx_scan(e, P->cnt_c, nb, nullptr)) || (r = tx_scan(e, cnt_e_m, nb, nullptr)) || (r = tx_scan(e, cnt_t_m, nb, &ntok))) return r;
   if ((r = pd_alloc(e, &P->tok, ntok)) || (r = pd_alloc(e, &P->ctok, ntok)) || (r = pd_alloc(e, &etok_m, ntok))) return r;
   tx_turns(nb, [&](uint64_t b0, dim3 g) {
-    hipLaunchKernelGGL((k_pd_mark<true>), g, dim3(TX_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)P->tok.p,
+    hipLaunchKernelGGL(k_write, g, dim3(TX_BLOCK), 0, e->stream, T, b0, cnt_t, cnt_c, cnt_e, sum_m.u8(), (unsigned long long*)P->tok.p,
                        (unsigned long long*)P->ctok.p, (unsigned long long*)etok_m.p, err);
   });
   // ---- files, certificates
@@ -72,14 +82,15 @@ int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64
     hipLaunchKernelGGL(k_pd_fstart, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)cnt_c, nb, (unsigned long long*)cfile_m.p);
   });
   tx_turns(tx_blocks(F + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
-    hipLaunchKernelGGL(k_pd_files, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)P->tok.p, ntok, (unsigned long long*)tfirst_m.p,
+    hipLaunchKernelGGL(k_files, g, dim3(RP_BLOCK), 0, e->stream, T, b0, (const unsigned long long*)P->tok.p, ntok, (unsigned long long*)tfirst_m.p,
                        (unsigned long long*)P->ffirst.p, err);
   });
   uint64_t n = 0;
   if ((r = scan_u64(e, (uint64_t*)P->ffirst.p, F + 1, false, SC_MISC))) return r;
   unsigned long long h_err[3] = {0, 0, 0};
   HIPCHK(e, hipMemcpyAsync(&n, (uint64_t*)P->ffirst.p + F, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipMemcpyAsync(h_err, err, 24, hipMemcpyDeviceToHost, e->stream));
+  if (each) HIPCHK(e, hipMemcpyAsync(gate_m.p, err, F * 8, hipMemcpyDeviceToDevice, e->stream));
+  else HIPCHK(e, hipMemcpyAsync(h_err, err, 24, hipMemcpyDeviceToHost, e->stream));
   if ((r = tx_drain(e))) return r;
   const uint64_t f_limit = h_err[0];  // the files from this one on are outside the grammar or need no verdict: the check skips them
   if ((r = pd_alloc(e, &P->offsets, n + 1)) || (r = pd_alloc(e, &P->src, n)) || (r = pd_alloc(e, &P->lay, n)) || (r = pd_alloc(e, &P->sqoff, n + 1)) ||
@@ -90,10 +101,57 @@ int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64
                     (const unsigned long long*)tfirst_m.p,  (const unsigned long long*)P->ffirst.p,  (const unsigned long long*)cfile_m.p,
                     (unsigned long long*)P->offsets.p,      (unsigned long long*)P->src.p,           (unsigned long long*)P->lay.p,
                     (unsigned long long*)P->sqoff.p,        (unsigned long long*)P->sqtiles.p};
-    tx_turns(tx_blocks(ntok, RP_BLOCK), [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_pd_check, g, dim3(RP_BLOCK), 0, e->stream, T, b0, C, f_limit, err); });
+    tx_turns(tx_blocks(ntok, RP_BLOCK), [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_check, g, dim3(RP_BLOCK), 0, e->stream, T, b0, C, f_limit, (const unsigned long long*)gate_m.p, irr, err);
+    });
   }
-  HIPCHK(e, hipMemcpyAsync(h_err, err, 24, hipMemcpyDeviceToHost, e->stream));
-  if ((r = tx_drain(e))) return r;
+  if (each) {
+    h_err[0] = h_err[1] = ~0ull;
+    unsigned long long low = ~0ull;
+    HIPCHK(e, hipMemcpyAsync(&low, err + F, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(h_err + 2, irr, 8, hipMemcpyDeviceToHost, e->stream));
+    if ((r = tx_drain(e))) return r;
+    if (low != ~0ull) {
+      // the files with a verdict leave: their counts to zero, ffirst scanned again, and the five tables the check wrote
+      // under the old numbering gathered under the new one (certificate-sized; a second check would be token-sized and
+      // read the layouts from the text again).  The irregular blocks are counted again over what stays.
+      P->any_bad = true;
+      info.bad_file = low;
+      const uint64_t n0 = n;
+      DevMem ffirst2, len2, src2, lay2, sqlen2, sqtiles2;
+      if ((r = pd_alloc(e, &ffirst2, F + 1))) return r;
+      HIPCHK(e, hipMemcpyAsync(&info.bad_offset, err + low, 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipMemsetAsync(irr, 0, 8, e->stream));
+      tx_turns(tx_blocks(F + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
+        hipLaunchKernelGGL(k_ej_drop, g, dim3(RP_BLOCK), 0, e->stream, b0, F, (const unsigned long long*)err, (const unsigned long long*)P->ffirst.p,
+                           (unsigned long long*)ffirst2.p);
+      });
+      if ((r = scan_u64(e, (uint64_t*)ffirst2.p, F + 1, false, SC_MISC))) return r;
+      HIPCHK(e, hipMemcpyAsync(&n, (uint64_t*)ffirst2.p + F, 8, hipMemcpyDeviceToHost, e->stream));
+      if ((r = tx_drain(e))) return r;
+      if ((r = pd_alloc(e, &len2, n + 1)) || (r = pd_alloc(e, &src2, n)) || (r = pd_alloc(e, &lay2, n)) || (r = pd_alloc(e, &sqlen2, n + 1)) ||
+          (r = pd_alloc(e, &sqtiles2, n + 1)))
+        return r;
+      if (n) {
+        const PdGather G{(const unsigned long long*)err,          (const unsigned long long*)P->ffirst.p,  (const unsigned long long*)ffirst2.p,
+                         (const unsigned long long*)P->offsets.p, (const unsigned long long*)P->src.p,     (const unsigned long long*)P->lay.p,
+                         (const unsigned long long*)P->sqoff.p,   (const unsigned long long*)P->sqtiles.p, (unsigned long long*)len2.p,
+                         (unsigned long long*)src2.p,             (unsigned long long*)lay2.p,             (unsigned long long*)sqlen2.p,
+                         (unsigned long long*)sqtiles2.p};
+        tx_turns(tx_blocks(n0, RP_BLOCK), [&](uint64_t b0, dim3 g) { hipLaunchKernelGGL(k_pd_gather, g, dim3(RP_BLOCK), 0, e->stream, b0, F, n0, G, irr); });
+      }
+      HIPCHK(e, hipMemcpyAsync(h_err + 2, irr, 8, hipMemcpyDeviceToHost, e->stream));
+      if ((r = tx_drain(e))) return r;  // (the old tables are freed when this block ends)
+      std::swap(P->ffirst.p, ffirst2.p);
+      std::swap(P->offsets.p, len2.p);
+      std::swap(P->src.p, src2.p);
+      std::swap(P->lay.p, lay2.p);
+      std::swap(P->sqoff.p, sqlen2.p);
+      std::swap(P->sqtiles.p, sqtiles2.p);
+    }
+  } else {
+    HIPCHK(e, hipMemcpyAsync(h_err, err, 24, hipMemcpyDeviceToHost, e->stream));
+    if ((r = tx_drain(e))) return r;
+  }
   if (h_err[0] != ~0ull) {
     info.bad_file = h_err[0];
     info.bad_offset = h_err[1];
@@ -144,21 +202,31 @@ int pem_decode_file_first(ctmr_engine* e, const PemDecode& P, uint64_t F, uint64
   return CTMR_OK;
 }
 
-// ctmr_pem_decode (host: text, payload and offsets are host memory, staged here) and ctmr_pem_decode_device
+// each: the verdicts of the F files to host memory.  Only a call with a bad file fetches the table.
+int pem_decode_file_bad(ctmr_engine* e, const PemDecode& P, uint64_t F, uint64_t* file_bad) {
+  if (!F) return CTMR_OK;
+  if (P.any_bad) HIPCHK(e, hipMemcpy(file_bad, P.bad.p, F * 8, hipMemcpyDeviceToHost));
+  else memset(file_bad, 0xff, F * 8);
+  return CTMR_OK;
+}
+
+// ctmr_pem_decode (host: text, payload and offsets are host memory, staged here) and ctmr_pem_decode_device; each, with
+// file_bad: the …_each* forms
 int pem_decode_call(ctmr_engine* e, bool host, const void* text, const uint64_t* file_bounds, uint64_t n_files, void* payload, size_t payload_cap,
-                    uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first, ctmr_pem_decode_info* info) {
+                    uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first, uint64_t* file_bad, bool each, ctmr_pem_decode_info* info) {
   if (!e || !info) return CTMR_E_INVAL;
   pd_info_none(info, n_files);  // (a bad argument names no file)
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (n_files && !file_bounds) return fail(e, CTMR_E_INVAL, "%s: null file_bounds", PEM_DECODE);
+  if (each && !file_bad) return fail(e, CTMR_E_INVAL, "%s: null file_bad", PEM_DECODE);
   DevMem d_text, d_payload;
   const uint8_t* s;
   int r;
   if ((r = tx_stage(e, PEM_DECODE, (const uint8_t*)text, file_bounds, n_files, host ? &d_text : nullptr, &s))) return r;
   if (!host && ((uintptr_t)payload & 15u)) return fail(e, CTMR_E_INVAL, "%s: the payload is not 16-byte aligned", PEM_DECODE);
   PemDecode P;
-  r = pem_decode_core(e, s, file_bounds, n_files, &P);
+  r = pem_decode_core(e, s, file_bounds, n_files, &P, each);
   *info = P.info;
   if (r) return r;
   if ((r = tx_fits(e, PEM_DECODE, P.n, "certificates", P.info.payload_bytes, "payload", payload, payload_cap, offsets, certs_cap))) return r;
@@ -167,6 +235,7 @@ int pem_decode_call(ctmr_engine* e, bool host, const void* text, const uint64_t*
   if ((r = pem_decode_decode(e, P, host ? d_payload.u8() : (uint8_t*)payload))) return r;
   if (host) HIPCHK(e, hipMemcpy(payload, d_payload.p, P.info.payload_bytes + CTMR_PAYLOAD_PAD, hipMemcpyDeviceToHost));
   HIPCHK(e, hipMemcpy(offsets, P.offsets.p, (P.n + 1) * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+  if (each && (r = pem_decode_file_bad(e, P, n_files, file_bad))) return r;
   return pem_decode_file_first(e, P, n_files, file_first);
 }
 
@@ -175,11 +244,20 @@ int pem_decode_call(ctmr_engine* e, bool host, const void* text, const uint64_t*
 
 int ctmr_pem_decode_device(ctmr_engine* e, const void* d_text, const uint64_t* file_bounds, uint64_t n_files, void* d_payload, size_t payload_cap,
                            uint64_t* d_offsets, uint64_t certs_cap, uint64_t* file_first, ctmr_pem_decode_info* info) {
-  return pem_decode_call(e, false, d_text, file_bounds, n_files, d_payload, payload_cap, d_offsets, certs_cap, file_first, info);
+  return pem_decode_call(e, false, d_text, file_bounds, n_files, d_payload, payload_cap, d_offsets, certs_cap, file_first, nullptr, false, info);
 }
 
 int ctmr_pem_decode(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files, uint8_t* payload, size_t payload_cap,
                     uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first, ctmr_pem_decode_info* info) {
-  return pem_decode_call(e, true, text, file_bounds, n_files, payload, payload_cap, offsets, certs_cap, file_first, info);
+  return pem_decode_call(e, true, text, file_bounds, n_files, payload, payload_cap, offsets, certs_cap, file_first, nullptr, false, info);
 }
 
+int ctmr_pem_decode_each_device(ctmr_engine* e, const void* d_text, const uint64_t* file_bounds, uint64_t n_files, void* d_payload, size_t payload_cap,
+                                uint64_t* d_offsets, uint64_t certs_cap, uint64_t* file_first, uint64_t* file_bad, ctmr_pem_decode_info* info) {
+  return pem_decode_call(e, false, d_text, file_bounds, n_files, d_payload, payload_cap, d_offsets, certs_cap, file_first, file_bad, true, info);
+}
+
+int ctmr_pem_decode_each(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files, uint8_t* payload, size_t payload_cap,
+                         uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first, uint64_t* file_bad, ctmr_pem_decode_info* info) {
+  return pem_decode_call(e, true, text, file_bounds, n_files, payload, payload_cap, offsets, certs_cap, file_first, file_bad, true, info);
+}

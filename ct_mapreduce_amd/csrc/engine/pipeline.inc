@@ -1,7 +1,8 @@
-// engine/pipeline.inc — asynchronous host ingestion: ctmr_submit_batch / ctmr_wait / ctmr_flush, and the raw-entry and
-// get-entries JSON forms of both (ctmr_submit_entries*, ctmr_wait_entries*).
+// engine/pipeline.inc — asynchronous host ingestion: ctmr_submit_batch / ctmr_wait / ctmr_flush, the raw-entry and
+// get-entries JSON forms of both (ctmr_submit_entries*, ctmr_wait_entries*) and the PEM form (ctmr_submit_pem, ctmr_wait_pem).
 // Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/map.inc; the
-// worker's step for the JSON form is engine/pipeline_json.inc, behind engine/entries_json.inc.
+// worker's step for the JSON form is engine/pipeline_json.inc, behind engine/entries_json.inc, and the one for the PEM
+// form engine/pipeline_pem.inc, behind engine/pem_decode.inc.
 //
 // The reference's downloader hands insertCTWorker one get-entries response at a time — at most 1 001 entries
 // (cmd/ct-fetch/ct-fetch.go:417-424) — through a 16 384-entry channel (:132), and the workers drain it concurrently
@@ -27,15 +28,20 @@ constexpr uint32_t PIPE_SLOTS = 4;
 constexpr uint32_t PIPE_MAX_STREAMS = 4;  // copy streams: consecutive submits' DMA transfers overlap their set-up
 constexpr uint64_t PIPE_CLOSE_ENTRIES = 65536, PIPE_CLOSE_BYTES = 96ull << 20;
 constexpr uint64_t PIPE_CLOSE_BODIES = 4096;  // JSON super-batches: the entries are not known before the worker has run
+constexpr uint64_t PIPE_CLOSE_FILES = 65536;  // PEM super-batches: nor are the certificates; the reference writes one a file
 
 // What a super-batch holds: the packed form (ctmr_submit_batch), blob + bounds u64[2n+1] (ctmr_submit_entries), or
-// get-entries bodies as text (ctmr_submit_entries_json).  One form per super-batch.
-enum PipeForm : uint8_t { PF_PACKED = 0, PF_RAW, PF_JSON };
+// get-entries bodies as text (ctmr_submit_entries_json), or PEM files as text (ctmr_submit_pem).  One form per super-batch.
+enum PipeForm : uint8_t { PF_PACKED = 0, PF_RAW, PF_JSON, PF_PEM };
+// the two text forms: bodies (JSON: responses, PEM: files) judged alone by the worker, the tickets sized by what it finds
+bool pipe_is_text(PipeForm f) { return f == PF_JSON || f == PF_PEM; }
+// the forms whose entries are raw get-entries pairs: timestamps, entry types and Chain[0] lengths come back with them
+bool pipe_is_raw(PipeForm f) { return f == PF_RAW || f == PF_JSON; }
 
 struct PipeTicket {
-  uint64_t first, n;  // its entries in the super-batch (JSON: known when the worker is done)
+  uint64_t first, n;  // its entries in the super-batch (JSON, PEM: known when the worker is done)
   bool consumed;
-  uint64_t body0 = 0, nbody = 0;  // JSON: its bodies in the super-batch,
+  uint64_t body0 = 0, nbody = 0;  // JSON, PEM: its bodies (responses, files) in the super-batch,
   uint64_t text_at = 0;           //   where its text starts in the slot's,
   uint64_t text_base = 0;         //   and resp_bounds[0] of the submit: offsets go back to the caller's text pointer
 };
@@ -63,11 +69,13 @@ struct PipeSlot {
   uint64_t n = 0, bytes = 0;
   bool any_type = false;
   PipeForm form = PF_PACKED;
-  // JSON super-batches: d_payload holds the text.  The bodies' bounds in it live here, not in the meta buffers, which
+  // JSON and PEM super-batches: d_payload holds the text.  The bodies' bounds in it live here, not in the meta buffers, which
   // pipe_slot_reserve frees when the worker sizes the slot by the entries found.
   std::vector<uint64_t> body_rb;                        // bodies + 1
   std::vector<uint64_t> body_first, body_bad;           // the worker's: each body's first entry (bodies + 1), its verdict
-  uint8_t* d_blob = nullptr; size_t blob_cap = 0;       // the decoded entries; h_meta: their bounds u64[2n+1]
+  uint8_t* d_blob = nullptr; size_t blob_cap = 0;       // the decoded entries; h_meta: their bounds u64[2n+1] (PEM: offsets u64[n+1])
+  std::vector<uint32_t> file_iss;                       // PEM: the issuer index of every file
+  std::vector<uint64_t> cert_lay;                       // PEM, the worker's: the layout of every certificate (a ticket's regular / irregular)
   ctmr_decode_stats dstats{};
   std::vector<PipeTicket> tickets;
   hipEvent_t ev_h2d[PIPE_MAX_STREAMS] = {};
@@ -145,7 +153,7 @@ int pipe_close_locked(ctmr_engine* e, ctmr_pipeline* p) {
   if (p->open < 0) return CTMR_OK;
   PipeSlot& s = p->slots[p->open];
   HIPCHK(e, hipSetDevice(e->device));
-  if (s.form == PF_JSON) {
+  if (pipe_is_text(s.form)) {
     // (the bodies' bounds go to the device with the worker's call)
   } else if (s.form == PF_RAW) {
     slot_h_offsets(s)[2 * s.n] = s.bytes;
@@ -165,6 +173,23 @@ int pipe_close_locked(ctmr_engine* e, ctmr_pipeline* p) {
 }
 
 int pipe_run_json(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view);  // engine/pipeline_json.inc
+int pipe_run_pem(ctmr_engine* e, PipeSlot& s);                          // engine/pipeline_pem.inc
+
+// The slot's blob holds `bytes` decoded bytes and the padding behind them (the text forms, sized by the worker).
+int pipe_blob_reserve(ctmr_engine* e, PipeSlot& s, uint64_t bytes) {
+  if (bytes + CTMR_PAYLOAD_PAD + 16 <= s.blob_cap) return CTMR_OK;
+  (void)hipFree(s.d_blob);
+  s.d_blob = nullptr;
+  s.blob_cap = 0;
+  const size_t cap = (size_t)pow2_at_least(bytes + CTMR_PAYLOAD_PAD + 16);
+  if (hipMalloc(&s.d_blob, cap) != hipSuccess) {
+    (void)hipGetLastError();
+    s.d_blob = nullptr;
+    return fail(e, CTMR_E_NOMEM, "no device memory for %llu decoded bytes", (unsigned long long)bytes);
+  }
+  s.blob_cap = cap;
+  return CTMR_OK;
+}
 
 void pipe_worker(ctmr_engine* e) {
   ctmr_pipeline* p = e->pipe.load(std::memory_order_acquire);
@@ -189,6 +214,8 @@ void pipe_worker(ctmr_engine* e) {
       ctmr_entry_view view{};
       if (rc == CTMR_OK && s.form == PF_JSON)  // every body judged, the good ones decoded into s.d_blob, then as a raw super-batch
         rc = pipe_run_json(e, s, &view);
+      else if (rc == CTMR_OK && s.form == PF_PEM)  // every file judged, the good ones decoded into s.d_blob, then as a packed super-batch
+        rc = pipe_run_pem(e, s);
       else if (rc == CTMR_OK && s.form == PF_RAW)  // decode + Chain[0] match (issuers registered on the way) + map/reduce, as ctmr_map_entries_device
         rc = s.n ? map_entries_locked(e, s.d_payload, (const uint64_t*)s.d_meta, s.n, s.d_records, s.d_new, s.d_ts, &s.dstats,
                                       &s.stats, &view)
@@ -199,7 +226,7 @@ void pipe_worker(ctmr_engine* e) {
                                &s.stats, nullptr, 0, s.bytes);
       if (rc == CTMR_OK) {
         hipError_t h = hipMemcpyAsync(s.h_records, s.d_records, s.n * sizeof(ctmr_record), hipMemcpyDeviceToHost, e->stream);
-        if (h == hipSuccess && s.form != PF_PACKED && s.n) {
+        if (h == hipSuccess && pipe_is_raw(s.form) && s.n) {
           h = hipMemcpyAsync(s.h_ts, s.d_ts, s.n * 8, hipMemcpyDeviceToHost, e->stream);
           if (h == hipSuccess) h = hipMemcpyAsync(s.h_etype, view.entry_type, s.n, hipMemcpyDeviceToHost, e->stream);
           if (h == hipSuccess) h = hipMemcpyAsync(s.h_c0len, view.chain0_len, s.n * 4, hipMemcpyDeviceToHost, e->stream);
@@ -216,7 +243,7 @@ void pipe_worker(ctmr_engine* e) {
     }
     {
       std::lock_guard<std::mutex> lk(p->mu);
-      if (s.form == PF_JSON && rc == CTMR_OK)  // now the tickets' entries are known
+      if (pipe_is_text(s.form) && rc == CTMR_OK)  // now the tickets' entries are known
         for (auto& t : s.tickets) {
           t.first = s.body_first[t.body0];
           t.n = s.body_first[t.body0 + t.nbody] - t.first;
@@ -323,6 +350,7 @@ int pipe_open_for(ctmr_engine* e, ctmr_pipeline* p, std::unique_lock<std::mutex>
   s.body_rb.assign(1, 0);
   s.body_first.clear();
   s.body_bad.clear();
+  s.file_iss.clear();
   s.rc = CTMR_OK;
   s.err.clear();
   memset(&s.stats, 0, sizeof s.stats);
@@ -342,7 +370,8 @@ int pipe_append(ctmr_engine* e, ctmr_pipeline* p, const uint8_t* src, uint64_t b
   *ticket = (s.seq << 20) | (uint64_t)(s.tickets.size() - 1);  // ≤ 2^20 tickets per super-batch (it closes at 65 536 entries; empty batches: see below)
   s.n += n;
   s.bytes += bytes;
-  if (s.n >= PIPE_CLOSE_ENTRIES || s.bytes >= PIPE_CLOSE_BYTES || s.tickets.size() >= (1u << 20) - 1 || s.body_rb.size() > PIPE_CLOSE_BODIES)
+  if (s.n >= PIPE_CLOSE_ENTRIES || s.bytes >= PIPE_CLOSE_BYTES || s.tickets.size() >= (1u << 20) - 1 ||
+      s.body_rb.size() > (s.form == PF_PEM ? PIPE_CLOSE_FILES : PIPE_CLOSE_BODIES))
     return pipe_close_locked(e, p);
   return CTMR_OK;
 }
@@ -426,6 +455,45 @@ int ctmr_submit_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t
   return r;
 }
 
+int ctmr_submit_pem(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files, const uint32_t* issuer_idx,
+                    ctmr_ticket* ticket) {
+  if (!e || !ticket || (n_files && (!file_bounds || !issuer_idx))) return CTMR_E_INVAL;
+  for (uint64_t i = 0; i < n_files; i++)
+    if (file_bounds[i + 1] < file_bounds[i]) return fail(e, CTMR_E_INVAL, "file_bounds not monotone at %llu", (unsigned long long)i);
+  const uint64_t base = n_files ? file_bounds[0] : 0, bytes = n_files ? file_bounds[n_files] - base : 0;
+  if (bytes && !text) return fail(e, CTMR_E_INVAL, "null text");
+  if (n_files >= (1ull << 30)) return fail(e, CTMR_E_INVAL, "batch too large");
+  ctmr_pipeline* p;
+  int r;
+  if ((r = pipe_get(e, &p))) return r;
+  std::unique_lock<std::mutex> lk(p->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((r = pipe_open_for(e, p, lk, PF_PEM, 0, bytes))) return r;
+  PipeSlot& s = p->slots[p->open];
+  const uint64_t body0 = s.body_rb.size() - 1, at = s.bytes;
+  try {
+    for (uint64_t i = 1; i <= n_files; i++) s.body_rb.push_back(at + (file_bounds[i] - base));
+    s.file_iss.insert(s.file_iss.end(), issuer_idx, issuer_idx + n_files);
+  } catch (const std::bad_alloc&) {
+    s.body_rb.resize(body0 + 1);
+    s.file_iss.resize(body0);
+    return fail(e, CTMR_E_NOMEM, "no host memory for the bounds of %llu files", (unsigned long long)n_files);
+  }
+  const size_t had = s.tickets.size();
+  r = pipe_append(e, p, bytes ? text + base : nullptr, bytes, 0, ticket);
+  if (s.tickets.size() == had) {  // the copy failed: no ticket, no files
+    s.body_rb.resize(body0 + 1);
+    s.file_iss.resize(body0);
+    return r;
+  }
+  PipeTicket& t = s.tickets[had];  // (p->mu is held: the worker has not seen the slot, closed or not)
+  t.body0 = body0;
+  t.nbody = n_files;
+  t.text_at = at;
+  t.text_base = base;
+  return r;
+}
+
 int ctmr_flush(ctmr_engine* e) {
   if (!e) return CTMR_E_INVAL;
   ctmr_pipeline* p;
@@ -435,11 +503,18 @@ int ctmr_flush(ctmr_engine* e) {
   return pipe_close_locked(e, p);
 }
 
-// json: the call is ctmr_wait_entries_json, which alone collects a ticket of the JSON form (the others have no capacity
-// argument) and collects no other; entries_cap, resp_first, resp_bad and info are its arguments.
+// What ctmr_wait_entries_json and ctmr_wait_pem have beyond the others: each alone collects a ticket of its text form (the
+// others have no capacity argument) and collects no other.  first / bad: resp_first / resp_bad, or file_first / file_bad.
+struct PipeTextWait {
+  PipeForm form;
+  uint64_t cap;
+  uint64_t *first, *bad;
+  ctmr_entries_json_info* jinfo;
+  ctmr_pem_decode_info* pinfo;
+};
+
 static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
-                     ctmr_decode_stats* dstats, ctmr_batch_stats* stats, bool json = false, uint64_t entries_cap = 0,
-                     uint64_t* resp_first = nullptr, uint64_t* resp_bad = nullptr, ctmr_entries_json_info* info = nullptr) {
+                     ctmr_decode_stats* dstats, ctmr_batch_stats* stats, const PipeTextWait* tw = nullptr) {
   if (!e) return CTMR_E_INVAL;
   ctmr_pipeline* p;
   int r;
@@ -451,8 +526,14 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
     if (c.state != PS_FREE && c.seq == seq) s = &c;
   if (!s || tix >= s->tickets.size() || s->tickets[tix].consumed)
     return fail(e, CTMR_E_NOTFOUND, "unknown or already collected ticket");
-  if ((s->form == PF_JSON) != json)  // (the ticket stays collectable)
-    return fail(e, CTMR_E_INVAL, json ? "not a ticket of ctmr_submit_entries_json" : "a ticket of ctmr_submit_entries_json: ctmr_wait_entries_json collects it");
+  if (pipe_is_text(s->form) ? (!tw || tw->form != s->form) : tw != nullptr)  // (the ticket stays collectable)
+    return fail(e, CTMR_E_INVAL, s->form == PF_JSON  ? "a ticket of ctmr_submit_entries_json: ctmr_wait_entries_json collects it"
+                                 : s->form == PF_PEM ? "a ticket of ctmr_submit_pem: ctmr_wait_pem collects it"
+                                 : tw->form == PF_PEM ? "not a ticket of ctmr_submit_pem"
+                                                      : "not a ticket of ctmr_submit_entries_json");
+  const bool json = tw && tw->form == PF_JSON, pem = tw && tw->form == PF_PEM;
+  ctmr_entries_json_info* const info = tw ? tw->jinfo : nullptr;
+  ctmr_pem_decode_info* const pinfo = tw ? tw->pinfo : nullptr;
   if (s->state == PS_OPEN && (r = pipe_close_locked(e, p))) return r;  // nobody else will launch it
   p->cv.wait(lk, [&] { return s->state == PS_DONE; });
   PipeTicket& t = s->tickets[tix];
@@ -462,11 +543,16 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
     info->responses = t.nbody;
     info->bad_response = info->bad_offset = ~0ull;
   }
-  if (rc == CTMR_OK && json) {
+  if (rc != CTMR_OK && pem && pinfo) {  // the super-batch failed: no file was judged
+    memset(pinfo, 0, sizeof *pinfo);
+    pinfo->files = t.nbody;
+    pinfo->bad_file = pinfo->bad_offset = ~0ull;
+  }
+  if (rc == CTMR_OK && tw) {
     const uint64_t* rb = s->body_rb.data() + t.body0;
     const uint64_t* bad = s->body_bad.data() + t.body0;
     const uint64_t back = t.text_base - t.text_at;  // an offset in the slot's text → one from the submit's text pointer
-    if (info) {
+    if (json && info) {
       memset(info, 0, sizeof *info);
       info->responses = t.nbody;
       info->entries = t.n;
@@ -479,12 +565,27 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
           info->bad_offset = bad[i] + back;
         }
     }
-    if (entries_cap < t.n)
-      return fail(e, CTMR_E_RANGE, "the ticket holds %llu entries", (unsigned long long)t.n);
-    if (resp_first)
-      for (uint64_t i = 0; i <= t.nbody; i++) resp_first[i] = s->body_first[t.body0 + i] - t.first;
-    if (resp_bad)
-      for (uint64_t i = 0; i < t.nbody; i++) resp_bad[i] = bad[i] == ~0ull ? ~0ull : bad[i] + back;
+    if (pem && pinfo) {
+      memset(pinfo, 0, sizeof *pinfo);
+      pinfo->files = t.nbody;
+      pinfo->certificates = t.n;
+      pinfo->text_bytes = rb[t.nbody] - rb[0];
+      pinfo->payload_bytes = slot_h_offsets(*s)[t.first + t.n] - slot_h_offsets(*s)[t.first];
+      for (uint64_t i = 0; i < t.n; i++) pinfo->irregular += (s->cert_lay[t.first + i] & 3ull) == PD_IRREGULAR;
+      pinfo->regular = t.n - pinfo->irregular;
+      pinfo->bad_file = pinfo->bad_offset = ~0ull;
+      for (uint64_t i = t.nbody; i-- > 0;)
+        if (bad[i] != ~0ull) {
+          pinfo->bad_file = i;
+          pinfo->bad_offset = bad[i] + back;
+        }
+    }
+    if (tw->cap < t.n)
+      return fail(e, CTMR_E_RANGE, "the ticket holds %llu %s", (unsigned long long)t.n, pem ? "certificates" : "entries");
+    if (tw->first)
+      for (uint64_t i = 0; i <= t.nbody; i++) tw->first[i] = s->body_first[t.body0 + i] - t.first;
+    if (tw->bad)
+      for (uint64_t i = 0; i < t.nbody; i++) tw->bad[i] = bad[i] == ~0ull ? ~0ull : bad[i] + back;
   }
   if (rc == CTMR_OK) {
     if (records && t.n) memcpy(records, s->h_records + t.first, t.n * sizeof(ctmr_record));
@@ -507,7 +608,7 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
       stats->n_new = (uint64_t)(hi - lo);
       stats->n_dup = stats->by_status[CTMR_ST_PASS] - stats->n_new;
       stats->n_host_set = host_set;
-      stats->payload_bytes = s->form != PF_PACKED ? slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first]
+      stats->payload_bytes = pipe_is_raw(s->form) ? slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first]
                                     : slot_h_offsets(*s)[t.first + t.n] - slot_h_offsets(*s)[t.first];
       stats->map_launches = 1;
       stats->ms_map = s->stats.ms_map; stats->ms_insert = s->stats.ms_insert; stats->ms_resolve = s->stats.ms_resolve;
@@ -515,12 +616,12 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
       (void)new_flag;
     }
     if (timestamp) {
-      if (s->form != PF_PACKED) memcpy(timestamp, s->h_ts + t.first, t.n * 8);
+      if (pipe_is_raw(s->form)) memcpy(timestamp, s->h_ts + t.first, t.n * 8);
       else memset(timestamp, 0, t.n * 8);  // a packed batch carries no timestamps
     }
     if (dstats) {
       memset(dstats, 0, sizeof *dstats);
-      if (s->form != PF_PACKED) {
+      if (pipe_is_raw(s->form)) {
         dstats->n = t.n;
         for (uint64_t i = 0; i < t.n; i++) {
           const uint8_t et = s->h_etype[t.first + i];
@@ -559,5 +660,12 @@ int ctmr_wait_entries(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, 
 int ctmr_wait_entries_json(ctmr_engine* e, ctmr_ticket ticket, uint64_t entries_cap, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
                            uint64_t* resp_first, uint64_t* resp_bad, ctmr_entries_json_info* info, ctmr_decode_stats* dstats,
                            ctmr_batch_stats* stats) {
-  return pipe_wait(e, ticket, records, new_idx, timestamp, dstats, stats, true, entries_cap, resp_first, resp_bad, info);
+  const PipeTextWait tw{PF_JSON, entries_cap, resp_first, resp_bad, info, nullptr};
+  return pipe_wait(e, ticket, records, new_idx, timestamp, dstats, stats, &tw);
+}
+
+int ctmr_wait_pem(ctmr_engine* e, ctmr_ticket ticket, uint64_t certs_cap, ctmr_record* records, uint64_t* new_idx, uint64_t* file_first,
+                  uint64_t* file_bad, ctmr_pem_decode_info* info, ctmr_batch_stats* stats) {
+  const PipeTextWait tw{PF_PEM, certs_cap, file_first, file_bad, nullptr, info};
+  return pipe_wait(e, ticket, records, new_idx, nullptr, nullptr, stats, &tw);
 }

@@ -21,18 +21,7 @@ int pipe_run_json(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view) {
     return fail(e, CTMR_E_NOMEM, "no host memory for the verdicts of %llu bodies", (unsigned long long)R);
   }
   if ((r = pipe_slot_reserve(e, s, n, 0))) return r;
-  if (bb + CTMR_PAYLOAD_PAD + 16 > s.blob_cap) {
-    (void)hipFree(s.d_blob);
-    s.d_blob = nullptr;
-    s.blob_cap = 0;
-    const size_t cap = (size_t)pow2_at_least(bb + CTMR_PAYLOAD_PAD + 16);
-    if (hipMalloc(&s.d_blob, cap) != hipSuccess) {
-      (void)hipGetLastError();
-      s.d_blob = nullptr;
-      return fail(e, CTMR_E_NOMEM, "no device memory for %llu decoded bytes", (unsigned long long)bb);
-    }
-    s.blob_cap = cap;
-  }
+  if ((r = pipe_blob_reserve(e, s, bb))) return r;
   if ((r = entries_json_decode(e, J, s.d_blob))) return r;
   if ((r = entries_json_resp_first(e, J, R, s.body_first.data()))) return r;
   HIPCHK(e, hipMemcpy(s.h_meta, J.bounds.p, (2 * n + 1) * 8, hipMemcpyDeviceToHost));  // the tickets' blob bytes

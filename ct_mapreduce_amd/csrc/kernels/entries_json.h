@@ -14,7 +14,7 @@
 //             '=' at the end) and writes the decoded lengths, leaf first whatever the order in the text.
 //   decode    the hot path: one tile of TX_DTILE characters of one string per block → TX_DOUT bytes (tx_decode_tile).
 // Every body judged on its own (ctmr_entries_json_each*): mark, resp and check take EACH = true and report
-// to a table of one word per response (ej_verdict) instead of the call's one pair; behind check, k_ej_drop zeroes the
+// to a table of one word per response (ej_verdict) instead of the call's one pair; behind check, k_ej_drop (kernels/text_scan.h) zeroes the
 // entry count of every response with a verdict and k_ej_gather moves the good entries' lengths and sources to their
 // places under the new numbering.  EACH = false compiles to what the strict call has always run.
 // The text, its segments (here: the responses), the chunks and tiles it is read in, the wave's scan and report and the
@@ -260,16 +260,6 @@ __global__ void __launch_bounds__(RP_BLOCK) k_ej_check(TxText T, uint64_t b0, Ej
     }
   }
   ej_verdict<EACH>(err, bad, r, pos);
-}
-
-// each, behind check: the entry count of a response with a verdict, from whichever pass, goes to zero.  cnt[r] = the
-// entries of response r when bad_at[r] says none, else 0; cnt[R] = 0 (the scan's total).  efirst0: the scan of k_ej_resp's
-// counts, which k_ej_check numbered its entries by.
-__global__ void __launch_bounds__(RP_BLOCK) k_ej_drop(uint64_t b0, uint64_t R, const unsigned long long* bad_at, const unsigned long long* efirst0,
-                                                      unsigned long long* cnt) {
-  const uint64_t r = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
-  if (r > R) return;
-  cnt[r] = (r < R && bad_at[r] == ~0ull) ? efirst0[r + 1] - efirst0[r] : 0ull;
 }
 
 // each, behind the scan of k_ej_drop's counts (efirst): the lengths and sources k_ej_check wrote, compacted over the good

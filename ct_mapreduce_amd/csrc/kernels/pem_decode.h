@@ -17,6 +17,10 @@
 //   squeeze   irregular blocks only: their characters copied contiguously into a working buffer.
 //   decode    the hot path: one tile of TX_DTILE characters of one certificate per block → TX_DOUT bytes.  A lane finds
 //             its quantum at body + (r / L)(L + e) + r % L, straight in the text, and packs 4 → 3 (tx_decode_tile).
+// Every file judged on its own (ctmr_pem_decode_each*): mark, files and check take EACH = true and report to
+// a table of one word per file (pd_verdict) instead of the call's one pair; behind check, k_ej_drop zeroes the certificate
+// count of every file with a verdict and k_pd_gather moves the good certificates' five tables to their places under the
+// new numbering.  EACH = false compiles to what the strict call has always run.
 // The text, its segments (here: the files), the chunks and tiles it is read in, the wave's scan and report and the decode
 // of a tile are those of kernels/text_scan.h; what is here is PEM.  gfx950 (CDNA4, wave64) only; part of kernels.h.
 #pragma once
@@ -41,6 +45,23 @@ __device__ __forceinline__ bool pd_spells(const uint8_t* s, uint64_t at, const c
 #pragma unroll
   for (uint32_t k = 0; k + 1u < N; k++) diff |= (uint32_t)s[at + k] ^ (uint32_t)(uint8_t)lit[k];
   return diff == 0u;
+}
+
+// EACH = false: err is the call's pair (lowest file, lowest offset) and the wave reduces first (tx_report).
+// EACH = true (ctmr_pem_decode_each*): err is a table of one word per file, ~0 = inside the grammar so far,
+// and the word behind them, err[S], the lowest file with a verdict — the host reads that one word and fetches the table
+// only when a file is bad.  A lane with a finding does its own atomicMin: a wave holds lanes of any number of files, so
+// nothing is reduced over it; findings are rare.  f < S wherever bad is set.
+template <bool EACH>
+__device__ __forceinline__ void pd_verdict(unsigned long long* err, uint64_t S, bool bad, uint64_t f, uint64_t off) {
+  if (EACH) {
+    if (bad) {
+      atomicMin(err + f, (unsigned long long)off);
+      atomicMin(err + S, (unsigned long long)f);
+    }
+  } else {
+    tx_report(err, bad, f, off);
+  }
 }
 
 // the offset from s of the first byte of mark block blk (below lo, even negative, for block 0)
@@ -82,7 +103,10 @@ __device__ __forceinline__ uint32_t pd_before(const TxText& T, const uint8_t* su
 // summary, and what a block can know alone is reported.  WRITE = true, behind the exclusive scans: tok[] = position << 1
 // | kind of every armor line, ctok[] / etok[] = the characters / '=' of the text in front of it; what needs the
 // summaries is reported.
-template <bool WRITE>
+// EACH (pd_verdict): a lane reports its first finding in every file its 16 bytes touch — a file can be one byte long, so
+// up to 16 of them — and a character at a file's start counts as having nothing in front of it whatever the file before
+// ends with.
+template <bool WRITE, bool EACH = false>
 __global__ void __launch_bounds__(TX_BLOCK) k_pd_mark(TxText T, uint64_t b0, unsigned long long* cnt_t, unsigned long long* cnt_c,
                                                       unsigned long long* cnt_e, uint8_t* sum, unsigned long long* tok,
                                                       unsigned long long* ctok, unsigned long long* etok, unsigned long long* err) {
@@ -113,6 +137,7 @@ __global__ void __launch_bounds__(TX_BLOCK) k_pd_mark(TxText T, uint64_t b0, uns
   // A run's first dash at a line start is a token and spells a literal; elsewhere it closes one.
   const uint32_t prev_alpha = __shfl_up(alpha >> 15, 1);  // the byte in front of the lane's first (lane 0: unknown)
   uint32_t tokm = 0u, kinds = 0u;
+  uint32_t viol = other;  // EACH: every finding of the lane
   bool bad = other != 0u;
   uint64_t bad_at = bad ? (uint64_t)(p0 + (int64_t)(__ffs(other) - 1)) : 0ull;
   {
@@ -139,16 +164,31 @@ __global__ void __launch_bounds__(TX_BLOCK) k_pd_mark(TxText T, uint64_t b0, uns
       } else {
         ok = (p - fs >= 22u && pd_spells(T.s, p - 22u, "-----BEGIN CERTIFICATE")) || (p - fs >= 20u && pd_spells(T.s, p - 20u, "-----END CERTIFICATE"));
       }
-      if (!ok && !bad) {
+      if (EACH) {
+        if (!ok) viol |= 1u << q;
+      } else if (!ok && !bad) {
         bad = true;
         bad_at = p;
       }
     }
   }
   if (!WRITE) {
-    uint64_t vr = 0;
-    if (bad) vr = uniform ? r_lo : tx_segment_of(T.sb, T.S, bad_at);
-    tx_report(err, bad, vr, bad_at);
+    if (EACH) {
+      uint64_t last = ~0ull;
+#pragma unroll 1
+      while (viol) {  // ascending: the first finding of every file
+        const uint64_t p = (uint64_t)(p0 + (int64_t)(__ffs(viol) - 1));
+        viol &= viol - 1u;
+        const uint64_t f = uniform ? r_lo : tx_segment_of(T.sb, T.S, p);
+        if (f != last) pd_verdict<true>(err, T.S, true, f, p);
+        last = f;
+        if (uniform) break;
+      }
+    } else {
+      uint64_t vr = 0;
+      if (bad) vr = uniform ? r_lo : tx_segment_of(T.sb, T.S, bad_at);
+      tx_report(err, bad, vr, bad_at);
+    }
   }
   // counts: tokens and characters in one scan (each at most TX_TILE), the '=' in another
   uint32_t total, total_e;
@@ -178,9 +218,19 @@ __global__ void __launch_bounds__(TX_BLOCK) k_pd_mark(TxText T, uint64_t b0, uns
   }
   // a character with no alphabet character right in front of it: what precedes it, ws skipped, decides
   {
-    uint32_t m = chars & ~((alpha << 1) | ((lane != 0u && prev_alpha) ? 1u : 0u));
+    uint32_t cont = (alpha << 1) | ((lane != 0u && prev_alpha) ? 1u : 0u);
+    if (EACH && !uniform) {  // the files that start in this block (a wave-uniform walk): their first bytes continue nothing
+      const int64_t blk_end = pd_block_pos(T, blk + 1);
+#pragma unroll 1
+      for (uint64_t r = r_lo + 1; r < T.S; r++) {
+        const int64_t d = (int64_t)T.sb[r] - p0;
+        if ((int64_t)T.sb[r] >= blk_end) break;
+        if (d >= 0 && d < (int64_t)TX_PER) cont &= ~(1u << (uint32_t)d);
+      }
+    }
+    uint32_t m = chars & ~cont;
     bool bad2 = false;
-    uint64_t at2 = 0, f2 = 0;
+    uint64_t at2 = 0, f2 = 0, last = ~0ull;
     while (m) {
       const uint32_t q = (uint32_t)__ffs(m) - 1u;
       m &= m - 1u;
@@ -196,13 +246,18 @@ __global__ void __launch_bounds__(TX_BLOCK) k_pd_mark(TxText T, uint64_t b0, uns
         if (T.s[p - 1] == 0x2du) ok = !is_eq && p - fs >= 5u && (p - fs == 5u || T.s[p - 6] == 0x0au);  // the letter behind a line's first dashes
         else ok = seen_lf;
       } else ok = true;
-      if (!ok && !bad2) {
+      if (EACH) {
+        if (!ok && f != last) {
+          pd_verdict<true>(err, T.S, true, f, p);
+          last = f;
+        }
+      } else if (!ok && !bad2) {
         bad2 = true;
         at2 = p;
         f2 = f;
       }
     }
-    tx_report(err, bad2, f2, at2);
+    if (!EACH) tx_report(err, bad2, f2, at2);
   }
   unsigned long long at = cnt_t[blk] + (packed & 0xffffu);
   const unsigned long long c_lane = cnt_c[blk] + (packed >> 16), e_lane = cnt_e[blk] + eq_before;
@@ -233,6 +288,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_pd_fstart(TxText T, uint64_t b0, c
 
 // files: tfirst[r] = the tokens before sb[r] (r <= R); ccnt[r] = the certificates of file r, half its tokens — an odd
 // count is reported; ccnt[R] = 0 (the scan's total)
+template <bool EACH = false>
 __global__ void __launch_bounds__(RP_BLOCK) k_pd_files(TxText T, uint64_t b0, const unsigned long long* tok, uint64_t ntok,
                                                        unsigned long long* tfirst, unsigned long long* ccnt, unsigned long long* err) {
   const uint64_t r = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
@@ -250,7 +306,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_pd_files(TxText T, uint64_t b0, co
     }
     ccnt[r] = n;
   }
-  tx_report(err, bad, r, off);
+  pd_verdict<EACH>(err, T.S, bad, r, off);
 }
 
 // the tables the check reads and writes
@@ -271,8 +327,12 @@ struct PdCheck {
 
 // check: one lane per token.  f_limit: the lowest file the passes before have reported, or none (~0).  The check relies on
 // armor lines that are spelled right and come in pairs, so it looks at the files below that one only: a violation of its
-// own in one of them is the lower one.
-__global__ void __launch_bounds__(RP_BLOCK) k_pd_check(TxText T, uint64_t b0, PdCheck C, uint64_t f_limit, unsigned long long* err) {
+// own in one of them is the lower one.  irr: the irregular blocks of the files looked at are added to it.
+// EACH: the files looked at are those whose word in `gate` says none so far.  gate is a copy of the table made before the
+// launch, not the table the check's own lanes write: which lanes run, and what they count, does not depend on timing.
+template <bool EACH = false>
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_check(TxText T, uint64_t b0, PdCheck C, uint64_t f_limit, const unsigned long long* gate,
+                                                       unsigned long long* irr, unsigned long long* err) {
   const uint64_t t = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
   bool bad = false, irregular = false, is_end = false;
   uint64_t f = 0, pos = 0, i = 0, cc = 0, ne = 0, p0 = 0, b = 0;
@@ -284,7 +344,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_pd_check(TxText T, uint64_t b0, Pd
     const uint32_t kind = (uint32_t)(tk & 1ull);
     f = tx_segment_of(T.sb, T.S, pos);
     const uint64_t j = t - C.tfirst[f], nt = C.tfirst[f + 1] - C.tfirst[f];
-    if (f < f_limit && !(nt & 1ull)) {  // (else the file has been reported, or lies behind one that has)
+    if ((EACH ? gate[f] == ~0ull : f < f_limit) && !(nt & 1ull)) {  // (else the file has been reported, or lies behind one that has)
       bad = kind != (uint32_t)(j & 1ull);
       if (!(j & 1ull)) {
         bad = bad || C.ctok[t] != (j == 0 ? C.cfile[f] : C.ctok[t - 1] + PD_END_CHARS);
@@ -354,9 +414,51 @@ __global__ void __launch_bounds__(RP_BLOCK) k_pd_check(TxText T, uint64_t b0, Pd
     const uint64_t s0 = (uint64_t)(uintptr_t)T.s;
     C.sqtiles[i] = irregular ? (s0 + pos - 1 - T.a0) / TX_TILE - (s0 + p0 + PD_BEGIN_LEN - T.a0) / TX_TILE + 1 : 0ull;
   }
-  const unsigned long long irr = __ballot(irregular);
-  if ((threadIdx.x & 63u) == 0 && irr) atomicAdd(err + 2, (unsigned long long)__popcll(irr));
-  tx_report(err, bad, f, pos);
+  const unsigned long long irr_m = __ballot(irregular);
+  if ((threadIdx.x & 63u) == 0 && irr_m) atomicAdd(irr, (unsigned long long)__popcll(irr_m));
+  pd_verdict<EACH>(err, T.S, bad, f, pos);
+}
+
+// the tables of the gather: what k_pd_check wrote under the old numbering, and where it goes
+struct PdGather {
+  const unsigned long long* bad_at;   // F: the verdicts
+  const unsigned long long* ffirst0;  // F + 1: the scan of k_pd_files' counts, which k_pd_check numbered its certificates by
+  const unsigned long long* ffirst;   // F + 1: the scan of k_ej_drop's counts
+  const unsigned long long *len0, *src0, *lay0, *sqlen0, *sqtiles0;
+  unsigned long long *len, *src, *lay, *sqlen, *sqtiles;
+};
+
+// each, behind the scan of k_ej_drop's counts: the five tables of the check compacted over the good files.  One lane per
+// certificate i0 of the old numbering (n0 = ffirst0[F] > 0); its file is the last f with ffirst0[f] <= i0, which has
+// certificates, so it is that one and no empty neighbour.  src of an irregular block is a token index: tokens keep their
+// numbers.  *irr += the irregular blocks among the good files' certificates: the check has counted those of the files it
+// found bad itself as well.
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_gather(uint64_t b0, uint64_t F, uint64_t n0, PdGather G, unsigned long long* irr) {
+  const uint64_t i0 = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
+  bool irregular = false;
+  if (i0 < n0) {
+    const uint64_t f = tx_segment_of((const uint64_t*)G.ffirst0, F, i0);
+    if (G.bad_at[f] == ~0ull) {
+      const uint64_t i = G.ffirst[f] + (i0 - G.ffirst0[f]);
+      const unsigned long long lay = G.lay0[i0];
+      G.len[i] = G.len0[i0];
+      G.src[i] = G.src0[i0];
+      G.lay[i] = lay;
+      G.sqlen[i] = G.sqlen0[i0];
+      G.sqtiles[i] = G.sqtiles0[i0];
+      irregular = (lay & 3ull) == PD_IRREGULAR;
+    }
+  }
+  const unsigned long long m = __ballot(irregular);
+  if ((threadIdx.x & 63u) == 0 && m) atomicAdd(irr, (unsigned long long)__popcll(m));
+}
+
+// issuer: the issuer index of every certificate from its file's (ctmr_submit_pem): a lane per certificate i < n, its file
+// the last f with ffirst[f] <= i (k_pd_gather's argument)
+__global__ void __launch_bounds__(RP_BLOCK) k_pd_issuer(uint64_t b0, uint64_t F, uint64_t n, const unsigned long long* ffirst,
+                                                        const uint32_t* file_issuer, uint32_t* issuer_idx) {
+  const uint64_t i = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
+  if (i < n) issuer_idx[i] = file_issuer[tx_segment_of((const uint64_t*)ffirst, F, i)];
 }
 
 // squeeze: block = tile t of irregular certificate i = tile_cert[t]: the characters of one mark block between the

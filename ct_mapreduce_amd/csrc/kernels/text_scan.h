@@ -151,6 +151,16 @@ __device__ __forceinline__ void tx_report(unsigned long long* err, bool bad, uin
   }
 }
 
+// each (every segment judged on its own), behind check: the item count of a segment with a verdict, from whichever pass,
+// goes to zero.  cnt[r] = the items of segment r when bad_at[r] says none, else 0; cnt[R] = 0 (the scan's total).  first0:
+// the scan of the counts the check numbered its items by.  Both decoders launch it, as they do the two kernels below.
+__global__ void __launch_bounds__(RP_BLOCK) k_ej_drop(uint64_t b0, uint64_t R, const unsigned long long* bad_at, const unsigned long long* first0,
+                                                      unsigned long long* cnt) {
+  const uint64_t r = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;
+  if (r > R) return;
+  cnt[r] = (r < R && bad_at[r] == ~0ull) ? first0[r + 1] - first0[r] : 0ull;
+}
+
 // tiles[i] = the decode tiles of item i (bounds: the scanned decoded lengths)
 __global__ void __launch_bounds__(RP_BLOCK) k_ej_tiles(uint64_t b0, const unsigned long long* bounds, uint64_t nstr, unsigned long long* tiles) {
   const uint64_t i = (b0 + blockIdx.x) * RP_BLOCK + threadIdx.x;

@@ -115,6 +115,10 @@ class BatchResult:
     records: np.ndarray      # RECORD_DTYPE[n]
     new_idx: np.ndarray      # u64[n_new], ascending
     stats: N.BatchStats
+    file_first: np.ndarray = None   # wait_pem: u64[F+1], each file's first certificate in this ticket
+    bad: list = None                # wait_pem: per file None, or the offset (from the submit's first byte) that puts it
+                                    # outside the grammar; such a file has no certificates
+    info: N.PemDecodeInfo = None    # wait_pem: the ticket's own
 
 
 class Engine:
@@ -135,6 +139,7 @@ class Engine:
         self.device = device
         self.collect_meta = bool(collect_meta)
         self._json_bodies = {}   # ticket of submit_entries_json → its bodies: wait_entries_json sizes resp_first and bad by it
+        self._pem_files = {}     # ticket of submit_pem → its files: wait_pem sizes file_first and bad by it
 
     # ---- lifecycle
     def close(self):
@@ -308,6 +313,48 @@ class Engine:
         self._ck(rc)
         return EntriesResult(records, new_idx[:st.n_new], ts[:n], st, ds, first,
                              [None if int(b) == 2**64 - 1 else int(b) for b in bad[:R]])
+
+    def submit_pem(self, files, issuer_idx) -> int:
+        """PEM certificate files as they lie (a list of bytes; or (text, file_bounds) with text an array or an address,
+        e.g. a pinned buffer of pinned_array kept untouched until the wait) and one issuer table index per FILE, or
+        NO_ISSUER.  Returns the ticket (ctmr_submit_pem)."""
+        from . import pem_text
+        if isinstance(files, tuple):
+            text, fb = files
+            fb = np.ascontiguousarray(fb, dtype=np.uint64)
+            addr = text.ctypes.data if hasattr(text, "ctypes") else text
+        else:
+            text, fb = pem_text.join(files)
+            addr = np.frombuffer(text, np.uint8).ctypes.data if text else None   # pageable: staged before the call returns
+        F = len(fb) - 1
+        iss = np.ascontiguousarray(issuer_idx, dtype=np.uint32)
+        if iss.shape != (F,):
+            raise ValueError("issuer_idx: one per file")
+        t = C.c_uint64(0)
+        self._ck(self._lib.ctmr_submit_pem(self._h, addr, fb.ctypes.data, F, iss.ctypes.data if F else None, C.byref(t)))
+        self._pem_files[t.value] = F
+        return t.value
+
+    def wait_pem(self, ticket: int) -> BatchResult:
+        """The ticket's result (ctmr_wait_pem; the size query is done here): BatchResult with file_first, bad and info.
+        A file outside the grammar has no certificates and its offset in bad; the call does not fail for it."""
+        F = self._pem_files.get(ticket)
+        if F is None:
+            raise CtmrError(N.E_NOTFOUND, "not a ticket of submit_pem, or already collected")
+        info, st = N.PemDecodeInfo(), N.BatchStats()
+        first = np.zeros(F + 1, np.uint64)
+        bad = np.zeros(max(F, 1), np.uint64)
+        # the size query; a ticket without certificates is collected by it, so the verdicts are asked for here too
+        rc = self._lib.ctmr_wait_pem(self._h, ticket, 0, None, None, first.ctypes.data, bad.ctypes.data, C.byref(info), C.byref(st))
+        n = int(info.certificates) if rc == N.E_RANGE else 0
+        records = np.zeros(n, dtype=RECORD_DTYPE)
+        new_idx = np.zeros(max(n, 1), dtype=np.uint64)
+        if rc == N.E_RANGE:
+            rc = self._lib.ctmr_wait_pem(self._h, ticket, n, records.ctypes.data, new_idx.ctypes.data, first.ctypes.data, bad.ctypes.data,
+                                         C.byref(info), C.byref(st))
+        del self._pem_files[ticket]   # collected, or failed with its super-batch: either way it is gone
+        self._ck(rc)
+        return BatchResult(records, new_idx[:st.n_new], st, first, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:F]], info)
 
     def map_batch_device(self, d_payload, d_offsets, d_issuer_idx, d_entry_type, n, d_records=0,
                          d_new_idx=0) -> N.BatchStats:
@@ -521,6 +568,44 @@ class Engine:
             lambda pb, no, nf: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(no, dtype=torch.int64, device=dev),
                                 np.empty(nf, np.uint64)))
         return d_payload, d_offsets, first, info
+
+    def pem_decode_each(self, files):
+        """pem_decode with every file judged on its own (ctmr_pem_decode_each; CPU twin:
+        pem_text.parse_each) → (payload, offsets, file_first, info, bad): nothing is raised for a file outside the
+        grammar — it has no certificates, and bad[f] holds its offset (None for the others)."""
+        from . import pem_text
+        text, fb = pem_text.join(files)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        bad = np.empty(max(len(files), 1), np.uint64)
+        addr = lambda a: a.ctypes.data if a is not None else None
+        (payload, offsets, first), info = self._pd_call(
+            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_each(self._h, buf.ctypes.data, fb.ctypes.data, len(files), addr(p), pc,
+                                                                          addr(o), oc, addr(ff), bad.ctypes.data, C.byref(info)),
+            lambda pb, no, nf: (np.empty(pb, np.uint8), np.empty(no, np.uint64), np.empty(nf, np.uint64)))
+        return payload, offsets, first, info, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:len(files)]]
+
+    def pem_decode_each_device(self, d_text, file_bounds):
+        """pem_decode_device with every file judged on its own → (d_payload, d_offsets, file_first, info, bad); bad as in
+        pem_decode_each, offsets counted as file_bounds counts."""
+        import torch
+        if not hasattr(d_text, "data_ptr"):
+            raise TypeError("d_text: a torch tensor on this engine's device")
+        fb = np.ascontiguousarray(file_bounds, dtype=np.uint64)
+        F = len(fb) - 1
+        if F < 0 or (F and ((fb[1:] < fb[:-1]).any() or int(fb[F]) > d_text.numel())):
+            raise ValueError("file_bounds do not ascend or reach beyond the text")
+        dev = "cuda:%d" % self.device
+        torch.cuda.synchronize(self.device)     # the engine runs on a stream of its own: what was queued to write d_text is done first
+        text = C.c_void_p(d_text.data_ptr()) if F and fb[F] > fb[0] else None
+        bad = np.empty(max(F, 1), np.uint64)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        (d_payload, d_offsets, first), info = self._pd_call(
+            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_each_device(self._h, text, fb.ctypes.data, F, ptr(p), pc, ptr(o), oc,
+                                                                                 ff.ctypes.data if ff is not None else None,
+                                                                                 bad.ctypes.data, C.byref(info)),
+            lambda pb, no, nf: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(no, dtype=torch.int64, device=dev),
+                                np.empty(nf, np.uint64)))
+        return d_payload, d_offsets, first, info, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:F]]
 
     def map_pem(self, files, issuer_idx, want_records=True, want_new=True) -> BatchResult:
         """map_batch over PEM files (a list of bytes): text → packed batch on the device → map_batch_device, no DER in

@@ -1,9 +1,10 @@
 """PEM certificate files ↔ a packed batch on the CPU: the twin of ctmr_pem_decode* (include/ctmr.h).
 
 `parse` is a sequential restatement of the header's grammar, byte by byte; it shares nothing with the device code.  It
-judges every byte itself and leaves only the arithmetic of four characters to three bytes to `base64`.  `layout` says
-which blocks the device decodes where they lie.  `write` is the writer the tests and scripts/bench_pem_decode.py use.
-No GPU is needed for any of it.
+judges every byte itself and leaves only the arithmetic of four characters to three bytes to `base64`.  `parse_each`
+judges every file on its own, the twin of ctmr_pem_decode_each* (DESIGN.md §23).  `layout` says which blocks the device
+decodes where they lie.  `write` is the writer the tests and scripts/bench_pem_decode.py use.  No GPU is needed for any
+of it.
 """
 import base64
 
@@ -132,6 +133,22 @@ def parse(files):
             offsets.append(at)
         file_first.append(len(offsets) - 1)
     return b"".join(parts), np.asarray(offsets, np.uint64), np.asarray(file_first, np.uint64)
+
+
+def parse_each(files):
+    """Every file judged on its own, the twin of ctmr_pem_decode_each* (DESIGN.md §23): (ders — the certificates of the
+    good files in order, file_first u64[F+1], bad — per file None, or the offset that puts it outside the grammar, counted
+    as in parse).  parse_one per file with the error caught: a bad file has no certificates and fails nothing."""
+    ders, file_first, bad, base = [], [0], [], 0
+    for t in files:
+        try:
+            ders += [der for der, _ in parse_one(t)]
+            bad.append(None)
+        except _Bad as b:
+            bad.append(base + max(b.at, 0))
+        file_first.append(len(ders))
+        base += len(t)
+    return ders, np.asarray(file_first, np.uint64), bad
 
 
 def layout(files):

@@ -996,6 +996,28 @@ int ctmr_pem_decode_device(ctmr_engine* e, const void* d_text, const uint64_t* f
                            void* d_payload, size_t payload_cap, uint64_t* d_offsets, uint64_t certs_cap,
                            uint64_t* file_first, ctmr_pem_decode_info* info);
 
+/* Every file judged on its own: ctmr_pem_decode* with a verdict per file instead of one for the call.  DESIGN.md §23.
+ * Arguments as above, and file_bad, a HOST array u64[n_files], required (NULL: CTMR_E_INVAL).  The grammar is exactly
+ * the one above, not a byte wider.
+ *   file_bad[f] = UINT64_MAX: file f is inside the grammar.  Any other value: it is outside, and the value is an advisory
+ *   byte offset in [file_bounds[f], file_bounds[f + 1]).  A file of ws only, or of 0 bytes, is valid here as above.  The
+ *   verdict of file f is what ctmr_pem_decode says of that file alone: nothing in a neighbour changes it.
+ * A file outside the grammar fails nothing and contributes no certificates: file_first[f + 1] == file_first[f] for it, the
+ *   call returns CTMR_OK, info.bad_file / info.bad_offset name the LOWEST such file (UINT64_MAX: none), and
+ *   info.certificates, payload_bytes, regular and irregular count the other files only.  payload, offsets, certificates
+ *   and payload_bytes are byte for byte what ctmr_pem_decode* returns for the sub-sequence of good files, the zeroed
+ *   CTMR_PAYLOAD_PAD included; with no bad file every output of ctmr_pem_decode* is reproduced bit for bit.  The host
+ *   decodes the files named in file_bad itself and nothing is handed over twice.
+ * n_files = 0 and files that are all empty give CTMR_OK, all-good verdicts and the empty batch.
+ * Sizing is by the good files: CTMR_E_RANGE as above, with *info filled.  CTMR_E_RANGE, CTMR_E_NOMEM and argument
+ *   errors leave every output buffer, file_bad included, as it was. */
+int ctmr_pem_decode_each(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files,
+                         uint8_t* payload, size_t payload_cap, uint64_t* offsets, uint64_t certs_cap, uint64_t* file_first,
+                         uint64_t* file_bad, ctmr_pem_decode_info* info);
+int ctmr_pem_decode_each_device(ctmr_engine* e, const void* d_text, const uint64_t* file_bounds, uint64_t n_files,
+                                void* d_payload, size_t payload_cap, uint64_t* d_offsets, uint64_t certs_cap,
+                                uint64_t* file_first, uint64_t* file_bad, ctmr_pem_decode_info* info);
+
 /* Asynchronous ingestion (ctmr_submit_batch above) for RAW get-entries responses — what the reference's downloader actually holds (ct-fetch.go:446-462):
  * blob = leaf_input_0 ‖ extra_data_0 ‖ leaf_input_1 ‖ …, bounds u64[2n+1] (ctmr_map_entries' input).  Submits of
  * either form share the pipeline and its ordering; a super-batch holds one form (a change of form closes the open one).
@@ -1035,6 +1057,35 @@ int ctmr_submit_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t
 int ctmr_wait_entries_json(ctmr_engine* e, ctmr_ticket ticket, uint64_t entries_cap, ctmr_record* records,
                            uint64_t* new_idx, uint64_t* timestamp, uint64_t* resp_first, uint64_t* resp_bad,
                            ctmr_entries_json_info* info, ctmr_decode_stats* dstats, ctmr_batch_stats* stats);
+/* The fourth form: PEM certificate files as they lie (the text ctmr_pem_decode_each takes), one or more per submit: the
+ * warm start from what LocalDiskBackend wrote, one certificate a file.  DESIGN.md §23.
+ * ctmr_submit_pem returns at once: the bytes inside the bounds go to HBM behind the previous submit's on the copy
+ *   streams — straight DMA when text came from ctmr_alloc_pinned (keep it untouched until the wait), otherwise staged
+ *   before the call returns — and the files' bounds and issuer_idx, u32[n_files], one issuer table index per FILE or
+ *   CTMR_NO_ISSUER (under the reference's layout a file lies below its issuer's directory), are kept with the ticket.
+ *   Submits coalesce into a super-batch of this form; it closes at 96 MB of text, at 65 536 files, on ctmr_flush, when
+ *   one of its tickets is waited for, and when a submit of another form arrives (the number of certificates is not
+ *   known before it runs).
+ * The worker judges every file alone (ctmr_pem_decode_each_device), decodes the good files' certificates, expands the
+ *   issuer indices to one per certificate on the device (entry_type is 0 throughout) and maps them as ONE batch, like a
+ *   packed super-batch.  A file outside the grammar costs its own ticket its certificates and no other ticket
+ *   anything.  Failures of the whole super-batch (CTMR_E_FULL, CTMR_E_HIP) reach every ticket of it.
+ * ctmr_wait_pem blocks until the ticket's super-batch is done.  info: files, text_bytes, certificates = n,
+ *   payload_bytes, regular and irregular of THIS ticket, bad_file the lowest bad file of the ticket (UINT64_MAX: none),
+ *   bad_offset its offset.  certs_cap < n: CTMR_E_RANGE with *info filled, nothing written and the ticket NOT consumed —
+ *   a first call with certs_cap = 0 is the size query.  Otherwise records[n], new_idx (relative to the ticket,
+ *   ascending) and stats as ctmr_wait slices them, file_first u64[F + 1] relative to the ticket, file_bad u64[F] with
+ *   offsets relative to the text pointer the submit was given; any output pointer may be NULL.  A ticket with bad files
+ *   still returns CTMR_OK.
+ * ctmr_wait, ctmr_wait_entries and ctmr_wait_entries_json refuse a ticket of this form with CTMR_E_INVAL and leave it
+ *   collectable; ctmr_wait_pem refuses the tickets of the other forms in the same way.
+ * Ordering: files keep submission order, certificates file order, super-batches run in order with the other forms:
+ *   records, NEW lists and the engine's sets are those of one synchronous ctmr_pem_decode_each + ctmr_map_batch per
+ *   submit, in submission order. */
+int ctmr_submit_pem(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files,
+                    const uint32_t* issuer_idx, ctmr_ticket* ticket);
+int ctmr_wait_pem(ctmr_engine* e, ctmr_ticket ticket, uint64_t certs_cap, ctmr_record* records, uint64_t* new_idx,
+                  uint64_t* file_first, uint64_t* file_bad, ctmr_pem_decode_info* info, ctmr_batch_stats* stats);
 /* Issuer registration policy of the raw-entry calls.  on = 1 (default): a Chain[0] certificate met for the first time
  * is registered by the call.  on = 0: nothing is registered; when a batch contains unregistered Chain[0]
  * certificates the decode fails with CTMR_E_NOTFOUND and ctmr_pending_issuers lists them (distinct, [u32 len][DER]…,
