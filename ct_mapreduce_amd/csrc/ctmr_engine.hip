@@ -343,6 +343,26 @@ struct DevMem {
   uint8_t* u8() const { return (uint8_t*)p; }
 };
 
+// The same for page-locked host memory.
+struct PinMem {
+  void* p = nullptr;
+  PinMem() = default;
+  PinMem(const PinMem&) = delete;
+  PinMem& operator=(const PinMem&) = delete;
+  ~PinMem() { if (p) (void)hipHostFree(p); }
+  hipError_t alloc(size_t bytes) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    const hipError_t r = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (r != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+    }
+    return r;
+  }
+  uint8_t* u8() const { return (uint8_t*)p; }
+};
+
 // a positive integer from an environment variable (the test-only overrides); 0: unset, empty or zero
 uint64_t env_u64(const char* name) {
   const char* v = getenv(name);

@@ -130,14 +130,7 @@ int entries_json_core(ctmr_engine* e, const uint8_t* s, const uint64_t* rb, uint
       // and read the keys and pads from the text again)
       const uint64_t n0 = n;
       DevMem efirst2, len2, src2;
-      if ((r = ej_alloc(e, &efirst2, R + 1))) return r;
-      tx_turns(tx_blocks(R + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
-        hipLaunchKernelGGL(k_ej_drop, g, dim3(RP_BLOCK), 0, e->stream, b0, R, (const unsigned long long*)err, (const unsigned long long*)J->efirst.p,
-                           (unsigned long long*)efirst2.p);
-      });
-      if ((r = scan_u64(e, (uint64_t*)efirst2.p, R + 1, false, SC_MISC))) return r;
-      HIPCHK(e, hipMemcpyAsync(&n, (uint64_t*)efirst2.p + R, 8, hipMemcpyDeviceToHost, e->stream));
-      if ((r = tx_drain(e))) return r;
+      if ((r = ej_alloc(e, &efirst2, R + 1)) || (r = tx_drop(e, R, err, J->efirst, efirst2, &n))) return r;
       if ((r = ej_alloc(e, &len2, 2 * n + 1)) || (r = ej_alloc(e, &src2, 2 * n))) return r;
       if (n)
         tx_turns(tx_blocks(n0, RP_BLOCK), [&](uint64_t b0, dim3 g) {

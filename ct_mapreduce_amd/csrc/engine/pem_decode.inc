@@ -121,13 +121,7 @@ int pem_decode_core(ctmr_engine* e, const uint8_t* s, const uint64_t* fb, uint64
       if ((r = pd_alloc(e, &ffirst2, F + 1))) return r;
       HIPCHK(e, hipMemcpyAsync(&info.bad_offset, err + low, 8, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(e, hipMemsetAsync(irr, 0, 8, e->stream));
-      tx_turns(tx_blocks(F + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
-        hipLaunchKernelGGL(k_ej_drop, g, dim3(RP_BLOCK), 0, e->stream, b0, F, (const unsigned long long*)err, (const unsigned long long*)P->ffirst.p,
-                           (unsigned long long*)ffirst2.p);
-      });
-      if ((r = scan_u64(e, (uint64_t*)ffirst2.p, F + 1, false, SC_MISC))) return r;
-      HIPCHK(e, hipMemcpyAsync(&n, (uint64_t*)ffirst2.p + F, 8, hipMemcpyDeviceToHost, e->stream));
-      if ((r = tx_drain(e))) return r;
+      if ((r = tx_drop(e, F, err, P->ffirst, ffirst2, &n))) return r;
       if ((r = pd_alloc(e, &len2, n + 1)) || (r = pd_alloc(e, &src2, n)) || (r = pd_alloc(e, &lay2, n)) || (r = pd_alloc(e, &sqlen2, n + 1)) ||
           (r = pd_alloc(e, &sqtiles2, n + 1)))
         return r;

@@ -3,6 +3,10 @@
 // Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/map.inc; the
 // worker's step for the JSON form is engine/pipeline_json.inc, behind engine/entries_json.inc, and the one for the PEM
 // form engine/pipeline_pem.inc, behind engine/pem_decode.inc.
+// What the four forms share stands once: a slot owns its buffers (DevMem, PinMem), the layout of a meta buffer and the decoded
+// bytes of a ticket have one spelling each (slot_iss, slot_et, slot_ticket_bytes), the worker runs a pipe_run_* of one
+// signature per form, and the two text forms have one submit (pipe_submit_text), one opening of their worker steps
+// (pipe_text_reserve) and one account of a ticket's bodies (PipeTextWait::info), put into either public struct.
 //
 // The reference's downloader hands insertCTWorker one get-entries response at a time — at most 1 001 entries
 // (cmd/ct-fetch/ct-fetch.go:417-424) — through a 16 384-entry channel (:132), and the workers drain it concurrently
@@ -51,29 +55,29 @@ enum PipeState { PS_FREE = 0, PS_OPEN, PS_QUEUED, PS_DONE };
 struct PipeSlot {
   PipeState state = PS_FREE;
   uint64_t seq = 0;
-  // device side
-  uint8_t* d_payload = nullptr; size_t payload_cap = 0;
-  uint8_t* d_meta = nullptr; size_t meta_cap = 0;       // offsets u64[cap+1] | issuer_idx u32[cap] | entry_type u8[cap] — or, raw: bounds u64[2cap+1]
-  ctmr_record* d_records = nullptr;
-  uint64_t* d_new = nullptr;
+  // device side (the slot owns its buffers: freed with it, pipe_shutdown)
+  DevMem d_payload; size_t payload_cap = 0;
+  DevMem d_meta;                                        // offsets u64[cap+1] | issuer_idx u32[cap] | entry_type u8[cap] — or, raw: bounds u64[2cap+1]
+  DevMem d_records;                                     // ctmr_record[cap]
+  DevMem d_new;                                         // u64[cap]
   uint64_t ent_cap = 0;
   // pinned host side
-  uint8_t* h_meta = nullptr;                            // same layout as d_meta
-  ctmr_record* h_records = nullptr;
-  uint64_t* h_new = nullptr;
-  uint64_t* d_ts = nullptr;                             // raw super-batches: TimestampedEntry.Timestamp per entry
-  uint64_t* h_ts = nullptr;
-  uint8_t* h_etype = nullptr;                           // raw super-batches: the decoded entry types and Chain[0] lengths
-  uint32_t* h_c0len = nullptr;                          //   (per-ticket decode stats)
+  PinMem h_meta;                                        // same layout as d_meta
+  PinMem h_records;
+  PinMem h_new;
+  DevMem d_ts;                                          // raw super-batches: TimestampedEntry.Timestamp per entry, u64[cap]
+  PinMem h_ts;
+  PinMem h_etype;                                       // raw super-batches: the decoded entry types u8[cap] and Chain[0] lengths
+  PinMem h_c0len;                                       //   u32[cap] (per-ticket decode stats)
   // fill state
   uint64_t n = 0, bytes = 0;
   bool any_type = false;
   PipeForm form = PF_PACKED;
   // JSON and PEM super-batches: d_payload holds the text.  The bodies' bounds in it live here, not in the meta buffers, which
-  // pipe_slot_reserve frees when the worker sizes the slot by the entries found.
+  // pipe_slot_reserve replaces when the worker sizes the slot by the entries found.
   std::vector<uint64_t> body_rb;                        // bodies + 1
   std::vector<uint64_t> body_first, body_bad;           // the worker's: each body's first entry (bodies + 1), its verdict
-  uint8_t* d_blob = nullptr; size_t blob_cap = 0;       // the decoded entries; h_meta: their bounds u64[2n+1] (PEM: offsets u64[n+1])
+  DevMem d_blob; size_t blob_cap = 0;                   // the decoded entries; h_meta: their bounds u64[2n+1] (PEM: offsets u64[n+1])
   std::vector<uint32_t> file_iss;                       // PEM: the issuer index of every file
   std::vector<uint64_t> cert_lay;                       // PEM, the worker's: the layout of every certificate (a ticket's regular / irregular)
   ctmr_decode_stats dstats{};
@@ -113,56 +117,53 @@ int pipe_slot_reserve(ctmr_engine* e, PipeSlot& s, uint64_t entries, uint64_t by
   if (entries > s.ent_cap) {
     uint64_t cap = s.ent_cap ? s.ent_cap : 2 * PIPE_CLOSE_ENTRIES;
     while (cap < entries) cap *= 2;
-    (void)hipFree(s.d_meta); (void)hipFree(s.d_records); (void)hipFree(s.d_new); (void)hipFree(s.d_ts);
-    (void)hipHostFree(s.h_meta); (void)hipHostFree(s.h_records); (void)hipHostFree(s.h_new); (void)hipHostFree(s.h_ts);
-    (void)hipHostFree(s.h_etype); (void)hipHostFree(s.h_c0len);
-    s.d_meta = nullptr; s.d_records = nullptr; s.d_new = nullptr; s.h_meta = nullptr; s.h_records = nullptr; s.h_new = nullptr;
-    s.d_ts = nullptr; s.h_ts = nullptr; s.h_etype = nullptr; s.h_c0len = nullptr;
-    s.ent_cap = 0;
-    HIPCHK(e, hipMalloc(&s.d_meta, pipe_meta_bytes(cap)));
-    HIPCHK(e, hipMalloc(&s.d_records, cap * sizeof(ctmr_record)));
-    HIPCHK(e, hipMalloc(&s.d_new, cap * 8));
-    HIPCHK(e, hipHostMalloc((void**)&s.h_meta, pipe_meta_bytes(cap), hipHostMallocDefault));
-    HIPCHK(e, hipHostMalloc((void**)&s.h_records, cap * sizeof(ctmr_record), hipHostMallocDefault));
-    HIPCHK(e, hipHostMalloc((void**)&s.h_new, cap * 8, hipHostMallocDefault));
-    HIPCHK(e, hipMalloc(&s.d_ts, cap * 8));
-    HIPCHK(e, hipHostMalloc((void**)&s.h_ts, cap * 8, hipHostMallocDefault));
-    HIPCHK(e, hipHostMalloc((void**)&s.h_etype, cap, hipHostMallocDefault));
-    HIPCHK(e, hipHostMalloc((void**)&s.h_c0len, cap * 4, hipHostMallocDefault));
-    s.meta_cap = pipe_meta_bytes(cap);
+    s.ent_cap = 0;  // (until all ten stand)
+    HIPCHK(e, s.d_meta.alloc(pipe_meta_bytes(cap)));
+    HIPCHK(e, s.d_records.alloc(cap * sizeof(ctmr_record)));
+    HIPCHK(e, s.d_new.alloc(cap * 8));
+    HIPCHK(e, s.h_meta.alloc(pipe_meta_bytes(cap)));
+    HIPCHK(e, s.h_records.alloc(cap * sizeof(ctmr_record)));
+    HIPCHK(e, s.h_new.alloc(cap * 8));
+    HIPCHK(e, s.d_ts.alloc(cap * 8));
+    HIPCHK(e, s.h_ts.alloc(cap * 8));
+    HIPCHK(e, s.h_etype.alloc(cap));
+    HIPCHK(e, s.h_c0len.alloc(cap * 4));
     s.ent_cap = cap;
   }
   if (bytes + CTMR_PAYLOAD_PAD + 16 > s.payload_cap) {
     size_t cap = s.payload_cap ? s.payload_cap : 2 * PIPE_CLOSE_BYTES;
     while (cap < bytes + CTMR_PAYLOAD_PAD + 16) cap *= 2;
-    (void)hipFree(s.d_payload);
-    s.d_payload = nullptr;
     s.payload_cap = 0;
-    HIPCHK(e, hipMalloc(&s.d_payload, cap));
+    HIPCHK(e, s.d_payload.alloc(cap));
     s.payload_cap = cap;
   }
   return CTMR_OK;
 }
 
-uint64_t* slot_h_offsets(PipeSlot& s) { return (uint64_t*)s.h_meta; }
-uint32_t* slot_h_iss(PipeSlot& s) { return (uint32_t*)(s.h_meta + (s.ent_cap + 1) * 8); }
-uint8_t* slot_h_et(PipeSlot& s) { return s.h_meta + (s.ent_cap + 1) * 8 + s.ent_cap * 4; }
+uint64_t* slot_h_offsets(const PipeSlot& s) { return (uint64_t*)s.h_meta.p; }
+// The packed layout of a meta buffer: where the issuer indices and the entry types lie behind `meta` (h_meta's or d_meta's bytes).
+uint32_t* slot_iss(const PipeSlot& s, uint8_t* meta) { return (uint32_t*)(meta + (s.ent_cap + 1) * 8); }
+uint8_t* slot_et(const PipeSlot& s, uint8_t* meta) { return (uint8_t*)(slot_iss(s, meta) + s.ent_cap); }
+// The decoded bytes of a ticket (its DER, or its leaf_input and extra_data: the raw forms keep two bounds an entry).
+uint64_t slot_ticket_bytes(const PipeSlot& s, const PipeTicket& t) {
+  const uint64_t per = pipe_is_raw(s.form) ? 2 : 1;
+  return slot_h_offsets(s)[per * (t.first + t.n)] - slot_h_offsets(s)[per * t.first];
+}
 
 // Close the open super-batch: its small arrays follow the DER on the copy stream; the worker takes it from the queue.
 int pipe_close_locked(ctmr_engine* e, ctmr_pipeline* p) {
   if (p->open < 0) return CTMR_OK;
   PipeSlot& s = p->slots[p->open];
   HIPCHK(e, hipSetDevice(e->device));
-  if (pipe_is_text(s.form)) {
-    // (the bodies' bounds go to the device with the worker's call)
-  } else if (s.form == PF_RAW) {
+  // (the text forms copy nothing here: the bodies' bounds go to the device with the worker's call)
+  if (s.form == PF_RAW) {
     slot_h_offsets(s)[2 * s.n] = s.bytes;
-    HIPCHK(e, hipMemcpyAsync(s.d_meta, s.h_meta, (2 * s.n + 1) * 8, hipMemcpyHostToDevice, p->copy_stream[0]));
-  } else {
+    HIPCHK(e, hipMemcpyAsync(s.d_meta.p, s.h_meta.p, (2 * s.n + 1) * 8, hipMemcpyHostToDevice, p->copy_stream[0]));
+  } else if (s.form == PF_PACKED) {
     slot_h_offsets(s)[s.n] = s.bytes;
-    HIPCHK(e, hipMemcpyAsync(s.d_meta, s.h_meta, (s.n + 1) * 8, hipMemcpyHostToDevice, p->copy_stream[0]));
-    HIPCHK(e, hipMemcpyAsync(s.d_meta + (s.ent_cap + 1) * 8, slot_h_iss(s), s.n * 4, hipMemcpyHostToDevice, p->copy_stream[0]));
-    HIPCHK(e, hipMemcpyAsync(s.d_meta + (s.ent_cap + 1) * 8 + s.ent_cap * 4, slot_h_et(s), s.n, hipMemcpyHostToDevice, p->copy_stream[0]));
+    HIPCHK(e, hipMemcpyAsync(s.d_meta.p, s.h_meta.p, (s.n + 1) * 8, hipMemcpyHostToDevice, p->copy_stream[0]));
+    HIPCHK(e, hipMemcpyAsync(slot_iss(s, s.d_meta.u8()), slot_iss(s, s.h_meta.u8()), s.n * 4, hipMemcpyHostToDevice, p->copy_stream[0]));
+    HIPCHK(e, hipMemcpyAsync(slot_et(s, s.d_meta.u8()), slot_et(s, s.h_meta.u8()), s.n, hipMemcpyHostToDevice, p->copy_stream[0]));
   }
   for (uint32_t k = 0; k < p->n_streams; k++) HIPCHK(e, hipEventRecord(s.ev_h2d[k], p->copy_stream[k]));
   s.state = PS_QUEUED;
@@ -172,23 +173,54 @@ int pipe_close_locked(ctmr_engine* e, ctmr_pipeline* p) {
   return CTMR_OK;
 }
 
+// The worker's step for each form, the engine's mutex held and the slot's bytes on their way (pipe_worker).  view: what the
+// raw forms' decode leaves on the device, for the tickets' decode stats.
 int pipe_run_json(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view);  // engine/pipeline_json.inc
-int pipe_run_pem(ctmr_engine* e, PipeSlot& s);                          // engine/pipeline_pem.inc
+int pipe_run_pem(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view);   // engine/pipeline_pem.inc
+
+// The map + reduce over s.n certificates at `der` (s.d_payload, or what the PEM step decoded), their offsets in s.d_meta.
+int pipe_map_packed(ctmr_engine* e, PipeSlot& s, const uint8_t* der, const uint8_t* entry_type, uint64_t bytes) {
+  return map_device_locked(e, der, (const uint64_t*)s.d_meta.p, slot_iss(s, s.d_meta.u8()), entry_type, s.n, (ctmr_record*)s.d_records.p,
+                           (uint64_t*)s.d_new.p, &s.stats, nullptr, 0, bytes);
+}
+int pipe_run_packed(ctmr_engine* e, PipeSlot& s, ctmr_entry_view*) {
+  return pipe_map_packed(e, s, s.d_payload.u8(), s.any_type ? slot_et(s, s.d_meta.u8()) : nullptr, s.bytes);
+}
+
+// Decode + Chain[0] match (issuers registered on the way) + map/reduce, as ctmr_map_entries_device, over s.n raw entries at
+// `blob` (s.d_payload, or what the JSON step decoded), their bounds in s.d_meta.
+int pipe_map_raw(ctmr_engine* e, PipeSlot& s, const uint8_t* blob, ctmr_entry_view* view) {
+  return map_entries_locked(e, blob, (const uint64_t*)s.d_meta.p, s.n, (ctmr_record*)s.d_records.p, (uint64_t*)s.d_new.p, (uint64_t*)s.d_ts.p,
+                            &s.dstats, &s.stats, view);
+}
+int pipe_run_raw(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view) { return s.n ? pipe_map_raw(e, s, s.d_payload.u8(), view) : CTMR_OK; }
 
 // The slot's blob holds `bytes` decoded bytes and the padding behind them (the text forms, sized by the worker).
 int pipe_blob_reserve(ctmr_engine* e, PipeSlot& s, uint64_t bytes) {
   if (bytes + CTMR_PAYLOAD_PAD + 16 <= s.blob_cap) return CTMR_OK;
-  (void)hipFree(s.d_blob);
-  s.d_blob = nullptr;
   s.blob_cap = 0;
   const size_t cap = (size_t)pow2_at_least(bytes + CTMR_PAYLOAD_PAD + 16);
-  if (hipMalloc(&s.d_blob, cap) != hipSuccess) {
-    (void)hipGetLastError();
-    s.d_blob = nullptr;
-    return fail(e, CTMR_E_NOMEM, "no device memory for %llu decoded bytes", (unsigned long long)bytes);
-  }
+  if (s.d_blob.alloc(cap) != hipSuccess) return fail(e, CTMR_E_NOMEM, "no device memory for %llu decoded bytes", (unsigned long long)bytes);
   s.blob_cap = cap;
   return CTMR_OK;
+}
+
+// The opening of the two text steps, once the decoder's core has judged the slot's bodies and found n items of `bytes`
+// decoded bytes in the good ones: room for every body's verdict and first item, and everything sized by items, the blob
+// among it (at most 3/4 of the text).  pipe_slot_reserve replaces the meta buffers when it grows them; the bodies' bounds
+// (and the files' issuers) are in s.body_rb (s.file_iss), not there.
+int pipe_text_reserve(ctmr_engine* e, PipeSlot& s, uint64_t n, uint64_t bytes) {
+  const uint64_t B = s.body_rb.size() - 1;
+  int r;
+  try {
+    s.body_bad.assign(B, ~0ull);
+    s.body_first.assign(B + 1, 0);
+    s.cert_lay.assign(s.form == PF_PEM ? n : 0, 0);
+  } catch (const std::bad_alloc&) {
+    return fail(e, CTMR_E_NOMEM, "no host memory for the verdicts of %llu %s", (unsigned long long)B, s.form == PF_PEM ? "files" : "bodies");
+  }
+  if ((r = pipe_slot_reserve(e, s, n, 0))) return r;
+  return pipe_blob_reserve(e, s, bytes);
 }
 
 void pipe_worker(ctmr_engine* e) {
@@ -212,27 +244,23 @@ void pipe_worker(ctmr_engine* e) {
       for (uint32_t q = 0; q < p->n_streams; q++)
         if (hipStreamWaitEvent(e->stream, s.ev_h2d[q], 0) != hipSuccess) rc = CTMR_E_HIP;
       ctmr_entry_view view{};
-      if (rc == CTMR_OK && s.form == PF_JSON)  // every body judged, the good ones decoded into s.d_blob, then as a raw super-batch
-        rc = pipe_run_json(e, s, &view);
-      else if (rc == CTMR_OK && s.form == PF_PEM)  // every file judged, the good ones decoded into s.d_blob, then as a packed super-batch
-        rc = pipe_run_pem(e, s);
-      else if (rc == CTMR_OK && s.form == PF_RAW)  // decode + Chain[0] match (issuers registered on the way) + map/reduce, as ctmr_map_entries_device
-        rc = s.n ? map_entries_locked(e, s.d_payload, (const uint64_t*)s.d_meta, s.n, s.d_records, s.d_new, s.d_ts, &s.dstats,
-                                      &s.stats, &view)
-                 : CTMR_OK;
-      else if (rc == CTMR_OK)
-        rc = map_device_locked(e, s.d_payload, (const uint64_t*)s.d_meta, (const uint32_t*)(s.d_meta + (s.ent_cap + 1) * 8),
-                               s.any_type ? s.d_meta + (s.ent_cap + 1) * 8 + s.ent_cap * 4 : nullptr, s.n, s.d_records, s.d_new,
-                               &s.stats, nullptr, 0, s.bytes);
       if (rc == CTMR_OK) {
-        hipError_t h = hipMemcpyAsync(s.h_records, s.d_records, s.n * sizeof(ctmr_record), hipMemcpyDeviceToHost, e->stream);
+        switch (s.form) {
+          case PF_PACKED: rc = pipe_run_packed(e, s, &view); break;
+          case PF_RAW: rc = pipe_run_raw(e, s, &view); break;
+          case PF_JSON: rc = pipe_run_json(e, s, &view); break;  // every body judged, the good ones decoded into s.d_blob, then as a raw super-batch
+          case PF_PEM: rc = pipe_run_pem(e, s, &view); break;    // every file judged, the good ones decoded into s.d_blob, then as a packed one
+        }
+      }
+      if (rc == CTMR_OK) {
+        hipError_t h = hipMemcpyAsync(s.h_records.p, s.d_records.p, s.n * sizeof(ctmr_record), hipMemcpyDeviceToHost, e->stream);
         if (h == hipSuccess && pipe_is_raw(s.form) && s.n) {
-          h = hipMemcpyAsync(s.h_ts, s.d_ts, s.n * 8, hipMemcpyDeviceToHost, e->stream);
-          if (h == hipSuccess) h = hipMemcpyAsync(s.h_etype, view.entry_type, s.n, hipMemcpyDeviceToHost, e->stream);
-          if (h == hipSuccess) h = hipMemcpyAsync(s.h_c0len, view.chain0_len, s.n * 4, hipMemcpyDeviceToHost, e->stream);
+          h = hipMemcpyAsync(s.h_ts.p, s.d_ts.p, s.n * 8, hipMemcpyDeviceToHost, e->stream);
+          if (h == hipSuccess) h = hipMemcpyAsync(s.h_etype.p, view.entry_type, s.n, hipMemcpyDeviceToHost, e->stream);
+          if (h == hipSuccess) h = hipMemcpyAsync(s.h_c0len.p, view.chain0_len, s.n * 4, hipMemcpyDeviceToHost, e->stream);
         }
         if (h == hipSuccess && s.stats.n_new)
-          h = hipMemcpyAsync(s.h_new, s.d_new, s.stats.n_new * 8, hipMemcpyDeviceToHost, e->stream);
+          h = hipMemcpyAsync(s.h_new.p, s.d_new.p, s.stats.n_new * 8, hipMemcpyDeviceToHost, e->stream);
         if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
         if (h != hipSuccess) rc = fail(e, CTMR_E_HIP, "%s", hipGetErrorString(h));
       }
@@ -292,17 +320,12 @@ void pipe_shutdown(ctmr_engine* e) {
   p->cv.notify_all();
   if (p->worker.joinable()) p->worker.join();
   (void)hipSetDevice(e->device);
-  for (auto& s : p->slots) {
-    (void)hipFree(s.d_payload); (void)hipFree(s.d_meta); (void)hipFree(s.d_records); (void)hipFree(s.d_new); (void)hipFree(s.d_ts);
-    (void)hipFree(s.d_blob);
-    (void)hipHostFree(s.h_meta); (void)hipHostFree(s.h_records); (void)hipHostFree(s.h_new); (void)hipHostFree(s.h_ts);
-    (void)hipHostFree(s.h_etype); (void)hipHostFree(s.h_c0len);
+  for (auto& s : p->slots)
     for (auto ev : s.ev_h2d)
       if (ev) (void)hipEventDestroy(ev);
-  }
   for (auto cs : p->copy_stream)
     if (cs) (void)hipStreamDestroy(cs);
-  delete p;
+  delete p;  // (the slots free their buffers)
   e->pipe.store(nullptr, std::memory_order_release);
 }
 
@@ -363,7 +386,7 @@ int pipe_open_for(ctmr_engine* e, ctmr_pipeline* p, std::unique_lock<std::mutex>
 int pipe_append(ctmr_engine* e, ctmr_pipeline* p, const uint8_t* src, uint64_t bytes, uint64_t n, ctmr_ticket* ticket) {
   PipeSlot& s = p->slots[p->open];
   if (bytes) {
-    HIPCHK(e, hipMemcpyAsync(s.d_payload + s.bytes, src, bytes, hipMemcpyHostToDevice, p->copy_stream[p->rr]));
+    HIPCHK(e, hipMemcpyAsync(s.d_payload.u8() + s.bytes, src, bytes, hipMemcpyHostToDevice, p->copy_stream[p->rr]));
     p->rr = (p->rr + 1) % p->n_streams;
   }
   s.tickets.push_back({s.n, n, false});
@@ -396,9 +419,9 @@ int ctmr_submit_batch(ctmr_engine* e, const uint8_t* payload, const uint64_t* of
   PipeSlot& s = p->slots[p->open];
   uint64_t* ho = slot_h_offsets(s) + s.n;
   for (uint64_t i = 0; i < n; i++) ho[i] = s.bytes + (offsets[i] - base);
-  memcpy(slot_h_iss(s) + s.n, issuer_idx, n * 4);
-  if (entry_type) { memcpy(slot_h_et(s) + s.n, entry_type, n); s.any_type = true; }
-  else memset(slot_h_et(s) + s.n, 0, n);
+  memcpy(slot_iss(s, s.h_meta.u8()) + s.n, issuer_idx, n * 4);
+  if (entry_type) { memcpy(slot_et(s, s.h_meta.u8()) + s.n, entry_type, n); s.any_type = true; }
+  else memset(slot_et(s, s.h_meta.u8()) + s.n, 0, n);
   return pipe_append(e, p, payload + base, bytes, n, ticket);
 }
 
@@ -420,78 +443,58 @@ int ctmr_submit_entries(ctmr_engine* e, const uint8_t* blob, const uint64_t* bou
   return pipe_append(e, p, blob + base, bytes, n, ticket);
 }
 
-int ctmr_submit_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses, ctmr_ticket* ticket) {
-  if (!e || !ticket || (n_responses && !resp_bounds)) return CTMR_E_INVAL;
-  for (uint64_t i = 0; i < n_responses; i++)
-    if (resp_bounds[i + 1] < resp_bounds[i]) return fail(e, CTMR_E_INVAL, "resp_bounds not monotone at %llu", (unsigned long long)i);
-  const uint64_t base = n_responses ? resp_bounds[0] : 0, bytes = n_responses ? resp_bounds[n_responses] - base : 0;
+// The submit of the two text forms: n bodies at text[bounds[i], bounds[i + 1]), and for PEM the issuer index of each.
+static int pipe_submit_text(ctmr_engine* e, PipeForm form, const uint8_t* text, const uint64_t* bounds, uint64_t n,
+                            const uint32_t* issuer_idx /* PEM only */, ctmr_ticket* ticket) {
+  const bool pem = form == PF_PEM;
+  for (uint64_t i = 0; i < n; i++)
+    if (bounds[i + 1] < bounds[i])
+      return fail(e, CTMR_E_INVAL, "%s not monotone at %llu", pem ? "file_bounds" : "resp_bounds", (unsigned long long)i);
+  const uint64_t base = n ? bounds[0] : 0, bytes = n ? bounds[n] - base : 0;
   if (bytes && !text) return fail(e, CTMR_E_INVAL, "null text");
-  if (n_responses >= (1ull << 30)) return fail(e, CTMR_E_INVAL, "batch too large");
+  if (n >= (1ull << 30)) return fail(e, CTMR_E_INVAL, "batch too large");
   ctmr_pipeline* p;
   int r;
   if ((r = pipe_get(e, &p))) return r;
   std::unique_lock<std::mutex> lk(p->mu);
   HIPCHK(e, hipSetDevice(e->device));
-  if ((r = pipe_open_for(e, p, lk, PF_JSON, 0, bytes))) return r;
+  if ((r = pipe_open_for(e, p, lk, form, 0, bytes))) return r;
   PipeSlot& s = p->slots[p->open];
   const uint64_t body0 = s.body_rb.size() - 1, at = s.bytes;
-  try {
-    for (uint64_t i = 1; i <= n_responses; i++) s.body_rb.push_back(at + (resp_bounds[i] - base));
-  } catch (const std::bad_alloc&) {
+  const auto undo = [&] {  // no ticket, no bodies
     s.body_rb.resize(body0 + 1);
-    return fail(e, CTMR_E_NOMEM, "no host memory for the bounds of %llu bodies", (unsigned long long)n_responses);
+    if (pem) s.file_iss.resize(body0);
+  };
+  try {
+    for (uint64_t i = 1; i <= n; i++) s.body_rb.push_back(at + (bounds[i] - base));
+    if (pem) s.file_iss.insert(s.file_iss.end(), issuer_idx, issuer_idx + n);
+  } catch (const std::bad_alloc&) {
+    undo();
+    return fail(e, CTMR_E_NOMEM, "no host memory for the bounds of %llu %s", (unsigned long long)n, pem ? "files" : "bodies");
   }
   const size_t had = s.tickets.size();
   r = pipe_append(e, p, bytes ? text + base : nullptr, bytes, 0, ticket);
-  if (s.tickets.size() == had) {  // the copy failed: no ticket, no bodies
-    s.body_rb.resize(body0 + 1);
+  if (s.tickets.size() == had) {  // the copy failed
+    undo();
     return r;
   }
   PipeTicket& t = s.tickets[had];  // (p->mu is held: the worker has not seen the slot, closed or not)
   t.body0 = body0;
-  t.nbody = n_responses;
+  t.nbody = n;
   t.text_at = at;
   t.text_base = base;
   return r;
 }
 
+int ctmr_submit_entries_json(ctmr_engine* e, const uint8_t* text, const uint64_t* resp_bounds, uint64_t n_responses, ctmr_ticket* ticket) {
+  if (!e || !ticket || (n_responses && !resp_bounds)) return CTMR_E_INVAL;
+  return pipe_submit_text(e, PF_JSON, text, resp_bounds, n_responses, nullptr, ticket);
+}
+
 int ctmr_submit_pem(ctmr_engine* e, const uint8_t* text, const uint64_t* file_bounds, uint64_t n_files, const uint32_t* issuer_idx,
                     ctmr_ticket* ticket) {
   if (!e || !ticket || (n_files && (!file_bounds || !issuer_idx))) return CTMR_E_INVAL;
-  for (uint64_t i = 0; i < n_files; i++)
-    if (file_bounds[i + 1] < file_bounds[i]) return fail(e, CTMR_E_INVAL, "file_bounds not monotone at %llu", (unsigned long long)i);
-  const uint64_t base = n_files ? file_bounds[0] : 0, bytes = n_files ? file_bounds[n_files] - base : 0;
-  if (bytes && !text) return fail(e, CTMR_E_INVAL, "null text");
-  if (n_files >= (1ull << 30)) return fail(e, CTMR_E_INVAL, "batch too large");
-  ctmr_pipeline* p;
-  int r;
-  if ((r = pipe_get(e, &p))) return r;
-  std::unique_lock<std::mutex> lk(p->mu);
-  HIPCHK(e, hipSetDevice(e->device));
-  if ((r = pipe_open_for(e, p, lk, PF_PEM, 0, bytes))) return r;
-  PipeSlot& s = p->slots[p->open];
-  const uint64_t body0 = s.body_rb.size() - 1, at = s.bytes;
-  try {
-    for (uint64_t i = 1; i <= n_files; i++) s.body_rb.push_back(at + (file_bounds[i] - base));
-    s.file_iss.insert(s.file_iss.end(), issuer_idx, issuer_idx + n_files);
-  } catch (const std::bad_alloc&) {
-    s.body_rb.resize(body0 + 1);
-    s.file_iss.resize(body0);
-    return fail(e, CTMR_E_NOMEM, "no host memory for the bounds of %llu files", (unsigned long long)n_files);
-  }
-  const size_t had = s.tickets.size();
-  r = pipe_append(e, p, bytes ? text + base : nullptr, bytes, 0, ticket);
-  if (s.tickets.size() == had) {  // the copy failed: no ticket, no files
-    s.body_rb.resize(body0 + 1);
-    s.file_iss.resize(body0);
-    return r;
-  }
-  PipeTicket& t = s.tickets[had];  // (p->mu is held: the worker has not seen the slot, closed or not)
-  t.body0 = body0;
-  t.nbody = n_files;
-  t.text_at = at;
-  t.text_base = base;
-  return r;
+  return pipe_submit_text(e, PF_PEM, text, file_bounds, n_files, issuer_idx, ticket);
 }
 
 int ctmr_flush(ctmr_engine* e) {
@@ -505,16 +508,22 @@ int ctmr_flush(ctmr_engine* e) {
 
 // What ctmr_wait_entries_json and ctmr_wait_pem have beyond the others: each alone collects a ticket of its text form (the
 // others have no capacity argument) and collects no other.  first / bad: resp_first / resp_bad, or file_first / file_bad.
+// info: what the ticket's bodies (responses, files) came to, in neither call's names; each puts it into its public struct
+// when `judged` says it was filled — not for an unknown ticket or one of another form, which stays collectable.
 struct PipeTextWait {
   PipeForm form;
   uint64_t cap;
   uint64_t *first, *bad;
-  ctmr_entries_json_info* jinfo;
-  ctmr_pem_decode_info* pinfo;
+  bool judged = false;
+  struct {
+    uint64_t bodies, items, text_bytes, decoded_bytes;
+    uint64_t bad_body, bad_offset;  // the lowest body outside the grammar, or ~0
+    uint64_t irregular;             // PEM: the items decoded through the squeezed copy
+  } info{};
 };
 
 static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
-                     ctmr_decode_stats* dstats, ctmr_batch_stats* stats, const PipeTextWait* tw = nullptr) {
+                     ctmr_decode_stats* dstats, ctmr_batch_stats* stats, PipeTextWait* tw = nullptr) {
   if (!e) return CTMR_E_INVAL;
   ctmr_pipeline* p;
   int r;
@@ -531,66 +540,40 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
                                  : s->form == PF_PEM ? "a ticket of ctmr_submit_pem: ctmr_wait_pem collects it"
                                  : tw->form == PF_PEM ? "not a ticket of ctmr_submit_pem"
                                                       : "not a ticket of ctmr_submit_entries_json");
-  const bool json = tw && tw->form == PF_JSON, pem = tw && tw->form == PF_PEM;
-  ctmr_entries_json_info* const info = tw ? tw->jinfo : nullptr;
-  ctmr_pem_decode_info* const pinfo = tw ? tw->pinfo : nullptr;
   if (s->state == PS_OPEN && (r = pipe_close_locked(e, p))) return r;  // nobody else will launch it
   p->cv.wait(lk, [&] { return s->state == PS_DONE; });
   PipeTicket& t = s->tickets[tix];
   int rc = s->rc;
-  if (rc != CTMR_OK && json && info) {  // the super-batch failed: no body was judged
-    memset(info, 0, sizeof *info);
-    info->responses = t.nbody;
-    info->bad_response = info->bad_offset = ~0ull;
-  }
-  if (rc != CTMR_OK && pem && pinfo) {  // the super-batch failed: no file was judged
-    memset(pinfo, 0, sizeof *pinfo);
-    pinfo->files = t.nbody;
-    pinfo->bad_file = pinfo->bad_offset = ~0ull;
+  if (tw) {
+    tw->judged = true;
+    tw->info = {t.nbody, 0, 0, 0, ~0ull, ~0ull, 0};  // should the super-batch have failed: no body was judged
   }
   if (rc == CTMR_OK && tw) {
     const uint64_t* rb = s->body_rb.data() + t.body0;
     const uint64_t* bad = s->body_bad.data() + t.body0;
     const uint64_t back = t.text_base - t.text_at;  // an offset in the slot's text → one from the submit's text pointer
-    if (json && info) {
-      memset(info, 0, sizeof *info);
-      info->responses = t.nbody;
-      info->entries = t.n;
-      info->text_bytes = rb[t.nbody] - rb[0];
-      info->blob_bytes = slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first];
-      info->bad_response = info->bad_offset = ~0ull;
-      for (uint64_t i = t.nbody; i-- > 0;)
-        if (bad[i] != ~0ull) {
-          info->bad_response = i;
-          info->bad_offset = bad[i] + back;
-        }
-    }
-    if (pem && pinfo) {
-      memset(pinfo, 0, sizeof *pinfo);
-      pinfo->files = t.nbody;
-      pinfo->certificates = t.n;
-      pinfo->text_bytes = rb[t.nbody] - rb[0];
-      pinfo->payload_bytes = slot_h_offsets(*s)[t.first + t.n] - slot_h_offsets(*s)[t.first];
-      for (uint64_t i = 0; i < t.n; i++) pinfo->irregular += (s->cert_lay[t.first + i] & 3ull) == PD_IRREGULAR;
-      pinfo->regular = t.n - pinfo->irregular;
-      pinfo->bad_file = pinfo->bad_offset = ~0ull;
-      for (uint64_t i = t.nbody; i-- > 0;)
-        if (bad[i] != ~0ull) {
-          pinfo->bad_file = i;
-          pinfo->bad_offset = bad[i] + back;
-        }
-    }
+    tw->info.items = t.n;
+    tw->info.text_bytes = rb[t.nbody] - rb[0];
+    tw->info.decoded_bytes = slot_ticket_bytes(*s, t);
+    for (uint64_t i = t.nbody; i-- > 0;)
+      if (bad[i] != ~0ull) {
+        tw->info.bad_body = i;
+        tw->info.bad_offset = bad[i] + back;
+      }
+    if (s->form == PF_PEM)
+      for (uint64_t i = 0; i < t.n; i++) tw->info.irregular += (s->cert_lay[t.first + i] & 3ull) == PD_IRREGULAR;
     if (tw->cap < t.n)
-      return fail(e, CTMR_E_RANGE, "the ticket holds %llu %s", (unsigned long long)t.n, pem ? "certificates" : "entries");
+      return fail(e, CTMR_E_RANGE, "the ticket holds %llu %s", (unsigned long long)t.n, s->form == PF_PEM ? "certificates" : "entries");
     if (tw->first)
       for (uint64_t i = 0; i <= t.nbody; i++) tw->first[i] = s->body_first[t.body0 + i] - t.first;
     if (tw->bad)
       for (uint64_t i = 0; i < t.nbody; i++) tw->bad[i] = bad[i] == ~0ull ? ~0ull : bad[i] + back;
   }
   if (rc == CTMR_OK) {
-    if (records && t.n) memcpy(records, s->h_records + t.first, t.n * sizeof(ctmr_record));
+    const ctmr_record* recs = (const ctmr_record*)s->h_records.p + t.first;
+    if (records && t.n) memcpy(records, recs, t.n * sizeof(ctmr_record));
     // this batch's slice of the super-batch's NEW list (ascending), rebased to the batch
-    const uint64_t* nb = s->h_new;
+    const uint64_t* nb = (const uint64_t*)s->h_new.p;
     const uint64_t* lo = std::lower_bound(nb, nb + s->stats.n_new, t.first);
     const uint64_t* hi = std::lower_bound(lo, nb + s->stats.n_new, t.first + t.n);
     if (new_idx)
@@ -598,39 +581,38 @@ static int pipe_wait(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, u
     if (stats) {
       memset(stats, 0, sizeof *stats);
       stats->n = t.n;
-      uint64_t host_set = 0, new_flag = 0;
+      uint64_t host_set = 0;
       for (uint64_t i = 0; i < t.n; i++) {
-        const ctmr_record& rc2 = s->h_records[t.first + i];
+        const ctmr_record& rc2 = recs[i];
         stats->by_status[rc2.status < CTMR_ST__COUNT ? rc2.status : CTMR_ST_PARSE_ERROR]++;
         host_set += rc2.status == CTMR_ST_PASS && rc2.serial_len > CTMR_MAX_SERIAL;
-        new_flag += (rc2.flags & CTMR_FL_WAS_UNKNOWN) != 0;
       }
       stats->n_new = (uint64_t)(hi - lo);
       stats->n_dup = stats->by_status[CTMR_ST_PASS] - stats->n_new;
       stats->n_host_set = host_set;
-      stats->payload_bytes = pipe_is_raw(s->form) ? slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first]
-                                    : slot_h_offsets(*s)[t.first + t.n] - slot_h_offsets(*s)[t.first];
+      stats->payload_bytes = slot_ticket_bytes(*s, t);
       stats->map_launches = 1;
       stats->ms_map = s->stats.ms_map; stats->ms_insert = s->stats.ms_insert; stats->ms_resolve = s->stats.ms_resolve;
       stats->ms_compact = s->stats.ms_compact; stats->ms_total = s->stats.ms_total;  // of the whole super-batch
-      (void)new_flag;
     }
     if (timestamp) {
-      if (pipe_is_raw(s->form)) memcpy(timestamp, s->h_ts + t.first, t.n * 8);
+      if (pipe_is_raw(s->form)) memcpy(timestamp, (const uint64_t*)s->h_ts.p + t.first, t.n * 8);
       else memset(timestamp, 0, t.n * 8);  // a packed batch carries no timestamps
     }
     if (dstats) {
       memset(dstats, 0, sizeof *dstats);
       if (pipe_is_raw(s->form)) {
         dstats->n = t.n;
+        const uint8_t* etype = s->h_etype.u8() + t.first;
+        const uint32_t* c0len = (const uint32_t*)s->h_c0len.p + t.first;
         for (uint64_t i = 0; i < t.n; i++) {
-          const uint8_t et = s->h_etype[t.first + i];
+          const uint8_t et = etype[i];
           dstats->n_x509 += et == 0;
           dstats->n_precert += et == 1;
           dstats->n_decode_error += et == CTMR_ENTRY_INVALID;
-          dstats->n_no_chain += et != CTMR_ENTRY_INVALID && s->h_c0len[t.first + i] == 0;
+          dstats->n_no_chain += et != CTMR_ENTRY_INVALID && c0len[i] == 0;
         }
-        dstats->blob_bytes = slot_h_offsets(*s)[2 * (t.first + t.n)] - slot_h_offsets(*s)[2 * t.first];
+        dstats->blob_bytes = slot_ticket_bytes(*s, t);
         dstats->n_issuers_added = s->dstats.n_issuers_added;  // of the whole super-batch
         dstats->ms_decode = s->dstats.ms_decode; dstats->ms_match = s->dstats.ms_match;
       }
@@ -660,12 +642,18 @@ int ctmr_wait_entries(ctmr_engine* e, ctmr_ticket ticket, ctmr_record* records, 
 int ctmr_wait_entries_json(ctmr_engine* e, ctmr_ticket ticket, uint64_t entries_cap, ctmr_record* records, uint64_t* new_idx, uint64_t* timestamp,
                            uint64_t* resp_first, uint64_t* resp_bad, ctmr_entries_json_info* info, ctmr_decode_stats* dstats,
                            ctmr_batch_stats* stats) {
-  const PipeTextWait tw{PF_JSON, entries_cap, resp_first, resp_bad, info, nullptr};
-  return pipe_wait(e, ticket, records, new_idx, timestamp, dstats, stats, &tw);
+  PipeTextWait tw{PF_JSON, entries_cap, resp_first, resp_bad};
+  const int rc = pipe_wait(e, ticket, records, new_idx, timestamp, dstats, stats, &tw);
+  const auto& w = tw.info;
+  if (info && tw.judged) *info = {w.bodies, w.items, w.text_bytes, w.decoded_bytes, w.bad_body, w.bad_offset};
+  return rc;
 }
 
 int ctmr_wait_pem(ctmr_engine* e, ctmr_ticket ticket, uint64_t certs_cap, ctmr_record* records, uint64_t* new_idx, uint64_t* file_first,
                   uint64_t* file_bad, ctmr_pem_decode_info* info, ctmr_batch_stats* stats) {
-  const PipeTextWait tw{PF_PEM, certs_cap, file_first, file_bad, nullptr, info};
-  return pipe_wait(e, ticket, records, new_idx, nullptr, nullptr, stats, &tw);
+  PipeTextWait tw{PF_PEM, certs_cap, file_first, file_bad};
+  const int rc = pipe_wait(e, ticket, records, new_idx, nullptr, nullptr, stats, &tw);
+  const auto& w = tw.info;
+  if (info && tw.judged) *info = {w.bodies, w.items, w.text_bytes, w.decoded_bytes, w.items - w.irregular, w.irregular, w.bad_body, w.bad_offset};
+  return rc;
 }

@@ -5,29 +5,22 @@
 extern "C++" {
 namespace {
 
-// The engine's mutex is held and the slot's text has arrived (pipe_worker).  Everything sized by entries is sized here,
-// once efirst is known: the blob (at most 3/4 of the text), records, NEW list, timestamps, entry types, Chain[0] lengths.
-// pipe_slot_reserve frees the meta buffers when it grows them; the bodies' bounds are in s.body_rb, not there.
+// Everything sized by entries is sized once efirst is known (pipe_text_reserve): the blob, records, NEW list, timestamps,
+// entry types, Chain[0] lengths.
 int pipe_run_json(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view) {
   const uint64_t R = s.body_rb.size() - 1;
   int r;
   EntriesJson J;
-  if ((r = entries_json_core(e, s.d_payload, s.body_rb.data(), R, &J, true))) return r;
-  const uint64_t n = J.info.entries, bb = J.info.blob_bytes;
-  try {
-    s.body_bad = J.bad;
-    s.body_first.assign(R + 1, 0);
-  } catch (const std::bad_alloc&) {
-    return fail(e, CTMR_E_NOMEM, "no host memory for the verdicts of %llu bodies", (unsigned long long)R);
-  }
-  if ((r = pipe_slot_reserve(e, s, n, 0))) return r;
-  if ((r = pipe_blob_reserve(e, s, bb))) return r;
-  if ((r = entries_json_decode(e, J, s.d_blob))) return r;
+  if ((r = entries_json_core(e, s.d_payload.u8(), s.body_rb.data(), R, &J, true))) return r;
+  const uint64_t n = J.info.entries;
+  if ((r = pipe_text_reserve(e, s, n, J.info.blob_bytes))) return r;
+  s.body_bad.swap(J.bad);  // (R verdicts either)
+  if ((r = entries_json_decode(e, J, s.d_blob.u8()))) return r;
   if ((r = entries_json_resp_first(e, J, R, s.body_first.data()))) return r;
-  HIPCHK(e, hipMemcpy(s.h_meta, J.bounds.p, (2 * n + 1) * 8, hipMemcpyDeviceToHost));  // the tickets' blob bytes
-  HIPCHK(e, hipMemcpyAsync(s.d_meta, J.bounds.p, (2 * n + 1) * 8, hipMemcpyDeviceToDevice, e->stream));  // (J's tables end with this call)
+  HIPCHK(e, hipMemcpy(s.h_meta.p, J.bounds.p, (2 * n + 1) * 8, hipMemcpyDeviceToHost));  // the tickets' blob bytes
+  HIPCHK(e, hipMemcpyAsync(s.d_meta.p, J.bounds.p, (2 * n + 1) * 8, hipMemcpyDeviceToDevice, e->stream));  // (J's tables end with this call)
   s.n = n;
-  return map_entries_locked(e, s.d_blob, (const uint64_t*)s.d_meta, n, s.d_records, s.d_new, s.d_ts, &s.dstats, &s.stats, view);
+  return pipe_map_raw(e, s, s.d_blob.u8(), view);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // engine/text_decode.inc — the host code the two text decoders share (engine/entries_json.inc, engine/pem_decode.inc;
-// kernels/text_scan.h): launching a pass in turns, tables of words, scans that end in a total, opening a text in segments
-// for the kernels, staging a host text, listing the decode tiles of n items, the check of the caller's buffers and the end
-// of a decode.  `who` is the caller's name in front of its error messages ("entries json", "pem decode").
+// kernels/text_scan.h): launching a pass in turns, tables of words, scans that end in a total, dropping the judged-bad
+// bodies, opening a text in segments for the kernels, staging a host text, listing the decode tiles of n items, the check
+// of the caller's buffers and the end of a decode.  `who` is the caller's name in front of its error messages ("entries json", "pem decode").
 // Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/resp_parse.inc.
 
 extern "C++" {
@@ -33,6 +33,18 @@ int tx_scan(ctmr_engine* e, DevMem& data, uint64_t n, uint64_t* total) {
   if ((r = scan_u64(e, (uint64_t*)data.p, n + 1, false, SC_MISC))) return r;
   if (!total) return CTMR_OK;
   HIPCHK(e, hipMemcpyAsync(total, (uint64_t*)data.p + n, 8, hipMemcpyDeviceToHost, e->stream));
+  return tx_drain(e);
+}
+
+// The bodies with a verdict leave (bad_at[i] != ~0, i < R): first2 (R + 1 words) gets the items of every body out of
+// first0, the scan that counted them, those of the judged-bad ones as zero, and is scanned; *n = the items that stay.  Drains.
+int tx_drop(ctmr_engine* e, uint64_t R, const unsigned long long* bad_at, const DevMem& first0, DevMem& first2, uint64_t* n) {
+  tx_turns(tx_blocks(R + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
+    hipLaunchKernelGGL(k_ej_drop, g, dim3(RP_BLOCK), 0, e->stream, b0, R, bad_at, (const unsigned long long*)first0.p, (unsigned long long*)first2.p);
+  });
+  int r;
+  if ((r = scan_u64(e, (uint64_t*)first2.p, R + 1, false, SC_MISC))) return r;
+  HIPCHK(e, hipMemcpyAsync(n, (uint64_t*)first2.p + R, 8, hipMemcpyDeviceToHost, e->stream));
   return tx_drain(e);
 }
 

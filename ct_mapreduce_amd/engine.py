@@ -18,6 +18,19 @@ RECORD_DTYPE = np.dtype([("status", "u1"), ("flags", "u1"), ("serial_len", "<u2"
 assert RECORD_DTYPE.itemsize == 32
 
 
+def _addr(a):
+    """an array's address; a raw address (an int: e.g. a pinned buffer) or None as it is"""
+    return a.ctypes.data if hasattr(a, "ctypes") else a
+
+
+def _text_arg(bodies, join):
+    """(text, bounds) with text an array or an address, or a list of bytes → (text: array, address or None, bounds u64)"""
+    if isinstance(bodies, tuple):
+        return bodies[0], np.ascontiguousarray(bodies[1], dtype=np.uint64)
+    text, bounds = join(bodies)
+    return (np.frombuffer(text, np.uint8) if text else None), bounds   # pageable: staged before the call returns
+
+
 class CtmrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"ctmr error {code}: {msg}")
@@ -138,8 +151,7 @@ class Engine:
         self._h = h
         self.device = device
         self.collect_meta = bool(collect_meta)
-        self._json_bodies = {}   # ticket of submit_entries_json → its bodies: wait_entries_json sizes resp_first and bad by it
-        self._pem_files = {}     # ticket of submit_pem → its files: wait_pem sizes file_first and bad by it
+        self._text_tickets = {}   # ticket of submit_entries_json / submit_pem → (which, its bodies): the wait sizes first and bad by it
 
     # ---- lifecycle
     def close(self):
@@ -237,11 +249,8 @@ class Engine:
     def submit_batch(self, payload, offsets, issuer_idx, entry_type, n) -> int:
         """Arrays (numpy, contiguous) or raw addresses (ints: e.g. pinned buffers of alloc_pinned).  Returns the ticket.
         The caller keeps the arrays alive — and pinned payloads untouched — until wait(ticket)."""
-        def addr(a):
-            return a.ctypes.data if hasattr(a, "ctypes") else a
         t = C.c_uint64(0)
-        self._ck(self._lib.ctmr_submit_batch(self._h, addr(payload), addr(offsets), addr(issuer_idx),
-                                             addr(entry_type) if entry_type is not None else None, n, C.byref(t)))
+        self._ck(self._lib.ctmr_submit_batch(self._h, _addr(payload), _addr(offsets), _addr(issuer_idx), _addr(entry_type), n, C.byref(t)))
         return t.value
 
     def flush(self):
@@ -257,10 +266,8 @@ class Engine:
 
     def submit_entries(self, blob, bounds, n) -> int:
         """Raw get-entries form of submit_batch (ctmr_submit_entries): blob u8, bounds u64[2n+1] — arrays or addresses."""
-        def addr(a):
-            return a.ctypes.data if hasattr(a, "ctypes") else a
         t = C.c_uint64(0)
-        self._ck(self._lib.ctmr_submit_entries(self._h, addr(blob), addr(bounds), n, C.byref(t)))
+        self._ck(self._lib.ctmr_submit_entries(self._h, _addr(blob), _addr(bounds), n, C.byref(t)))
         return t.value
 
     def wait_entries(self, ticket: int, n: int) -> EntriesResult:
@@ -273,88 +280,71 @@ class Engine:
                                              C.byref(ds), C.byref(st)))
         return EntriesResult(records, new_idx[:st.n_new], ts[:n], st, ds)
 
+    def _wait_text(self, name, ticket, items, call):
+        """The two text waits: call(cap, records, new_idx, timestamp, first, bad) → rc, as the size query first (a ticket
+        without items is collected by it, so the verdicts are asked for there too), then, knowing items(), to collect.
+        → (records, new_idx, timestamp, first, bad as a list of None or offsets)"""
+        name_of, B = self._text_tickets.get(ticket, (None, 0))
+        if name_of != name:
+            raise CtmrError(N.E_NOTFOUND, f"not a ticket of {name}, or already collected")
+        first = np.zeros(B + 1, np.uint64)
+        bad = np.zeros(max(B, 1), np.uint64)
+        rc = call(0, None, None, None, first, bad)
+        n = items() if rc == N.E_RANGE else 0
+        records = np.zeros(n, dtype=RECORD_DTYPE)
+        new_idx = np.zeros(max(n, 1), dtype=np.uint64)
+        ts = np.zeros(max(n, 1), dtype=np.uint64)
+        if rc == N.E_RANGE:
+            rc = call(n, records, new_idx, ts, first, bad)
+        del self._text_tickets[ticket]   # collected, or failed with its super-batch: either way it is gone
+        self._ck(rc)
+        return records, new_idx, ts[:n], first, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:B]]
+
     def submit_entries_json(self, bodies) -> int:
         """get-entries HTTP bodies as they lie (a list of bytes — a downloader submits one; or (text, resp_bounds) with
         text an array or an address, e.g. a pinned buffer of pinned_array kept untouched until the wait).  Returns the
         ticket (ctmr_submit_entries_json)."""
         from . import get_entries
-        if isinstance(bodies, tuple):
-            text, rb = bodies
-            rb = np.ascontiguousarray(rb, dtype=np.uint64)
-            addr = text.ctypes.data if hasattr(text, "ctypes") else text
-        else:
-            text, rb = get_entries.join(bodies)
-            addr = np.frombuffer(text, np.uint8).ctypes.data if text else None   # pageable: staged before the call returns
+        text, rb = _text_arg(bodies, get_entries.join)
         t = C.c_uint64(0)
-        self._ck(self._lib.ctmr_submit_entries_json(self._h, addr, rb.ctypes.data, len(rb) - 1, C.byref(t)))
-        self._json_bodies[t.value] = len(rb) - 1
+        self._ck(self._lib.ctmr_submit_entries_json(self._h, _addr(text), rb.ctypes.data, len(rb) - 1, C.byref(t)))
+        self._text_tickets[t.value] = ("submit_entries_json", len(rb) - 1)
         return t.value
 
     def wait_entries_json(self, ticket: int) -> EntriesResult:
         """The ticket's result (ctmr_wait_entries_json; the size query is done here): EntriesResult with resp_first and
         bad.  A body outside the grammar has no entries and its offset in bad; the call does not fail for it."""
-        R = self._json_bodies.get(ticket)
-        if R is None:
-            raise CtmrError(N.E_NOTFOUND, "not a ticket of submit_entries_json, or already collected")
         info, st, ds = N.EntriesJsonInfo(), N.BatchStats(), N.DecodeStats()
-        first = np.zeros(R + 1, np.uint64)
-        bad = np.zeros(max(R, 1), np.uint64)
-        # the size query; a ticket without entries is collected by it, so the verdicts are asked for here too
-        rc = self._lib.ctmr_wait_entries_json(self._h, ticket, 0, None, None, None, first.ctypes.data, bad.ctypes.data, C.byref(info),
-                                              C.byref(ds), C.byref(st))
-        n = int(info.entries) if rc == N.E_RANGE else 0
-        records = np.zeros(n, dtype=RECORD_DTYPE)
-        new_idx = np.zeros(max(n, 1), dtype=np.uint64)
-        ts = np.zeros(max(n, 1), dtype=np.uint64)
-        if rc == N.E_RANGE:
-            rc = self._lib.ctmr_wait_entries_json(self._h, ticket, n, records.ctypes.data, new_idx.ctypes.data, ts.ctypes.data,
-                                                  first.ctypes.data, bad.ctypes.data, C.byref(info), C.byref(ds), C.byref(st))
-        del self._json_bodies[ticket]   # collected, or failed with its super-batch: either way it is gone
-        self._ck(rc)
-        return EntriesResult(records, new_idx[:st.n_new], ts[:n], st, ds, first,
-                             [None if int(b) == 2**64 - 1 else int(b) for b in bad[:R]])
+        records, new_idx, ts, first, bad = self._wait_text(
+            "submit_entries_json", ticket, lambda: int(info.entries),
+            lambda cap, rec, new, ts, first, bad: self._lib.ctmr_wait_entries_json(
+                self._h, ticket, cap, _addr(rec), _addr(new), _addr(ts), first.ctypes.data, bad.ctypes.data, C.byref(info), C.byref(ds), C.byref(st)))
+        return EntriesResult(records, new_idx[:st.n_new], ts, st, ds, first, bad)
 
     def submit_pem(self, files, issuer_idx) -> int:
         """PEM certificate files as they lie (a list of bytes; or (text, file_bounds) with text an array or an address,
         e.g. a pinned buffer of pinned_array kept untouched until the wait) and one issuer table index per FILE, or
         NO_ISSUER.  Returns the ticket (ctmr_submit_pem)."""
         from . import pem_text
-        if isinstance(files, tuple):
-            text, fb = files
-            fb = np.ascontiguousarray(fb, dtype=np.uint64)
-            addr = text.ctypes.data if hasattr(text, "ctypes") else text
-        else:
-            text, fb = pem_text.join(files)
-            addr = np.frombuffer(text, np.uint8).ctypes.data if text else None   # pageable: staged before the call returns
+        text, fb = _text_arg(files, pem_text.join)
         F = len(fb) - 1
         iss = np.ascontiguousarray(issuer_idx, dtype=np.uint32)
         if iss.shape != (F,):
             raise ValueError("issuer_idx: one per file")
         t = C.c_uint64(0)
-        self._ck(self._lib.ctmr_submit_pem(self._h, addr, fb.ctypes.data, F, iss.ctypes.data if F else None, C.byref(t)))
-        self._pem_files[t.value] = F
+        self._ck(self._lib.ctmr_submit_pem(self._h, _addr(text), fb.ctypes.data, F, iss.ctypes.data if F else None, C.byref(t)))
+        self._text_tickets[t.value] = ("submit_pem", F)
         return t.value
 
     def wait_pem(self, ticket: int) -> BatchResult:
         """The ticket's result (ctmr_wait_pem; the size query is done here): BatchResult with file_first, bad and info.
         A file outside the grammar has no certificates and its offset in bad; the call does not fail for it."""
-        F = self._pem_files.get(ticket)
-        if F is None:
-            raise CtmrError(N.E_NOTFOUND, "not a ticket of submit_pem, or already collected")
         info, st = N.PemDecodeInfo(), N.BatchStats()
-        first = np.zeros(F + 1, np.uint64)
-        bad = np.zeros(max(F, 1), np.uint64)
-        # the size query; a ticket without certificates is collected by it, so the verdicts are asked for here too
-        rc = self._lib.ctmr_wait_pem(self._h, ticket, 0, None, None, first.ctypes.data, bad.ctypes.data, C.byref(info), C.byref(st))
-        n = int(info.certificates) if rc == N.E_RANGE else 0
-        records = np.zeros(n, dtype=RECORD_DTYPE)
-        new_idx = np.zeros(max(n, 1), dtype=np.uint64)
-        if rc == N.E_RANGE:
-            rc = self._lib.ctmr_wait_pem(self._h, ticket, n, records.ctypes.data, new_idx.ctypes.data, first.ctypes.data, bad.ctypes.data,
-                                         C.byref(info), C.byref(st))
-        del self._pem_files[ticket]   # collected, or failed with its super-batch: either way it is gone
-        self._ck(rc)
-        return BatchResult(records, new_idx[:st.n_new], st, first, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:F]], info)
+        records, new_idx, _, first, bad = self._wait_text(
+            "submit_pem", ticket, lambda: int(info.certificates),
+            lambda cap, rec, new, ts, first, bad: self._lib.ctmr_wait_pem(
+                self._h, ticket, cap, _addr(rec), _addr(new), first.ctypes.data, bad.ctypes.data, C.byref(info), C.byref(st)))
+        return BatchResult(records, new_idx[:st.n_new], st, first, bad, info)
 
     def map_batch_device(self, d_payload, d_offsets, d_issuer_idx, d_entry_type, n, d_records=0,
                          d_new_idx=0) -> N.BatchStats:
@@ -540,10 +530,9 @@ class Engine:
         from . import pem_text
         text, fb = pem_text.join(files)
         buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
-        addr = lambda a: a.ctypes.data if a is not None else None
         (payload, offsets, first), info = self._pd_call(
-            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode(self._h, buf.ctypes.data, fb.ctypes.data, len(files), addr(p), pc,
-                                                                     addr(o), oc, addr(ff), C.byref(info)),
+            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode(self._h, buf.ctypes.data, fb.ctypes.data, len(files), _addr(p), pc,
+                                                                     _addr(o), oc, _addr(ff), C.byref(info)),
             lambda pb, no, nf: (np.empty(pb, np.uint8), np.empty(no, np.uint64), np.empty(nf, np.uint64)))
         return payload, offsets, first, info
 
@@ -577,10 +566,9 @@ class Engine:
         text, fb = pem_text.join(files)
         buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
         bad = np.empty(max(len(files), 1), np.uint64)
-        addr = lambda a: a.ctypes.data if a is not None else None
         (payload, offsets, first), info = self._pd_call(
-            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_each(self._h, buf.ctypes.data, fb.ctypes.data, len(files), addr(p), pc,
-                                                                          addr(o), oc, addr(ff), bad.ctypes.data, C.byref(info)),
+            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_each(self._h, buf.ctypes.data, fb.ctypes.data, len(files), _addr(p), pc,
+                                                                          _addr(o), oc, _addr(ff), bad.ctypes.data, C.byref(info)),
             lambda pb, no, nf: (np.empty(pb, np.uint8), np.empty(no, np.uint64), np.empty(nf, np.uint64)))
         return payload, offsets, first, info, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:len(files)]]
 
