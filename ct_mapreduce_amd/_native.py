@@ -76,6 +76,14 @@ class MetaItem(C.Structure):
                 ("off", C.c_uint32), ("len", C.c_uint32), ("pad", C.c_uint32)]
 
 
+WB_PEM, WB_META = 1, 2
+
+
+class WritebackInfo(C.Structure):
+    _fields_ = [("n_new", C.c_uint64), ("pem_bytes", C.c_uint64), ("n_items", C.c_uint64), ("item_bytes", C.c_uint64),
+                ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class IssuerInfo(C.Structure):
     _fields_ = [("valid", C.c_int32), ("canonical_idx", C.c_uint32), ("spki_sha256", C.c_uint8 * 32),
                 ("issuer_id", C.c_char * 48)]
@@ -268,6 +276,9 @@ SIGNATURES = {
     "ctmr_meta_new_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ctmr_meta_new": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
     "ctmr_meta_reset": (C.c_int, [_P]),
+    "ctmr_set_pipeline_writeback": (C.c_int, [_P, C.c_uint32]),
+    "ctmr_ticket_writeback": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64,
+                                        C.POINTER(WritebackInfo)]),
     "ctmr_fingerprint_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, C.POINTER(C.c_float)]),
     # include/ctmr_bench.h — the synthetic corpus generator: exported by the same library, NOT part of the drop-in ABI
     "ctmr_synth_entries_host": (C.c_uint64, [C.POINTER(SynthConfig), C.c_uint64, C.c_uint64, _P, _P, C.c_uint64]),

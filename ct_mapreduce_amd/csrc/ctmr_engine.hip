@@ -179,6 +179,7 @@ struct ctmr_engine {
   std::mutex mu;
   std::atomic<ctmr_pipeline*> pipe{nullptr};  // asynchronous host ingestion (engine/pipeline.inc), created on first use
   std::mutex pipe_mu;
+  std::atomic<uint32_t> pipe_wb{0};           // ctmr_set_pipeline_writeback: CTMR_WB_* of the super-batches opened from now on
   mutable std::string err;
   mutable std::mutex err_mu;
   int device = 0;
@@ -262,8 +263,8 @@ struct ctmr_engine {
   DevStats* d_stats = nullptr;
   uint32_t* d_result = nullptr;        // 2 words for point ops
   unsigned long long* d_count = nullptr;
-  void* d_scratch[28] = {};            // growable buffers
-  size_t scratch_cap[28] = {};
+  void* d_scratch[32] = {};            // growable buffers
+  size_t scratch_cap[32] = {};
   RoundCtx rd;                         // the last batch (engine/map.inc)
   // the last ctmr_map_batch (host variant): what ctmr_pem_new encodes
   uint64_t last_n = 0, last_n_new = 0;
@@ -283,7 +284,9 @@ enum { SC_RECORDS = 0, SC_SLOTID, SC_BLKNEW, SC_BLKBASE, SC_ENT, SC_STAGE_A, SC_
        SC_NFX,    // (round 3: strict_strings' pre-pass; unused since the check moved into the walk)
        SC_KEYPOS, // strict_spki: where the EC points lie that owe the curve equation (map → k_ec_resolve)
        SC_PEMBLK, // k_pem_blocks: per 7 KiB output block (PEM_S) of the PEM stream, the first certificate in it
-       SC_PEMINFO // k_pem_len: (offset, length) of every certificate of the NEW list
+       SC_PEMINFO,// k_pem_len: (offset, length) of every certificate of the NEW list
+       SC_WB,     // the pipeline's write-back: the tables of its item passes (engine/pipeline_writeback.inc)
+       SC_WBBYTES // … and the items' packed bytes
        };  // strict_strings: the pre-pass's finding per entry  // owner-computes exchange (engine/exchange.inc)
 constexpr uint32_t UNREG_CAP = 16384;
 
@@ -711,6 +714,7 @@ extern "C" {
 #include "engine/pipeline.inc"
 #include "engine/meta.inc"
 #include "engine/pem.inc"
+#include "engine/pipeline_writeback.inc"
 #include "engine/exchange.inc"
 #include "engine/sets.inc"
 #include "engine/group.inc"

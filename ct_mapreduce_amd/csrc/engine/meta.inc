@@ -79,6 +79,31 @@ static int meta_device_locked(ctmr_engine* e, const uint8_t* d_payload, const ui
   return CTMR_OK;
 }
 
+// The first sightings among the nn new certificates of a batch into SC_ITEMS, sized here: ctmr_meta_new's and the ingestion
+// pipeline's write-back (engine/pipeline_writeback.inc) both collect through this one loop.  An item buffer that turns out
+// too small clears the memo (meta_device_locked) and the run is repeated, up to three runs.
+static int meta_collect_locked(ctmr_engine* e, const uint8_t* d_payload, const uint64_t* d_offsets, const uint64_t* d_ends,
+                               const ctmr_record* d_records, const uint64_t* d_new_idx, uint64_t nn, uint64_t* n_items) {
+  *n_items = 0;
+  if (nn == 0) return CTMR_OK;
+  int r;
+  uint64_t cap = std::min<uint64_t>(3 * nn + 1024, 16ull << 20);
+  for (int attempt = 0;; attempt++) {
+    if ((r = ensure(e, SC_ITEMS, cap * sizeof(ctmr_meta_item)))) return r;
+    uint64_t got = 0;
+    r = meta_device_locked(e, d_payload, d_offsets, d_ends, d_records, d_new_idx, nn, (ctmr_meta_item*)e->d_scratch[SC_ITEMS], cap, &got);
+    if (r == CTMR_OK) {
+      *n_items = got;
+      return CTMR_OK;
+    }
+    if (r != CTMR_E_RANGE || attempt == 2) return r;
+    // the memo was cleared: the next run re-reports everything into a buffer that fits.  `got` of the FIRST run counted
+    // against the memo earlier batches left — a cold memo reports those items again, and when they are more than the
+    // 1024 of slack the second run overflows too; its own count is the cold one, which the third run repeats.
+    cap = got + 1024;
+  }
+}
+
 int ctmr_meta_new_device(ctmr_engine* e, const uint8_t* d_payload, const uint64_t* d_offsets, const uint64_t* d_ends,
                          const ctmr_record* d_records, const uint64_t* d_new_idx, uint64_t n_new,
                          ctmr_meta_item* d_items, uint64_t items_cap, uint64_t* n_items) {
@@ -109,23 +134,9 @@ int ctmr_meta_new(ctmr_engine* e, ctmr_meta_item* items, uint64_t items_cap, uin
   const uint64_t* ends = e->last_is_view ? (const uint64_t*)(V + e->last_o_end) : nullptr;
   int r;
   if (!e->last_meta_valid) {
-    uint64_t cap = std::min<uint64_t>(3 * nn + 1024, 16ull << 20);
-    for (int attempt = 0;; attempt++) {
-      if ((r = ensure(e, SC_ITEMS, cap * sizeof(ctmr_meta_item)))) return r;
-      uint64_t got = 0;
-      r = meta_device_locked(e, (const uint8_t*)e->d_scratch[SC_STAGE_A], offs, ends,
-                             (const ctmr_record*)e->d_scratch[SC_RECORDS], (const uint64_t*)(B + e->last_o_new), nn,
-                             (ctmr_meta_item*)e->d_scratch[SC_ITEMS], cap, &got);
-      if (r == CTMR_OK) {
-        e->last_meta_items = got;
-        break;
-      }
-      if (r != CTMR_E_RANGE || attempt == 2) return r;
-      // the memo was cleared: the next run re-reports everything into a buffer that fits.  `got` of the FIRST run counted
-      // against the memo earlier batches left — a cold memo reports those items again, and when they are more than the
-      // 1024 of slack the second run overflows too; its own count is the cold one, which the third run repeats.
-      cap = got + 1024;
-    }
+    if ((r = meta_collect_locked(e, (const uint8_t*)e->d_scratch[SC_STAGE_A], offs, ends, (const ctmr_record*)e->d_scratch[SC_RECORDS],
+                                 (const uint64_t*)(B + e->last_o_new), nn, &e->last_meta_items)))
+      return r;
     e->last_meta_valid = true;
   }
   const uint64_t ni = e->last_meta_items;

@@ -7,6 +7,8 @@
 // bytes of a ticket have one spelling each (slot_iss, slot_et, slot_ticket_bytes), the worker runs a pipe_run_* of one
 // signature per form, and the two text forms have one submit (pipe_submit_text), one opening of their worker steps
 // (pipe_text_reserve) and one account of a ticket's bodies (PipeTextWait::info), put into either public struct.
+// The back of the pipeline — PEM and first sightings of what a super-batch found new, per ticket (ctmr_set_pipeline_writeback,
+// ctmr_ticket_writeback) — is engine/pipeline_writeback.inc, behind engine/meta.inc and engine/pem.inc.
 //
 // The reference's downloader hands insertCTWorker one get-entries response at a time — at most 1 001 entries
 // (cmd/ct-fetch/ct-fetch.go:417-424) — through a 16 384-entry channel (:132), and the workers drain it concurrently
@@ -82,6 +84,17 @@ struct PipeSlot {
   std::vector<uint64_t> cert_lay;                       // PEM, the worker's: the layout of every certificate (a ticket's regular / irregular)
   ctmr_decode_stats dstats{};
   std::vector<PipeTicket> tickets;
+  // write-back (engine/pipeline_writeback.inc): CTMR_WB_* as they stood when the super-batch was opened, and what the worker
+  // left for its tickets.  Pinned, grown by need, allocated only when a flag is on.
+  uint32_t wb = 0;
+  PinMem h_pem; size_t h_pem_cap = 0;                   // the PEM blocks of the NEW list, back to back
+  PinMem h_pemoff; size_t h_pemoff_cap = 0;             // u64[n_new + 1]
+  PinMem h_items; size_t h_items_cap = 0;               // ctmr_meta_item[wb_items]: by new entry, (kind, off) inside, entry from its ticket's first
+  PinMem h_istart; size_t h_istart_cap = 0;             // u64[n_new + 1]: where each new entry's items begin
+  PinMem h_iboff; size_t h_iboff_cap = 0;               // u64[wb_items + 1]: where each item's bytes begin
+  PinMem h_ibytes; size_t h_ibytes_cap = 0;             // the items' bytes, back to back in item order
+  uint64_t wb_pem_bytes = 0, wb_items = 0, wb_item_bytes = 0;
+  std::vector<uint64_t> wb_tfirst;                      // the tickets' first entries and the slot's n: the item passes rebase by it
   hipEvent_t ev_h2d[PIPE_MAX_STREAMS] = {};
   // result
   int rc = CTMR_OK;
@@ -177,6 +190,8 @@ int pipe_close_locked(ctmr_engine* e, ctmr_pipeline* p) {
 // raw forms' decode leaves on the device, for the tickets' decode stats.
 int pipe_run_json(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view);  // engine/pipeline_json.inc
 int pipe_run_pem(ctmr_engine* e, PipeSlot& s, ctmr_entry_view* view);   // engine/pipeline_pem.inc
+// … and behind whichever ran, when the super-batch asks for it (s.wb): PEM and first sightings of its NEW list
+int pipe_writeback_run(ctmr_engine* e, PipeSlot& s, const ctmr_entry_view& view);  // engine/pipeline_writeback.inc
 
 // The map + reduce over s.n certificates at `der` (s.d_payload, or what the PEM step decoded), their offsets in s.d_meta.
 int pipe_map_packed(ctmr_engine* e, PipeSlot& s, const uint8_t* der, const uint8_t* entry_type, uint64_t bytes) {
@@ -264,6 +279,7 @@ void pipe_worker(ctmr_engine* e) {
         if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
         if (h != hipSuccess) rc = fail(e, CTMR_E_HIP, "%s", hipGetErrorString(h));
       }
+      if (rc == CTMR_OK && s.wb) rc = pipe_writeback_run(e, s, view);
       if (rc != CTMR_OK) {
         std::lock_guard<std::mutex> eg2(e->err_mu);  // submitters may fail() concurrently under err_mu only
         err = e->err;
@@ -369,6 +385,8 @@ int pipe_open_for(ctmr_engine* e, ctmr_pipeline* p, std::unique_lock<std::mutex>
   s.n = s.bytes = 0;
   s.any_type = false;
   s.form = form;
+  s.wb = e->pipe_wb.load(std::memory_order_relaxed);
+  s.wb_pem_bytes = s.wb_items = s.wb_item_bytes = 0;
   s.tickets.clear();
   s.body_rb.assign(1, 0);
   s.body_first.clear();

@@ -15,6 +15,8 @@
 //   kernels/pem.h       k_pem_len, k_pem_encode
 //   kernels/entries.h   k_decode_match (decode + first Chain[0] match round), k_chain0_match, k_entry_decode (sweep builds)
 //   kernels/meta.h      k_meta_new
+//   kernels/writeback.h k_wb_count / k_wb_place / k_wb_order / k_wb_gather (a super-batch's first sightings grouped, ordered and
+//                       rebased per ticket, their bytes packed: the ingestion pipeline's write-back)
 //   kernels/misc.h      k_fingerprint, k_set_op / k_sweep / k_rehash / k_arena_compact / k_build_pairs / k_list,
 //                       k_synth_*
 //   kernels/image.h     k_pairs_slots / k_known_export / k_known_count / k_known_pack / k_known_bloom (the known-certificate image)
@@ -49,6 +51,7 @@
 #include "kernels/pem.h"
 #include "kernels/entries.h"
 #include "kernels/meta.h"
+#include "kernels/writeback.h"
 #include "kernels/misc.h"
 #include "kernels/image.h"
 #include "kernels/lists.h"

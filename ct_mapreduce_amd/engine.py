@@ -134,6 +134,22 @@ class BatchResult:
     info: N.PemDecodeInfo = None    # wait_pem: the ticket's own
 
 
+@dataclass
+class Writeback:
+    """Engine.ticket_writeback: what a ticket's super-batch wrote back for it."""
+    pem_buf: np.ndarray      # u8: the PEM blocks of the ticket's new entries, back to back, in the order of its new_idx
+    pem_offsets: np.ndarray  # u64[n_new + 1] (pem on), else [0]; both arrays go to HostWriter.submit as they are
+    items: list              # [(kind, entry, issuer_idx, exp_hour, bytes)] as Engine.meta_new(), entry relative to the ticket,
+                             # ordered by (entry, kind, off)
+    info: N.WritebackInfo = None
+    offs: list = None        # per item: where its bytes lie in its certificate (ctmr_meta_item.off)
+
+    def pem_blocks(self):
+        """The list of bytes Engine.pem_new() gives."""
+        raw = self.pem_buf.tobytes()
+        return [raw[int(self.pem_offsets[k]):int(self.pem_offsets[k + 1])] for k in range(len(self.pem_offsets) - 1)]
+
+
 class Engine:
     def __init__(self, device=0, table_slots=0, pair_slots=0, max_issuers=0, certs_per_tile=0,
                  lds_tile_bytes=0, map_variant=0, profile=False, collect_meta=False, max_table_slots=0):
@@ -345,6 +361,34 @@ class Engine:
             lambda cap, rec, new, ts, first, bad: self._lib.ctmr_wait_pem(
                 self._h, ticket, cap, _addr(rec), _addr(new), first.ctypes.data, bad.ctypes.data, C.byref(info), C.byref(st)))
         return BatchResult(records, new_idx[:st.n_new], st, first, bad, info)
+
+    # ---- write-back for tickets (ctmr_set_pipeline_writeback / ctmr_ticket_writeback): PEM and first sightings of what a
+    # ticket found new, without a synchronous call
+    def set_pipeline_writeback(self, pem=False, meta=False):
+        """For the super-batches opened from now on (flush() first to cut the stream here): pem — the PEM blocks of every
+        ticket's new entries, meta — their first sightings (needs collect_meta=True)."""
+        self._ck(self._lib.ctmr_set_pipeline_writeback(self._h, (N.WB_PEM if pem else 0) | (N.WB_META if meta else 0)))
+
+    def ticket_writeback(self, ticket: int) -> "Writeback":
+        """The ticket's slice of its super-batch's write-back (the size query is done here).  Call it BEFORE the ticket's
+        wait, any number of times; afterwards it raises CtmrError(E_NOTFOUND)."""
+        info = N.WritebackInfo()
+        rc = self._lib.ctmr_ticket_writeback(self._h, ticket, None, 0, None, None, 0, None, 0, C.byref(info))
+        if rc not in (0, N.E_RANGE):
+            self._ck(rc)
+        pem = np.zeros(max(int(info.pem_bytes), 1), np.uint8)
+        offs = np.zeros(int(info.n_new) + 1, np.uint64)
+        items = (N.MetaItem * max(int(info.n_items), 1))()
+        buf = np.zeros(max(int(info.item_bytes), 1), np.uint8)
+        if rc == N.E_RANGE:
+            self._ck(self._lib.ctmr_ticket_writeback(self._h, ticket, pem.ctypes.data, pem.size, offs.ctypes.data, items, int(info.n_items),
+                                                     buf.ctypes.data, buf.size, C.byref(info)))
+        raw, at, out = buf.tobytes(), 0, []
+        for it in items[:int(info.n_items)]:
+            out.append((it.kind, int(it.entry), it.issuer_idx, it.exp_hour, raw[at:at + it.len]))
+            at += it.len
+        n_new = int(info.n_new) if info.flags & N.WB_PEM else 0
+        return Writeback(pem[:int(info.pem_bytes)], offs[:n_new + 1], out, info, [int(it.off) for it in items[:int(info.n_items)]])
 
     def map_batch_device(self, d_payload, d_offsets, d_issuer_idx, d_entry_type, n, d_records=0,
                          d_new_idx=0) -> N.BatchStats:

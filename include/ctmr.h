@@ -190,7 +190,8 @@ int ctmr_map_batch_device(ctmr_engine* e, const uint8_t* d_payload, const uint64
  *      wins WasUnknown across everything in flight, as in a sequence of synchronous calls.  Up to 4 super-batches may
  *      be unfinished or uncollected; a submit that would need a fifth blocks while one is still running and fails
  *      with CTMR_E_RANGE when all four only wait to be collected.  Thread-safe (several downloader threads may submit
- *      and wait).  ctmr_pem_new / ctmr_meta_new refer to synchronous calls only. ---- */
+ *      and wait).  ctmr_pem_new / ctmr_meta_new refer to synchronous calls only; what they give, a ticket gets through
+ *      ctmr_set_pipeline_writeback / ctmr_ticket_writeback (below, behind ctmr_meta_new). ---- */
 typedef uint64_t ctmr_ticket;
 int ctmr_submit_batch(ctmr_engine* e, const uint8_t* payload, const uint64_t* offsets, const uint32_t* issuer_idx,
                       const uint8_t* entry_type, uint64_t n, ctmr_ticket* ticket);
@@ -1219,6 +1220,46 @@ int ctmr_meta_new_device(ctmr_engine* e, const uint8_t* d_payload, const uint64_
 int ctmr_meta_new(ctmr_engine* e, ctmr_meta_item* items, uint64_t items_cap, uint8_t* bytes, size_t bytes_cap,
                   uint64_t* n_items, size_t* bytes_need);
 int ctmr_meta_reset(ctmr_engine* e);
+
+/* ---- write-back for the tickets of the asynchronous pipeline: what FilesystemDatabase.Store does for a certificate that
+ *      WasUnknown (storage/filesystemdatabase.go:158-211) — IssuerMetadata.Accumulate, AllocateExpDateAndIssuer on a first
+ *      (issuer, expDate), StoreCertificatePEM(pem.EncodeToMemory(...)) — without a synchronous call per response.
+ *   ctmr_set_pipeline_writeback: the opt-in, per engine.  flags: CTMR_WB_PEM (the PEM blocks of the new entries, as
+ *      ctmr_pem_new) | CTMR_WB_META (their first sightings, as ctmr_meta_new; needs config.collect_meta, else
+ *      CTMR_E_INVAL); unknown bits → CTMR_E_INVAL.  The flags apply to super-batches OPENED after the call — call
+ *      ctmr_flush first to cut the stream exactly here.  0 (the default): the pipeline allocates, launches and copies
+ *      nothing for it.  With a flag on, the worker encodes / collects for every super-batch it has mapped, before its
+ *      tickets complete.
+ *   ctmr_ticket_writeback: the ticket's own slice, for the tickets of all four forms (ctmr_submit_batch,
+ *      ctmr_submit_entries, ctmr_submit_entries_json, ctmr_submit_pem).  Blocks as ctmr_wait* does (and launches the open
+ *      super-batch when the ticket is in it); does NOT collect the ticket: it may be called any number of times, with the
+ *      same answer, until the ticket's own ctmr_wait* collects it — afterwards CTMR_E_NOTFOUND.  When the super-batch
+ *      failed: the code the ticket's wait returns.  Thread-safe as the waits are.
+ *      Two-call convention: *info is always filled (all zero for a super-batch opened with flags 0: CTMR_OK, nothing
+ *      needed); a buffer that is NULL or too small for a non-empty part → CTMR_E_RANGE, nothing written; a part whose
+ *      flag was off reports 0 and needs no buffer.
+ *        PEM    pem[pem_offsets[k], pem_offsets[k+1]) is the block of the ticket's k-th new entry, in the order of the
+ *               new_idx its wait returns; pem_offsets has n_new + 1 slots, pem_offsets[0] == 0.  The bytes are those
+ *               ctmr_pem_new gives after a synchronous call over the same entries.
+ *        items  ctmr_meta_item as ctmr_meta_new returns them, `entry` relative to the TICKET, ordered by (entry, kind,
+ *               off); their bytes back to back in `bytes`, in item order (CTMR_MK_HOST and CTMR_MK_EXPDATE carry none and
+ *               have len 0).
+ *      ONE memo per engine, shared with the synchronous calls: a first sighting is reported once in the engine's life (until
+ *      ctmr_meta_reset), to ONE ticket — the one whose entry claimed it — and never again by a later ctmr_meta_new.  When
+ *      two new certificates of one super-batch bring the same item either of them may get it, hence either of their
+ *      tickets (as inside one synchronous batch; the host's sets "Must tolerate duplicate information",
+ *      issuermetadata.go:89).  The item-buffer overflow rule of ctmr_meta_new holds for the worker too: the memo is
+ *      cleared and the run repeated (up to three runs), so such a super-batch re-reports earlier sightings. ---- */
+enum { CTMR_WB_PEM = 1, CTMR_WB_META = 2 };
+int ctmr_set_pipeline_writeback(ctmr_engine* e, uint32_t flags);
+typedef struct {
+  uint64_t n_new, pem_bytes, n_items, item_bytes;  /* of this ticket */
+  uint32_t flags, pad;                             /* CTMR_WB_* of the ticket's super-batch */
+} ctmr_writeback_info;
+int ctmr_ticket_writeback(ctmr_engine* e, ctmr_ticket t,
+                          uint8_t* pem, uint64_t pem_cap, uint64_t* pem_offsets /* n_new + 1 */,
+                          ctmr_meta_item* items, uint64_t items_cap, uint8_t* bytes, uint64_t bytes_cap,
+                          ctmr_writeback_info* info);
 
 /* ---- whole-certificate SHA-256 fingerprints (auxiliary; NOT on the reference's path, which never hashes a leaf —
  *      SURVEY.md D2; this is the one-certificate-per-lane SHA-256 kernel BASELINE.json's north_star names).
