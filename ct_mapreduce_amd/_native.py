@@ -134,6 +134,15 @@ class KnownListsInfo(C.Structure):
                 ("text_bytes", C.c_uint64), ("ids_bytes", C.c_uint64)]
 
 
+class KnownFindHit(C.Structure):
+    _fields_ = [("records", C.c_uint32), ("first_hour", C.c_int32), ("last_hour", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class KnownFindInfo(C.Structure):
+    _fields_ = [("probes", C.c_uint64), ("host_probes", C.c_uint64), ("found", C.c_uint64), ("host_found", C.c_uint64),
+                ("sets_kept", C.c_uint64), ("members_read", C.c_uint64)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_issuers", C.c_uint32), ("zipf", C.c_uint32),
                 ("dup_permille", C.c_uint32), ("ca_permille", C.c_uint32),
@@ -200,6 +209,10 @@ SIGNATURES = {
                                          C.POINTER(KnownListsInfo)]),
     "ctmr_known_image_lists_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_int64, _P, C.c_size_t, _P, C.c_size_t,
                                                 _P, C.c_size_t, C.POINTER(KnownListsInfo)]),
+    "ctmr_known_image_find": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int64, _P, C.c_size_t, _P, C.c_size_t,
+                                        C.POINTER(KnownFindInfo)]),
+    "ctmr_known_image_find_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, C.c_int64,
+                                               _P, C.c_uint64, _P, C.c_size_t, C.POINTER(KnownFindInfo)]),
     "ctmr_known_image_resp": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t, C.POINTER(KnownRespInfo)]),
     "ctmr_known_image_resp_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, _P, C.c_size_t,
                                                C.POINTER(KnownRespInfo)]),

@@ -724,6 +724,7 @@ extern "C" {
 #include "engine/resp.inc"
 #include "engine/sort.inc"
 #include "engine/merge.inc"
+#include "engine/find.inc"
 #include "engine/resp_parse.inc"
 #include "engine/text_decode.inc"
 #include "engine/entries_json.inc"

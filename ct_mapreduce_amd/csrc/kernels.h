@@ -37,6 +37,8 @@
 //                       order inside a known-certificate set: a segmented radix sort of member records)
 //   kernels/merge.h     k_merge_ascending / k_merge_unique / k_merge_first / k_merge_rank / k_merge_sets / k_merge_place
 //                       (set algebra on known-certificate images: union, minus, intersect of canonical member records)
+//   kernels/find.h      k_find_build / k_find_scan / k_find_finish (serials looked up in a known image whatever their
+//                       expiration date: the probes in a hash table, the image streamed once against it)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once
 #include "kernels/readers.h"
@@ -62,3 +64,4 @@
 #include "kernels/pem_decode.h"
 #include "kernels/sort.h"
 #include "kernels/merge.h"
+#include "kernels/find.h"

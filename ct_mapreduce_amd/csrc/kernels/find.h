@@ -1,0 +1,174 @@
+// kernels/find.h — serials looked up in a known image whatever their expiration date (include/ctmr.h
+// ctmr_known_image_find*).  The probes (the small side) go into an open-addressed table of 8-byte words
+// that stays in cache (k_find_build); the member records of the known image's kept sets (the large side) are streamed
+// once where they lie and walked against it (k_find_scan); a finish pass turns the working hits into the caller's
+// (k_find_finish).  No sort, no staging of the image, no table of the engine.
+// gfx950 (CDNA4, wave64) only; part of kernels.h, which includes the pieces in dependency order.
+#pragma once
+#include "lists.h"
+
+namespace ctmr {
+
+constexpr uint32_t FIND_NO_ISSUER = 0xffffffffu;  // a probe whose Issuer.ID the known image does not name
+
+// What is hashed and compared besides the serial words: the K ordinal of the Issuer.ID and the serial's length — a
+// key_meta of hour 0, with all 32 bits of the ordinal.
+__device__ __forceinline__ unsigned long long find_meta(uint32_t kord, unsigned long long len) {
+  return (len << 56) | (unsigned long long)kord;
+}
+
+// The probes: P's member records where they lie, then n_extra records of the call's own — the members of P's host
+// section that a member record of K can equal (at most 40 octets, an Issuer.ID K names).  Probe i < n_main belongs to
+// the last set of P whose first member is <= i.
+struct FindProbes {
+  const uint8_t* recs;         // n_main records
+  const uint8_t* extra;        // n_extra records
+  const uint32_t* extra_kord;  // the K ordinal of each
+  const uint64_t* set_first;   // n_sets + 1
+  const uint32_t* set_kord;    // per set of P: the K ordinal of its issuer (P ordinal → K ordinal, looked up per set)
+  uint64_t n_main, n_extra;
+  uint32_t n_sets;
+  __device__ __forceinline__ const uint4* rec(uint64_t i) const {
+    return (const uint4*)(i < n_main ? recs + i * KNOWN_REC_BYTES : extra + (i - n_main) * KNOWN_REC_BYTES);
+  }
+};
+
+// The probe table: words of tag (24 bits, key_tag) | probe index + 1 (40 bits); 0 = empty.  mask + 1 is a power of two
+// above the number of probes, so every chain ends at an empty word.
+struct FindTable {
+  unsigned long long* words;
+  uint64_t mask;
+};
+
+// serial_len and the five serial words of a record; → 0, or 1 for a serial_len above 40, 2 for padding that is not zero
+__device__ __forceinline__ uint32_t find_load(const uint4* p, unsigned long long& len, unsigned long long s[5]) {
+  const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
+  len = (unsigned long long)v0.x | ((unsigned long long)v0.y << 32);
+  s[0] = (unsigned long long)v0.z | ((unsigned long long)v0.w << 32);
+  s[1] = (unsigned long long)v1.x | ((unsigned long long)v1.y << 32);
+  s[2] = (unsigned long long)v1.z | ((unsigned long long)v1.w << 32);
+  s[3] = (unsigned long long)v2.x | ((unsigned long long)v2.y << 32);
+  s[4] = (unsigned long long)v2.z | ((unsigned long long)v2.w << 32);
+  if (len > CTMR_MAX_SERIAL) return 1u;
+  uint32_t bad = 0u;
+#pragma unroll
+  for (uint32_t q = 0; q < 5; q++) {  // octets behind serial_len are zero
+    const uint64_t lo = 8ull * q;
+    const unsigned long long pad = len <= lo ? ~0ull : (len >= lo + 8 ? 0ull : (~0ull << (8ull * (len - lo))));
+    if (s[q] & pad) bad = 2u;
+  }
+  return bad;
+}
+
+// One lane per probe.  The working hit of the probe is initialised — records 0, first_hour INT32_MAX, last_hour
+// INT32_MIN, and in the reserved word the probe's K ordinal, which k_find_scan compares and k_find_finish clears — and
+// the probe claims the first empty word from its home slot on (atomicCAS, linear).  Equal probes take one word each.
+// A bad record (*err as k_known_count reports it) and a probe whose issuer K does not name are not inserted.
+__global__ void __launch_bounds__(256) k_find_build(FindProbes p, FindTable t, uint4* hits, uint32_t* err) {
+  const uint64_t n = p.n_main + p.n_extra;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t bad = 0u;
+  if (i < n) {
+    unsigned long long len, s[5];
+    bad = find_load(p.rec(i), len, s);
+    uint32_t kord = FIND_NO_ISSUER;
+    if (i < p.n_main) {
+      const uint64_t wfirst = i - lane, wlast = wfirst + 63u < p.n_main ? wfirst + 63u : p.n_main - 1u;
+      const uint32_t s_lo = known_set_of(p.set_first, 0u, p.n_sets - 1u, wfirst);
+      const uint32_t s_hi = known_set_of(p.set_first, s_lo, p.n_sets - 1u, wlast);
+      kord = p.set_kord[known_set_of(p.set_first, s_lo, s_hi, i)];
+    } else {
+      kord = p.extra_kord[i - p.n_main];
+    }
+    if (bad) kord = FIND_NO_ISSUER;
+    hits[i] = make_uint4(0u, 0x7fffffffu, 0x80000000u, kord);
+    if (kord != FIND_NO_ISSUER) {
+      const unsigned long long h = key_hash(find_meta(kord, len), s);
+      const unsigned long long word = ((unsigned long long)key_tag(h) << 40) | (i + 1ull);
+      uint64_t j = h & t.mask;
+      for (uint64_t k = 0; k <= t.mask; k++) {
+        if (atomicCAS(&t.words[j], 0ull, word) == 0ull) break;
+        j = (j + 1ull) & t.mask;
+      }
+    }
+  }
+  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
+  if (lane == 0 && (mb1 | mb2)) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
+}
+
+// A run of k whole kept sets of K as segments of a virtual record sequence (ListSegs): segment s holds the virtual
+// records [dst[s], dst[s + 1]) and lies at records [src[s], …) of recs; hour[s] and kord[s] are its set's.
+struct FindSegs {
+  const uint8_t* recs;
+  const uint64_t* dst;  // k + 1
+  const uint64_t* src;  // k
+  const int32_t* hour;
+  const uint32_t* kord;
+  uint32_t k;
+};
+
+// One lane per member record of the run: three 16-byte loads (a wave reads 3 KiB in a row), the record validated as
+// k_image_lists_count validates, then the walk from its home slot to the first empty word.  A word of the record's tag
+// names a probe below `limit` whose 48 bytes and K ordinal are compared in full; an equal one gets records + 1 and the
+// set's hour into first_hour / last_hour.  A record that matches nothing reads one table word.
+__global__ void __launch_bounds__(256) k_find_scan(FindSegs g, uint64_t n, FindTable t, FindProbes p, uint64_t limit, uint4* hits,
+                                                   uint32_t* err) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t bad = 0u;
+  if (i < n) {
+    const uint64_t v0 = g.dst[0], wi = i - lane;
+    const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
+    const uint32_t s_lo = known_set_of(g.dst, 0u, g.k - 1u, wfirst);
+    const uint32_t s_hi = known_set_of(g.dst, s_lo, g.k - 1u, wlast);
+    const uint32_t set = known_set_of(g.dst, s_lo, s_hi, v);
+    unsigned long long len, s[5];
+    bad = find_load((const uint4*)(g.recs + (g.src[set] + (v - g.dst[set])) * KNOWN_REC_BYTES), len, s);
+    if (!bad) {
+      const uint32_t kord = g.kord[set];
+      const int32_t hour = g.hour[set];
+      const unsigned long long h = key_hash(find_meta(kord, len), s);
+      const unsigned long long tag = (unsigned long long)key_tag(h);
+      uint64_t j = h & t.mask;
+      for (uint64_t k = 0; k <= t.mask; k++) {
+        const unsigned long long w = t.words[j];
+        if (w == 0ull) break;
+        const uint64_t pi = (w & REF_MASK) - 1ull;
+        if ((w >> 40) == tag && pi < limit) {
+          unsigned long long plen, ps[5];
+          find_load(p.rec(pi), plen, ps);
+          const bool eq = (hits[pi].w == kord) & (plen == len) & (ps[0] == s[0]) & (ps[1] == s[1]) & (ps[2] == s[2]) &
+                          (ps[3] == s[3]) & (ps[4] == s[4]);
+          if (eq) {
+            atomicAdd(&hits[pi].x, 1u);
+            atomicMin((int*)&hits[pi].y, hour);
+            atomicMax((int*)&hits[pi].z, hour);
+          }
+        }
+        j = (j + 1ull) & t.mask;
+      }
+    }
+  }
+  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
+  if (lane == 0 && (mb1 | mb2)) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
+}
+
+// The working hits → the caller's (in place when out == in): the hours of a probe without a record become 0, the
+// reserved word 0; cnt[blk] = the block's probes with records > 0.
+__global__ void __launch_bounds__(256) k_find_finish(const uint4* in, uint4* out, uint64_t n, unsigned long long* cnt) {
+  __shared__ uint32_t ws[4];
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  bool found = false;
+  if (i < n) {
+    const uint4 h = in[i];
+    found = h.x != 0u;
+    out[i] = found ? make_uint4(h.x, h.y, h.z, 0u) : make_uint4(0u, 0u, 0u, 0u);
+  }
+  const unsigned long long m = __ballot(found);
+  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
+}
+
+}  // namespace ctmr

@@ -149,6 +149,15 @@ class Group:
             out = got if out is None else (out[0] | got[0], out[1] | got[1])
         return out
 
+    def known_find(self, probes, now):
+        """Engine.known_find over the group → (hits, host_hits): every local rank answers for what it holds and the host
+        adds the records and takes the lowest first_hour and the highest last_hour over the ranks that found the probe
+        (known_image.merge_hits).  A Bloom-mode rank's SHADOW keys are left out of its export, so each key counts once.
+        In-process groups only."""
+        from .known_image import merge_hits
+        got = [e.known_find(probes, now) for e in self.engines]
+        return merge_hits([g[0] for g in got]), merge_hits([g[1] for g in got])
+
     def known_remove(self, image) -> list:
         """SetRemove on every local rank for every member of `image` → the per-rank stats.  In-process groups only."""
         return [e.known_remove(image) for e in self.engines]

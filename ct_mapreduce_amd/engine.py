@@ -1182,6 +1182,54 @@ class Engine:
         writer.store_known_lists(ids, ioff, text, toff)
         return int(info.issuers)
 
+    # ---- serials looked up in an image whatever their expiration date (include/ctmr.h ctmr_known_image_find*, DESIGN.md
+    # §25; CPU twin: known_image.find)
+    def known_image_find(self, known, probes, now):
+        """For every member of the probe image `probes` (known_image.probes builds one): under how many sets of `known`
+        kept at `now` the same Issuer.ID holds the same serial, and the lowest and highest exp hour among them.
+        → (hits per member record of `probes`, host_hits per host-section member: numpy known_image.HIT_DTYPE; info dict).
+        The engine's own sets and issuers play no part."""
+        from .known_image import HIT_DTYPE
+        known, probes = bytes(known), bytes(probes)
+        n, n_host = self._header_counts(probes)
+        hits, host_hits = np.zeros(max(n, 1), HIT_DTYPE), np.zeros(max(n_host, 1), HIT_DTYPE)
+        info = N.KnownFindInfo()
+        self._ck(self._lib.ctmr_known_image_find(self._h, known, len(known), probes, len(probes), int(now), hits.ctypes.data, n,
+                                                 host_hits.ctypes.data, n_host, C.byref(info)))
+        return hits[:n], host_hits[:n_host], self._stats_dict(info)
+
+    def known_image_find_device(self, k_meta, d_k_members, p_meta, d_p_members, now):
+        """known_image_find with the member records of both images in device memory (torch uint8 tensors) → (hits: torch
+        int32 tensor of shape (probes, 4) on this engine's device — records, first_hour, last_hour, 0 —, host_hits: numpy
+        known_image.HIT_DTYPE, info dict)."""
+        import torch
+        from .known_image import HIT_DTYPE
+        k_meta, p_meta = bytes(k_meta), bytes(p_meta)
+        nk, kptr = self._members_ptr(d_k_members)
+        n, pptr = self._members_ptr(d_p_members)
+        n_host = self._header_counts(p_meta)[1]
+        hits = torch.empty((max(n, 1), 4), dtype=torch.int32, device="cuda:%d" % self.device)
+        host_hits = np.zeros(max(n_host, 1), HIT_DTYPE)
+        info = N.KnownFindInfo()
+        self._ck(self._lib.ctmr_known_image_find_device(self._h, k_meta, len(k_meta), kptr, nk, p_meta, len(p_meta), pptr, n,
+                                                        int(now), C.c_void_p(hits.data_ptr()), n, host_hits.ctypes.data, n_host,
+                                                        C.byref(info)))
+        return hits[:n], host_hits[:n_host], self._stats_dict(info)
+
+    def known_find(self, probes, now):
+        """known_image_find over the engine's own sets: known_export_device followed by known_image_find_device, nothing
+        cleverer.  → (hits, host_hits: numpy known_image.HIT_DTYPE; info dict)."""
+        import torch
+        from .known_image import HIT_DTYPE
+        probes = bytes(probes)
+        n = self._header_counts(probes)[0]
+        k_meta, d_k = self.known_export_device()
+        at = len(probes) - 48 * n
+        d_p = torch.frombuffer(bytearray(probes[at:]), dtype=torch.uint8).to("cuda:%d" % self.device) if n else \
+            torch.empty(0, dtype=torch.uint8, device="cuda:%d" % self.device)
+        hits, host_hits, info = self.known_image_find_device(k_meta, d_k, probes[:at], d_p, now)
+        return hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits, info
+
     # ---- the Redis protocol stream of an image (include/ctmr.h ctmr_known_image_resp*, DESIGN.md §18; CPU twin:
     # known_image.image_resp)
     def _known_resp_call(self, fn, alloc, buf, n):

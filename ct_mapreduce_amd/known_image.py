@@ -7,7 +7,8 @@ checks before it applies an image; `build` is the canonical writer; `sort` is th
 (every set's member records in ascending order, repeats kept); `query` / `subtract` are the twins of
 `Engine.known_query` / `Engine.known_remove` over a dict of sets; `union` / `minus` / `intersect` are the twins of
 `Engine.known_merge` (set algebra on images, key by key); `image_lists` is the twin of `Engine.known_image_lists`
-(per-issuer lists straight from an image, in the image's order); `image_resp` is the twin of `Engine.known_image_resp`
+(per-issuer lists straight from an image, in the image's order); `find` is the twin of `Engine.known_image_find`
+(serials looked up whatever their expiration date) and `probes` builds its probe image; `image_resp` is the twin of `Engine.known_image_resp`
 (the SADD + EXPIREAT stream of an image as it lies, key by key) and `resp_image` its inverse, the twin of
 `Engine.known_resp_image` (a SADD / EXPIREAT stream as it lies → an image, members in stream order); `to_resp` /
 `from_resp` turn an image into the SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start
@@ -463,6 +464,89 @@ def image_lists(image, now) -> list:
             continue
         by_id.setdefault(parts[2], {}).setdefault((span[0], parts[1]), []).append(member)
     return [(i, b"".join(line(m) for k in sorted(by_id[i]) for m in by_id[i][k])) for i in sorted(by_id)]
+
+
+# ---- serials looked up in an image whatever their expiration date (include/ctmr.h ctmr_known_image_find),
+# without a GPU
+
+HIT_DTYPE = np.dtype([("records", "<u4"), ("first_hour", "<i4"), ("last_hour", "<i4"), ("reserved", "<u4")])
+
+
+def probes(serials_by_digest) -> bytes:
+    """The probe image of {32-byte issuer digest: [serials]}: canonical, every set under hour 0 (the hour of a probe is
+    ignored), serials above 40 octets in the host section."""
+    return build({set_key(0, bytes(d)): ms for d, ms in serials_by_digest.items()})
+
+
+def _sections(image):
+    """→ ([(exp hour or None, Issuer.ID, serial)] per member record in image order, the same per host-section member in
+    section order; the hour of a host key is that of its date's first second, None when the date does not parse, with
+    the second at which the key expires beside it): the two sections as `find` reads them."""
+    parse(image)
+    b = bytes(image)
+    _, _, _, n_iss, _, n_sets, n_mem, _, _, _ = _HEADER.unpack_from(b, 0)
+    so = HEADER_BYTES + 32 * n_iss
+    rec = np.frombuffer(b, MEMBER_DTYPE, count=n_mem, offset=len(b) - n_mem * MEMBER_BYTES)
+    dev = []
+    for s in range(n_sets):
+        eh, ordinal, first, count = _SET.unpack_from(b, so + SET_BYTES * s)
+        ident = issuer_id(b[HEADER_BYTES + 32 * ordinal:HEADER_BYTES + 32 * (ordinal + 1)])
+        r = rec[first:first + count]
+        dev += [(eh, ident, bytes(m[:int(l)])) for l, m in zip(r["len"], r["serial"])]
+    host = []
+    for key, member in records(image)[1]:
+        parts = key.split(b"::")
+        if len(parts) != 3:
+            raise ListsError("unexpected key format: %r" % key)
+        host.append((exp_date_span(parts[1]), parts[2], member))
+    return dev, host
+
+
+def find(known, probes, now):
+    """Engine.known_image_find(known, probes, now) without a GPU → (hits, host_hits): numpy HIT_DTYPE, one per member
+    record of `probes` in image order and one per member of its host section in section order.  A probe is (Issuer.ID,
+    serial); its answer counts the member records and host-section members of the sets of `known` kept at `now` under
+    the same ID with the same serial, and gives the lowest and highest exp hour among them (zeros when there are none).
+    Raises ImageError for what `parse` rejects and ListsError for a host key that does not split into three "::" parts,
+    in either operand."""
+    k_dev, k_host = _sections(known)
+    p_dev, p_host = _sections(probes)
+    held = {}
+    for eh, ident, m in k_dev:
+        if _HOUR_LO <= eh < _HOUR_HI and now < (eh + 1) * 3600:
+            held.setdefault((ident, m), []).append(eh)
+    for span, ident, m in k_host:
+        if span is not None and now < span[1]:
+            held.setdefault((ident, m), []).append(span[0] // 3600)
+    out = []
+    for part in (p_dev, p_host):
+        h = np.zeros(len(part), HIT_DTYPE)
+        for i, (_, ident, m) in enumerate(part):
+            hours = held.get((ident, m))
+            if hours:
+                h[i] = (len(hours) % 2 ** 32, min(hours), max(hours), 0)
+        out.append(h)
+    return tuple(out)
+
+
+def merge_hits(per_rank):
+    """The hits of several ranks for the same probes (each a HIT_DTYPE array) as one: the records added, first_hour the
+    minimum and last_hour the maximum over the ranks with records > 0.  The ranks of a group hold each key once."""
+    per_rank = [np.asarray(h) for h in per_rank]
+    out = np.zeros(len(per_rank[0]), HIT_DTYPE)
+    first = np.full(len(out), 2 ** 31 - 1, np.int64)
+    last = np.full(len(out), -2 ** 31, np.int64)
+    total = np.zeros(len(out), np.uint64)
+    for h in per_rank:
+        got = h["records"] > 0
+        total += h["records"]
+        first = np.where(got, np.minimum(first, h["first_hour"]), first)
+        last = np.where(got, np.maximum(last, h["last_hour"]), last)
+    any_ = total > 0
+    out["records"] = (total % np.uint64(2 ** 32)).astype(np.uint32)
+    out["first_hour"] = np.where(any_, first, 0)
+    out["last_hour"] = np.where(any_, last, 0)
+    return out
 
 
 def merge_lists(per_rank) -> list:

@@ -510,6 +510,63 @@ int ctmr_known_image_lists_device(ctmr_engine* e, const uint8_t* meta, size_t me
                                   uint64_t n_members, int64_t now_unix, void* d_text, size_t text_cap, uint8_t* ids,
                                   size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info);
 
+/* ---- serials looked up in an image v1 whatever their expiration date: what a CRL entry, an OCSP response or an incident
+ *      report asks, which name an issuer and a serial and nothing else.  DESIGN.md §25.
+ *
+ * Operands.  Two images v1: K, the known image — any image ctmr_known_import accepts, sorted or not, with or without
+ *   repeated records — and P, the probe image.  P's member records and the members of its host section are the probes;
+ *   the hours in P's set records and in its host keys are ignored: the hour is the wildcard.
+ * Probes.  A probe is the Issuer.ID string of its set and its serial octets.  A set record's ID is the padded base64url
+ *   of the digest the image names (as in ctmr_known_image_lists); a host key's ID is the key's own third part.  A host
+ *   key that does not split into exactly three "::" parts fails the call with CTMR_E_INVAL, in either operand.
+ * Answer.  For every probe, over the KEPT sets of K with the same Issuer.ID that hold a member equal to the probe's
+ *   serial (same length, same octets), a ctmr_known_find_hit (below).
+ * Kept sets.  Exactly the sets ctmr_known_image_lists keeps at now_unix: a set of exp hour h is kept iff
+ *   now_unix < (h + 1) × 3600, and hours outside the years 0000..9999 are skipped; a host key's date is parsed as
+ *   NewExpDate parses it (hour or day resolution; its hour is its first second / 3600, a day key is kept until its last
+ *   second) and a key it cannot parse is skipped.  now_unix = INT64_MIN keeps everything that parses.
+ * Sections.  Both sections of both operands count and a member matches wherever it lies: a pair of K's host section
+ *   whose member has at most CTMR_MAX_SERIAL octets is compared with P's member records as if it were a member record,
+ *   and the other way round (the rule of ctmr_known_merge).  Members above 40 octets can only meet in the two host
+ *   sections.
+ * Repeats.  The call neither sorts nor deduplicates: a record repeated in K counts each time, probes repeated in P each
+ *   get the full answer, a probe whose issuer K does not name gets zeros.
+ * Output.  hits[i] answers P's member record i in image order, host_hits[j] P's host-section member j in section order.
+ *   The two-call convention: a buffer that is too small gives CTMR_E_RANGE with *info filled (found and host_found 0)
+ *   and nothing written; a caller can size from P's header alone.
+ * Validation.  Both metas are checked as ctmr_known_import checks them.  On the device, before the first hit is written,
+ *   every record of P and every record of a kept set of K is checked for serial_len <= 40 and zero padding; the records
+ *   of sets that are not kept are not read.  CTMR_E_INVAL and CTMR_E_NOMEM leave both output buffers as they were; every
+ *   working buffer is allocated before the first output byte.
+ * Read-only.  Nothing of the engine's state is read or changed (table, pair statistics, counters, host-side store,
+ *   Bloom filter, ctmr_table_info), as for ctmr_known_sort: the issuers need not be registered, the operands are const.
+ * K's kept member records are read once where they lie, in runs of whole kept sets of at most 2^27 records, against a
+ * hash table of the probes.  ctmr_known_image_find takes whole images in host memory (both member sections staged on the
+ * device once); ctmr_known_image_find_device takes each operand's meta and member records (device memory of this
+ * engine's device, 16-byte aligned) apart and leaves the hits of P's member records in device memory (16-byte aligned).
+ * Both return after the engine's stream has drained. */
+typedef struct {
+  uint32_t records;     /* member records / host-section members of kept sets equal to the probe.  In an image without
+                           repeated records (a sorted export, any ctmr_known_merge result) this is the number of expDates
+                           under which the issuer's serial is known.  Modulo 2^32. */
+  int32_t first_hour;   /* lowest exp hour among them; 0 when records == 0 */
+  int32_t last_hour;    /* highest: until when the certificate matters; 0 when records == 0 */
+  uint32_t reserved;    /* 0 */
+} ctmr_known_find_hit;
+typedef struct {
+  uint64_t probes, host_probes;  /* P's member records, P's host-section members */
+  uint64_t found, host_found;    /* … of them with records > 0 */
+  uint64_t sets_kept;            /* K's kept set records plus its kept host-section keys (a key of both sections twice) */
+  uint64_t members_read;         /* the member records of K's kept sets */
+} ctmr_known_find_info;
+int ctmr_known_image_find(ctmr_engine* e, const uint8_t* known, size_t known_len, const uint8_t* probes, size_t probes_len,
+                          int64_t now_unix, ctmr_known_find_hit* hits, size_t hits_cap, ctmr_known_find_hit* host_hits,
+                          size_t host_hits_cap, ctmr_known_find_info* info);
+int ctmr_known_image_find_device(ctmr_engine* e, const uint8_t* k_meta, size_t k_meta_len, const void* d_k_members,
+                                 uint64_t k_members, const uint8_t* p_meta, size_t p_meta_len, const void* d_p_members,
+                                 uint64_t p_members, int64_t now_unix, void* d_hits, uint64_t hits_cap,
+                                 ctmr_known_find_hit* host_hits, size_t host_hits_cap, ctmr_known_find_info* info);
+
 /* ---- the Redis protocol stream of an image v1: the SADD commands of every serials:: key and the EXPIREAT
  *      KnownCertificates.setExpiryFlag puts on it (storage/knowncertificates.go:98-104), as `redis-cli --pipe` loads them
  *      into the Redis of a reference deployment.  DESIGN.md §18.
