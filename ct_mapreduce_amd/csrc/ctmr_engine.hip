@@ -422,6 +422,17 @@ int scan_u64(ctmr_engine* e, uint64_t* d_data, uint64_t n, bool inclusive, int w
   return CTMR_OK;
 }
 
+// scan_u64 over n >= 1 words, then the last word to *total: the sum of an inclusive scan, or of an exclusive one whose
+// last word was a zero behind the counts.  Drains the stream; `check`: hipGetLastError behind it, where the site had one.
+int scan_total(ctmr_engine* e, uint64_t* d_data, uint64_t n, bool inclusive, int which, uint64_t* total, bool check = true) {
+  int r;
+  if ((r = scan_u64(e, d_data, n, inclusive, which))) return r;
+  HIPCHK(e, hipMemcpyAsync(total, d_data + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (check) HIPCHK(e, hipGetLastError());
+  return CTMR_OK;
+}
+
 int point_op(ctmr_engine* e, int op, int32_t exp_hour, uint32_t canon, const uint8_t* m, size_t n,
              int* out) {
   unsigned long long s[5];

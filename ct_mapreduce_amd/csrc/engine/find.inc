@@ -11,15 +11,6 @@ namespace {
 
 constexpr uint64_t FIND_CHUNK = 1ull << 27;  // member records of K per launch
 
-// a host-section key as strings.Split(key, "::") splits it: three parts, or false
-bool find_split_key(const std::string& k, std::string* date, std::string* id) {
-  const size_t a = k.find("::"), b = a == std::string::npos ? a : k.find("::", a + 2);
-  if (b == std::string::npos || k.find("::", b + 2) != std::string::npos) return false;
-  *date = k.substr(a + 2, b - a - 2);
-  *id = k.substr(b + 2);
-  return true;
-}
-
 // what the host knows of a probe's answer before the device's part is added
 struct FindAcc {
   uint64_t records = 0;
@@ -44,14 +35,6 @@ struct FindPack {
   template <class T> size_t put(const std::vector<T>& v) { return put(v.data(), v.size() * sizeof(T)); }
 };
 
-void find_record(const std::string& m, std::vector<uint8_t>* out) {
-  const uint64_t len = m.size();
-  const size_t at = out->size();
-  out->resize(at + KNOWN_REC_BYTES, 0);
-  memcpy(&(*out)[at], &len, 8);
-  memcpy(&(*out)[at + 8], m.data(), m.size());
-}
-
 // Both metas are parsed and the member records of both images are on the device.  d_hits: device memory for
 // p.n_members hits (the device variant's buffer), or null: then the hits of P's member records go to `hits` on the host.
 int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const KnownMeta& p, const uint8_t* d_p, int64_t now,
@@ -59,7 +42,7 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
               ctmr_known_find_info* info) {
   const char* what = "known image find";
   int r;
-  if ((k.n_members && !d_k) || (p.n_members && !d_p)) return fail(e, CTMR_E_INVAL, "%s: null member records", what);
+  if ((r = known_bind(e, k, d_k, what)) || (r = known_bind(e, p, d_p, what))) return r;
   if (((uintptr_t)d_k | (uintptr_t)d_p | (uintptr_t)d_hits) & 15u)
     return fail(e, CTMR_E_INVAL, "%s: device memory that is not 16-byte aligned", what);
   // ---- K: the Issuer.IDs it names (K ordinals), its kept sets in image order, its kept host pairs
@@ -100,7 +83,7 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
     for (auto& hm : k.host) {
       if (!prev || *prev != hm.first) {  // (the section is in key order: a key's date is parsed once)
         std::string date, id;
-        if (!find_split_key(hm.first, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, hm.first.c_str());
+        if (!known_split_key(hm.first, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, hm.first.c_str());
         int64_t start, end;
         prev_kept = lists_parse_date(date, &start, &end) && now < end;
         prev = &hm.first;
@@ -139,7 +122,7 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
       auto& hm = p.host[j];
       if (!prev || *prev != hm.first) {
         std::string date, id;  // (the date is not looked at: the hour is the wildcard)
-        if (!find_split_key(hm.first, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, hm.first.c_str());
+        if (!known_split_key(hm.first, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, hm.first.c_str());
         ko = find_kord(id);
         prev = &hm.first;
       }
@@ -147,7 +130,7 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
       auto it = kh_by.find({ko, hm.second});
       if (it != kh_by.end()) host_acc[j] = it->second;
       if (hm.second.size() <= CTMR_MAX_SERIAL && kept_records) {
-        find_record(hm.second, &extra_rec);
+        known_put_record(hm.second, &extra_rec);
         extra_kord.push_back(ko);
         extra_of.push_back(j);
       }
@@ -166,7 +149,7 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
         hr_src.push_back(hr_src.size());
         hr_hour.push_back(h.hour);
         hr_kord.push_back(h.kord);
-        find_record(*h.member, &hr_rec);
+        known_put_record(*h.member, &hr_rec);
       }
   const uint64_t n_hr = hr_src.size();
   hr_dst.push_back(n_hr);

@@ -35,6 +35,15 @@ uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
 void put64(std::vector<uint8_t>& o, uint64_t v) { o.insert(o.end(), (const uint8_t*)&v, (const uint8_t*)&v + 8); }
 void put32(std::vector<uint8_t>& o, uint32_t v) { o.insert(o.end(), (const uint8_t*)&v, (const uint8_t*)&v + 4); }
 
+// the member record of a member of at most 40 octets, appended to *out: u64 serial_len, the octets, zeros to 48 bytes
+void known_put_record(const std::string& m, std::vector<uint8_t>* out) {
+  const uint64_t len = m.size();
+  const size_t at = out->size();
+  out->resize(at + KNOWN_REC_BYTES, 0);
+  memcpy(&(*out)[at], &len, 8);
+  memcpy(&(*out)[at + 8], m.data(), m.size());
+}
+
 // The meta part of an image (header, issuers, sets, host section, padding): every check but the member records' own,
 // which the count pass makes on the device.  len = the meta part's length (device variant) or the whole image's.
 int known_parse_meta(ctmr_engine* e, const uint8_t* m, size_t len, bool whole, KnownMeta* km) {
@@ -107,14 +116,70 @@ int known_parse_meta(ctmr_engine* e, const uint8_t* m, size_t len, bool whole, K
   return CTMR_OK;
 }
 
-// What an entry point is given: the meta part parsed and, for the device variants (n_given: their record count), held
-// against the header.  `what` names the call in the message.
+// The one writer of what known_parse_meta reads: the meta part of the image whose issuers are `digs` (32 bytes each, in
+// ordinal order), whose sets are `sets` (in key order; each set's first member is worked out here) and whose host
+// section is `host` (in (key, member) order) → *meta, padded to 64 bytes, and *info (an image's, or a longer struct
+// that begins as it does).
+struct KnownSetEntry { int32_t hour; uint32_t ordinal; uint64_t count; };
+using KnownHostPairs = std::vector<std::pair<std::string, std::string>>;
+
+template <class Info>
+void known_write_meta(const std::vector<const uint8_t*>& digs, const std::vector<KnownSetEntry>& sets, const KnownHostPairs& host,
+                      std::vector<uint8_t>* meta, Info* info) {
+  uint64_t n_members = 0, host_bytes = 0;
+  for (auto& s : sets) n_members += s.count;
+  for (auto& hm : host) host_bytes += 8 + hm.first.size() + hm.second.size();
+  std::vector<uint8_t>& o = *meta;
+  o.assign(KNOWN_MAGIC, KNOWN_MAGIC + 8);
+  put32(o, KNOWN_VERSION);
+  put32(o, KNOWN_HEADER);
+  put32(o, (uint32_t)digs.size());
+  put32(o, 0);
+  put64(o, sets.size());
+  put64(o, n_members);
+  put64(o, host_bytes);
+  put64(o, host.size());
+  put64(o, 0);
+  for (const uint8_t* d : digs) o.insert(o.end(), d, d + 32);
+  uint64_t first = 0;
+  for (auto& s : sets) {
+    put32(o, (uint32_t)s.hour);
+    put32(o, s.ordinal);
+    put64(o, first);
+    put64(o, s.count);
+    first += s.count;
+  }
+  for (auto& hm : host) {
+    put32(o, (uint32_t)hm.first.size());
+    o.insert(o.end(), hm.first.begin(), hm.first.end());
+    put32(o, (uint32_t)hm.second.size());
+    o.insert(o.end(), hm.second.begin(), hm.second.end());
+  }
+  o.resize((o.size() + 63) & ~(size_t)63, 0);
+  info->members = n_members;
+  info->sets = sets.size();
+  info->host_members = host.size();
+  info->meta_bytes = o.size();
+  info->image_bytes = o.size() + n_members * KNOWN_REC_BYTES;
+  info->issuers = (uint32_t)digs.size();
+  info->reserved = 0;
+}
+
+// What an entry point is given, step 1: the meta part parsed and, for the device variants (n_given: their record
+// count), held against the header.  `what` names the call in the message.
 int known_open(ctmr_engine* e, const uint8_t* m, size_t len, const uint64_t* n_given, const char* what, KnownMeta* km) {
   int r;
   if ((r = known_parse_meta(e, m, len, !n_given, km))) return r;
   if (n_given && km->n_members != *n_given)
     return fail(e, CTMR_E_INVAL, "%s: %llu member records given, the header says %llu", what, (unsigned long long)*n_given,
                 (unsigned long long)km->n_members);
+  return CTMR_OK;
+}
+
+// Step 2, where the call's own checks have it today: the member records a core works on are there.  The host variants
+// have staged theirs by then (known_stage_members), so this refuses the device variants' null pointer.
+int known_bind(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, const char* what) {
+  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "%s: null member records", what);
   return CTMR_OK;
 }
 
@@ -171,54 +236,22 @@ int known_export_prepare(ctmr_engine* e, KnownExport* x) {
   std::sort(canons.begin(), canons.end(), [e](uint32_t a, uint32_t b) { return memcmp(e->issuers[a].digest, e->issuers[b].digest, 32) < 0; });
   std::vector<uint32_t> ordinal(e->issuers.size(), 0);
   for (uint32_t k = 0; k < canons.size(); k++) ordinal[canons[k]] = k;
-  std::vector<std::pair<std::string, std::string>> host;
+  KnownHostPairs host;
   for (auto& kv : e->hstore)
     if (kv.first.compare(0, 9, "serials::") == 0)
       for (auto& m : kv.second) host.emplace_back(kv.first, m);
-  std::vector<uint8_t>& o = x->meta;
-  o.reserve(KNOWN_HEADER + canons.size() * 32 + sets.size() * 24 + 64);
-  o.assign(KNOWN_MAGIC, KNOWN_MAGIC + 8);
-  put32(o, KNOWN_VERSION);
-  put32(o, KNOWN_HEADER);
-  put32(o, (uint32_t)canons.size());
-  put32(o, 0);
-  const size_t at_members = o.size();
-  put64(o, sets.size());
-  put64(o, 0);  // n_members, patched below
-  const size_t at_host = o.size();
-  put64(o, 0);  // host_bytes, patched below
-  put64(o, host.size());
-  put64(o, 0);
-  for (uint32_t c : canons) o.insert(o.end(), e->issuers[c].digest, e->issuers[c].digest + 32);
+  std::vector<const uint8_t*> digs;
+  for (uint32_t c : canons) digs.push_back(e->issuers[c].digest);
+  std::vector<KnownSetEntry> entries;
   x->cursor.assign(e->npairs, 0ull);
   uint64_t first = 0;
   for (auto& s : sets) {
-    put32(o, (uint32_t)s.exp_hour);
-    put32(o, ordinal[s.canon]);
-    put64(o, first);
-    put64(o, s.count);
+    entries.push_back({s.exp_hour, ordinal[s.canon], s.count});
     x->cursor[s.slot] = first;
     x->set_range.push_back({first, s.count});
     first += s.count;
   }
-  const size_t host_start = o.size();
-  for (auto& hm : host) {
-    put32(o, (uint32_t)hm.first.size());
-    o.insert(o.end(), hm.first.begin(), hm.first.end());
-    put32(o, (uint32_t)hm.second.size());
-    o.insert(o.end(), hm.second.begin(), hm.second.end());
-  }
-  const uint64_t host_bytes = o.size() - host_start;
-  o.resize((o.size() + 63) & ~(size_t)63, 0);
-  memcpy(&o[at_members + 8], &first, 8);
-  memcpy(&o[at_host], &host_bytes, 8);
-  x->info.members = first;
-  x->info.sets = sets.size();
-  x->info.host_members = host.size();
-  x->info.meta_bytes = o.size();
-  x->info.image_bytes = o.size() + first * KNOWN_REC_BYTES;
-  x->info.issuers = (uint32_t)canons.size();
-  x->info.reserved = 0;
+  known_write_meta(digs, entries, host, &x->meta, &x->info);
   return CTMR_OK;
 }
 
@@ -271,7 +304,8 @@ int known_sets_prepare(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_mem
   if (world == 0 || rank >= world) return fail(e, CTMR_E_INVAL, "%s: rank %u of world %u", what, rank, world);
   if (e->rd.valid && e->rd.mode == XM_OWNER && !e->rd.resolved)
     return fail(e, CTMR_E_INVAL, "%s: an owner-computes round is open on this engine", what);
-  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "%s: null member records", what);
+  int r;
+  if ((r = known_bind(e, km, d_members, what))) return r;
   // image issuer ordinal → canonical index here (0xffffffff: not registered)
   std::vector<uint32_t> remap(km.n_issuers, 0xffffffffu);
   for (uint32_t k = 0; k < km.n_issuers; k++) {
@@ -354,6 +388,21 @@ int known_count_chunk(ctmr_engine* e, const KnownDev& kd, uint64_t c, const char
   HIPCHK(e, hipStreamSynchronize(e->stream));
   HIPCHK(e, hipGetLastError());
   return known_record_error(e, err, what);
+}
+
+// Every member record validated and nothing else (the sort, an operand of the merge): the count pass with no set
+// taken, in chunks of `chunk` records.  Drains the stream.
+int known_validate_records(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_members, uint64_t chunk, const char* what) {
+  KnownSets ks;
+  ks.set_meta.assign(km.n_sets, 0ull);
+  KnownDev kd;
+  int r;
+  if ((r = known_dev_upload(e, km, ks, d_members, 1, 0, chunk, &kd))) return r;
+  for (uint64_t c = 0; c < kd.nch; c++) {
+    unsigned long long tot[2];
+    if ((r = known_count_chunk(e, kd, c, what, tot))) return r;
+  }
+  return CTMR_OK;
 }
 
 // Set s, of an issuer not registered here: its records copied down, f(key, member, index in the set) for each.

@@ -59,6 +59,15 @@ struct KnownLists {
 // compares to it
 struct ListDev { uint64_t key, count, slot; };
 
+// a host-side key as strings.Split(key, "::") splits it: serials, expDate and Issuer.ID — exactly three parts, or false
+bool known_split_key(const std::string& k, std::string* date, std::string* id) {
+  const size_t a = k.find("::"), b = a == std::string::npos ? a : k.find("::", a + 2);
+  if (b == std::string::npos || k.find("::", b + 2) != std::string::npos) return false;
+  *date = k.substr(a + 2, b - a - 2);
+  *id = k.substr(b + 2);
+  return true;
+}
+
 // Which sets, grouped and ordered: the device sets `dev` (kept ones only; ids[rank] = the Issuer.ID of a rank, ascending)
 // and the serials:: keys of `store`, kept while now < the end of their expDate; per Issuer.ID ascending, expDates
 // ascending (by their first second, then as strings).
@@ -69,17 +78,11 @@ int known_lists_arrange(ctmr_engine* e, const std::map<std::string, std::set<std
   for (auto& kv : store) {
     const std::string& k = kv.first;
     if (k.compare(0, 9, "serials::") != 0 || kv.second.empty()) continue;
-    std::vector<std::string> parts;  // strings.Split(key, "::")
-    for (size_t a = 0;;) {
-      const size_t b = k.find("::", a);
-      parts.push_back(k.substr(a, b == std::string::npos ? std::string::npos : b - a));
-      if (b == std::string::npos) break;
-      a = b + 2;
-    }
-    if (parts.size() != 3) return fail(e, CTMR_E_INVAL, "known lists: unexpected key format: %s", k.c_str());
+    std::string date, id;
+    if (!known_split_key(k, &date, &id)) return fail(e, CTMR_E_INVAL, "known lists: unexpected key format: %s", k.c_str());
     int64_t start, end;
-    if (!lists_parse_date(parts[1], &start, &end) || now >= end) continue;  // unparsable: skipped, as the reference does
-    by_id[parts[2]][{start, parts[1]}].host = &kv.second;
+    if (!lists_parse_date(date, &start, &end) || now >= end) continue;  // unparsable: skipped, as the reference does
+    by_id[id][{start, date}].host = &kv.second;
   }
   std::sort(dev.begin(), dev.end(), [](const ListDev& p, const ListDev& q) { return p.key < q.key; });
   KnownExport& x = L->x;
@@ -392,10 +395,10 @@ int image_lists_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_membe
                      size_t text_cap, uint8_t* ids, size_t ids_cap, uint64_t* offs, size_t offs_cap, ctmr_known_lists_info* info) {
   ListSource src;
   src.what = "known image lists";
-  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "%s: null member records", src.what);
+  int r;
+  if ((r = known_bind(e, km, d_members, src.what))) return r;
   std::map<std::string, std::set<std::string>> host;
   KnownLists L;
-  int r;
   if ((r = image_lists_prepare(e, km, now, &host, &L))) return r;
   src.segments = true;
   src.image = d_members;

@@ -78,16 +78,7 @@ struct MergeKept {
     return CTMR_OK;
   }
   // cnt[] → kept records before each block, cnt[nb] = all of them (*total)
-  int scan(ctmr_engine* e, uint64_t* total) {
-    int r;
-    if ((r = scan_u64(e, (uint64_t*)cnt(), nb + 1, false, SC_TMP))) return r;
-    unsigned long long t = 0;
-    HIPCHK(e, hipMemcpyAsync(&t, cnt() + nb, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipGetLastError());
-    *total = t;
-    return CTMR_OK;
-  }
+  int scan(ctmr_engine* e, uint64_t* total) { return scan_total(e, (uint64_t*)cnt(), nb + 1, false, SC_TMP, total); }
 };
 
 int merge_upload_first(ctmr_engine* e, MergeOperand& o, const std::vector<uint32_t>& pair_of) {
@@ -99,29 +90,19 @@ int merge_upload_first(ctmr_engine* e, MergeOperand& o, const std::vector<uint32
   return CTMR_OK;
 }
 
-// An operand opened: its meta parsed, its records validated, and then canonical — the sets in key order, each ascending
-// with every member once, the host-section pairs the member section can carry among them.  A sorted export passes the
-// check and is used where it lies; anything else is copied aside, sorted (known_sort_sets) and squeezed.
-int merge_open(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const uint64_t* n_given, const uint8_t* d_rec,
-               const char* what, MergeOperand* o) {
+// An operand whose meta known_open has parsed into o->km (no meta: the empty image), its records at d_rec: they are
+// validated, and then made canonical — the sets in key order, each ascending with every member once, the host-section
+// pairs the member section can carry among them.  A sorted export passes the check and is used where it lies; anything
+// else is copied aside, sorted (known_sort_sets) and squeezed.
+int merge_open(ctmr_engine* e, const uint8_t* d_rec, const char* what, MergeOperand* o) {
   int r;
-  if (!meta && meta_len == 0) {  // the empty image
+  const KnownMeta& km = o->km;
+  if (km.set_first.empty()) {  // the empty image (a parsed meta has n_sets + 1 firsts)
     o->first.assign(1, 0ull);
     return CTMR_OK;
   }
-  if ((r = known_open(e, meta, meta_len, n_given, what, &o->km))) return r;
-  const KnownMeta& km = o->km;
-  if (km.n_members && !d_rec) return fail(e, CTMR_E_INVAL, "%s: null member records", what);
-  {  // every record validated, as the import's count pass does
-    KnownSets ks;
-    ks.set_meta.assign(km.n_sets, 0ull);
-    KnownDev kd;
-    if ((r = known_dev_upload(e, km, ks, d_rec, 1, 0, known_sort_chunk(), &kd))) return r;
-    for (uint64_t c = 0; c < kd.nch; c++) {
-      unsigned long long tot[2];
-      if ((r = known_count_chunk(e, kd, c, what, tot))) return r;
-    }
-  }
+  if ((r = known_bind(e, km, d_rec, what))) return r;
+  if ((r = known_validate_records(e, km, d_rec, known_sort_chunk(), what))) return r;
   std::vector<MergeSetKey> own(km.n_sets);
   for (uint64_t s = 0; s < km.n_sets; s++) {
     own[s].hour = km.set_hour[s];
@@ -164,12 +145,8 @@ int merge_open(ctmr_engine* e, const uint8_t* meta, size_t meta_len, const uint6
     o->n = km.n_members + moved.size();
     if (o->work.alloc(o->n * KNOWN_REC_BYTES) != hipSuccess)
       return fail(e, CTMR_E_NOMEM, "%s: no device memory for a copy of %llu member records", what, (unsigned long long)o->n);
-    std::vector<uint8_t> recs(moved.size() * KNOWN_REC_BYTES, 0);
-    for (size_t k = 0; k < moved.size(); k++) {
-      const uint64_t len = moved[k].second.size();
-      memcpy(&recs[k * KNOWN_REC_BYTES], &len, 8);
-      memcpy(&recs[k * KNOWN_REC_BYTES + 8], moved[k].second.data(), len);
-    }
+    std::vector<uint8_t> recs;
+    for (auto& mv : moved) known_put_record(mv.second, &recs);
     uint64_t at = 0, run_src = 0, run_dst = 0;  // the records of sets not yet copied: [run_src, first of s) → run_dst
     size_t s = 0, m = 0;
     auto flush = [&](uint64_t src_end) -> int {
@@ -305,51 +282,15 @@ int merge_prepare(ctmr_engine* e, MergePlan* mp) {
   auto dig_less = [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; };
   std::sort(digs.begin(), digs.end(), dig_less);
   digs.erase(std::unique(digs.begin(), digs.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) == 0; }), digs.end());
-  std::vector<uint8_t>& o = mp->meta;
-  o.assign(KNOWN_MAGIC, KNOWN_MAGIC + 8);
-  put32(o, KNOWN_VERSION);
-  put32(o, KNOWN_HEADER);
-  put32(o, (uint32_t)digs.size());
-  put32(o, 0);
-  const size_t at_sets = o.size();
-  put64(o, 0);  // n_sets, n_members, host_bytes: patched below
-  put64(o, 0);
-  put64(o, 0);
-  put64(o, host.size());
-  put64(o, 0);
-  for (const uint8_t* d : digs) o.insert(o.end(), d, d + 32);
-  uint64_t first = 0, n_sets = 0;
-  for (size_t p = 0; p < np; p++) {
-    if (!counts[p]) continue;
-    put32(o, (uint32_t)pkey[p]->hour);
-    put32(o, (uint32_t)(std::lower_bound(digs.begin(), digs.end(), pkey[p]->digest, dig_less) - digs.begin()));
-    put64(o, first);
-    put64(o, counts[p]);
-    first += counts[p];
-    n_sets++;
-  }
-  const size_t host_start = o.size();
-  for (auto& hm : host) {
-    put32(o, (uint32_t)hm.first.size());
-    o.insert(o.end(), hm.first.begin(), hm.first.end());
-    put32(o, (uint32_t)hm.second.size());
-    o.insert(o.end(), hm.second.begin(), hm.second.end());
-  }
-  const uint64_t host_bytes = o.size() - host_start;
-  o.resize((o.size() + 63) & ~(size_t)63, 0);
-  memcpy(&o[at_sets], &n_sets, 8);
-  memcpy(&o[at_sets + 8], &first, 8);
-  memcpy(&o[at_sets + 16], &host_bytes, 8);
-  if (first != (is_union ? a.n + kept : kept))
-    return fail(e, CTMR_E_HIP, "known merge: the sets hold %llu members, the kept records are %llu", (unsigned long long)first,
+  std::vector<KnownSetEntry> sets;
+  for (size_t p = 0; p < np; p++)
+    if (counts[p])
+      sets.push_back({pkey[p]->hour, (uint32_t)(std::lower_bound(digs.begin(), digs.end(), pkey[p]->digest, dig_less) - digs.begin()),
+                      counts[p]});
+  known_write_meta(digs, sets, host, &mp->meta, &mp->info);
+  if (mp->info.members != (is_union ? a.n + kept : kept))
+    return fail(e, CTMR_E_HIP, "known merge: the sets hold %llu members, the kept records are %llu", (unsigned long long)mp->info.members,
                 (unsigned long long)(is_union ? a.n + kept : kept));
-  mp->info.members = first;
-  mp->info.sets = n_sets;
-  mp->info.host_members = host.size();
-  mp->info.meta_bytes = o.size();
-  mp->info.image_bytes = o.size() + first * KNOWN_REC_BYTES;
-  mp->info.issuers = (uint32_t)digs.size();
-  mp->info.reserved = 0;
   return CTMR_OK;
 }
 
@@ -397,8 +338,10 @@ int ctmr_known_merge_device(ctmr_engine* e, int op, const uint8_t* a_meta, size_
   int r;
   if ((r = merge_check_op(e, op))) return r;
   if (!b_meta && b_members) return fail(e, CTMR_E_INVAL, "known merge: %llu member records given for the empty image", (unsigned long long)b_members);
-  if ((r = merge_open(e, a_meta, a_meta_len, &a_members, (const uint8_t*)d_a, "known merge (A)", &mp.a))) return r;
-  if ((r = merge_open(e, b_meta, b_meta_len, &b_members, (const uint8_t*)d_b, "known merge (B)", &mp.b))) return r;
+  if ((r = known_open(e, a_meta, a_meta_len, &a_members, "known merge (A)", &mp.a.km))) return r;
+  if ((r = merge_open(e, (const uint8_t*)d_a, "known merge (A)", &mp.a))) return r;
+  if (b_meta && (r = known_open(e, b_meta, b_meta_len, &b_members, "known merge (B)", &mp.b.km))) return r;
+  if ((r = merge_open(e, (const uint8_t*)d_b, "known merge (B)", &mp.b))) return r;
   if ((r = merge_prepare(e, &mp))) return r;
   *info = mp.info;
   if (!out_meta || out_meta_cap < mp.info.meta_bytes || out_members_cap < mp.info.members || (mp.info.members && !d_out))
@@ -419,18 +362,13 @@ int ctmr_known_merge(ctmr_engine* e, int op, const uint8_t* a, size_t a_len, con
   DevMem da, db, d_out;
   int r;
   if ((r = merge_check_op(e, op))) return r;
-  {  // both metas before anything is staged
-    KnownMeta ka, kb;
-    if ((r = known_open(e, a, a_len, nullptr, "known merge (A)", &ka))) return r;
-    if (b && (r = known_open(e, b, b_len, nullptr, "known merge (B)", &kb))) return r;
-    if ((r = known_stage_members(e, ka, a, 0, "known merge (A)", &da))) return r;
-    if (b && (r = known_stage_members(e, kb, b, 0, "known merge (B)", &db))) return r;
-    a_len = ka.meta_bytes;
-    if (b) b_len = kb.meta_bytes;
-    const uint64_t na = ka.n_members, nb = kb.n_members;
-    if ((r = merge_open(e, a, a_len, &na, da.u8(), "known merge (A)", &mp.a))) return r;
-    if ((r = merge_open(e, b, b_len, &nb, db.u8(), "known merge (B)", &mp.b))) return r;
-  }
+  // both metas before anything is staged
+  if ((r = known_open(e, a, a_len, nullptr, "known merge (A)", &mp.a.km))) return r;
+  if (b && (r = known_open(e, b, b_len, nullptr, "known merge (B)", &mp.b.km))) return r;
+  if ((r = known_stage_members(e, mp.a.km, a, 0, "known merge (A)", &da))) return r;
+  if (b && (r = known_stage_members(e, mp.b.km, b, 0, "known merge (B)", &db))) return r;
+  if ((r = merge_open(e, da.u8(), "known merge (A)", &mp.a))) return r;
+  if ((r = merge_open(e, db.u8(), "known merge (B)", &mp.b))) return r;
   if ((r = merge_prepare(e, &mp))) return r;
   *info = mp.info;
   if (!out || cap < mp.info.image_bytes) return fail(e, CTMR_E_RANGE, "known merge: %llu bytes needed", (unsigned long long)mp.info.image_bytes);

@@ -38,10 +38,8 @@ static int pem_device_locked(ctmr_engine* e, const uint8_t* d_payload, const uin
   PemCertInfo* d_info = (PemCertInfo*)e->d_scratch[SC_PEMINFO];
   hipLaunchKernelGGL(k_pem_len, dim3((unsigned)((n_idx + 1 + 255) / 256)), dim3(256), 0, e->stream, d_offsets, d_ends,
                      d_idx, n_idx, d_pem_offsets, d_info);
-  if ((r = scan_u64(e, d_pem_offsets, n_idx + 1, false, SC_TMP))) return r;
   uint64_t total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, d_pem_offsets + n_idx, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if ((r = scan_total(e, d_pem_offsets, n_idx + 1, false, SC_TMP, &total, false))) return r;
   if (pem_bytes) *pem_bytes = total;
   if (!d_pem) return CTMR_OK;  // size query
   if (total > pem_cap) return fail(e, CTMR_E_RANGE, "PEM buffer too small: need %llu bytes", (unsigned long long)total);

@@ -142,10 +142,10 @@ int known_resp_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_member
                     size_t text_cap, ctmr_known_resp_info* info) {
   const char* what = "known image resp";
   if (per < 1 || per > RESP_PER_MAX) return fail(e, CTMR_E_INVAL, "%s: %u members per command, 1..2^20 expected", what, per);
-  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "%s: null member records", what);
+  int r;
+  if ((r = known_bind(e, km, d_members, what))) return r;
   if (km.n_sets > 0xffffffffull) return fail(e, CTMR_E_NOMEM, "%s: %llu sets", what, (unsigned long long)km.n_sets);
   KnownResp R;
-  int r;
   if ((r = known_resp_prepare(e, km, per, &R))) return r;
   const uint64_t N = km.n_members, S = km.n_sets;
   memset(info, 0, sizeof *info);

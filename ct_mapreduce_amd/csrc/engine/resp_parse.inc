@@ -65,45 +65,6 @@ int rp_check(ctmr_engine* e, unsigned long long* d_err, const char* saying, unsi
   return CTMR_OK;
 }
 
-void rp_meta(RespImage* R, const std::vector<const uint8_t*>& digs, const std::vector<std::array<uint64_t, 4>>& sets,
-             const std::vector<std::pair<std::string, std::string>>& host, uint64_t n_members) {
-  std::vector<uint8_t>& o = R->meta;
-  o.assign(KNOWN_MAGIC, KNOWN_MAGIC + 8);
-  put32(o, KNOWN_VERSION);
-  put32(o, KNOWN_HEADER);
-  put32(o, (uint32_t)digs.size());
-  put32(o, 0);
-  put64(o, sets.size());
-  put64(o, n_members);
-  const size_t at_host_bytes = o.size();
-  put64(o, 0);
-  put64(o, host.size());
-  put64(o, 0);
-  for (const uint8_t* d : digs) o.insert(o.end(), d, d + 32);
-  for (auto& s : sets) {  // {hour, ordinal, first, count}
-    put32(o, (uint32_t)s[0]);
-    put32(o, (uint32_t)s[1]);
-    put64(o, s[2]);
-    put64(o, s[3]);
-  }
-  const size_t host_start = o.size();
-  for (auto& hm : host) {
-    put32(o, (uint32_t)hm.first.size());
-    o.insert(o.end(), hm.first.begin(), hm.first.end());
-    put32(o, (uint32_t)hm.second.size());
-    o.insert(o.end(), hm.second.begin(), hm.second.end());
-  }
-  const uint64_t host_bytes = o.size() - host_start;
-  memcpy(&o[at_host_bytes], &host_bytes, 8);
-  o.resize((o.size() + 63) & ~(size_t)63, 0);
-  R->info.members = n_members;
-  R->info.sets = sets.size();
-  R->info.host_members = host.size();
-  R->info.meta_bytes = o.size();
-  R->info.image_bytes = o.size() + n_members * KNOWN_REC_BYTES;
-  R->info.issuers = (uint32_t)digs.size();
-}
-
 // Everything but the records: the stream (device memory, any alignment) validated, R->meta and R->info made, the tables
 // of the place pass left on the device.  Drains the stream.
 int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R) {
@@ -112,7 +73,7 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
   R->len = len;
   memset(&R->info, 0, sizeof R->info);
   if (!len) {
-    rp_meta(R, {}, {}, {}, 0);
+    known_write_meta({}, {}, {}, &R->meta, &R->info);
     return CTMR_OK;
   }
   const uint64_t nb = (len + RP_TILE - 1) / RP_TILE;
@@ -125,11 +86,8 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
   // ---- mark
   HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
   hipLaunchKernelGGL((k_resp_mark<false>), dim3((unsigned)nb), dim3(RP_BLOCK), 0, e->stream, s, len, cnt, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  if ((r = scan_u64(e, (uint64_t*)cnt, nb + 1, false, SC_MISC))) return r;
-  unsigned long long nc = 0;
-  HIPCHK(e, hipMemcpyAsync(&nc, cnt + nb, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
+  uint64_t nc = 0;
+  if ((r = scan_total(e, (uint64_t*)cnt, nb + 1, false, SC_MISC, &nc))) return r;
   if (!nc) return fail(e, CTMR_E_INVAL, "%s: offset 0: no command starts here", RESP_IMAGE);
   const uint64_t ncb = (nc + RP_TILE - 1) / RP_TILE;
   if ((r = rp_alloc(e, &cand_m, nc * 4)) || (r = rp_alloc(e, &nxt_m, nc * 4)) || (r = rp_alloc(e, &flag_m, nc)) ||
@@ -233,7 +191,7 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
   }
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
   std::vector<MergeSetKey> set_key;
-  std::vector<std::array<uint64_t, 4>> sets;
+  std::vector<KnownSetEntry> sets;
   std::vector<unsigned long long> run_dst(nrun, 0);
   uint64_t first = 0;
   for (size_t i = 0; i < order.size(); i++) {
@@ -242,10 +200,10 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
       MergeSetKey mk;
       if (!merge_parse_key(key[q], &mk)) return fail(e, CTMR_E_HIP, "%s: the device took a key the host does not: %s", RESP_IMAGE, key[q].c_str());
       set_key.push_back(mk);
-      sets.push_back({(uint64_t)(uint32_t)mk.hour, 0, first, 0});
+      sets.push_back({mk.hour, 0u, 0ull});
     }
     run_dst[q] = first;
-    sets.back()[3] += count[q];
+    sets.back().count += count[q];
     first += count[q];
   }
   if (first != nrec) return fail(e, CTMR_E_HIP, "%s: the runs hold %llu records, the stream %llu", RESP_IMAGE, (unsigned long long)first, (unsigned long long)nrec);
@@ -254,12 +212,12 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
   auto dig_less = [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; };
   std::sort(digs.begin(), digs.end(), dig_less);
   digs.erase(std::unique(digs.begin(), digs.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) == 0; }), digs.end());
-  for (size_t i = 0; i < sets.size(); i++) sets[i][1] = (uint64_t)(std::lower_bound(digs.begin(), digs.end(), set_key[i].digest, dig_less) - digs.begin());
-  std::vector<std::pair<std::string, std::string>> host(npair);
+  for (size_t i = 0; i < sets.size(); i++) sets[i].ordinal = (uint32_t)(std::lower_bound(digs.begin(), digs.end(), set_key[i].digest, dig_less) - digs.begin());
+  KnownHostPairs host(npair);
   for (uint64_t p = 0; p < npair; p++) host[p] = {key[pairs[p].z], text(nrun + p)};
   std::sort(host.begin(), host.end());
   host.erase(std::unique(host.begin(), host.end()), host.end());
-  rp_meta(R, digs, sets, host, nrec);
+  known_write_meta(digs, sets, host, &R->meta, &R->info);
   if (nrun) {
     HIPCHK(e, hipMemcpyAsync(R->run_dst.p, run_dst.data(), nrun * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));  // (run_dst goes out of scope)

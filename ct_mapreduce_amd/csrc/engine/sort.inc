@@ -133,19 +133,12 @@ int known_sort_sets(ctmr_engine* e, uint8_t* d_rec, const std::vector<uint64_t>&
   return CTMR_OK;
 }
 
-// What ctmr_known_sort and ctmr_known_sort_device share behind the meta checks: every record validated on the device
-// (k_known_count, as the import's count pass), then the sort.
+// What ctmr_known_sort and ctmr_known_sort_device share behind the meta checks: every record validated on the device,
+// then the sort.
 int known_sort_core(ctmr_engine* e, const KnownMeta& km, uint8_t* d_members) {
-  if (km.n_members && !d_members) return fail(e, CTMR_E_INVAL, "known sort: null member records");
-  KnownSets ks;
-  ks.set_meta.assign(km.n_sets, 0ull);  // no record is taken: the pass only validates
-  KnownDev kd;
   int r;
-  if ((r = known_dev_upload(e, km, ks, d_members, 1, 0, known_sort_chunk(), &kd))) return r;
-  for (uint64_t c = 0; c < kd.nch; c++) {
-    unsigned long long tot[2];
-    if ((r = known_count_chunk(e, kd, c, "known sort", tot))) return r;
-  }
+  if ((r = known_bind(e, km, d_members, "known sort"))) return r;
+  if ((r = known_validate_records(e, km, d_members, known_sort_chunk(), "known sort"))) return r;
   return known_sort_sets(e, d_members, km.set_first);
 }
 

@@ -73,10 +73,8 @@ int ctmr_synth_device(ctmr_engine* e, const ctmr_synth_config* c, uint64_t first
   SynthCfg s = to_synth(c, (const uint32_t*)e->d_scratch[SC_MISC]);
   const unsigned blocks = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(k_synth_len, dim3(blocks), dim3(256), 0, e->stream, s, first, n, d_offsets);
-  if ((r = scan_u64(e, d_offsets + 1, n, true, SC_STAGE_B))) return r;
   uint64_t total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, d_offsets + n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if ((r = scan_total(e, d_offsets + 1, n, true, SC_STAGE_B, &total, false))) return r;
   if (payload_bytes) *payload_bytes = total;
   if (!d_payload) return CTMR_OK;
   if (total + CTMR_PAYLOAD_PAD > payload_cap) return fail(e, CTMR_E_RANGE, "payload needs %llu bytes (+%d pad)", (unsigned long long)total, CTMR_PAYLOAD_PAD);
@@ -104,10 +102,8 @@ int ctmr_synth_view_device(ctmr_engine* e, const ctmr_synth_config* c, uint64_t 
   SynthCfg s = to_synth(c, (const uint32_t*)e->d_scratch[SC_MISC]);
   const unsigned blocks = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(k_synth_len_view, dim3(blocks), dim3(256), 0, e->stream, s, first, n, align, d_starts, d_ends);
-  if ((r = scan_u64(e, d_starts + 1, n, true, SC_STAGE_B))) return r;
   uint64_t total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, d_starts + n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if ((r = scan_total(e, d_starts + 1, n, true, SC_STAGE_B, &total, false))) return r;
   if (payload_bytes) *payload_bytes = total;
   if (!d_payload) return CTMR_OK;
   if (total + CTMR_PAYLOAD_PAD > payload_cap) return fail(e, CTMR_E_RANGE, "payload needs %llu bytes (+%d pad)", (unsigned long long)total, CTMR_PAYLOAD_PAD);
@@ -154,10 +150,8 @@ int ctmr_synth_entries_device(ctmr_engine* e, const ctmr_synth_config* c, uint64
   SynthCfg s = to_synth(c, (const uint32_t*)e->d_scratch[SC_MISC]);
   const unsigned blocks = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(k_synth_entries_len, dim3(blocks), dim3(256), 0, e->stream, s, first, n, d_bounds);
-  if ((r = scan_u64(e, d_bounds + 1, 2 * n, true, SC_TMP))) return r;
   uint64_t total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, d_bounds + 2 * n, 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if ((r = scan_total(e, d_bounds + 1, 2 * n, true, SC_TMP, &total, false))) return r;
   if (blob_bytes) *blob_bytes = total;
   if (!d_blob) return CTMR_OK;
   if (total + CTMR_PAYLOAD_PAD > blob_cap) return fail(e, CTMR_E_RANGE, "blob needs %llu bytes (+%d pad)", (unsigned long long)total, CTMR_PAYLOAD_PAD);

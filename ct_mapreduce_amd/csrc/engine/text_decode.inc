@@ -28,12 +28,9 @@ int tx_drain(ctmr_engine* e) {
 
 // data[0, n) → its exclusive prefix sums, data[n] → the total, which also goes to *total when asked for.  Drains then.
 int tx_scan(ctmr_engine* e, DevMem& data, uint64_t n, uint64_t* total) {
-  int r;
   HIPCHK(e, hipMemsetAsync((uint64_t*)data.p + n, 0, 8, e->stream));
-  if ((r = scan_u64(e, (uint64_t*)data.p, n + 1, false, SC_MISC))) return r;
-  if (!total) return CTMR_OK;
-  HIPCHK(e, hipMemcpyAsync(total, (uint64_t*)data.p + n, 8, hipMemcpyDeviceToHost, e->stream));
-  return tx_drain(e);
+  if (!total) return scan_u64(e, (uint64_t*)data.p, n + 1, false, SC_MISC);
+  return scan_total(e, (uint64_t*)data.p, n + 1, false, SC_MISC, total);
 }
 
 // The bodies with a verdict leave (bad_at[i] != ~0, i < R): first2 (R + 1 words) gets the items of every body out of
@@ -42,10 +39,7 @@ int tx_drop(ctmr_engine* e, uint64_t R, const unsigned long long* bad_at, const 
   tx_turns(tx_blocks(R + 1, RP_BLOCK), [&](uint64_t b0, dim3 g) {
     hipLaunchKernelGGL(k_ej_drop, g, dim3(RP_BLOCK), 0, e->stream, b0, R, bad_at, (const unsigned long long*)first0.p, (unsigned long long*)first2.p);
   });
-  int r;
-  if ((r = scan_u64(e, (uint64_t*)first2.p, R + 1, false, SC_MISC))) return r;
-  HIPCHK(e, hipMemcpyAsync(n, (uint64_t*)first2.p + R, 8, hipMemcpyDeviceToHost, e->stream));
-  return tx_drain(e);
+  return scan_total(e, (uint64_t*)first2.p, R + 1, false, SC_MISC, n);
 }
 
 // Opens the text for the kernels: segment r at s[sb[r], sb[r + 1]) (s: device memory, any alignment; sb: S + 1 bounds on

@@ -40,30 +40,10 @@ struct FindTable {
   uint64_t mask;
 };
 
-// serial_len and the five serial words of a record; → 0, or 1 for a serial_len above 40, 2 for padding that is not zero
-__device__ __forceinline__ uint32_t find_load(const uint4* p, unsigned long long& len, unsigned long long s[5]) {
-  const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
-  len = (unsigned long long)v0.x | ((unsigned long long)v0.y << 32);
-  s[0] = (unsigned long long)v0.z | ((unsigned long long)v0.w << 32);
-  s[1] = (unsigned long long)v1.x | ((unsigned long long)v1.y << 32);
-  s[2] = (unsigned long long)v1.z | ((unsigned long long)v1.w << 32);
-  s[3] = (unsigned long long)v2.x | ((unsigned long long)v2.y << 32);
-  s[4] = (unsigned long long)v2.z | ((unsigned long long)v2.w << 32);
-  if (len > CTMR_MAX_SERIAL) return 1u;
-  uint32_t bad = 0u;
-#pragma unroll
-  for (uint32_t q = 0; q < 5; q++) {  // octets behind serial_len are zero
-    const uint64_t lo = 8ull * q;
-    const unsigned long long pad = len <= lo ? ~0ull : (len >= lo + 8 ? 0ull : (~0ull << (8ull * (len - lo))));
-    if (s[q] & pad) bad = 2u;
-  }
-  return bad;
-}
-
 // One lane per probe.  The working hit of the probe is initialised — records 0, first_hour INT32_MAX, last_hour
 // INT32_MIN, and in the reserved word the probe's K ordinal, which k_find_scan compares and k_find_finish clears — and
 // the probe claims the first empty word from its home slot on (atomicCAS, linear).  Equal probes take one word each.
-// A bad record (*err as k_known_count reports it) and a probe whose issuer K does not name are not inserted.
+// A bad record (known_load; reported in *err) and a probe whose issuer K does not name are not inserted.
 __global__ void __launch_bounds__(256) k_find_build(FindProbes p, FindTable t, uint4* hits, uint32_t* err) {
   const uint64_t n = p.n_main + p.n_extra;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -71,13 +51,11 @@ __global__ void __launch_bounds__(256) k_find_build(FindProbes p, FindTable t, u
   uint32_t bad = 0u;
   if (i < n) {
     unsigned long long len, s[5];
-    bad = find_load(p.rec(i), len, s);
+    bad = known_load(p.rec(i), len, s);
     uint32_t kord = FIND_NO_ISSUER;
     if (i < p.n_main) {
       const uint64_t wfirst = i - lane, wlast = wfirst + 63u < p.n_main ? wfirst + 63u : p.n_main - 1u;
-      const uint32_t s_lo = known_set_of(p.set_first, 0u, p.n_sets - 1u, wfirst);
-      const uint32_t s_hi = known_set_of(p.set_first, s_lo, p.n_sets - 1u, wlast);
-      kord = p.set_kord[known_set_of(p.set_first, s_lo, s_hi, i)];
+      kord = p.set_kord[known_set_in_wave(p.set_first, p.n_sets, i, wfirst, wlast)];
     } else {
       kord = p.extra_kord[i - p.n_main];
     }
@@ -93,8 +71,7 @@ __global__ void __launch_bounds__(256) k_find_build(FindProbes p, FindTable t, u
       }
     }
   }
-  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
-  if (lane == 0 && (mb1 | mb2)) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
+  known_report_bad(bad, err);
 }
 
 // A run of k whole kept sets of K as segments of a virtual record sequence (ListSegs): segment s holds the virtual
@@ -108,8 +85,8 @@ struct FindSegs {
   uint32_t k;
 };
 
-// One lane per member record of the run: three 16-byte loads (a wave reads 3 KiB in a row), the record validated as
-// k_image_lists_count validates, then the walk from its home slot to the first empty word.  A word of the record's tag
+// One lane per member record of the run: three 16-byte loads (a wave reads 3 KiB in a row), the record validated
+// (known_load), then the walk from its home slot to the first empty word.  A word of the record's tag
 // names a probe below `limit` whose 48 bytes and K ordinal are compared in full; an equal one gets records + 1 and the
 // set's hour into first_hour / last_hour.  A record that matches nothing reads one table word.
 __global__ void __launch_bounds__(256) k_find_scan(FindSegs g, uint64_t n, FindTable t, FindProbes p, uint64_t limit, uint4* hits,
@@ -120,11 +97,9 @@ __global__ void __launch_bounds__(256) k_find_scan(FindSegs g, uint64_t n, FindT
   if (i < n) {
     const uint64_t v0 = g.dst[0], wi = i - lane;
     const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-    const uint32_t s_lo = known_set_of(g.dst, 0u, g.k - 1u, wfirst);
-    const uint32_t s_hi = known_set_of(g.dst, s_lo, g.k - 1u, wlast);
-    const uint32_t set = known_set_of(g.dst, s_lo, s_hi, v);
+    const uint32_t set = known_set_in_wave(g.dst, g.k, v, wfirst, wlast);
     unsigned long long len, s[5];
-    bad = find_load((const uint4*)(g.recs + (g.src[set] + (v - g.dst[set])) * KNOWN_REC_BYTES), len, s);
+    bad = known_load((const uint4*)(g.recs + (g.src[set] + (v - g.dst[set])) * KNOWN_REC_BYTES), len, s);
     if (!bad) {
       const uint32_t kord = g.kord[set];
       const int32_t hour = g.hour[set];
@@ -137,7 +112,7 @@ __global__ void __launch_bounds__(256) k_find_scan(FindSegs g, uint64_t n, FindT
         const uint64_t pi = (w & REF_MASK) - 1ull;
         if ((w >> 40) == tag && pi < limit) {
           unsigned long long plen, ps[5];
-          find_load(p.rec(pi), plen, ps);
+          known_load(p.rec(pi), plen, ps);
           const bool eq = (hits[pi].w == kord) & (plen == len) & (ps[0] == s[0]) & (ps[1] == s[1]) & (ps[2] == s[2]) &
                           (ps[3] == s[3]) & (ps[4] == s[4]);
           if (eq) {
@@ -150,8 +125,7 @@ __global__ void __launch_bounds__(256) k_find_scan(FindSegs g, uint64_t n, FindT
       }
     }
   }
-  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
-  if (lane == 0 && (mb1 | mb2)) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
+  known_report_bad(bad, err);
 }
 
 // The working hits → the caller's (in place when out == in): the hours of a probe without a record become 0, the

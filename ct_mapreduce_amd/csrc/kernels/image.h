@@ -97,6 +97,45 @@ __device__ __forceinline__ uint32_t known_set_of(const uint64_t* first, uint32_t
   return lo;
 }
 
+// The same for the lane of a wave whose records are virtual records wfirst..wlast of first[0..n_sets]: the search is
+// narrowed to the sets of the wave's first and last record, which every lane finds alike, and then made for the
+// lane's own record v between the two.  The one segment search of the image's kernels.
+__device__ __forceinline__ uint32_t known_set_in_wave(const uint64_t* first, uint32_t n_sets, uint64_t v, uint64_t wfirst,
+                                                      uint64_t wlast) {
+  const uint32_t s_lo = known_set_of(first, 0u, n_sets - 1u, wfirst);
+  const uint32_t s_hi = known_set_of(first, s_lo, n_sets - 1u, wlast);
+  return known_set_of(first, s_lo, s_hi, v);
+}
+
+// A member record loaded (three 16-byte loads) and held to the rule that makes it valid: serial_len is
+// at most 40 and the octets behind it are zero.  → 0 with len and the five serial words, or 1 for a serial_len above
+// 40, 2 for padding that is not zero — the bits of the error word the calls report (known_report_bad).
+__device__ __forceinline__ uint32_t known_load(const uint4* p, unsigned long long& len, unsigned long long s[5]) {
+  const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
+  len = (unsigned long long)v0.x | ((unsigned long long)v0.y << 32);
+  s[0] = (unsigned long long)v0.z | ((unsigned long long)v0.w << 32);
+  s[1] = (unsigned long long)v1.x | ((unsigned long long)v1.y << 32);
+  s[2] = (unsigned long long)v1.z | ((unsigned long long)v1.w << 32);
+  s[3] = (unsigned long long)v2.x | ((unsigned long long)v2.y << 32);
+  s[4] = (unsigned long long)v2.z | ((unsigned long long)v2.w << 32);
+  if (len > CTMR_MAX_SERIAL) return 1u;
+  uint32_t bad = 0u;
+#pragma unroll
+  for (uint32_t q = 0; q < 5; q++) {  // octets behind serial_len are zero
+    const uint64_t lo = 8ull * q;
+    const unsigned long long pad = len <= lo ? ~0ull : (len >= lo + 8 ? 0ull : (~0ull << (8ull * (len - lo))));
+    if (s[q] & pad) bad = 2u;
+  }
+  return bad;
+}
+
+// What a wave saw of bad records (bad: known_load's result, 0 in a lane without a record) → *err, one atomicOr by
+// lane 0 of a wave that saw one.  Every lane of the wave calls it.
+__device__ __forceinline__ void known_report_bad(uint32_t bad, uint32_t* err) {
+  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
+  if ((threadIdx.x & 63u) == 0 && (mb1 | mb2)) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
+}
+
 struct KnownImportArgs {
   const uint8_t* members;      // the chunk's member records
   uint64_t n;                  // records in the chunk
@@ -121,6 +160,7 @@ __device__ __forceinline__ void known_set_span(const KnownImportArgs& a, uint64_
 __device__ __forceinline__ uint32_t known_record_in(const KnownImportArgs& a, uint64_t i, uint32_t s_lo, uint32_t s_hi,
                                                     unsigned long long& meta, unsigned long long s[5], uint32_t& bad) {
   bad = 0u;
+  // (known_load defines the rule; the import, query and remove hot loops keep these loads of their own: EXPERIMENTS.md)
   const uint4* p = (const uint4*)(a.members + i * KNOWN_REC_BYTES);
   const uint4 v0 = p[0], v1 = p[1], v2 = p[2];
   const unsigned long long len = (unsigned long long)v0.x | ((unsigned long long)v0.y << 32);

@@ -136,8 +136,7 @@ __global__ void __launch_bounds__(LIST_BLOCK) k_lists_write(const uint8_t* recs,
 // ---- the lists of an image (ctmr_known_image_lists*).  A launch covers n virtual records of k whole segments: segment s
 // holds the virtual records [dst[s], dst[s + 1]) (dst ascending, every segment non-empty, dst[0] = the launch's first
 // virtual record, dst[k] = dst[0] + n) and lies at records [src[s], src[s] + dst[s + 1] − dst[s]) of the image.  Record i
-// of the launch is virtual record dst[0] + i; its segment comes from known_set_of over dst, narrowed first to the
-// segments of its wave's first and last record (k_sort_keys, k_merge_rank).
+// of the launch is virtual record dst[0] + i; its segment comes from known_set_in_wave over dst (kernels/image.h).
 struct ListSegs {
   const uint8_t* recs;  // the image's member records
   const uint64_t* dst;  // k + 1
@@ -146,48 +145,26 @@ struct ListSegs {
   __device__ __forceinline__ const uint4* operator()(uint64_t i, uint64_t n) const {
     const uint64_t v0 = dst[0], wi = i - (threadIdx.x & 63u);
     const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-    const uint32_t s_lo = known_set_of(dst, 0u, k - 1u, wfirst);
-    const uint32_t s_hi = known_set_of(dst, s_lo, k - 1u, wlast);
-    const uint32_t s = known_set_of(dst, s_lo, s_hi, v);
+    const uint32_t s = known_set_in_wave(dst, k, v, wfirst, wlast);
     return (const uint4*)(recs + (src[s] + (v - dst[s])) * KNOWN_REC_BYTES);
   }
 };
 
 // Count pass over the segments: cnt[blk] = the text bytes of the launch's records [256 blk, 256 blk + 256), and every
-// record read is validated as k_known_count validates — *err |= 1 for a serial_len above 40, |= 2 for padding octets
-// that are not zero, one atomicOr per wave that saw one.
+// record read is validated (known_load) and a bad one reported in *err (known_report_bad).
 __global__ void __launch_bounds__(LIST_BLOCK) k_image_lists_count(ListSegs g, uint64_t n, unsigned long long* cnt, uint32_t* err) {
   __shared__ uint32_t ws[LIST_BLOCK / 64];
   const uint64_t i = (uint64_t)blockIdx.x * LIST_BLOCK + threadIdx.x;
   uint32_t b = 0u, bad = 0u;
   if (i < n) {
-    const uint4* rec = g(i, n);
-    const uint4 v0 = rec[0], v1 = rec[1], v2 = rec[2];
-    const unsigned long long len = (unsigned long long)v0.x | ((unsigned long long)v0.y << 32);
-    const unsigned long long s[5] = {(unsigned long long)v0.z | ((unsigned long long)v0.w << 32),
-                                     (unsigned long long)v1.x | ((unsigned long long)v1.y << 32),
-                                     (unsigned long long)v1.z | ((unsigned long long)v1.w << 32),
-                                     (unsigned long long)v2.x | ((unsigned long long)v2.y << 32),
-                                     (unsigned long long)v2.z | ((unsigned long long)v2.w << 32)};
-    if (len > CTMR_MAX_SERIAL) {
-      bad = 1u;
-    } else {
-#pragma unroll
-      for (uint32_t q = 0; q < 5; q++) {  // octets behind serial_len are zero
-        const uint64_t lo = 8ull * q;
-        const unsigned long long pad = len <= lo ? ~0ull : (len >= lo + 8 ? 0ull : (~0ull << (8ull * (len - lo))));
-        if (s[q] & pad) bad = 2u;
-      }
-    }
+    unsigned long long len, s[5];
+    bad = known_load(g(i, n), len, s);
     b = 2u * (uint32_t)(len < (unsigned long long)CTMR_MAX_SERIAL ? len : (unsigned long long)CTMR_MAX_SERIAL) + 1u;
   }
-  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
+  known_report_bad(bad, err);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d);
-  if ((threadIdx.x & 63u) == 0) {
-    ws[threadIdx.x >> 6] = b;
-    if (mb1 | mb2) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
-  }
+  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = b;
   __syncthreads();
   if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
 }

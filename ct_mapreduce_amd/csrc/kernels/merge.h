@@ -43,12 +43,10 @@ __device__ __forceinline__ uint64_t merge_kept_before(const unsigned long long* 
   return r + (uint64_t)__popcll(bits[w] & ((1ull << (q & 63u)) - 1ull));
 }
 
-// the set of record i of a side: every lane searches between the sets of its wave's first and last record (k_sort_keys)
+// the set of record i of a side (known_set_in_wave, kernels/image.h)
 __device__ __forceinline__ uint32_t merge_set_of(const MergeSide& s, uint64_t i) {
   const uint64_t wfirst = i - (threadIdx.x & 63u), wlast = wfirst + 63u < s.n ? wfirst + 63u : s.n - 1u;
-  const uint32_t s_lo = known_set_of(s.first, 0u, s.ns - 1u, wfirst);
-  const uint32_t s_hi = known_set_of(s.first, s_lo, s.ns - 1u, wlast);
-  return known_set_of(s.first, s_lo, s_hi, i);
+  return known_set_in_wave(s.first, s.ns, i, wfirst, wlast);
 }
 
 // A record as the order compares it: the five octet words as big-endian numbers, then serial_len.

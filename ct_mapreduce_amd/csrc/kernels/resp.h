@@ -38,13 +38,11 @@ struct RespArgs {
   uint32_t k, per;
 };
 
-// the set of record i of the launch, narrowed first to the sets of its wave's first and last record (ListSegs)
+// the set of record i of the launch (known_set_in_wave, kernels/image.h)
 __device__ __forceinline__ uint32_t resp_set_of(const RespArgs& a, uint64_t i, uint64_t n) {
   const uint64_t v0 = a.first[0], wi = i - (threadIdx.x & 63u);
   const uint64_t wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-  const uint32_t s_lo = known_set_of(a.first, 0u, a.k - 1u, wfirst);
-  const uint32_t s_hi = known_set_of(a.first, s_lo, a.k - 1u, wlast);
-  return known_set_of(a.first, s_lo, s_hi, v0 + i);
+  return known_set_in_wave(a.first, a.k, v0 + i, wfirst, wlast);
 }
 
 // decimal digits of v (at most 12: |hour × 3600| of the years 0000..9999)
@@ -97,43 +95,23 @@ __device__ __forceinline__ uint32_t resp_rec_bytes(const RespRec& r, uint32_t le
   return b;
 }
 
-// Count pass: cnt[blk] = the text bytes of the launch's records [256 blk, 256 blk + 256), and every record is validated as
-// k_image_lists_count validates — err[0] |= 1 for a serial_len above 40, |= 2 for padding octets that are not zero, one
-// atomicOr per wave that saw one.  err[1] = the largest cnt[blk] of the launch (the write pass's LDS): an atomicMax by
-// the blocks that raise it.
+// Count pass: cnt[blk] = the text bytes of the launch's records [256 blk, 256 blk + 256), and every record is validated
+// (known_load) and a bad one reported in err[0] (known_report_bad).  err[1] = the largest cnt[blk] of the launch (the
+// write pass's LDS): an atomicMax by the blocks that raise it.
 __global__ void __launch_bounds__(RESP_BLOCK) k_image_resp_count(RespArgs a, uint64_t n, unsigned long long* cnt, uint32_t* err) {
   __shared__ uint32_t ws[RESP_BLOCK / 64];
   const uint64_t i = (uint64_t)blockIdx.x * RESP_BLOCK + threadIdx.x;
   uint32_t b = 0u, bad = 0u;
   if (i < n) {
-    const uint4* rec = (const uint4*)(a.recs + i * KNOWN_REC_BYTES);
-    const uint4 v0 = rec[0], v1 = rec[1], v2 = rec[2];
-    const unsigned long long len = (unsigned long long)v0.x | ((unsigned long long)v0.y << 32);
-    const unsigned long long s[5] = {(unsigned long long)v0.z | ((unsigned long long)v0.w << 32),
-                                     (unsigned long long)v1.x | ((unsigned long long)v1.y << 32),
-                                     (unsigned long long)v1.z | ((unsigned long long)v1.w << 32),
-                                     (unsigned long long)v2.x | ((unsigned long long)v2.y << 32),
-                                     (unsigned long long)v2.z | ((unsigned long long)v2.w << 32)};
-    if (len > CTMR_MAX_SERIAL) {
-      bad = 1u;
-    } else {
-#pragma unroll
-      for (uint32_t q = 0; q < 5; q++) {  // octets behind serial_len are zero
-        const uint64_t lo = 8ull * q;
-        const unsigned long long pad = len <= lo ? ~0ull : (len >= lo + 8 ? 0ull : (~0ull << (8ull * (len - lo))));
-        if (s[q] & pad) bad = 2u;
-      }
-    }
+    unsigned long long len, s[5];
+    bad = known_load((const uint4*)(a.recs + i * KNOWN_REC_BYTES), len, s);
     const uint32_t l = (uint32_t)(len < (unsigned long long)CTMR_MAX_SERIAL ? len : (unsigned long long)CTMR_MAX_SERIAL);
     b = resp_rec_bytes(resp_rec(a, resp_set_of(a, i, n), i), l);
   }
-  const unsigned long long mb1 = __ballot(bad == 1u), mb2 = __ballot(bad == 2u);
+  known_report_bad(bad, err);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d);
-  if ((threadIdx.x & 63u) == 0) {
-    ws[threadIdx.x >> 6] = b;
-    if (mb1 | mb2) atomicOr(err, (mb1 ? 1u : 0u) | (mb2 ? 2u : 0u));
-  }
+  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = b;
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t total = ws[0] + ws[1] + ws[2] + ws[3];
