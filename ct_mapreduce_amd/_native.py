@@ -119,6 +119,11 @@ class KnownRespImageInfo(C.Structure):
     _fields_ = KnownImageInfo._fields_ + [("commands", C.c_uint64), ("skipped_members", C.c_uint64)]
 
 
+class CrlInfo(C.Structure):
+    _fields_ = [("crls", C.c_uint64), ("entries", C.c_uint64), ("records", C.c_uint64), ("host_members", C.c_uint64),
+                ("empty_crls", C.c_uint64), ("candidates", C.c_uint64), ("bad_crl", C.c_uint64), ("bad_offset", C.c_uint64)]
+
+
 class EntriesJsonInfo(C.Structure):
     _fields_ = [("responses", C.c_uint64), ("entries", C.c_uint64), ("text_bytes", C.c_uint64), ("blob_bytes", C.c_uint64),
                 ("bad_response", C.c_uint64), ("bad_offset", C.c_uint64)]
@@ -219,6 +224,10 @@ SIGNATURES = {
     "ctmr_known_resp_image": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(KnownRespImageInfo)]),
     "ctmr_known_resp_image_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_uint64,
                                                C.POINTER(KnownRespImageInfo)]),
+    "ctmr_crl_probes": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, C.c_size_t, C.POINTER(KnownImageInfo),
+                                  C.POINTER(CrlInfo)]),
+    "ctmr_crl_probes_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_size_t, _P, C.c_uint64,
+                                         C.POINTER(KnownImageInfo), C.POINTER(CrlInfo)]),
     "ctmr_set_known_order": (C.c_int, [_P, C.c_int]),
     "ctmr_known_sort": (C.c_int, [_P, _P, C.c_size_t]),
     "ctmr_known_sort_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64]),

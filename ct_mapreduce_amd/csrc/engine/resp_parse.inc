@@ -25,9 +25,9 @@ const char* const RESP_IMAGE = "known resp image";
 
 unsigned rp_grid(uint64_t n, uint32_t per) { return (unsigned)((n + per - 1) / per); }
 
-int rp_alloc(ctmr_engine* e, DevMem* m, size_t bytes) {
+int rp_alloc(ctmr_engine* e, DevMem* m, size_t bytes, const char* what = RESP_IMAGE) {  // what: the call, for the message
   if (m->alloc(bytes ? bytes : 1) != hipSuccess)
-    return fail(e, CTMR_E_NOMEM, "%s: no device memory for a table of %llu bytes", RESP_IMAGE, (unsigned long long)bytes);
+    return fail(e, CTMR_E_NOMEM, "%s: no device memory for a table of %llu bytes", what, (unsigned long long)bytes);
   return CTMR_OK;
 }
 

@@ -269,6 +269,23 @@ __global__ void __launch_bounds__(RP_BLOCK) k_resp_chain(const uint32_t* tok_pos
   rp_report(err, bad, off);
 }
 
+// the same proof for a caller whose first token need not be a '*' (kernels/crl.h): it starts at 0, every nxt is the next
+// kept position, the last is len
+__global__ void __launch_bounds__(RP_BLOCK) k_resp_chain_from0(const uint32_t* tok_pos, const uint32_t* tok_nxt, uint64_t n, uint64_t len,
+                                                               unsigned long long* err) {
+  const uint64_t t = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x;
+  bool bad = false;
+  uint64_t off = 0;
+  if (t < n) {
+    if (t == 0 && tok_pos[0] != 0u) bad = true;  // (off = 0)
+    else if (tok_nxt[t] != (t + 1 < n ? (uint64_t)tok_pos[t + 1] : len)) {
+      bad = true;
+      off = tok_nxt[t];
+    }
+  }
+  rp_report(err, bad, off);
+}
+
 // cmd_tok[c] = the token of command c (cidx[t]: the '*' tokens before t)
 __global__ void __launch_bounds__(RP_BLOCK) k_resp_cmdtok(const uint8_t* star, const uint32_t* cidx, uint64_t n, uint32_t* cmd_tok) {
   const uint64_t t = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x;

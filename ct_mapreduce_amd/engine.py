@@ -1333,6 +1333,104 @@ class Engine:
         self._resp_meta_cap = max(meta_cap, info.meta_bytes)
         return meta[:info.meta_bytes].tobytes(), out[:info.members * 48]
 
+    # ---- DER CertificateLists → a probe image (include/ctmr.h ctmr_crl_probes*; CPU twin:
+    # crl.probes_image)
+    @staticmethod
+    def _crl_args(crls, digests):
+        """A list of CRLs (bytes each) or (blob, offsets) → (blob or None, total length, offsets u64[n + 1], n, digests)."""
+        if isinstance(crls, tuple):
+            blob, offsets = crls
+            offsets = np.ascontiguousarray(offsets, np.uint64)
+            total = blob.numel() if hasattr(blob, "data_ptr") else len(blob)
+        else:
+            crls = [bytes(c) for c in crls]
+            blob = b"".join(crls)
+            offsets = np.zeros(len(crls) + 1, np.uint64)
+            offsets[1:] = np.cumsum([len(c) for c in crls], dtype=np.uint64)
+            total = len(blob)
+        n = len(offsets) - 1
+        digests = b"".join(bytes(d) for d in digests) if not isinstance(digests, (bytes, bytearray)) else bytes(digests)
+        if n < 0 or len(digests) != 32 * n:
+            raise ValueError("one 32-byte digest per CRL")
+        return blob, total, offsets, n, digests
+
+    def _crl_fail(self, rc, cinfo):
+        if rc == N.E_INVAL and cinfo.bad_crl != (1 << 64) - 1:
+            from .crl import CrlError
+            raise CrlError(cinfo.bad_offset, self._lib.ctmr_last_error(self._h).decode(errors="replace"), cinfo.bad_crl)
+        self._ck(rc)
+
+    def crl_probes(self, crls, digests):
+        """The probe image of the revoked serials of `crls` — a list of DER CRLs, or (blob bytes, offsets) — whose
+        issuers' SPKI digests are `digests`: one set per digest under exp hour 0, member records in input order, what
+        known_image_find takes as `probes`.  → (image bytes, info dict).  Raises crl.CrlError naming the lowest CRL
+        outside the grammar and the offset.  The engine's own sets and issuers play no part."""
+        blob, total, offsets, n, digests = self._crl_args(crls, digests)
+        blob = bytes(blob)
+        info, cinfo = N.KnownImageInfo(), N.CrlInfo()
+        cap = 64 + 56 * n + 48 * (total // 6)
+        for _ in range(2):
+            out = np.empty(max(cap, 64), np.uint8)
+            rc = self._lib.ctmr_crl_probes(self._h, blob, total, offsets.ctypes.data, n, digests, out.ctypes.data, out.nbytes,
+                                           C.byref(info), C.byref(cinfo))
+            if rc != N.E_RANGE:
+                break
+            cap = info.image_bytes
+        self._crl_fail(rc, cinfo)
+        return out[:info.image_bytes].tobytes(), self._stats_dict(cinfo)
+
+    def crl_probes_device(self, d_crls, offsets, digests, exact=None):
+        """crl_probes of a torch uint8 tensor on this engine's device (any alignment) holding the CRLs back to back;
+        offsets: u64[n + 1], ascending from 0 to the tensor's length → (meta bytes, torch uint8 tensor of the member
+        records on the device; a view, info dict).
+        Sizing.  The bound of the records is length / 6 of them, 8 bytes of records per byte of blob; a real CRL needs
+        about 1.3.  exact=False allocates the bound and makes one call (a second only when the meta's first guess was
+        short); exact=True asks for the sizes first (the two-call convention: every pass but the last runs twice) and
+        allocates what they say.  The default takes the bound while it is at most a quarter of the device's free memory,
+        and asks first otherwise."""
+        import torch
+        if not hasattr(d_crls, "data_ptr"):
+            raise TypeError("d_crls: a torch tensor on this engine's device")
+        _, total, offsets, n, digests = self._crl_args((d_crls, offsets), digests)
+        ptr = C.c_void_p(d_crls.data_ptr()) if total else None
+        info, cinfo = N.KnownImageInfo(), N.CrlInfo()
+        dev = "cuda:%d" % self.device
+        meta_cap, members_cap = 64 + 56 * n + (1 << 12), max(total // 6, 1)
+        if exact is None:
+            exact = 48 * members_cap > torch.cuda.mem_get_info(self.device)[0] // 4
+        if exact:
+            rc = self._lib.ctmr_crl_probes_device(self._h, ptr, total, offsets.ctypes.data, n, digests, None, 0, None, 0,
+                                                  C.byref(info), C.byref(cinfo))
+            if rc != N.E_RANGE:
+                self._crl_fail(rc, cinfo)
+            meta_cap, members_cap = info.meta_bytes, max(info.members, 1)
+        out = torch.empty(members_cap * 48, dtype=torch.uint8, device=dev)
+        for _ in range(2):
+            meta = np.empty(meta_cap, np.uint8)
+            rc = self._lib.ctmr_crl_probes_device(self._h, ptr, total, offsets.ctypes.data, n, digests, meta.ctypes.data, meta_cap,
+                                                  C.c_void_p(out.data_ptr()), members_cap, C.byref(info), C.byref(cinfo))
+            if rc != N.E_RANGE:
+                break
+            meta_cap = info.meta_bytes
+        self._crl_fail(rc, cinfo)
+        return meta[:info.meta_bytes].tobytes(), out[:info.members * 48], self._stats_dict(cinfo)
+
+    def known_revoked(self, crls, digests, now):
+        """Which revoked serials the engine knows, and until when they matter: crl_probes_device → known_export_device →
+        known_image_find_device, with no probe image in host memory.  crls: a list of DER CRLs, or (torch uint8 tensor
+        on this engine's device, offsets).  → (the probe image's meta, hits: numpy known_image.HIT_DTYPE per member
+        record of the probe image in its order, host_hits per host-section pair)."""
+        import torch
+        from .known_image import HIT_DTYPE
+        if not isinstance(crls, tuple):
+            blob, _, offsets, _, digests = self._crl_args(crls, digests)
+            raw = np.frombuffer(blob, np.uint8)
+            crls = (torch.from_numpy(raw.copy()).to("cuda:%d" % self.device), offsets)
+        p_meta, d_p, _ = self.crl_probes_device(crls[0], crls[1], digests)
+        k_meta, d_k = self.known_export_device()
+        hits, host_hits, _ = self.known_image_find_device(k_meta, d_k, p_meta, d_p, now)
+        return p_meta, hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits
+
     def known_import_resp(self, stream, world=1, rank=0) -> dict:
         """The warm start from a reference deployment's Redis contents: every serials:: member of the stream (bytes, or
         a torch uint8 tensor on this engine's device) this rank takes, as SetInsert would add it.  Stream → member

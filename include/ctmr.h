@@ -665,6 +665,82 @@ int ctmr_known_resp_image(ctmr_engine* e, const uint8_t* stream, size_t len, uin
 int ctmr_known_resp_image_device(ctmr_engine* e, const void* d_stream, size_t len, uint8_t* out_meta, size_t out_meta_cap,
                                  void* d_out, uint64_t out_members_cap, ctmr_known_resp_image_info* info);
 
+/* ---- DER CertificateLists as they lie → a probe image: the revoked serials of every CRL as member records, which
+ *      ctmr_known_image_find* takes as P.  The CRL distribution points of an issuer are what k_meta_new collects into the
+ *      crl::<Issuer.ID> sets; this is the step between fetching those CRLs and asking which revoked serials are known.
+ *      DESIGN.md §26.
+ *
+ * Input.  CRL k is crls[offsets[k], offsets[k + 1]); offsets is a HOST array u64[n_crls + 1] that ascends and is
+ *   contiguous: offsets[0] == 0, offsets[n_crls] == len.  digests is a HOST array of n_crls × 32 octets: for each CRL the
+ *   SHA-256 of its issuer's SubjectPublicKeyInfo, as ctmr_issuer_info gives it.  The CRL's issuer Name is not matched
+ *   against anything: the caller knows the issuer from the crl:: set the URL came from.  n_crls = 0 with len = 0 gives
+ *   the empty image.
+ * Grammar of one CRL.  Binary DER, no PEM armour.
+ *   Lengths.  Every length is definite and minimal: one octet below 128, 81 xx from 128, 82 xx xx from 256, 83 … from
+ *     65 536, 84 … from 2^24.  Nothing else is a length (80, 81 7f, 82 00 80, 85 …).
+ *   CertificateList = SEQUENCE { tbsCertList SEQUENCE, signatureAlgorithm SEQUENCE, signatureValue BIT STRING (03) },
+ *     filling its slice exactly; a slice of 0 bytes is outside the grammar.
+ *   tbsCertList holds, in this order and filling it exactly: optional INTEGER (02) version; SEQUENCE signature; SEQUENCE
+ *     issuer; Time thisUpdate; optional Time nextUpdate; optional SEQUENCE revokedCertificates; optional [0] (A0)
+ *     crlExtensions.  A Time is a TLV of tag 17 or 18.
+ *   The contents of version, the two AlgorithmIdentifiers, issuer, the Times, crlExtensions and signatureValue are spanned
+ *     by their lengths and NOT read: they may hold anything, a whole CRL included.
+ *   revokedCertificates holds entries back to back, filling its value exactly; an empty value is accepted.  An entry is
+ *     SEQUENCE { INTEGER userCertificate, Time revocationDate, optional SEQUENCE crlEntryExtensions }, filled exactly by
+ *     those two or three TLVs.  The contents of the three are not read.
+ *   Serial.  The content octets of userCertificate, raw, of any length from 0: the octets NewSerial keeps of a
+ *     certificate's serial (a leading 00 stays, nothing is normalised), so a probe equals the member the map stored for
+ *     the same certificate.
+ *   Dates and reason codes are neither validated nor output.
+ *   EVERYTHING ELSE fails the whole call with CTMR_E_INVAL and writes nothing: cinfo.bad_crl is the LOWEST-numbered CRL
+ *     outside the grammar and cinfo.bad_offset the offset in `crls` of the first TLV of that CRL that is not what the
+ *     grammar wants there (its tag octet; where a structure ends early, the offset at which the missing TLV would start;
+ *     for trailing bytes, the first of them).  A CRL's outer TLVs are judged before its entries; inside
+ *     revokedCertificates the offset is the start of the first entry that is not one — whatever is wrong inside it, and
+ *     also when it would run past the end of the value.  ctmr_last_error() says the same in words.
+ *   The offsets themselves are judged first, before a byte of `crls` is read: offsets[0] != 0 gives bad_crl 0 and
+ *     bad_offset 0; offsets[k + 1] < offsets[k] gives bad_crl k and bad_offset offsets[k] (the lowest such k);
+ *     offsets[n_crls] != len gives bad_crl n_crls and bad_offset len.
+ * Result.  An image v1 that ctmr_known_import and ctmr_known_image_find* accept, not necessarily canonical: the issuers
+ *   are the distinct digests that have at least one member record, in digest order; one set per such digest under exp
+ *   hour 0 (a probe's hour is ignored), in key order — the order of the Issuer.ID text, which is not digest order; a
+ *   set's member records in INPUT ORDER, CRL by CRL and entry by entry, repeats kept: the CRLs of one digest (shards of
+ *   a partitioned CRL, or the same CRL twice) share a set.  A serial above CTMR_MAX_SERIAL octets becomes the host-section
+ *   pair ("serials::1970-01-01-00::<Issuer.ID>", serial); the pairs are sorted, each once.  The call neither sorts nor
+ *   deduplicates: ctmr_known_merge(CTMR_KNOWN_UNION, image, NULL) does.
+ * Sizing.  The two-call convention of ctmr_known_resp_image*: a buffer that is too small gives CTMR_E_RANGE with *info
+ *   and *cinfo filled and nothing written.  A caller can bound the member records without a first call: at most
+ *   len / 6, the shortest entry being 30 04 02 00 17 00.  The meta is 64 + 56 × distinct digests + the host section,
+ *   padded to 64.
+ * Length.  len >= 2^32 − 64 is CTMR_E_INVAL, decided before the first byte is read: a larger collection is split
+ *   between two CRLs and the images joined with CTMR_KNOWN_UNION.
+ * CTMR_E_INVAL and CTMR_E_NOMEM leave every output buffer as it was: all working memory is allocated, and every CRL
+ *   validated, before the first output byte.
+ * Read-only.  Nothing of the engine's state is read or changed (table, pair statistics, counters, host-side store,
+ *   Bloom filter, ctmr_table_info), as for ctmr_known_sort; the blob is const and no byte beyond len is read.
+ * Cost.  The blob is read where it lies; entry starts are found in parallel (a candidate test per byte of a
+ *   revokedCertificates value, then the candidates no earlier one spans).  A serial or an extension body that holds a
+ *   well-formed fake entry opens a conflict region that one lane resolves by walking it, as in ctmr_known_resp_image.
+ * ctmr_crl_probes takes the blob in host memory (staged on the device once) and writes the whole image to host memory;
+ * ctmr_crl_probes_device takes it in device memory of this engine's device at ANY alignment, writes the meta to host
+ * memory and the member records to device memory (16-byte aligned).  Both return after the engine's stream has drained. */
+typedef struct {
+  uint64_t crls;          /* n_crls */
+  uint64_t entries;       /* revoked entries of all CRLs */
+  uint64_t records;       /* … whose serial has at most CTMR_MAX_SERIAL octets: the member records */
+  uint64_t host_members;  /* the host section's pairs: the DISTINCT (issuer, serial) among the other entries */
+  uint64_t empty_crls;    /* CRLs without an entry: revokedCertificates absent or empty */
+  uint64_t candidates;    /* entry candidates the mark pass found, the two frames per CRL counted in; candidates −
+                             entries − frames = the fake entries the passes behind it threw out */
+  uint64_t bad_crl;       /* on CTMR_E_INVAL from the grammar or the offsets: see above; else UINT64_MAX */
+  uint64_t bad_offset;    /* … and its offset in `crls`; else UINT64_MAX */
+} ctmr_crl_info;
+int ctmr_crl_probes(ctmr_engine* e, const uint8_t* crls, size_t len, const uint64_t* offsets, uint32_t n_crls,
+                    const uint8_t* digests, uint8_t* out, size_t cap, ctmr_known_image_info* info, ctmr_crl_info* cinfo);
+int ctmr_crl_probes_device(ctmr_engine* e, const void* d_crls, uint64_t len, const uint64_t* offsets, uint32_t n_crls,
+                           const uint8_t* digests, uint8_t* meta, size_t meta_cap, void* d_members, uint64_t members_cap,
+                           ctmr_known_image_info* info, ctmr_crl_info* cinfo);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner
