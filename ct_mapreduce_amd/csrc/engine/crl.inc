@@ -20,8 +20,6 @@ struct CrlProbes {
 
 const char* const CRL_PROBES = "crl probes";
 
-int crl_alloc(ctmr_engine* e, DevMem* m, size_t bytes) { return rp_alloc(e, m, bytes, CRL_PROBES); }
-
 int crl_bad(ctmr_engine* e, CrlProbes* P, uint64_t crl, uint64_t at, const char* saying) {
   P->cinfo.bad_crl = crl;
   P->cinfo.bad_offset = at;
@@ -55,76 +53,46 @@ int crl_core(ctmr_engine* e, const uint8_t* s, uint64_t len, const uint64_t* off
   }
   if (!len) return crl_bad(e, P, 0, 0, "a CRL of 0 bytes");
   const uint64_t nb = (len + RP_TILE - 1) / RP_TILE;
-  DevMem off_m, span_m, tile_m, cnt_m, err_m, cand_m, nxt_m, flag_m, bm_m, tidx_m, tok_pos, tok_nxt, tok_hdr, star;
-  if ((r = crl_alloc(e, &off_m, ((size_t)n + 1) * 8)) || (r = crl_alloc(e, &span_m, (size_t)n * 8)) || (r = crl_alloc(e, &tile_m, (nb + 1) * 4)) ||
-      (r = crl_alloc(e, &cnt_m, (nb + 2) * 8)) || (r = crl_alloc(e, &err_m, 16)))
+  DevMem off_m, span_m, tile_m, tok_pos;
+  RpStage st;  // err[0]: the head's finding (CRL << 32 | offset), err[1]: the chain's (offset)
+  if ((r = rp_alloc(e, &off_m, ((size_t)n + 1) * 8, CRL_PROBES)) || (r = rp_alloc(e, &span_m, (size_t)n * 8, CRL_PROBES)) ||
+      (r = rp_alloc(e, &tile_m, (nb + 1) * 4, CRL_PROBES)) || (r = st.begin(e, CRL_PROBES, len, ~0ull)))
     return r;
-  unsigned long long* cnt = (unsigned long long*)cnt_m.p;
-  unsigned long long* err = (unsigned long long*)err_m.p;
-  const unsigned long long err0[2] = {~0ull, ~0ull};  // the head's finding (CRL << 32 | offset), the chain's (offset)
-  HIPCHK(e, hipMemcpyAsync(err, err0, 16, hipMemcpyHostToDevice, e->stream));
+  unsigned long long* const cnt = st.cnt;
   HIPCHK(e, hipMemcpyAsync(off_m.p, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, e->stream));
   const CrlBlob B{s, len, (const unsigned long long*)off_m.p, (const uint2*)span_m.p, n};
-  // ---- head, mark
-  hipLaunchKernelGGL(k_crl_head, dim3(rp_grid(n, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, s, B.off, n, (uint2*)span_m.p, err);
+  const CrlCand C{B, (const uint32_t*)tile_m.p};
+  // ---- head, then candidates → tokens (engine/resp_parse.inc RpStage)
+  hipLaunchKernelGGL(k_crl_head, dim3(rp_grid(n, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, s, B.off, n, (uint2*)span_m.p, st.err);
   hipLaunchKernelGGL(k_crl_tiles, dim3(rp_grid(nb + 1, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, B.off, n, nb, (uint32_t*)tile_m.p);
-  HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
-  hipLaunchKernelGGL((k_crl_mark<false>), dim3((unsigned)nb), dim3(RP_BLOCK), 0, e->stream, B, (const uint32_t*)tile_m.p, cnt, (uint32_t*)nullptr,
-                     (uint32_t*)nullptr);
-  uint64_t nc = 0;
-  if ((r = scan_total(e, (uint64_t*)cnt, nb + 1, false, SC_MISC, &nc))) return r;
+  if ((r = st.count(e, C))) return r;
   std::vector<uint2> span(n);
   HIPCHK(e, hipMemcpy(span.data(), span_m.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-  // (nc >= 1: byte 0 starts a CRL and is a frame)
-  const uint64_t ncb = (nc + RP_TILE - 1) / RP_TILE;
-  if ((r = crl_alloc(e, &cand_m, nc * 4)) || (r = crl_alloc(e, &nxt_m, nc * 4)) || (r = crl_alloc(e, &flag_m, nc)) ||
-      (r = crl_alloc(e, &bm_m, ncb * 4)) || (r = crl_alloc(e, &tidx_m, nc * 4)))
-    return r;
-  uint32_t* cand = (uint32_t*)cand_m.p;
-  uint32_t* nxt = (uint32_t*)nxt_m.p;
-  hipLaunchKernelGGL((k_crl_mark<true>), dim3((unsigned)nb), dim3(RP_BLOCK), 0, e->stream, B, (const uint32_t*)tile_m.p, cnt, cand, nxt);
-  // ---- cuts, conflict regions, the kept candidates, and the proof that they are the chain: kernels/resp_parse.h
-  hipLaunchKernelGGL(k_resp_blockmax, dim3((unsigned)ncb), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)nxt, (uint64_t)nc, (uint32_t*)bm_m.p);
-  hipLaunchKernelGGL(k_resp_maxscan, dim3(1), dim3(1024), 0, e->stream, (uint32_t*)bm_m.p, ncb);
-  hipLaunchKernelGGL(k_resp_cuts, dim3((unsigned)ncb), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)cand, (const uint32_t*)nxt, (uint64_t)nc,
-                     (const uint32_t*)bm_m.p, flag_m.u8());
-  hipLaunchKernelGGL(k_resp_resolve, dim3(rp_grid(nc, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)cand, (const uint32_t*)nxt,
-                     (uint64_t)nc, flag_m.u8());
-  if ((r = rp_flag_scan(e, flag_m.u8(), nc, 3u, cnt, (uint32_t*)tidx_m.p, &P->ntok))) return r;
-  const uint64_t nt = P->ntok;  // (>= 1: candidate 0 is a cut)
-  if ((r = crl_alloc(e, &tok_pos, nt * 4)) || (r = crl_alloc(e, &tok_nxt, nt * 4)) || (r = crl_alloc(e, &tok_hdr, nt)) || (r = crl_alloc(e, &star, nt)))
-    return r;
-  hipLaunchKernelGGL(k_resp_tokens, dim3(rp_grid(nc, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, s, len, (const uint32_t*)cand, (const uint32_t*)nxt,
-                     (const uint8_t*)flag_m.u8(), (const uint32_t*)tidx_m.p, (uint64_t)nc, (uint32_t*)tok_pos.p, (uint32_t*)tok_nxt.p, tok_hdr.u8(),
-                     star.u8());
-  hipLaunchKernelGGL(k_resp_chain_from0, dim3(rp_grid(nt, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)tok_pos.p,
-                     (const uint32_t*)tok_nxt.p, nt, len, err + 1);
-  unsigned long long h[2] = {0, 0};
-  HIPCHK(e, hipMemcpyAsync(h, err, 16, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
-  // the lowest CRL: a CRL the head refused has no entry candidates, so the two findings never name the same one
-  const uint64_t head_crl = h[0] == ~0ull ? UINT64_MAX : h[0] >> 32;
-  uint64_t chain_crl = UINT64_MAX;
-  if (h[1] != ~0ull) chain_crl = (uint64_t)(std::upper_bound(offsets, offsets + n + 1, (uint64_t)h[1]) - offsets) - 1;
-  if (head_crl != UINT64_MAX && head_crl < chain_crl)
-    return crl_bad(e, P, head_crl, h[0] & 0xffffffffull, "not the TLV a CertificateList has here, or not a definite minimal length inside its structure");
-  if (chain_crl != UINT64_MAX)
-    return crl_bad(e, P, chain_crl, h[1], "not SEQUENCE { INTEGER, Time, optional SEQUENCE } filled exactly inside revokedCertificates");
-  rp_free(&cand_m);
-  rp_free(&nxt_m);
-  rp_free(&flag_m);
-  rp_free(&bm_m);
-  rp_free(&tidx_m);
-  rp_free(&tok_nxt);
-  rp_free(&tok_hdr);
-  rp_free(&star);
+  {  // (nc >= 1: byte 0 starts a CRL and is a frame)
+    DevMem tok_nxt;
+    if ((r = st.tokens<false>(e, C, s, &tok_pos, &tok_nxt, nullptr, nullptr, nullptr, st.err + 1))) return r;
+    unsigned long long h[2] = {0, 0};
+    HIPCHK(e, hipMemcpyAsync(h, st.err, 16, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipGetLastError());
+    // the lowest CRL: a CRL the head refused has no entry candidates, so the two findings never name the same one
+    const uint64_t head_crl = h[0] == ~0ull ? UINT64_MAX : h[0] >> 32;
+    uint64_t chain_crl = UINT64_MAX;
+    if (h[1] != ~0ull) chain_crl = (uint64_t)(std::upper_bound(offsets, offsets + n + 1, (uint64_t)h[1]) - offsets) - 1;
+    if (head_crl != UINT64_MAX && head_crl < chain_crl)
+      return crl_bad(e, P, head_crl, h[0] & 0xffffffffull, "not the TLV a CertificateList has here, or not a definite minimal length inside its structure");
+    if (chain_crl != UINT64_MAX)
+      return crl_bad(e, P, chain_crl, h[1], "not SEQUENCE { INTEGER, Time, optional SEQUENCE } filled exactly inside revokedCertificates");
+    st.drop();
+  }
+  const uint64_t nc = st.nc, nt = P->ntok = st.ntok;
   // ---- classes, records per CRL, host pairs
   uint64_t nrec = 0, npair = 0;
   DevMem pair_before, pairs_m;
-  if ((r = crl_alloc(e, &P->cls, nt)) || (r = crl_alloc(e, &P->tok_crl, nt * 4)) || (r = crl_alloc(e, &P->tok_ser, nt * 4)) ||
-      (r = crl_alloc(e, &P->rec_before, nt * 4)) || (r = crl_alloc(e, &pair_before, nt * 4)) || (r = crl_alloc(e, &P->crl_rec0, (size_t)n * 4)) ||
-      (r = crl_alloc(e, &P->crl_dst, (size_t)n * 8)))
+  if ((r = rp_alloc(e, &P->cls, nt, CRL_PROBES)) || (r = rp_alloc(e, &P->tok_crl, nt * 4, CRL_PROBES)) ||
+      (r = rp_alloc(e, &P->tok_ser, nt * 4, CRL_PROBES)) || (r = rp_alloc(e, &P->rec_before, nt * 4, CRL_PROBES)) ||
+      (r = rp_alloc(e, &pair_before, nt * 4, CRL_PROBES)) || (r = rp_alloc(e, &P->crl_rec0, (size_t)n * 4, CRL_PROBES)) ||
+      (r = rp_alloc(e, &P->crl_dst, (size_t)n * 8, CRL_PROBES)))
     return r;
   hipLaunchKernelGGL(k_crl_class, dim3(rp_grid(nt, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, B, (const uint32_t*)tok_pos.p, nt, P->cls.u8(),
                      (uint32_t*)P->tok_crl.p, (uint32_t*)P->tok_ser.p);
@@ -136,36 +104,22 @@ int crl_core(ctmr_engine* e, const uint8_t* s, uint64_t len, const uint64_t* off
   std::vector<uint4> pairs(npair);
   HIPCHK(e, hipMemcpyAsync(rec0.data(), P->crl_rec0.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
   if (npair) {
-    if ((r = crl_alloc(e, &pairs_m, npair * 16))) return r;
+    if ((r = rp_alloc(e, &pairs_m, npair * 16, CRL_PROBES))) return r;
     hipLaunchKernelGGL(k_crl_pairs, dim3(rp_grid(nt, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, B, (const uint8_t*)P->cls.u8(),
                        (const uint32_t*)P->tok_crl.p, (const uint32_t*)P->tok_ser.p, (const uint32_t*)pair_before.p, nt, (uint4*)pairs_m.p);
     HIPCHK(e, hipMemcpyAsync(pairs.data(), pairs_m.p, npair * 16, hipMemcpyDeviceToHost, e->stream));
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
   HIPCHK(e, hipGetLastError());
-  // ---- the serials above 40 octets: gathered on the device, copied once
-  std::vector<unsigned long long> dst(npair + 1, 0);
-  std::vector<uint2> seg(npair);
-  for (uint64_t g = 0; g < npair; g++) {
-    seg[g] = make_uint2(pairs[g].x, pairs[g].y);
-    dst[g + 1] = dst[g] + pairs[g].y;
-  }
-  std::vector<uint8_t> bytes(dst[npair]);
-  if (npair) {
-    DevMem seg_m, dst_m, out_m;
-    if ((r = crl_alloc(e, &seg_m, npair * 8)) || (r = crl_alloc(e, &dst_m, npair * 8)) || (r = crl_alloc(e, &out_m, bytes.size()))) return r;
-    HIPCHK(e, hipMemcpyAsync(seg_m.p, seg.data(), npair * 8, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(dst_m.p, dst.data(), npair * 8, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_resp_gather, dim3(rp_grid(npair, RP_BLOCK / 64)), dim3(RP_BLOCK), 0, e->stream, s, (const uint2*)seg_m.p,
-                       (const unsigned long long*)dst_m.p, npair, out_m.u8());
-    HIPCHK(e, hipMemcpyAsync(bytes.data(), out_m.p, bytes.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipGetLastError());
-  }
+  // ---- the serials above 40 octets
+  std::vector<uint2> seg;
+  seg.reserve(npair);
+  for (const uint4& x : pairs) seg.push_back(make_uint2(x.x, x.y));
+  std::vector<unsigned long long> dst;
+  std::vector<uint8_t> bytes;
+  if ((r = rp_gather(e, CRL_PROBES, s, seg, &dst, &bytes))) return r;
   // ---- CRLs → sets by digest, the sets in Issuer.ID order, every CRL's place in its set
   auto dig = [&](uint32_t k) { return digests + (size_t)k * 32; };
-  auto dig_less = [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; };
-  auto dig_same = [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) == 0; };
   std::vector<uint64_t> count(n);
   std::vector<const uint8_t*> digs;
   for (uint32_t k = 0; k < n; k++) {
@@ -173,8 +127,7 @@ int crl_core(ctmr_engine* e, const uint8_t* s, uint64_t len, const uint64_t* off
     if (count[k]) digs.push_back(dig(k));
     if (span[k].x == span[k].y) P->cinfo.empty_crls++;
   }
-  std::sort(digs.begin(), digs.end(), dig_less);
-  digs.erase(std::unique(digs.begin(), digs.end(), dig_same), digs.end());
+  known_number_digests(&digs);
   std::vector<std::string> ids(digs.size());
   std::vector<uint32_t> by_id(digs.size());
   for (size_t i = 0; i < digs.size(); i++) {
@@ -186,7 +139,7 @@ int crl_core(ctmr_engine* e, const uint8_t* s, uint64_t len, const uint64_t* off
   std::vector<uint32_t> ord(n, 0);
   for (uint32_t k = 0; k < n; k++)
     if (count[k]) {
-      ord[k] = (uint32_t)(std::lower_bound(digs.begin(), digs.end(), dig(k), dig_less) - digs.begin());
+      ord[k] = known_digest_ordinal(digs, dig(k));
       set_count[ord[k]] += count[k];
     }
   std::vector<KnownSetEntry> sets;
@@ -207,8 +160,7 @@ int crl_core(ctmr_engine* e, const uint8_t* s, uint64_t len, const uint64_t* off
   for (uint64_t p = 0; p < npair; p++)
     host[p] = {"serials::" + exp_date_id(0) + "::" + b64url(dig(pairs[p].z), 32),
                std::string((const char*)bytes.data() + dst[p], (size_t)(dst[p + 1] - dst[p]))};
-  std::sort(host.begin(), host.end());
-  host.erase(std::unique(host.begin(), host.end()), host.end());
+  known_finish_pairs(&host);
   known_write_meta(digs, sets, host, &P->meta, &P->info);
   P->cinfo.candidates = nc;
   P->cinfo.entries = nrec + npair;
@@ -219,15 +171,13 @@ int crl_core(ctmr_engine* e, const uint8_t* s, uint64_t len, const uint64_t* off
   return CTMR_OK;
 }
 
-// The place pass: info.members records to d_out.  Drains the stream.
-int crl_place(ctmr_engine* e, const CrlProbes& P, uint8_t* d_out) {
-  if (!P.info.members) return CTMR_OK;
-  hipLaunchKernelGGL(k_crl_place, dim3(rp_grid(P.ntok, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, P.s, (const uint8_t*)P.cls.u8(),
-                     (const uint32_t*)P.tok_crl.p, (const uint32_t*)P.tok_ser.p, (const uint32_t*)P.rec_before.p, (const uint32_t*)P.crl_rec0.p,
-                     (const unsigned long long*)P.crl_dst.p, P.ntok, d_out);
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
-  return CTMR_OK;
+// The place pass as rp_emit_* take it: info.members records to d.
+auto crl_place(ctmr_engine* e, const CrlProbes& P) {
+  return [e, &P](uint8_t* d) {
+    hipLaunchKernelGGL(k_crl_place, dim3(rp_grid(P.ntok, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, P.s, (const uint8_t*)P.cls.u8(),
+                       (const uint32_t*)P.tok_crl.p, (const uint32_t*)P.tok_ser.p, (const uint32_t*)P.rec_before.p,
+                       (const uint32_t*)P.crl_rec0.p, (const unsigned long long*)P.crl_dst.p, P.ntok, d);
+  };
 }
 
 }  // namespace
@@ -244,13 +194,7 @@ int ctmr_crl_probes_device(ctmr_engine* e, const void* d_crls, uint64_t len, con
   if (!r) r = crl_core(e, (const uint8_t*)d_crls, len, offsets, n_crls, digests, &P);
   *cinfo = P.cinfo;
   if (r) return r;
-  *info = P.info;
-  if (!meta || meta_cap < P.info.meta_bytes || members_cap < P.info.members || (P.info.members && !d_members))
-    return fail(e, CTMR_E_RANGE, "%s: %llu meta bytes and %llu member records needed", CRL_PROBES, (unsigned long long)P.info.meta_bytes,
-                (unsigned long long)P.info.members);
-  if ((r = crl_place(e, P, (uint8_t*)d_members))) return r;
-  memcpy(meta, P.meta.data(), P.meta.size());
-  return CTMR_OK;
+  return rp_emit_device(e, CRL_PROBES, P.meta, P.info, crl_place(e, P), meta, meta_cap, d_members, members_cap, info);
 }
 
 int ctmr_crl_probes(ctmr_engine* e, const uint8_t* crls, size_t len, const uint64_t* offsets, uint32_t n_crls, const uint8_t* digests, uint8_t* out,
@@ -259,24 +203,11 @@ int ctmr_crl_probes(ctmr_engine* e, const uint8_t* crls, size_t len, const uint6
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   CrlProbes P;
-  DevMem d_crls, d_out;
+  DevMem d_crls;
   int r = crl_args(e, crls, len, offsets, n_crls, digests, &P);
-  if (!r && len) {
-    if (d_crls.alloc(len) != hipSuccess) {
-      *cinfo = P.cinfo;
-      return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu bytes", CRL_PROBES, (unsigned long long)len);
-    }
-    HIPCHK(e, hipMemcpyAsync(d_crls.p, crls, len, hipMemcpyHostToDevice, e->stream));
-  }
+  if (!r) r = rp_stage(e, CRL_PROBES, crls, len, &d_crls);
   if (!r) r = crl_core(e, d_crls.u8(), len, offsets, n_crls, digests, &P);
   *cinfo = P.cinfo;
   if (r) return r;
-  *info = P.info;
-  if (!out || cap < P.info.image_bytes) return fail(e, CTMR_E_RANGE, "%s: %llu bytes needed", CRL_PROBES, (unsigned long long)P.info.image_bytes);
-  if (P.info.members && d_out.alloc(P.info.members * KNOWN_REC_BYTES) != hipSuccess)
-    return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu member records", CRL_PROBES, (unsigned long long)P.info.members);
-  if ((r = crl_place(e, P, d_out.u8()))) return r;
-  if (P.info.members) HIPCHK(e, hipMemcpy(out + P.info.meta_bytes, d_out.p, P.info.members * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
-  memcpy(out, P.meta.data(), P.meta.size());
-  return CTMR_OK;
+  return rp_emit_host(e, CRL_PROBES, P.meta, P.info, crl_place(e, P), out, cap, info);
 }

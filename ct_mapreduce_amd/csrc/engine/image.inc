@@ -123,6 +123,23 @@ int known_parse_meta(ctmr_engine* e, const uint8_t* m, size_t len, bool whole, K
 struct KnownSetEntry { int32_t hour; uint32_t ordinal; uint64_t count; };
 using KnownHostPairs = std::vector<std::pair<std::string, std::string>>;
 
+// What its callers do before it.  Issuers: the digests the sets name (32 bytes each, any order, repeats) → the distinct
+// ones ascending, which is their ordinal order, and a digest's ordinal among them.  Host section: the pairs as found →
+// in order, each once.
+void known_number_digests(std::vector<const uint8_t*>* digs) {
+  std::sort(digs->begin(), digs->end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; });
+  digs->erase(std::unique(digs->begin(), digs->end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) == 0; }), digs->end());
+}
+
+uint32_t known_digest_ordinal(const std::vector<const uint8_t*>& digs, const uint8_t* d) {
+  return (uint32_t)(std::lower_bound(digs.begin(), digs.end(), d, [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; }) - digs.begin());
+}
+
+void known_finish_pairs(KnownHostPairs* host) {
+  std::sort(host->begin(), host->end());
+  host->erase(std::unique(host->begin(), host->end()), host->end());
+}
+
 template <class Info>
 void known_write_meta(const std::vector<const uint8_t*>& digs, const std::vector<KnownSetEntry>& sets, const KnownHostPairs& host,
                       std::vector<uint8_t>* meta, Info* info) {

@@ -279,14 +279,10 @@ int merge_prepare(ctmr_engine* e, MergePlan* mp) {
   std::vector<const uint8_t*> digs;
   for (size_t p = 0; p < np; p++)
     if (counts[p]) digs.push_back(pkey[p]->digest);
-  auto dig_less = [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; };
-  std::sort(digs.begin(), digs.end(), dig_less);
-  digs.erase(std::unique(digs.begin(), digs.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) == 0; }), digs.end());
+  known_number_digests(&digs);
   std::vector<KnownSetEntry> sets;
   for (size_t p = 0; p < np; p++)
-    if (counts[p])
-      sets.push_back({pkey[p]->hour, (uint32_t)(std::lower_bound(digs.begin(), digs.end(), pkey[p]->digest, dig_less) - digs.begin()),
-                      counts[p]});
+    if (counts[p]) sets.push_back({pkey[p]->hour, known_digest_ordinal(digs, pkey[p]->digest), counts[p]});
   known_write_meta(digs, sets, host, &mp->meta, &mp->info);
   if (mp->info.members != (is_union ? a.n + kept : kept))
     return fail(e, CTMR_E_HIP, "known merge: the sets hold %llu members, the kept records are %llu", (unsigned long long)mp->info.members,

@@ -3,6 +3,8 @@
 // kernels/resp_parse.h find its tokens, check its grammar and commands, and write the member records.  The host sees
 // one entry per run of commands of one key (its key text, how many records it has) and the host-section pairs, which
 // are rare: it orders the runs by key into sets, numbers the issuers, gives every run its place and writes the meta.
+// The first half of the file is what any parser of a length-prefixed input shares (engine/crl.inc is the second): the
+// token stage RpStage, the gather, and the two ways out of a call.
 // Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/merge.inc.
 
 extern "C++" {
@@ -65,6 +67,150 @@ int rp_check(ctmr_engine* e, unsigned long long* d_err, const char* saying, unsi
   return CTMR_OK;
 }
 
+// Candidates → tokens: the stage every parser of a length-prefixed input runs (DESIGN.md §19).  Its one variable part
+// is the candidate predicate Cand the two mark launches carry (kernels/resp_parse.h RespCand, kernels/crl.h CrlCand);
+// the cuts, conflict-region, compaction and chain kernels work on cand[] / nxt[] alone.  In three steps, because the
+// callers have work of their own between them: begin (the counters and the two error words), count (the count pass and
+// its scan → nc), tokens (the write pass … the chain kernel → ntok and the token tables).  The caller reads err its own
+// way, then calls drop(): the candidate tables go before the later tables of the call are allocated.
+struct RpStage {
+  const char* what = nullptr;  // the call, for the messages
+  uint64_t len = 0, nb = 0, nc = 0, ntok = 0;
+  DevMem cnt_m, err_m, cand_m, nxt_m, flag_m, bm_m, tidx_m;
+  unsigned long long* cnt = nullptr;  // nb + 2 words: the later flag scans of the call use them too
+  unsigned long long* err = nullptr;  // two words, err[0] = ~0; err[1] = err1 and its meaning are the caller's
+  unsigned long long err0[2] = {~0ull, 0ull};
+
+  int begin(ctmr_engine* e, const char* call, uint64_t bytes, unsigned long long err1) {
+    int r;
+    what = call;
+    len = bytes;
+    nb = (len + RP_TILE - 1) / RP_TILE;
+    err0[1] = err1;
+    if ((r = rp_alloc(e, &cnt_m, (nb + 2) * 8, what)) || (r = rp_alloc(e, &err_m, 16, what))) return r;
+    cnt = (unsigned long long*)cnt_m.p;
+    err = (unsigned long long*)err_m.p;
+    HIPCHK(e, hipMemcpyAsync(err, err0, 16, hipMemcpyHostToDevice, e->stream));
+    return CTMR_OK;
+  }
+
+  template <class Cand>
+  int count(ctmr_engine* e, const Cand& C) {
+    HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
+    hipLaunchKernelGGL((k_resp_mark<false, Cand>), dim3((unsigned)nb), dim3(RP_BLOCK), 0, e->stream, C, cnt, (uint32_t*)nullptr, (uint32_t*)nullptr);
+    return scan_total(e, (uint64_t*)cnt, nb + 1, false, SC_MISC, &nc);
+  }
+
+  // nc >= 1.  RESP: the tokens are a RESP stream's, s is read for tok_hdr / star, and the first token is a '*'; more: a
+  // table of a word per token the caller wants allocated behind them (may be null).  Else only tok_pos / tok_nxt are made.
+  template <bool RESP, class Cand>
+  int tokens(ctmr_engine* e, const Cand& C, const uint8_t* s, DevMem* tok_pos, DevMem* tok_nxt, DevMem* tok_hdr, DevMem* star, DevMem* more,
+             unsigned long long* chain_err) {
+    int r;
+    const uint64_t ncb = (nc + RP_TILE - 1) / RP_TILE;
+    if ((r = rp_alloc(e, &cand_m, nc * 4, what)) || (r = rp_alloc(e, &nxt_m, nc * 4, what)) || (r = rp_alloc(e, &flag_m, nc, what)) ||
+        (r = rp_alloc(e, &bm_m, ncb * 4, what)) || (r = rp_alloc(e, &tidx_m, nc * 4, what)))
+      return r;
+    uint32_t* cand = (uint32_t*)cand_m.p;
+    uint32_t* nxt = (uint32_t*)nxt_m.p;
+    hipLaunchKernelGGL((k_resp_mark<true, Cand>), dim3((unsigned)nb), dim3(RP_BLOCK), 0, e->stream, C, cnt, cand, nxt);
+    // cuts, conflict regions
+    hipLaunchKernelGGL(k_resp_blockmax, dim3((unsigned)ncb), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)nxt, (uint64_t)nc, (uint32_t*)bm_m.p);
+    hipLaunchKernelGGL(k_resp_maxscan, dim3(1), dim3(1024), 0, e->stream, (uint32_t*)bm_m.p, ncb);
+    hipLaunchKernelGGL(k_resp_cuts, dim3((unsigned)ncb), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)cand, (const uint32_t*)nxt, (uint64_t)nc,
+                       (const uint32_t*)bm_m.p, flag_m.u8());
+    hipLaunchKernelGGL(k_resp_resolve, dim3(rp_grid(nc, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)cand, (const uint32_t*)nxt,
+                       (uint64_t)nc, flag_m.u8());
+    // the kept candidates, and the proof that they are the chain
+    if ((r = rp_flag_scan(e, flag_m.u8(), nc, 3u, cnt, (uint32_t*)tidx_m.p, &ntok))) return r;
+    const uint64_t nt = ntok;  // (>= 1: candidate 0 is a cut)
+    if ((r = rp_alloc(e, tok_pos, nt * 4, what)) || (r = rp_alloc(e, tok_nxt, nt * 4, what))) return r;
+    if (RESP && ((r = rp_alloc(e, tok_hdr, nt, what)) || (r = rp_alloc(e, star, nt, what)))) return r;
+    if (more && (r = rp_alloc(e, more, nt * 4, what))) return r;
+    hipLaunchKernelGGL((k_resp_tokens<RESP>), dim3(rp_grid(nc, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, s, len, (const uint32_t*)cand,
+                       (const uint32_t*)nxt, (const uint8_t*)flag_m.u8(), (const uint32_t*)tidx_m.p, (uint64_t)nc, (uint32_t*)tok_pos->p,
+                       (uint32_t*)tok_nxt->p, RESP ? tok_hdr->u8() : nullptr, RESP ? star->u8() : nullptr);
+    hipLaunchKernelGGL((k_resp_chain<RESP>), dim3(rp_grid(nt, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)tok_pos->p,
+                       (const uint32_t*)tok_nxt->p, RESP ? (const uint8_t*)star->u8() : nullptr, nt, len, chain_err);
+    return CTMR_OK;
+  }
+
+  void drop() {
+    for (DevMem* m : {&cand_m, &nxt_m, &flag_m, &bm_m, &tidx_m}) rp_free(m);
+  }
+};
+
+// gather: the segments {offset, length} of the input → *bytes, segment g at (*dst)[g], behind the last (*dst)[n]; gathered
+// on the device, copied once.  Drains the stream.
+int rp_gather(ctmr_engine* e, const char* what, const uint8_t* s, const std::vector<uint2>& seg, std::vector<unsigned long long>* dst,
+              std::vector<uint8_t>* bytes) {
+  int r;
+  const uint64_t nseg = seg.size();
+  dst->assign(nseg + 1, 0);
+  for (uint64_t g = 0; g < nseg; g++) (*dst)[g + 1] = (*dst)[g] + seg[g].y;
+  bytes->resize((*dst)[nseg]);
+  if (!nseg) return CTMR_OK;
+  DevMem seg_m, dst_m, out_m;
+  if ((r = rp_alloc(e, &seg_m, nseg * 8, what)) || (r = rp_alloc(e, &dst_m, nseg * 8, what)) || (r = rp_alloc(e, &out_m, bytes->size(), what)))
+    return r;
+  HIPCHK(e, hipMemcpyAsync(seg_m.p, seg.data(), nseg * 8, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(dst_m.p, dst->data(), nseg * 8, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_resp_gather, dim3(rp_grid(nseg, RP_BLOCK / 64)), dim3(RP_BLOCK), 0, e->stream, s, (const uint2*)seg_m.p,
+                     (const unsigned long long*)dst_m.p, nseg, out_m.u8());
+  if (!bytes->empty()) HIPCHK(e, hipMemcpyAsync(bytes->data(), out_m.p, bytes->size(), hipMemcpyDeviceToHost, e->stream));  // (keys of no octets)
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  return CTMR_OK;
+}
+
+// The way in of a host variant: the input's len bytes to device memory.
+int rp_stage(ctmr_engine* e, const char* what, const void* src, uint64_t len, DevMem* d) {
+  if (!len) return CTMR_OK;
+  if (d->alloc(len) != hipSuccess) return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu bytes", what, (unsigned long long)len);
+  HIPCHK(e, hipMemcpyAsync(d->p, src, len, hipMemcpyHostToDevice, e->stream));
+  return CTMR_OK;
+}
+
+// The two ways out of a call whose core has made `meta` and `info` (an image's, or a longer struct that begins as it
+// does): *out_info, the refusal of short buffers, the place pass — place(d) launches it, info.members records to d — and
+// the meta.  Nothing is written to a buffer before the last thing that can fail.  Drain the stream.
+template <class Place>
+int rp_place(ctmr_engine* e, uint64_t members, Place place, uint8_t* d_out) {
+  if (!members) return CTMR_OK;
+  place(d_out);
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipGetLastError());
+  return CTMR_OK;
+}
+
+template <class Info, class Place>
+int rp_emit_device(ctmr_engine* e, const char* what, const std::vector<uint8_t>& meta, const Info& info, Place place, uint8_t* out_meta,
+                   size_t meta_cap, void* d_out, uint64_t members_cap, Info* out_info) {
+  int r;
+  *out_info = info;
+  if (!out_meta || meta_cap < info.meta_bytes || members_cap < info.members || (info.members && !d_out))
+    return fail(e, CTMR_E_RANGE, "%s: %llu meta bytes and %llu member records needed", what, (unsigned long long)info.meta_bytes,
+                (unsigned long long)info.members);
+  if ((r = rp_place(e, info.members, place, (uint8_t*)d_out))) return r;
+  memcpy(out_meta, meta.data(), meta.size());
+  return CTMR_OK;
+}
+
+template <class Info, class Place>
+int rp_emit_host(ctmr_engine* e, const char* what, const std::vector<uint8_t>& meta, const Info& info, Place place, uint8_t* out, size_t cap,
+                 Info* out_info) {
+  int r;
+  DevMem d_out;
+  *out_info = info;
+  if (!out || cap < info.image_bytes) return fail(e, CTMR_E_RANGE, "%s: %llu bytes needed", what, (unsigned long long)info.image_bytes);
+  if (info.members && d_out.alloc(info.members * KNOWN_REC_BYTES) != hipSuccess)
+    return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu member records", what, (unsigned long long)info.members);
+  if ((r = rp_place(e, info.members, place, d_out.u8()))) return r;
+  if (info.members) HIPCHK(e, hipMemcpy(out + info.meta_bytes, d_out.p, info.members * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
+  memcpy(out, meta.data(), meta.size());
+  return CTMR_OK;
+}
+
 // Everything but the records: the stream (device memory, any alignment) validated, R->meta and R->info made, the tables
 // of the place pass left on the device.  Drains the stream.
 int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R) {
@@ -76,50 +222,17 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
     known_write_meta({}, {}, {}, &R->meta, &R->info);
     return CTMR_OK;
   }
-  const uint64_t nb = (len + RP_TILE - 1) / RP_TILE;
-  DevMem cnt_m, err_m, cand_m, nxt_m, flag_m, bm_m, tidx_m;
-  if ((r = rp_alloc(e, &cnt_m, (nb + 2) * 8)) || (r = rp_alloc(e, &err_m, 16))) return r;
-  unsigned long long* cnt = (unsigned long long*)cnt_m.p;
-  unsigned long long* err = (unsigned long long*)err_m.p;
-  const unsigned long long err0[2] = {~0ull, 0ull};
-  HIPCHK(e, hipMemcpyAsync(err, err0, 16, hipMemcpyHostToDevice, e->stream));
-  // ---- mark
-  HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
-  hipLaunchKernelGGL((k_resp_mark<false>), dim3((unsigned)nb), dim3(RP_BLOCK), 0, e->stream, s, len, cnt, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  uint64_t nc = 0;
-  if ((r = scan_total(e, (uint64_t*)cnt, nb + 1, false, SC_MISC, &nc))) return r;
-  if (!nc) return fail(e, CTMR_E_INVAL, "%s: offset 0: no command starts here", RESP_IMAGE);
-  const uint64_t ncb = (nc + RP_TILE - 1) / RP_TILE;
-  if ((r = rp_alloc(e, &cand_m, nc * 4)) || (r = rp_alloc(e, &nxt_m, nc * 4)) || (r = rp_alloc(e, &flag_m, nc)) ||
-      (r = rp_alloc(e, &bm_m, ncb * 4)) || (r = rp_alloc(e, &tidx_m, nc * 4)))
-    return r;
-  uint32_t* cand = (uint32_t*)cand_m.p;
-  uint32_t* nxt = (uint32_t*)nxt_m.p;
-  hipLaunchKernelGGL((k_resp_mark<true>), dim3((unsigned)nb), dim3(RP_BLOCK), 0, e->stream, s, len, cnt, cand, nxt);
-  // ---- cuts, conflict regions
-  hipLaunchKernelGGL(k_resp_blockmax, dim3((unsigned)ncb), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)nxt, (uint64_t)nc, (uint32_t*)bm_m.p);
-  hipLaunchKernelGGL(k_resp_maxscan, dim3(1), dim3(1024), 0, e->stream, (uint32_t*)bm_m.p, ncb);
-  hipLaunchKernelGGL(k_resp_cuts, dim3((unsigned)ncb), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)cand, (const uint32_t*)nxt, (uint64_t)nc,
-                     (const uint32_t*)bm_m.p, flag_m.u8());
-  hipLaunchKernelGGL(k_resp_resolve, dim3(rp_grid(nc, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)cand, (const uint32_t*)nxt,
-                     (uint64_t)nc, flag_m.u8());
-  // ---- tokens, and the proof that they are the chain
-  if ((r = rp_flag_scan(e, flag_m.u8(), nc, 3u, cnt, (uint32_t*)tidx_m.p, &R->ntok))) return r;
-  const uint64_t nt = R->ntok;  // (>= 1: candidate 0 is a cut)
-  if ((r = rp_alloc(e, &R->tok_pos, nt * 4)) || (r = rp_alloc(e, &R->tok_nxt, nt * 4)) || (r = rp_alloc(e, &R->tok_hdr, nt)) ||
-      (r = rp_alloc(e, &R->star, nt)) || (r = rp_alloc(e, &R->cidx, nt * 4)))
-    return r;
-  hipLaunchKernelGGL(k_resp_tokens, dim3(rp_grid(nc, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, s, len, (const uint32_t*)cand, (const uint32_t*)nxt,
-                     (const uint8_t*)flag_m.u8(), (const uint32_t*)tidx_m.p, (uint64_t)nc, (uint32_t*)R->tok_pos.p, (uint32_t*)R->tok_nxt.p,
-                     R->tok_hdr.u8(), R->star.u8());
-  hipLaunchKernelGGL(k_resp_chain, dim3(rp_grid(nt, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)R->tok_pos.p,
-                     (const uint32_t*)R->tok_nxt.p, (const uint8_t*)R->star.u8(), nt, len, err);
-  if ((r = rp_check(e, err, "not the start of a command or of a bulk string that ends in CRLF inside the stream"))) return r;
-  rp_free(&cand_m);
-  rp_free(&nxt_m);
-  rp_free(&flag_m);
-  rp_free(&bm_m);
-  rp_free(&tidx_m);
+  // ---- candidates → tokens
+  RpStage st;
+  const RespCand C{s, len};
+  if ((r = st.begin(e, RESP_IMAGE, len, 0ull)) || (r = st.count(e, C))) return r;
+  if (!st.nc) return fail(e, CTMR_E_INVAL, "%s: offset 0: no command starts here", RESP_IMAGE);
+  if ((r = st.tokens<true>(e, C, s, &R->tok_pos, &R->tok_nxt, &R->tok_hdr, &R->star, &R->cidx, st.err))) return r;
+  if ((r = rp_check(e, st.err, "not the start of a command or of a bulk string that ends in CRLF inside the stream"))) return r;
+  st.drop();
+  unsigned long long* const cnt = st.cnt;
+  unsigned long long* const err = st.err;
+  const uint64_t nt = R->ntok = st.ntok;
   // ---- commands
   if ((r = rp_flag_scan(e, R->star.u8(), nt, 1u, cnt, (uint32_t*)R->cidx.p, &R->ncmd))) return r;
   const uint64_t ncmd = R->ncmd;
@@ -159,26 +272,13 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
   HIPCHK(e, hipStreamSynchronize(e->stream));
   HIPCHK(e, hipGetLastError());
   // ---- the bytes the host needs: every run's key, every pair's member — gathered on the device, copied once
-  const uint64_t nseg = nrun + npair;
-  std::vector<uint2> seg(nseg);
-  std::vector<unsigned long long> dst(nseg + 1, 0);
-  for (uint64_t g = 0; g < nseg; g++) {
-    const uint4& x = g < nrun ? runs[g] : pairs[g - nrun];
-    seg[g] = make_uint2(x.x, x.y);
-    dst[g + 1] = dst[g] + x.y;
-  }
-  std::vector<uint8_t> bytes(dst[nseg]);
-  if (nseg) {
-    DevMem seg_m, dst_m, out_m;
-    if ((r = rp_alloc(e, &seg_m, nseg * 8)) || (r = rp_alloc(e, &dst_m, nseg * 8)) || (r = rp_alloc(e, &out_m, bytes.size()))) return r;
-    HIPCHK(e, hipMemcpyAsync(seg_m.p, seg.data(), nseg * 8, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(dst_m.p, dst.data(), nseg * 8, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_resp_gather, dim3(rp_grid(nseg, RP_BLOCK / 64)), dim3(RP_BLOCK), 0, e->stream, s, (const uint2*)seg_m.p,
-                       (const unsigned long long*)dst_m.p, nseg, out_m.u8());
-    if (!bytes.empty()) HIPCHK(e, hipMemcpyAsync(bytes.data(), out_m.p, bytes.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipGetLastError());
-  }
+  std::vector<uint2> seg;
+  seg.reserve(nrun + npair);
+  for (const uint4& x : runs) seg.push_back(make_uint2(x.x, x.y));
+  for (const uint4& x : pairs) seg.push_back(make_uint2(x.x, x.y));
+  std::vector<unsigned long long> dst;
+  std::vector<uint8_t> bytes;
+  if ((r = rp_gather(e, RESP_IMAGE, s, seg, &dst, &bytes))) return r;
   auto text = [&](uint64_t g) { return std::string((const char*)bytes.data() + dst[g], (size_t)(dst[g + 1] - dst[g])); };
   // ---- the runs that have records, in key order (stable: a key's runs stay in stream order) → sets, issuers, places
   std::vector<std::string> key(nrun);
@@ -209,14 +309,11 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
   if (first != nrec) return fail(e, CTMR_E_HIP, "%s: the runs hold %llu records, the stream %llu", RESP_IMAGE, (unsigned long long)first, (unsigned long long)nrec);
   std::vector<const uint8_t*> digs;
   for (auto& mk : set_key) digs.push_back(mk.digest);
-  auto dig_less = [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) < 0; };
-  std::sort(digs.begin(), digs.end(), dig_less);
-  digs.erase(std::unique(digs.begin(), digs.end(), [](const uint8_t* x, const uint8_t* y) { return memcmp(x, y, 32) == 0; }), digs.end());
-  for (size_t i = 0; i < sets.size(); i++) sets[i].ordinal = (uint32_t)(std::lower_bound(digs.begin(), digs.end(), set_key[i].digest, dig_less) - digs.begin());
+  known_number_digests(&digs);
+  for (size_t i = 0; i < sets.size(); i++) sets[i].ordinal = known_digest_ordinal(digs, set_key[i].digest);
   KnownHostPairs host(npair);
   for (uint64_t p = 0; p < npair; p++) host[p] = {key[pairs[p].z], text(nrun + p)};
-  std::sort(host.begin(), host.end());
-  host.erase(std::unique(host.begin(), host.end()), host.end());
+  known_finish_pairs(&host);
   known_write_meta(digs, sets, host, &R->meta, &R->info);
   if (nrun) {
     HIPCHK(e, hipMemcpyAsync(R->run_dst.p, run_dst.data(), nrun * 8, hipMemcpyHostToDevice, e->stream));
@@ -225,14 +322,13 @@ int resp_parse_core(ctmr_engine* e, const uint8_t* s, uint64_t len, RespImage* R
   return CTMR_OK;
 }
 
-// The place pass: info.members records to d_out.  Drains the stream.
-int resp_parse_place(ctmr_engine* e, const RespImage& R, uint8_t* d_out) {
-  if (!R.info.members) return CTMR_OK;
-  hipLaunchKernelGGL(k_resp_place, dim3(rp_grid(R.ntok, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, R.tokens(), R.cmds(), (const uint8_t*)R.part.u8(),
-                     (const uint32_t*)R.rec_before.p, (const uint4*)R.runs.p, (const unsigned long long*)R.run_dst.p, d_out);
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, hipGetLastError());
-  return CTMR_OK;
+// The place pass as rp_emit_* take it: info.members records to d.
+auto resp_parse_place(ctmr_engine* e, const RespImage& R) {
+  return [e, &R](uint8_t* d) {
+    hipLaunchKernelGGL(k_resp_place, dim3(rp_grid(R.ntok, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, R.tokens(), R.cmds(),
+                       (const uint8_t*)R.part.u8(), (const uint32_t*)R.rec_before.p, (const uint4*)R.runs.p,
+                       (const unsigned long long*)R.run_dst.p, d);
+  };
 }
 
 int resp_parse_len(ctmr_engine* e, size_t len) {
@@ -254,13 +350,7 @@ int ctmr_known_resp_image_device(ctmr_engine* e, const void* d_stream, size_t le
   if (len && !d_stream) return fail(e, CTMR_E_INVAL, "%s: null stream", RESP_IMAGE);
   RespImage R;
   if ((r = resp_parse_core(e, (const uint8_t*)d_stream, len, &R))) return r;
-  *info = R.info;
-  if (!out_meta || out_meta_cap < R.info.meta_bytes || out_members_cap < R.info.members || (R.info.members && !d_out))
-    return fail(e, CTMR_E_RANGE, "%s: %llu meta bytes and %llu member records needed", RESP_IMAGE, (unsigned long long)R.info.meta_bytes,
-                (unsigned long long)R.info.members);
-  if ((r = resp_parse_place(e, R, (uint8_t*)d_out))) return r;
-  memcpy(out_meta, R.meta.data(), R.meta.size());
-  return CTMR_OK;
+  return rp_emit_device(e, RESP_IMAGE, R.meta, R.info, resp_parse_place(e, R), out_meta, out_meta_cap, d_out, out_members_cap, info);
 }
 
 int ctmr_known_resp_image(ctmr_engine* e, const uint8_t* stream, size_t len, uint8_t* out, size_t cap, ctmr_known_resp_image_info* info) {
@@ -270,20 +360,9 @@ int ctmr_known_resp_image(ctmr_engine* e, const uint8_t* stream, size_t len, uin
   int r;
   if ((r = resp_parse_len(e, len))) return r;
   if (len && !stream) return fail(e, CTMR_E_INVAL, "%s: null stream", RESP_IMAGE);
-  DevMem d_stream, d_out;
-  if (len) {
-    if (d_stream.alloc(len) != hipSuccess) return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu bytes", RESP_IMAGE, (unsigned long long)len);
-    HIPCHK(e, hipMemcpyAsync(d_stream.p, stream, len, hipMemcpyHostToDevice, e->stream));
-  }
+  DevMem d_stream;
+  if ((r = rp_stage(e, RESP_IMAGE, stream, len, &d_stream))) return r;
   RespImage R;
   if ((r = resp_parse_core(e, d_stream.u8(), len, &R))) return r;
-  *info = R.info;
-  if (!out || cap < R.info.image_bytes) return fail(e, CTMR_E_RANGE, "%s: %llu bytes needed", RESP_IMAGE, (unsigned long long)R.info.image_bytes);
-  if (R.info.members && d_out.alloc(R.info.members * KNOWN_REC_BYTES) != hipSuccess)
-    return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu member records", RESP_IMAGE, (unsigned long long)R.info.members);
-  if ((r = resp_parse_place(e, R, d_out.u8()))) return r;
-  if (R.info.members)
-    HIPCHK(e, hipMemcpy(out + R.info.meta_bytes, d_out.p, R.info.members * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
-  memcpy(out, R.meta.data(), R.meta.size());
-  return CTMR_OK;
+  return rp_emit_host(e, RESP_IMAGE, R.meta, R.info, resp_parse_place(e, R), out, cap, info);
 }

@@ -26,8 +26,9 @@
 //                       and EXPIREAT commands)
 //   kernels/resp_parse.h k_resp_mark / k_resp_cuts / k_resp_resolve / k_resp_chain / k_resp_commands / k_resp_place (a Redis
 //                       protocol stream of SADD and EXPIREAT commands as it lies → an image's member records)
-//   kernels/crl.h       k_crl_head / k_crl_mark / k_crl_class / k_crl_place (DER CertificateLists as they lie → the revoked
-//                       serials as a probe image's member records; the cuts and the chain proof are resp_parse.h's)
+//   kernels/crl.h       k_crl_head / CrlCand / k_crl_class / k_crl_place (DER CertificateLists as they lie → the revoked
+//                       serials as a probe image's member records; the mark kernel over CrlCand, the cuts and the chain
+//                       proof are resp_parse.h's)
 //   kernels/text_scan.h what the two text decoders below share: a text in segments read in 16-byte chunks, the wave's scan
 //                       and report, the base64 decode of a tile; k_ej_tiles / k_ej_tile_list (both decoders launch them)
 //   kernels/entries_json.h k_ej_quotes / k_ej_mark / k_ej_resp / k_ej_check / k_ej_decode (get-entries JSON bodies as they

@@ -1,12 +1,13 @@
 // kernels/crl.h — DER CertificateLists as they lie → the revoked serials as the member records of a probe image
 // (include/ctmr.h ctmr_crl_probes*).  A revokedCertificates value is a run of length-prefixed entries whose
 // serials and extension bodies are raw octets: an entry start cannot be found by pattern, and following the lengths is
-// one dependent chain.  The shape is that of kernels/resp_parse.h, whose cuts, conflict-region, compaction and chain
-// kernels work on cand[] / nxt[] alone and are launched as they are.  What is new here:
+// one dependent chain.  The shape is that of kernels/resp_parse.h, whose mark kernel is a template over the candidate
+// predicate and whose cuts, conflict-region, compaction and chain kernels work on cand[] / nxt[] alone.  What is new here:
 //   head      one lane per CRL walks the dozen outer TLVs → [lo, hi) of the revokedCertificates value, or the offset at
 //             which the CRL leaves the grammar.
-//   mark      every byte inside some [lo, hi) is tested as an entry start ("candidate": SEQUENCE { INTEGER, Time,
-//             optional SEQUENCE } filled exactly, ending at or before hi); every true entry is one.  Two frame candidates
+//   mark      CrlCand, the predicate k_resp_mark runs over: every byte inside some [lo, hi) is tested as an entry start
+//             ("candidate": SEQUENCE { INTEGER, Time, optional SEQUENCE } filled exactly, ending at or before hi); every
+//             true entry is one.  Two frame candidates
 //             per CRL cover the bytes outside its value — its start → lo, hi → its end — so that the true chain runs
 //             from 0 to len across all CRLs.
 //   class     per kept token, behind the chain proof: its CRL, whether it is a frame, a record (serial <= 40 octets) or a
@@ -196,29 +197,15 @@ __device__ __forceinline__ bool crl_candidate(const CrlBlob& B, uint32_t k0, uin
   return front || behind || end != 0;
 }
 
-// mark, as k_resp_mark.  WRITE = false: cnt[blk] = the candidates among the blob's bytes [1024 blk, 1024 blk + 1024).
-// WRITE = true, behind the exclusive scan of cnt[]: cand[] / nxt[] of those candidates, ascending.
-template <bool WRITE>
-__global__ void __launch_bounds__(RP_BLOCK) k_crl_mark(CrlBlob B, const uint32_t* tile_crl, unsigned long long* cnt, uint32_t* cand,
-                                                       uint32_t* nxt) {
-  __shared__ uint32_t ws[RP_BLOCK / 64];
-  const uint64_t base = WRITE ? cnt[blockIdx.x] : 0ull;
-  const uint32_t k0 = tile_crl[blockIdx.x], k1 = tile_crl[blockIdx.x + 1];
-  uint32_t run = 0u;
-#pragma unroll 1
-  for (uint32_t it = 0; it < RP_PER; it++) {
-    const uint64_t i = (uint64_t)blockIdx.x * RP_TILE + it * RP_BLOCK + threadIdx.x;
-    uint32_t nx = 0u, all;
-    const bool c = i < B.len && crl_candidate(B, k0, k1, i, &nx);
-    const uint32_t rank = rp_block_rank(c, ws, &all);
-    if (WRITE && c) {
-      cand[base + run + rank] = (uint32_t)i;
-      nxt[base + run + rank] = nx;
-    }
-    run += all;
-  }
-  if (!WRITE && threadIdx.x == 0) cnt[blockIdx.x] = run;
-}
+// the candidate predicate k_resp_mark takes (kernels/resp_parse.h RespCand): a block reads the CRLs of its tile's first
+// byte and of the byte behind its last, and every byte is searched between the two
+struct CrlCand {
+  CrlBlob B;
+  const uint32_t* tile_crl;
+  __device__ __forceinline__ uint64_t bytes() const { return B.len; }
+  __device__ __forceinline__ uint2 block() const { return make_uint2(tile_crl[blockIdx.x], tile_crl[blockIdx.x + 1]); }
+  __device__ __forceinline__ bool operator()(uint2 k, uint64_t i, uint32_t* next) const { return crl_candidate(B, k.x, k.y, i, next); }
+};
 
 // class, behind the chain proof (every token is a frame or a true entry): cls[t], tok_crl[t], and for an entry tok_ser[t]
 // = the offset of its serial's length octet
@@ -271,21 +258,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_crl_place(const uint8_t* s, const 
   const uint32_t k = tok_crl[t];
   const uint64_t at = crl_dst[k] + (rec_before[t] - crl_rec0[k]);
   const uint8_t* m = s + tok_ser[t];
-  const uint32_t L = m[0];  // <= 40: the short form
-  m++;
-  uint32_t w[10];
-#pragma unroll
-  for (uint32_t q = 0; q < 10; q++) {
-    uint32_t v = 0u;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; b++)
-      if (4u * q + b < L) v |= (uint32_t)m[4u * q + b] << (8u * b);
-    w[q] = v;
-  }
-  uint4* o = (uint4*)(out + at * KNOWN_REC_BYTES);
-  o[0] = make_uint4(L, 0u, w[0], w[1]);
-  o[1] = make_uint4(w[2], w[3], w[4], w[5]);
-  o[2] = make_uint4(w[6], w[7], w[8], w[9]);
+  known_store_octets(m[0], m + 1, out, at);  // (the length is <= 40: the short form)
 }
 
 }  // namespace ctmr

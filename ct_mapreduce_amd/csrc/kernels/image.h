@@ -129,6 +129,24 @@ __device__ __forceinline__ uint32_t known_load(const uint4* p, unsigned long lon
   return bad;
 }
 
+// The member record of the L <= 40 octets at m (any alignment; no octet at or beyond m + L is read) → record `at` of out:
+// u64 serial_len, the octets, zeros to 48 bytes
+__device__ __forceinline__ void known_store_octets(uint32_t L, const uint8_t* m, uint8_t* out, uint64_t at) {
+  uint32_t w[10];
+#pragma unroll
+  for (uint32_t q = 0; q < 10; q++) {
+    uint32_t v = 0u;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; b++)
+      if (4u * q + b < L) v |= (uint32_t)m[4u * q + b] << (8u * b);
+    w[q] = v;
+  }
+  uint4* o = (uint4*)(out + at * KNOWN_REC_BYTES);
+  o[0] = make_uint4(L, 0u, w[0], w[1]);
+  o[1] = make_uint4(w[2], w[3], w[4], w[5]);
+  o[2] = make_uint4(w[6], w[7], w[8], w[9]);
+}
+
 // What a wave saw of bad records (bad: known_load's result, 0 in a lane without a record) → *err, one atomicOr by
 // lane 0 of a wave that saw one.  Every lane of the wave calls it.
 __device__ __forceinline__ void known_report_bad(uint32_t bad, uint32_t* err) {

@@ -94,19 +94,31 @@ __device__ __forceinline__ uint32_t rp_block_rank(bool set, uint32_t* ws, uint32
   return pre + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
 }
 
-// mark.  WRITE = false: cnt[blk] = the candidates among the stream's bytes [1024 blk, 1024 blk + 1024).
+// the candidate predicate of a RESP stream, as k_resp_mark takes it: bytes() = how many to test, block() = what the
+// predicate reads once per block (nothing here), (that, i, &next) = whether byte i is a candidate and where it says the
+// next token starts
+struct RespCand {
+  const uint8_t* s;
+  uint64_t len;
+  struct Block {};
+  __device__ __forceinline__ uint64_t bytes() const { return len; }
+  __device__ __forceinline__ Block block() const { return {}; }
+  __device__ __forceinline__ bool operator()(Block, uint64_t i, uint32_t* next) const { return rp_candidate(s, len, i, next); }
+};
+
+// mark.  WRITE = false: cnt[blk] = the candidates among the bytes [1024 blk, 1024 blk + 1024).
 // WRITE = true, behind the exclusive scan of cnt[]: cand[] / nxt[] of those candidates, ascending.
-template <bool WRITE>
-__global__ void __launch_bounds__(RP_BLOCK) k_resp_mark(const uint8_t* s, uint64_t len, unsigned long long* cnt, uint32_t* cand,
-                                                        uint32_t* nxt) {
+template <bool WRITE, class Cand>
+__global__ void __launch_bounds__(RP_BLOCK) k_resp_mark(Cand C, unsigned long long* cnt, uint32_t* cand, uint32_t* nxt) {
   __shared__ uint32_t ws[RP_BLOCK / 64];
   const uint64_t base = WRITE ? cnt[blockIdx.x] : 0ull;
+  const auto blk = C.block();
   uint32_t run = 0u;
 #pragma unroll 1
   for (uint32_t it = 0; it < RP_PER; it++) {
     const uint64_t i = (uint64_t)blockIdx.x * RP_TILE + it * RP_BLOCK + threadIdx.x;
     uint32_t nx = 0u, all;
-    const bool c = i < len && rp_candidate(s, len, i, &nx);
+    const bool c = i < C.bytes() && C(blk, i, &nx);
     const uint32_t rank = rp_block_rank(c, ws, &all);
     if (WRITE && c) {
       cand[base + run + rank] = (uint32_t)i;
@@ -237,7 +249,9 @@ __global__ void __launch_bounds__(RP_BLOCK) k_resp_flag_index(const uint8_t* fla
   }
 }
 
-// tokens: the kept candidates (flag != 0) to their places tidx[k]; hdr = the bytes of "*<N>\r\n" / "$<L>\r\n"
+// tokens: the kept candidates (flag != 0) to their places tidx[k].  RESP: also hdr = the bytes of "*<N>\r\n" / "$<L>\r\n"
+// and star = whether the token is a '*'; a caller with other tokens (kernels/crl.h) has neither table and s is not read
+template <bool RESP>
 __global__ void __launch_bounds__(RP_BLOCK) k_resp_tokens(const uint8_t* s, uint64_t len, const uint32_t* cand, const uint32_t* nxt,
                                                           const uint8_t* flag, const uint32_t* tidx, uint64_t n, uint32_t* tok_pos,
                                                           uint32_t* tok_nxt, uint8_t* tok_hdr, uint8_t* star) {
@@ -246,38 +260,25 @@ __global__ void __launch_bounds__(RP_BLOCK) k_resp_tokens(const uint8_t* s, uint
   const uint32_t t = tidx[k], pos = cand[k];
   uint64_t v;
   uint32_t hdr = 0u;
-  (void)rp_number(s, len, pos, &v, &hdr);
+  if (RESP) (void)rp_number(s, len, pos, &v, &hdr);
   tok_pos[t] = pos;
   tok_nxt[t] = nxt[k];
-  tok_hdr[t] = (uint8_t)hdr;
-  star[t] = s[pos] == '*' ? 1u : 0u;
+  if (RESP) {
+    tok_hdr[t] = (uint8_t)hdr;
+    star[t] = s[pos] == '*' ? 1u : 0u;
+  }
 }
 
-// chain: the tokens are the sequential parse of the stream iff this finds nothing
+// chain: the tokens are the sequential parse iff this finds nothing: the list starts at 0 (STAR: with a '*'; a caller
+// whose first token need not be one, kernels/crl.h, passes no star[]), every nxt is the next kept position, the last is len
+template <bool STAR>
 __global__ void __launch_bounds__(RP_BLOCK) k_resp_chain(const uint32_t* tok_pos, const uint32_t* tok_nxt, const uint8_t* star, uint64_t n,
                                                          uint64_t len, unsigned long long* err) {
   const uint64_t t = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x;
   bool bad = false;
   uint64_t off = 0;
   if (t < n) {
-    if (t == 0 && (tok_pos[0] != 0u || !star[0])) bad = true;  // (off = 0)
-    else if (tok_nxt[t] != (t + 1 < n ? (uint64_t)tok_pos[t + 1] : len)) {
-      bad = true;
-      off = tok_nxt[t];
-    }
-  }
-  rp_report(err, bad, off);
-}
-
-// the same proof for a caller whose first token need not be a '*' (kernels/crl.h): it starts at 0, every nxt is the next
-// kept position, the last is len
-__global__ void __launch_bounds__(RP_BLOCK) k_resp_chain_from0(const uint32_t* tok_pos, const uint32_t* tok_nxt, uint64_t n, uint64_t len,
-                                                               unsigned long long* err) {
-  const uint64_t t = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x;
-  bool bad = false;
-  uint64_t off = 0;
-  if (t < n) {
-    if (t == 0 && tok_pos[0] != 0u) bad = true;  // (off = 0)
+    if (t == 0 && (tok_pos[0] != 0u || (STAR && !star[0]))) bad = true;  // (off = 0)
     else if (tok_nxt[t] != (t + 1 < n ? (uint64_t)tok_pos[t + 1] : len)) {
       bad = true;
       off = tok_nxt[t];
@@ -465,21 +466,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_resp_place(RespTokens T, RespCmds 
   if (t >= T.n || part[t] != RP_RECORD) return;
   const uint32_t r = C.run(C.cidx[t] - 1u);
   const uint64_t at = run_dst[r] + (rec_before[t] - runs[r].z);
-  const uint32_t L = T.size(t);
-  const uint8_t* m = T.s + T.data(t);
-  uint32_t w[10];
-#pragma unroll
-  for (uint32_t q = 0; q < 10; q++) {
-    uint32_t v = 0u;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; b++)
-      if (4u * q + b < L) v |= (uint32_t)m[4u * q + b] << (8u * b);
-    w[q] = v;
-  }
-  uint4* o = (uint4*)(out + at * KNOWN_REC_BYTES);
-  o[0] = make_uint4(L, 0u, w[0], w[1]);
-  o[1] = make_uint4(w[2], w[3], w[4], w[5]);
-  o[2] = make_uint4(w[6], w[7], w[8], w[9]);
+  known_store_octets(T.size(t), T.s + T.data(t), out, at);
 }
 
 }  // namespace ctmr

@@ -1232,6 +1232,18 @@ class Engine:
 
     # ---- the Redis protocol stream of an image (include/ctmr.h ctmr_known_image_resp*; CPU twin:
     # known_image.image_resp)
+    def _sized_call(self, call, cap, need, check=None):
+        """The sizing convention's loop: call(cap) → (rc, the buffer it made of `cap`), once with the first guess and a
+        second time, with need() — what the call's `info` says after CTMR_E_RANGE —, only when that was short.  check(rc)
+        raises for any other failure (default: _ck).  → (the buffer, the cap it was made of)."""
+        for _ in range(2):
+            rc, buf = call(cap)
+            if rc != N.E_RANGE:
+                break
+            cap = need()
+        (check or self._ck)(rc)
+        return buf, cap
+
     def _known_resp_call(self, fn, alloc, buf, n):
         """One call sized by the header's bound (include/ctmr.h) and a second, exact one only when the header understated
         the image (CTMR_E_RANGE fills `info`)."""
@@ -1240,14 +1252,11 @@ class Engine:
         per = min(max(int(fn.per), 1), 1 << 20)
         text_cap = resp_bound(n, min(h[5], len(buf) // 24), min(h[7], len(buf)), min(h[8], len(buf) // 8), per)
         info = N.KnownRespInfo()
-        for _ in range(2):
-            text = alloc(text_cap)
-            rc = fn(text, text_cap, C.byref(info))
-            if rc != N.E_RANGE:
-                break
-            text_cap = info.text_bytes
-        self._ck(rc)
-        return text, info
+
+        def call(cap):
+            text = alloc(cap)
+            return fn(text, cap, C.byref(info)), text
+        return self._sized_call(call, text_cap, lambda: info.text_bytes)[0], info
 
     def known_image_resp(self, image, members_per_command=512) -> bytes:
         """The SADD + EXPIREAT stream of the sets `image` holds, as `redis-cli --pipe` loads it: the keys in order, the
@@ -1298,14 +1307,11 @@ class Engine:
         does that.  The engine's own sets and issuers play no part."""
         stream = bytes(stream)
         info = N.KnownRespImageInfo()
-        cap = 1 << 16
-        for _ in range(2):
+
+        def call(cap):
             out = np.empty(cap, np.uint8)
-            rc = self._lib.ctmr_known_resp_image(self._h, stream, len(stream), out.ctypes.data, cap, C.byref(info))
-            if rc != N.E_RANGE:
-                break
-            cap = info.image_bytes
-        self._ck(rc)
+            return self._lib.ctmr_known_resp_image(self._h, stream, len(stream), out.ctypes.data, cap, C.byref(info)), out
+        out, _ = self._sized_call(call, 1 << 16, lambda: info.image_bytes)
         return out[:info.image_bytes].tobytes()
 
     def known_resp_image_device(self, d_stream, n=None):
@@ -1320,16 +1326,14 @@ class Engine:
             raise ValueError("n = %r of %d bytes" % (n, d_stream.numel()))
         ptr = C.c_void_p(d_stream.data_ptr()) if n else None
         info = N.KnownRespImageInfo()
-        meta_cap, members_cap = getattr(self, "_resp_meta_cap", 1 << 16), max(n // 6, 1)
+        members_cap = max(n // 6, 1)
         out = torch.empty(members_cap * 48, dtype=torch.uint8, device="cuda:%d" % self.device)
-        for _ in range(2):
+
+        def call(meta_cap):
             meta = np.empty(meta_cap, np.uint8)
-            rc = self._lib.ctmr_known_resp_image_device(self._h, ptr, n, meta.ctypes.data, meta_cap, C.c_void_p(out.data_ptr()),
-                                                        members_cap, C.byref(info))
-            if rc != N.E_RANGE:
-                break
-            meta_cap = info.meta_bytes
-        self._ck(rc)
+            return self._lib.ctmr_known_resp_image_device(self._h, ptr, n, meta.ctypes.data, meta_cap, C.c_void_p(out.data_ptr()),
+                                                          members_cap, C.byref(info)), meta
+        meta, meta_cap = self._sized_call(call, getattr(self, "_resp_meta_cap", 1 << 16), lambda: info.meta_bytes)
         self._resp_meta_cap = max(meta_cap, info.meta_bytes)
         return meta[:info.meta_bytes].tobytes(), out[:info.members * 48]
 
@@ -1368,15 +1372,12 @@ class Engine:
         blob, total, offsets, n, digests = self._crl_args(crls, digests)
         blob = bytes(blob)
         info, cinfo = N.KnownImageInfo(), N.CrlInfo()
-        cap = 64 + 56 * n + 48 * (total // 6)
-        for _ in range(2):
+
+        def call(cap):
             out = np.empty(max(cap, 64), np.uint8)
-            rc = self._lib.ctmr_crl_probes(self._h, blob, total, offsets.ctypes.data, n, digests, out.ctypes.data, out.nbytes,
-                                           C.byref(info), C.byref(cinfo))
-            if rc != N.E_RANGE:
-                break
-            cap = info.image_bytes
-        self._crl_fail(rc, cinfo)
+            return self._lib.ctmr_crl_probes(self._h, blob, total, offsets.ctypes.data, n, digests, out.ctypes.data, out.nbytes,
+                                             C.byref(info), C.byref(cinfo)), out
+        out, _ = self._sized_call(call, 64 + 56 * n + 48 * (total // 6), lambda: info.image_bytes, lambda rc: self._crl_fail(rc, cinfo))
         return out[:info.image_bytes].tobytes(), self._stats_dict(cinfo)
 
     def crl_probes_device(self, d_crls, offsets, digests, exact=None):
@@ -1405,14 +1406,12 @@ class Engine:
                 self._crl_fail(rc, cinfo)
             meta_cap, members_cap = info.meta_bytes, max(info.members, 1)
         out = torch.empty(members_cap * 48, dtype=torch.uint8, device=dev)
-        for _ in range(2):
+
+        def call(meta_cap):
             meta = np.empty(meta_cap, np.uint8)
-            rc = self._lib.ctmr_crl_probes_device(self._h, ptr, total, offsets.ctypes.data, n, digests, meta.ctypes.data, meta_cap,
-                                                  C.c_void_p(out.data_ptr()), members_cap, C.byref(info), C.byref(cinfo))
-            if rc != N.E_RANGE:
-                break
-            meta_cap = info.meta_bytes
-        self._crl_fail(rc, cinfo)
+            return self._lib.ctmr_crl_probes_device(self._h, ptr, total, offsets.ctypes.data, n, digests, meta.ctypes.data, meta_cap,
+                                                    C.c_void_p(out.data_ptr()), members_cap, C.byref(info), C.byref(cinfo)), meta
+        meta, _ = self._sized_call(call, meta_cap, lambda: info.meta_bytes, lambda rc: self._crl_fail(rc, cinfo))
         return meta[:info.meta_bytes].tobytes(), out[:info.members * 48], self._stats_dict(cinfo)
 
     def known_revoked(self, crls, digests, now):

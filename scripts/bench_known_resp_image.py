@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--slots", type=int, default=1 << 28)
     ap.add_argument("--per", type=int, default=512)
     ap.add_argument("--python-members", type=int, default=1_000_000)
+    ap.add_argument("--kernels-only", action="store_true", help="the parse leg alone: for an A/B of two libraries, or a run under rocprofv3")
     args = ap.parse_args()
     stream = torch.cuda.current_stream().cuda_stream
     cfg = synth.config(seed=20260921 + 7, n_issuers=256, zipf=1, dup_permille=20, ca_permille=10, expired_permille=10)
@@ -80,6 +81,10 @@ def main():
 
     line["parse"] = leg(p_ms, 3 * S + 48 * M)
     line["parse_first_ms"] = round(p_first, 3)
+    if args.kernels_only:
+        print(json.dumps(line))
+        e.close()
+        return
 
     def fresh():
         if keep.get("e"):
