@@ -124,6 +124,10 @@ class CrlInfo(C.Structure):
                 ("empty_crls", C.c_uint64), ("candidates", C.c_uint64), ("bad_crl", C.c_uint64), ("bad_offset", C.c_uint64)]
 
 
+class CrlVerdict(C.Structure):
+    _fields_ = [("bad_offset", C.c_uint64), ("records", C.c_uint32), ("long_entries", C.c_uint32)]
+
+
 class EntriesJsonInfo(C.Structure):
     _fields_ = [("responses", C.c_uint64), ("entries", C.c_uint64), ("text_bytes", C.c_uint64), ("blob_bytes", C.c_uint64),
                 ("bad_response", C.c_uint64), ("bad_offset", C.c_uint64)]
@@ -228,6 +232,10 @@ SIGNATURES = {
                                   C.POINTER(CrlInfo)]),
     "ctmr_crl_probes_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_size_t, _P, C.c_uint64,
                                          C.POINTER(KnownImageInfo), C.POINTER(CrlInfo)]),
+    "ctmr_crl_probes_each": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, C.c_size_t, C.POINTER(KnownImageInfo),
+                                       C.POINTER(CrlInfo), _P]),
+    "ctmr_crl_probes_each_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_size_t, _P, C.c_uint64,
+                                              C.POINTER(KnownImageInfo), C.POINTER(CrlInfo), _P]),
     "ctmr_set_known_order": (C.c_int, [_P, C.c_int]),
     "ctmr_known_sort": (C.c_int, [_P, _P, C.c_size_t]),
     "ctmr_known_sort_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64]),

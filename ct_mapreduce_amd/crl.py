@@ -5,7 +5,8 @@
 with the byte offset for anything outside the grammar.  `probes_image(crls, digests)` is the image the library writes
 for the same CRLs, byte for byte: one set per issuer digest under exp hour 0, its member records in input order, the
 serials above 40 octets as sorted host-section pairs.  `known_image.find(known, probes_image(...), now)` then says under
-which expDates the revoked serials are known.  Pure Python + numpy.
+which expDates the revoked serials are known.  `probes_each(crls, digests)` is the twin of `Engine.crl_probes_each`
+(DESIGN.md §27): every CRL judged on its own, a verdict per CRL, the image of the good ones.  Pure Python + numpy.
 """
 import struct
 
@@ -191,3 +192,32 @@ def probes_parts(crls, digests):
 def probes_image(crls, digests) -> bytes:
     """The probe image of the CRLs: what Engine.crl_probes writes, byte for byte."""
     return probes_parts(crls, digests)[0]
+
+
+def probes_each(crls, digests):
+    """Every CRL judged on its own (include/ctmr.h ctmr_crl_probes_each) → (image bytes, info dict,
+    verdicts): verdicts[k] = (bad_offset, records, long_entries) as ctmr_crl_verdict has them — bad_offset NONE for a CRL
+    inside the grammar, else the offset in the concatenation of the CRLs at which `entries` leaves it.  The image is
+    probes_parts of the good CRLs with their digests; the info counts those, `crls` all, and bad_crl / bad_offset name
+    the lowest bad CRL.  Nothing raises for a CRL's contents."""
+    crls, digests = [bytes(c) for c in crls], [bytes(d) for d in digests]
+    if len(crls) != len(digests) or any(len(d) != 32 for d in digests):
+        raise ValueError("one 32-byte digest per CRL")
+    if sum(len(c) for c in crls) >= MAX_LEN:
+        raise ValueError("2^32 - 64 bytes or more")
+    verdicts, good, at = [], [], 0
+    for k, c in enumerate(crls):
+        try:
+            serials = entries(c)
+            short = sum(len(s) <= KI.MAX_SERIAL for s in serials)
+            verdicts.append((NONE, short, len(serials) - short))
+            good.append(k)
+        except CrlError as x:
+            verdicts.append((at + x.offset, 0, 0))
+        at += len(c)
+    image, info = probes_parts([crls[k] for k in good], [digests[k] for k in good])
+    info["crls"] = len(crls)
+    bad = [k for k, v in enumerate(verdicts) if v[0] != NONE]
+    if bad:
+        info["bad_crl"], info["bad_offset"] = bad[0], verdicts[bad[0]][0]
+    return image, info, verdicts

@@ -81,16 +81,18 @@ struct RpStage {
   unsigned long long* err = nullptr;  // two words, err[0] = ~0; err[1] = err1 and its meaning are the caller's
   unsigned long long err0[2] = {~0ull, 0ull};
 
-  int begin(ctmr_engine* e, const char* call, uint64_t bytes, unsigned long long err1) {
+  // more: words behind the two, preset to all ones (a finding per input of the call: they come back in err's copy)
+  int begin(ctmr_engine* e, const char* call, uint64_t bytes, unsigned long long err1, uint64_t more = 0) {
     int r;
     what = call;
     len = bytes;
     nb = (len + RP_TILE - 1) / RP_TILE;
     err0[1] = err1;
-    if ((r = rp_alloc(e, &cnt_m, (nb + 2) * 8, what)) || (r = rp_alloc(e, &err_m, 16, what))) return r;
+    if ((r = rp_alloc(e, &cnt_m, (nb + 2) * 8, what)) || (r = rp_alloc(e, &err_m, 16 + more * 8, what))) return r;
     cnt = (unsigned long long*)cnt_m.p;
     err = (unsigned long long*)err_m.p;
     HIPCHK(e, hipMemcpyAsync(err, err0, 16, hipMemcpyHostToDevice, e->stream));
+    if (more) HIPCHK(e, hipMemsetAsync(err + 2, 0xff, more * 8, e->stream));
     return CTMR_OK;
   }
 
@@ -130,8 +132,9 @@ struct RpStage {
     hipLaunchKernelGGL((k_resp_tokens<RESP>), dim3(rp_grid(nc, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, s, len, (const uint32_t*)cand,
                        (const uint32_t*)nxt, (const uint8_t*)flag_m.u8(), (const uint32_t*)tidx_m.p, (uint64_t)nc, (uint32_t*)tok_pos->p,
                        (uint32_t*)tok_nxt->p, RESP ? tok_hdr->u8() : nullptr, RESP ? star->u8() : nullptr);
-    hipLaunchKernelGGL((k_resp_chain<RESP>), dim3(rp_grid(nt, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)tok_pos->p,
-                       (const uint32_t*)tok_nxt->p, RESP ? (const uint8_t*)star->u8() : nullptr, nt, len, chain_err);
+    if (chain_err)  // (null: the caller runs a chain check of its own over tok_pos / tok_nxt)
+      hipLaunchKernelGGL((k_resp_chain<RESP>), dim3(rp_grid(nt, RP_BLOCK)), dim3(RP_BLOCK), 0, e->stream, (const uint32_t*)tok_pos->p,
+                         (const uint32_t*)tok_nxt->p, RESP ? (const uint8_t*)star->u8() : nullptr, nt, len, chain_err);
     return CTMR_OK;
   }
 

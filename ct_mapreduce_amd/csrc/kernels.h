@@ -28,7 +28,8 @@
 //                       protocol stream of SADD and EXPIREAT commands as it lies → an image's member records)
 //   kernels/crl.h       k_crl_head / CrlCand / k_crl_class / k_crl_place (DER CertificateLists as they lie → the revoked
 //                       serials as a probe image's member records; the mark kernel over CrlCand, the cuts and the chain
-//                       proof are resp_parse.h's)
+//                       proof are resp_parse.h's; k_crl_head<true> /
+//                       k_crl_chain / k_crl_class<true>: a finding per CRL, for ctmr_crl_probes_each*)
 //   kernels/text_scan.h what the two text decoders below share: a text in segments read in 16-byte chunks, the wave's scan
 //                       and report, the base64 decode of a tile; k_ej_tiles / k_ej_tile_list (both decoders launch them)
 //   kernels/entries_json.h k_ej_quotes / k_ej_mark / k_ej_resp / k_ej_check / k_ej_decode (get-entries JSON bodies as they

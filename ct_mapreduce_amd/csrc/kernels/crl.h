@@ -10,6 +10,7 @@
 //             true entry is one.  Two frame candidates
 //             per CRL cover the bytes outside its value — its start → lo, hi → its end — so that the true chain runs
 //             from 0 to len across all CRLs.
+//   chain     (the each form) k_crl_chain: the chain proof with a finding per CRL instead of one for the blob.
 //   class     per kept token, behind the chain proof: its CRL, whether it is a frame, a record (serial <= 40 octets) or a
 //             host pair, and where its serial lies.
 //   place     per record: its rank among the records of its CRL → one 48-byte member record of its issuer's set.
@@ -76,6 +77,9 @@ __device__ __forceinline__ uint32_t crl_of(const unsigned long long* off, uint32
 
 // head.  span[k] = [lo, hi) of CRL k's revokedCertificates value; lo == hi inside the CRL when it has none or an empty
 // one; lo == hi == the CRL's end when the CRL is outside the grammar, and then err ← min(k << 32 | offset).
+// EACH (ctmr_crl_probes_each*): err is bad_at, a word per CRL preset to all ones, and the CRL's own lane
+// stores the offset into bad_at[k]: every refused CRL keeps its finding, nothing is reduced over the wave.
+template <bool EACH>
 __global__ void __launch_bounds__(RP_BLOCK) k_crl_head(const uint8_t* s, const unsigned long long* off, uint32_t n, uint2* span,
                                                        unsigned long long* err) {
   const uint64_t k = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x;
@@ -168,7 +172,11 @@ __global__ void __launch_bounds__(RP_BLOCK) k_crl_head(const uint8_t* s, const u
     span[k] = make_uint2((uint32_t)lo, (uint32_t)hi);
     bad = !ok;
   }
-  rp_report(err, bad, (k << 32) | at);
+  if (EACH) {
+    if (bad) err[k] = at;
+  } else {
+    rp_report(err, bad, (k << 32) | at);
+  }
 }
 
 // tile_crl[t] = the CRL of byte 1024 t (t = 0 .. tiles; behind the blob: the last CRL)
@@ -207,10 +215,35 @@ struct CrlCand {
   __device__ __forceinline__ bool operator()(uint2 k, uint64_t i, uint32_t* next) const { return crl_candidate(B, k.x, k.y, i, next); }
 };
 
+// chain, per CRL (EACH): the adjacency test of k_resp_chain<false>, and a lane with a mismatch blames its token's CRL:
+// bad_at[k] ← min(the nxt that is not the next kept position).  The first byte of every CRL is a candidate no earlier
+// one spans (no candidate reaches past its CRL's end), so it is kept: the tokens of CRL k are the sequential parse of
+// CRL k iff no lane of CRL k reports, whatever its neighbours hold.  crl_of runs only on a mismatch.  A kernel of its
+// own and not a parameter of k_resp_chain: that one knows a stream and one error word, this one needs the CRL table,
+// and the RESP instantiation stays untouched.
+__global__ void __launch_bounds__(RP_BLOCK) k_crl_chain(const uint32_t* tok_pos, const uint32_t* tok_nxt, uint64_t n, uint64_t len,
+                                                        const unsigned long long* off, uint32_t n_crls, unsigned long long* bad_at) {
+  const uint64_t t = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x;
+  if (t >= n) return;
+  const uint64_t pos = tok_pos[t], nx = tok_nxt[t];
+  const bool first = t == 0 && pos != 0;  // (off = 0, as k_resp_chain has it)
+  if (!first && nx == (t + 1 < n ? (uint64_t)tok_pos[t + 1] : len)) return;
+  atomicMin(bad_at + crl_of(off, 0u, n_crls - 1u, first ? 0ull : pos), first ? 0ull : (unsigned long long)nx);
+}
+
+// whether CRL k has a verdict: never without a bad_at table (the strict call), else bad_at[k] is not all ones
+__device__ __forceinline__ bool crl_refused(uint32_t) { return false; }
+__device__ __forceinline__ bool crl_refused(uint32_t k, const unsigned long long* bad_at) { return bad_at[k] != ~0ull; }
+
 // class, behind the chain proof (every token is a frame or a true entry): cls[t], tok_crl[t], and for an entry tok_ser[t]
-// = the offset of its serial's length octet
+// = the offset of its serial's length octet.  EACH: behind k_crl_chain, where bad_at is final; every token of a CRL with
+// a verdict is a frame, and crl_entry is not evaluated for it (its tokens are not proven to be entries).  bad_at is an
+// argument of the EACH instantiation alone (BadAt = const unsigned long long*): <false> has the arguments, and so the
+// code, it had before there was an each form.
+template <bool EACH, class... BadAt>
 __global__ void __launch_bounds__(RP_BLOCK) k_crl_class(CrlBlob B, const uint32_t* tok_pos, uint64_t n, uint8_t* cls, uint32_t* tok_crl,
-                                                        uint32_t* tok_ser) {
+                                                        uint32_t* tok_ser, BadAt... bad_at) {
+  static_assert(sizeof...(BadAt) == (EACH ? 1 : 0), "bad_at with EACH, and only then");
   const uint64_t t = (uint64_t)blockIdx.x * RP_BLOCK + threadIdx.x;
   if (t >= n) return;
   const uint64_t i = tok_pos[t];
@@ -218,7 +251,7 @@ __global__ void __launch_bounds__(RP_BLOCK) k_crl_class(CrlBlob B, const uint32_
   const uint2 sp = B.span[k];
   uint8_t c = CRL_FRAME;
   uint32_t ser = 0u;
-  if (i != B.off[k] && i != sp.y) {
+  if (i != B.off[k] && i != sp.y && !crl_refused(k, bad_at...)) {
     uint64_t serial = 0, body = 0, next = 0;
     (void)crl_entry(B.s, sp.y, i, &serial);
     (void)crl_len(B.s, serial, sp.y, &body, &next);

@@ -1369,16 +1369,34 @@ class Engine:
         issuers' SPKI digests are `digests`: one set per digest under exp hour 0, member records in input order, what
         known_image_find takes as `probes`.  → (image bytes, info dict).  Raises crl.CrlError naming the lowest CRL
         outside the grammar and the offset.  The engine's own sets and issuers play no part."""
+        return self._crl_probes(crls, digests, False)[:2]
+
+    def crl_probes_each(self, crls, digests):
+        """crl_probes with every CRL judged on its own (ctmr_crl_probes_each; CPU twin: crl.probes_each): a
+        CRL outside the grammar raises nothing and contributes nothing.  → (image bytes of the good CRLs, info dict,
+        verdicts: (bad_offset, records, long_entries) per CRL, bad_offset crl.NONE for a good one)."""
+        return self._crl_probes(crls, digests, True)
+
+    @staticmethod
+    def _crl_verdicts(n, each):
+        """→ (the ctmr_crl_verdict array of a call or None, what reads it into a list)"""
+        if not each:
+            return None, lambda: None
+        v = (N.CrlVerdict * max(n, 1))()
+        return v, lambda: [(x.bad_offset, x.records, x.long_entries) for x in v[:n]]
+
+    def _crl_probes(self, crls, digests, each):
         blob, total, offsets, n, digests = self._crl_args(crls, digests)
         blob = bytes(blob)
         info, cinfo = N.KnownImageInfo(), N.CrlInfo()
+        verdicts, read = self._crl_verdicts(n, each)
 
         def call(cap):
             out = np.empty(max(cap, 64), np.uint8)
-            return self._lib.ctmr_crl_probes(self._h, blob, total, offsets.ctypes.data, n, digests, out.ctypes.data, out.nbytes,
-                                             C.byref(info), C.byref(cinfo)), out
+            args = (self._h, blob, total, offsets.ctypes.data, n, digests, out.ctypes.data, out.nbytes, C.byref(info), C.byref(cinfo))
+            return (self._lib.ctmr_crl_probes_each(*args, C.byref(verdicts)) if each else self._lib.ctmr_crl_probes(*args)), out
         out, _ = self._sized_call(call, 64 + 56 * n + 48 * (total // 6), lambda: info.image_bytes, lambda rc: self._crl_fail(rc, cinfo))
-        return out[:info.image_bytes].tobytes(), self._stats_dict(cinfo)
+        return out[:info.image_bytes].tobytes(), self._stats_dict(cinfo), read()
 
     def crl_probes_device(self, d_crls, offsets, digests, exact=None):
         """crl_probes of a torch uint8 tensor on this engine's device (any alignment) holding the CRLs back to back;
@@ -1389,19 +1407,31 @@ class Engine:
         short); exact=True asks for the sizes first (the two-call convention: every pass but the last runs twice) and
         allocates what they say.  The default takes the bound while it is at most a quarter of the device's free memory,
         and asks first otherwise."""
+        return self._crl_probes_device(d_crls, offsets, digests, exact, False)[:3]
+
+    def crl_probes_each_device(self, d_crls, offsets, digests, exact=None):
+        """crl_probes_device with every CRL judged on its own (ctmr_crl_probes_each_device) → (meta bytes, member records
+        on the device, info dict, verdicts as crl_probes_each gives them)."""
+        return self._crl_probes_device(d_crls, offsets, digests, exact, True)
+
+    def _crl_probes_device(self, d_crls, offsets, digests, exact, each):
         import torch
         if not hasattr(d_crls, "data_ptr"):
             raise TypeError("d_crls: a torch tensor on this engine's device")
         _, total, offsets, n, digests = self._crl_args((d_crls, offsets), digests)
         ptr = C.c_void_p(d_crls.data_ptr()) if total else None
         info, cinfo = N.KnownImageInfo(), N.CrlInfo()
+        verdicts, read = self._crl_verdicts(n, each)
         dev = "cuda:%d" % self.device
         meta_cap, members_cap = 64 + 56 * n + (1 << 12), max(total // 6, 1)
         if exact is None:
             exact = 48 * members_cap > torch.cuda.mem_get_info(self.device)[0] // 4
+
+        def fn(meta, meta_cap, d_out, members_cap):
+            args = (self._h, ptr, total, offsets.ctypes.data, n, digests, meta, meta_cap, d_out, members_cap, C.byref(info), C.byref(cinfo))
+            return self._lib.ctmr_crl_probes_each_device(*args, C.byref(verdicts)) if each else self._lib.ctmr_crl_probes_device(*args)
         if exact:
-            rc = self._lib.ctmr_crl_probes_device(self._h, ptr, total, offsets.ctypes.data, n, digests, None, 0, None, 0,
-                                                  C.byref(info), C.byref(cinfo))
+            rc = fn(None, 0, None, 0)
             if rc != N.E_RANGE:
                 self._crl_fail(rc, cinfo)
             meta_cap, members_cap = info.meta_bytes, max(info.members, 1)
@@ -1409,26 +1439,31 @@ class Engine:
 
         def call(meta_cap):
             meta = np.empty(meta_cap, np.uint8)
-            return self._lib.ctmr_crl_probes_device(self._h, ptr, total, offsets.ctypes.data, n, digests, meta.ctypes.data, meta_cap,
-                                                    C.c_void_p(out.data_ptr()), members_cap, C.byref(info), C.byref(cinfo)), meta
+            return fn(meta.ctypes.data, meta_cap, C.c_void_p(out.data_ptr()), members_cap), meta
         meta, _ = self._sized_call(call, meta_cap, lambda: info.meta_bytes, lambda rc: self._crl_fail(rc, cinfo))
-        return meta[:info.meta_bytes].tobytes(), out[:info.members * 48], self._stats_dict(cinfo)
+        return meta[:info.meta_bytes].tobytes(), out[:info.members * 48], self._stats_dict(cinfo), read()
 
-    def known_revoked(self, crls, digests, now):
+    def known_revoked(self, crls, digests, now, each=False):
         """Which revoked serials the engine knows, and until when they matter: crl_probes_device → known_export_device →
         known_image_find_device, with no probe image in host memory.  crls: a list of DER CRLs, or (torch uint8 tensor
         on this engine's device, offsets).  → (the probe image's meta, hits: numpy known_image.HIT_DTYPE per member
-        record of the probe image in its order, host_hits per host-section pair)."""
+        record of the probe image in its order, host_hits per host-section pair).  each=True: every CRL is judged on its
+        own (crl_probes_each_device): the CRLs outside the grammar are left out instead of failing the call, and the
+        verdicts of all CRLs are a fourth element."""
         import torch
         from .known_image import HIT_DTYPE
         if not isinstance(crls, tuple):
             blob, _, offsets, _, digests = self._crl_args(crls, digests)
             raw = np.frombuffer(blob, np.uint8)
             crls = (torch.from_numpy(raw.copy()).to("cuda:%d" % self.device), offsets)
-        p_meta, d_p, _ = self.crl_probes_device(crls[0], crls[1], digests)
+        if each:
+            p_meta, d_p, _, verdicts = self.crl_probes_each_device(crls[0], crls[1], digests)
+        else:
+            p_meta, d_p, _ = self.crl_probes_device(crls[0], crls[1], digests)
         k_meta, d_k = self.known_export_device()
         hits, host_hits, _ = self.known_image_find_device(k_meta, d_k, p_meta, d_p, now)
-        return p_meta, hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits
+        out = (p_meta, hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits)
+        return out + (verdicts,) if each else out
 
     def known_import_resp(self, stream, world=1, rank=0) -> dict:
         """The warm start from a reference deployment's Redis contents: every serials:: member of the stream (bytes, or

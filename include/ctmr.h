@@ -741,6 +741,46 @@ int ctmr_crl_probes_device(ctmr_engine* e, const void* d_crls, uint64_t len, con
                            const uint8_t* digests, uint8_t* meta, size_t meta_cap, void* d_members, uint64_t members_cap,
                            ctmr_known_image_info* info, ctmr_crl_info* cinfo);
 
+/* Every CRL judged on its own: ctmr_crl_probes* with a verdict per CRL instead of one for the call.  DESIGN.md §27.
+ * Arguments as above, and verdicts, a HOST array [n_crls] that may be NULL (then nothing is lost but the verdicts: cinfo
+ * still names the lowest bad CRL).  The grammar is exactly the one above, not a byte wider.
+ * Return value.  A CRL outside the grammar fails nothing: the call returns CTMR_OK.
+ *   verdicts[k].bad_offset = UINT64_MAX: CRL k is inside the grammar.  Any other value: it is outside, and the value is
+ *   EXACT, not advisory: offsets[k] + the bad_offset ctmr_crl_probes* reports for CRL k submitted alone.  A CRL of 0 bytes
+ *   is bad at offsets[k].  Nothing in a neighbour changes a CRL's verdict: the first byte of every CRL is the start of a
+ *   frame no earlier token reaches past, so the rules above — the outer TLVs before the entries, inside
+ *   revokedCertificates the start of the first entry that is not one — hold CRL by CRL.
+ *   verdicts[k].records / .long_entries: the member records CRL k contributed, and its entries whose serials are above
+ *   CTMR_MAX_SERIAL octets, counted before the host section makes them unique; both 0 for a bad CRL.  Over all k,
+ *   the records sum to info.members and records + long_entries to cinfo.entries.
+ * The image.  A bad CRL contributes nothing: meta and member records are byte for byte what ctmr_crl_probes* writes for
+ *   the sub-sequence of good CRLs with their digests.  A digest whose every CRL is bad is not an issuer of the image; a bad
+ *   shard leaves the good shards of its digest in input order; a long serial of a bad CRL — also of one that is bad
+ *   only behind that entry — is not in the host section.  With no bad CRL every output of ctmr_crl_probes* is
+ *   reproduced bit for bit.
+ * cinfo.  crls is n_crls; entries, records, host_members and empty_crls count the good CRLs only; candidates is what
+ *   the mark pass found over the whole blob, the bad CRLs' included; bad_crl / bad_offset name the LOWEST bad CRL and
+ *   its verdict's offset, or are both UINT64_MAX.
+ * What still fails the whole call, being no CRL's fault: the three errors of the offsets (CTMR_E_INVAL, cinfo as
+ *   above), len >= 2^32 − 64, null arguments, CTMR_E_RANGE and CTMR_E_NOMEM.  Sizing is by the good CRLs, in the two-call
+ *   convention above: CTMR_E_RANGE with *info and *cinfo filled.  On every error every output buffer, verdicts included,
+ *   is as it was: verdicts is written last, behind the last thing that can fail.
+ * Empty input.  n_crls > 0 with len == 0 says every CRL has 0 bytes: every verdict is bad at offset 0, the call returns
+ *   CTMR_OK and the empty image, and nothing is launched.  n_crls = 0 gives the empty image and writes no verdict.
+ * Cost.  That of ctmr_crl_probes*: the blob is read by the two mark passes once, however many CRLs are bad; a bad CRL's
+ *   tokens are dropped behind them. */
+typedef struct {
+  uint64_t bad_offset;    /* UINT64_MAX: inside the grammar; else the offset in `crls`, see above */
+  uint32_t records;       /* member records this CRL contributed (serials <= CTMR_MAX_SERIAL octets); 0 when bad */
+  uint32_t long_entries;  /* its entries with longer serials, before the host section makes them unique; 0 when bad */
+} ctmr_crl_verdict;       /* 16 bytes */
+int ctmr_crl_probes_each(ctmr_engine* e, const uint8_t* crls, size_t len, const uint64_t* offsets, uint32_t n_crls,
+                         const uint8_t* digests, uint8_t* out, size_t cap, ctmr_known_image_info* info, ctmr_crl_info* cinfo,
+                         ctmr_crl_verdict* verdicts);
+int ctmr_crl_probes_each_device(ctmr_engine* e, const void* d_crls, uint64_t len, const uint64_t* offsets, uint32_t n_crls,
+                                const uint8_t* digests, uint8_t* meta, size_t meta_cap, void* d_members, uint64_t members_cap,
+                                ctmr_known_image_info* info, ctmr_crl_info* cinfo, ctmr_crl_verdict* verdicts);
+
 /* One rank's input of a multi-GPU round (ctmr_group_map_batch, ctmr_xchg_map_device): device pointers on that rank's
  * GPU, as ctmr_map_batch_device takes them; d_ends != NULL: an entry view (d_offsets = cert_start, d_ends = cert_end,
  * blob_bytes set).  order_base = log index of the shard's entry 0 (Bloom mode: the lowest order keeps WasUnknown; owner

@@ -12,7 +12,17 @@ and the wall time of
   python   crl.probes_image on the first CRLs that hold --python-entries entries — the device's image of that slice is
            held to it first.
 No speed is asserted anywhere; ratio_crl_over_resp_per_record > 1 means the call costs more per record than its relative.
-Kernel times: run under `rocprofv3 --kernel-trace --stats` separately; --kernels-only runs just the crl leg."""
+Kernel times: run under `rocprofv3 --kernel-trace --stats` separately; --kernels-only runs just the crl leg.
+
+--each runs four other legs instead, all through the C ABI with buffers allocated once, so that nothing but
+the call is between the events:
+  strict         ctmr_crl_probes_device of this build,
+  strict_parent  the same call of the library --parent-lib names, built from the parent commit (left out without it),
+  each           ctmr_crl_probes_each_device on the same blob: no bad CRL,
+  each_bad       … on the blob with one CRL in 64 cut short by one byte: the head refuses those,
+with the ratios strict / strict_parent, each / strict and each_bad / each, and whether strict's median lies inside the
+spread of strict_parent's calls.  --kernels-only with --each leaves strict_parent out: in a kernel trace the three legs
+are told apart by their k_crl_head dispatches, strict's first."""
 import argparse
 import json
 import os
@@ -75,6 +85,72 @@ def make_blob(n_crls, n_entries, seed):
     return blob.reshape(-1), offsets, digests, per
 
 
+def each_legs(args, blob, offsets, digests, n_entries, stream):
+    """The four legs of --each → the JSON line's dict."""
+    import ctypes as C
+    from ct_mapreduce_amd import _native as N
+    n = len(offsets) - 1
+    cut = np.arange(63, n, 64)                                                   # the CRLs that lose their last byte
+    short = np.delete(blob, (offsets[cut + 1] - np.uint64(1)).astype(np.int64))
+    short_offsets = offsets - np.searchsorted(cut, np.arange(n + 1), side="left").astype(np.uint64)
+    assert short_offsets[-1] == short.size
+    d_blob, d_short = torch.from_numpy(blob).to("cuda:0"), torch.from_numpy(short).to("cuda:0")
+    d_out = torch.empty(48 * n_entries, dtype=torch.uint8, device="cuda:0")
+    meta = np.empty(64 + 56 * n + (1 << 12), np.uint8)
+    dig = b"".join(digests)
+    verdicts = (N.CrlVerdict * n)()
+    info, cinfo = N.KnownImageInfo(), N.CrlInfo()
+
+    def engine(lib):
+        cfg = N.Config(struct_size=C.sizeof(N.Config), device=0, table_slots=1 << 12, pair_slots=1 << 10)
+        h = C.c_void_p()
+        assert lib.ctmr_create(C.byref(cfg), C.byref(h)) == 0
+        assert lib.ctmr_set_stream(h, C.c_void_p(stream)) == 0
+        return h
+
+    def caller(lib, h, name, d, offs):
+        fn = getattr(lib, name)
+        fn.restype = C.c_int
+        args = [h, C.c_void_p(d.data_ptr()), C.c_uint64(d.numel()), C.c_void_p(offs.ctypes.data), C.c_uint32(n), dig, C.c_void_p(meta.ctypes.data),
+                C.c_size_t(meta.nbytes), C.c_void_p(d_out.data_ptr()), C.c_uint64(n_entries), C.byref(info), C.byref(cinfo)]
+        args += [C.byref(verdicts)] if "each" in name else []
+
+        def call():
+            rc = fn(*args)
+            assert rc == 0, (name, rc)
+            return info.members, cinfo.bad_crl
+        return call
+
+    def leg(ms_list):
+        return {"ms_median": round(sorted(ms_list)[len(ms_list) // 2], 3), "ms_all": [round(x, 3) for x in ms_list]}
+
+    line = {"metric": "crl_probes_each", "crls": n, "entries": n_entries, "blob_bytes": int(blob.size), "bad_crls": int(len(cut))}
+    here = N.lib()
+    h = engine(here)
+    legs = [("strict", here, h, "ctmr_crl_probes_device", d_blob, offsets)]
+    parent = hp = None
+    if args.parent_lib and not args.kernels_only:
+        parent = C.CDLL(args.parent_lib)
+        hp = engine(parent)
+        legs.append(("strict_parent", parent, hp, "ctmr_crl_probes_device", d_blob, offsets))
+    legs += [("each", here, h, "ctmr_crl_probes_each_device", d_blob, offsets),
+             ("each_bad", here, h, "ctmr_crl_probes_each_device", d_short, short_offsets)]
+    for nm, lib, hh, fn, d, offs in legs:
+        _, ms, (members, bad) = timed(caller(lib, hh, fn, d, offs), args.reps)
+        want = n_entries - (len(cut) * (n_entries // n) if nm == "each_bad" else 0)
+        assert members == want and bad == (63 if nm == "each_bad" else CRL.NONE), (nm, members, want, bad)
+        line[nm] = leg(ms)
+    line["ratio_each_over_strict"] = round(line["each"]["ms_median"] / line["strict"]["ms_median"], 4)
+    line["ratio_each_bad_over_each"] = round(line["each_bad"]["ms_median"] / line["each"]["ms_median"], 4)
+    if parent is not None:
+        p = line["strict_parent"]["ms_all"]
+        line["ratio_strict_over_parent"] = round(line["strict"]["ms_median"] / line["strict_parent"]["ms_median"], 4)
+        line["strict_inside_parent_spread"] = bool(min(p) <= line["strict"]["ms_median"] <= max(p))
+        parent.ctmr_destroy(hp)
+    here.ctmr_destroy(h)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--crls", type=int, default=2048)
@@ -85,11 +161,20 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--python-entries", type=int, default=1_000_000)
     ap.add_argument("--kernels-only", action="store_true", help="the crl leg alone: for a run under rocprofv3 --kernel-trace --stats")
+    ap.add_argument("--each", action="store_true", help="the legs of the each form (DESIGN.md §27) instead")
+    ap.add_argument("--parent-lib", default="", help="--each: a libctmr.so built from the parent commit, for the strict_parent leg")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     stream = torch.cuda.current_stream().cuda_stream
     blob, offsets, digests, per = make_blob(args.crls, args.entries, 26)
     n_entries = per * args.crls
+    if args.each:
+        text = json.dumps(each_legs(args, blob, offsets, digests, n_entries, stream))
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     d_blob = torch.from_numpy(blob).to("cuda:0")
     e = ctmr.Engine(device=0, table_slots=1 << 12, pair_slots=1 << 10)
     e.set_stream(stream)
