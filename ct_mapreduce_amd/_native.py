@@ -152,6 +152,11 @@ class KnownFindInfo(C.Structure):
                 ("sets_kept", C.c_uint64), ("members_read", C.c_uint64)]
 
 
+class KnownSplitInfo(C.Structure):
+    _fields_ = [("hit", KnownImageInfo), ("miss", KnownImageInfo), ("probes", C.c_uint64), ("host_probes", C.c_uint64),
+                ("sets_kept", C.c_uint64), ("members_read", C.c_uint64)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_issuers", C.c_uint32), ("zipf", C.c_uint32),
                 ("dup_permille", C.c_uint32), ("ca_permille", C.c_uint32),
@@ -222,6 +227,11 @@ SIGNATURES = {
                                         C.POINTER(KnownFindInfo)]),
     "ctmr_known_image_find_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, C.c_int64,
                                                _P, C.c_uint64, _P, C.c_size_t, C.POINTER(KnownFindInfo)]),
+    "ctmr_known_image_split": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int64, _P, C.c_size_t, _P, C.c_size_t,
+                                         C.POINTER(KnownSplitInfo)]),
+    "ctmr_known_image_split_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, C.c_int64,
+                                                _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64,
+                                                C.POINTER(KnownSplitInfo)]),
     "ctmr_known_image_resp": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t, C.POINTER(KnownRespInfo)]),
     "ctmr_known_image_resp_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, _P, C.c_size_t,
                                                C.POINTER(KnownRespInfo)]),

@@ -35,52 +35,72 @@ struct FindPack {
   template <class T> size_t put(const std::vector<T>& v) { return put(v.data(), v.size() * sizeof(T)); }
 };
 
-// Both metas are parsed and the member records of both images are on the device.  d_hits: device memory for
-// p.n_members hits (the device variant's buffer), or null: then the hits of P's member records go to `hits` on the host.
-int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const KnownMeta& p, const uint8_t* d_p, int64_t now,
-              ctmr_known_find_hit* hits, uint8_t* d_hits, uint64_t hits_cap, ctmr_known_find_hit* host_hits, size_t host_hits_cap,
-              ctmr_known_find_info* info) {
-  const char* what = "known image find";
-  int r;
-  if ((r = known_bind(e, k, d_k, what)) || (r = known_bind(e, p, d_p, what))) return r;
-  if (((uintptr_t)d_k | (uintptr_t)d_p | (uintptr_t)d_hits) & 15u)
-    return fail(e, CTMR_E_INVAL, "%s: device memory that is not 16-byte aligned", what);
-  // ---- K: the Issuer.IDs it names (K ordinals), its kept sets in image order, its kept host pairs
+// What a call knows of its two operands before anything is launched — shared with engine/split.inc.  K: the Issuer.IDs
+// it names (K ordinals, per ID string: a digest the image lists twice is one ID), its kept sets in image order as the
+// segments of a virtual record sequence, its kept host pairs.  P: the K ordinal of every set's issuer and of every
+// host-section member's key, the host-section members a member record of K can equal as probes of their own (extra).
+// hr_*: the pairs of K's host section the member section could carry — one more run, against P's member records.
+struct FindHostPair { uint32_t kord; int32_t hour; const std::string* member; size_t at; };  // at: its index in K's host section
+
+struct FindPrep {
   std::unordered_map<std::string, uint32_t> kord_of;
-  auto kord = [&](const std::string& id) {
-    return kord_of.emplace(id, (uint32_t)kord_of.size()).first->second;
-  };
   KnownExport x;  // the kept sets as (first virtual record, count): what known_cut_sets cuts into runs
-  std::vector<uint64_t> seg_src;
+  std::vector<uint64_t> seg_src, seg_set;  // per kept set: its first record in K, the set record of K it is
   std::vector<int32_t> seg_hour;
   std::vector<uint32_t> seg_kord;
-  uint64_t kept_records = 0;
+  uint64_t kept_records = 0, sets_kept = 0;
+  std::vector<FindHostPair> kh;
+  std::vector<uint32_t> p_set_kord, p_host_kord;
+  bool main_named = false;  // a member record of P can match at all
+  uint64_t n_main = 0, n_hostp = 0;
+  std::vector<uint8_t> extra_rec;
+  std::vector<uint32_t> extra_kord;
+  std::vector<uint64_t> extra_of;  // the host-section member an extra probe stands for
+  std::vector<uint8_t> hr_rec;
+  std::vector<uint64_t> hr_dst, hr_src, hr_of;  // hr_of: the pair of kh a record of the run stands for
+  std::vector<int32_t> hr_hour;
+  std::vector<uint32_t> hr_kord;
+  uint64_t n_extra() const { return extra_kord.size(); }
+  uint64_t n_probes() const { return n_main + extra_kord.size(); }
+  uint64_t n_hr() const { return hr_src.size(); }
+};
+
+int find_prepare(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const KnownMeta& p, const uint8_t* d_p, int64_t now,
+                 const void* d_out0, const void* d_out1, const char* what, FindPrep* q) {
+  int r;
+  if ((r = known_bind(e, k, d_k, what)) || (r = known_bind(e, p, d_p, what))) return r;
+  if (((uintptr_t)d_k | (uintptr_t)d_p | (uintptr_t)d_out0 | (uintptr_t)d_out1) & 15u)
+    return fail(e, CTMR_E_INVAL, "%s: device memory that is not 16-byte aligned", what);
+  // ---- K: the Issuer.IDs it names (K ordinals), its kept sets in image order, its kept host pairs
+  auto kord = [&](const std::string& id) {
+    return q->kord_of.emplace(id, (uint32_t)q->kord_of.size()).first->second;
+  };
   std::vector<uint32_t> kord_of_ordinal(k.n_issuers);  // (a digest the image lists twice: one ID, one K ordinal)
   for (uint32_t o = 0; o < k.n_issuers; o++) kord_of_ordinal[o] = kord(k.ids[o]);
-  x.set_range.reserve(k.n_sets);
-  seg_src.reserve(k.n_sets);
-  seg_hour.reserve(k.n_sets);
-  seg_kord.reserve(k.n_sets);
+  q->x.set_range.reserve(k.n_sets);
+  q->seg_src.reserve(k.n_sets);
+  q->seg_set.reserve(k.n_sets);
+  q->seg_hour.reserve(k.n_sets);
+  q->seg_kord.reserve(k.n_sets);
   for (uint64_t s = 0; s < k.n_sets; s++) {  // (per set no string is touched: an image has many sets)
     if (!lists_hour_kept(k.set_hour[s], now)) continue;
     const uint64_t cnt = k.set_first[s + 1] - k.set_first[s];
-    x.set_range.push_back({kept_records, cnt});
-    seg_src.push_back(k.set_first[s]);
-    seg_hour.push_back(k.set_hour[s]);
-    seg_kord.push_back(kord_of_ordinal[k.set_issuer[s]]);
-    kept_records += cnt;
+    q->x.set_range.push_back({q->kept_records, cnt});
+    q->seg_src.push_back(k.set_first[s]);
+    q->seg_set.push_back(s);
+    q->seg_hour.push_back(k.set_hour[s]);
+    q->seg_kord.push_back(kord_of_ordinal[k.set_issuer[s]]);
+    q->kept_records += cnt;
   }
-  x.info.members = kept_records;
-  uint64_t sets_kept = x.set_range.size();
-  struct HostPair { uint32_t kord; int32_t hour; const std::string* member; };
-  std::vector<HostPair> kh;  // the kept pairs of K's host section
-  std::map<std::pair<uint32_t, std::string>, FindAcc> kh_by;  // … by (K ordinal, member)
+  q->x.info.members = q->kept_records;
+  q->sets_kept = q->x.set_range.size();
   {
     const std::string* prev = nullptr;
     bool prev_kept = false;
     uint32_t ko = 0;
     int32_t hour = 0;
-    for (auto& hm : k.host) {
+    for (size_t j = 0; j < k.host.size(); j++) {
+      auto& hm = k.host[j];
       if (!prev || *prev != hm.first) {  // (the section is in key order: a key's date is parsed once)
         std::string date, id;
         if (!known_split_key(hm.first, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, hm.first.c_str());
@@ -90,35 +110,31 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
         if (prev_kept) {
           ko = kord(id);
           hour = (int32_t)(start / 3600);
-          sets_kept++;
+          q->sets_kept++;
         }
       }
       if (!prev_kept) continue;
-      kh.push_back({ko, hour, &hm.second});
-      kh_by[{ko, hm.second}].add(1, hour, hour);
+      q->kh.push_back({ko, hour, &hm.second, j});
     }
   }
-  // ---- P: the K ordinal of every set's issuer; its host-section members, matched here against K's host pairs, and
-  // those a member record of K can equal as probes of their own
+  // ---- P: the K ordinal of every set's issuer; its host-section members, and those a member record of K can equal as
+  // probes of their own
   auto find_kord = [&](const std::string& id) {
-    auto it = kord_of.find(id);
-    return it == kord_of.end() ? FIND_NO_ISSUER : it->second;
+    auto it = q->kord_of.find(id);
+    return it == q->kord_of.end() ? FIND_NO_ISSUER : it->second;
   };
-  std::vector<uint32_t> p_set_kord(p.n_sets);
-  bool main_named = false;  // a member record of P can match at all
+  q->p_set_kord.resize(p.n_sets);
   for (uint64_t s = 0; s < p.n_sets; s++) {
-    p_set_kord[s] = find_kord(p.ids[p.set_issuer[s]]);
-    main_named = main_named || p_set_kord[s] != FIND_NO_ISSUER;
+    q->p_set_kord[s] = find_kord(p.ids[p.set_issuer[s]]);
+    q->main_named = q->main_named || q->p_set_kord[s] != FIND_NO_ISSUER;
   }
-  const uint64_t n_main = p.n_members, n_hostp = p.host.size();
-  std::vector<FindAcc> host_acc(n_hostp);
-  std::vector<uint8_t> extra_rec;
-  std::vector<uint32_t> extra_kord;
-  std::vector<uint64_t> extra_of;  // the host-section member an extra probe stands for
+  q->n_main = p.n_members;
+  q->n_hostp = p.host.size();
+  q->p_host_kord.assign(q->n_hostp, FIND_NO_ISSUER);
   {
     const std::string* prev = nullptr;
     uint32_t ko = FIND_NO_ISSUER;
-    for (size_t j = 0; j < n_hostp; j++) {
+    for (size_t j = 0; j < q->n_hostp; j++) {
       auto& hm = p.host[j];
       if (!prev || *prev != hm.first) {
         std::string date, id;  // (the date is not looked at: the hour is the wildcard)
@@ -126,38 +142,92 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
         ko = find_kord(id);
         prev = &hm.first;
       }
+      q->p_host_kord[j] = ko;
       if (ko == FIND_NO_ISSUER) continue;
-      auto it = kh_by.find({ko, hm.second});
-      if (it != kh_by.end()) host_acc[j] = it->second;
-      if (hm.second.size() <= CTMR_MAX_SERIAL && kept_records) {
-        known_put_record(hm.second, &extra_rec);
-        extra_kord.push_back(ko);
-        extra_of.push_back(j);
+      if (hm.second.size() <= CTMR_MAX_SERIAL && q->kept_records) {
+        known_put_record(hm.second, &q->extra_rec);
+        q->extra_kord.push_back(ko);
+        q->extra_of.push_back(j);
       }
     }
   }
-  const uint64_t n_extra = extra_kord.size(), n_probes = n_main + n_extra;
   // ---- the pairs of K's host section the member section could carry: one more run, against P's member records
-  std::vector<uint8_t> hr_rec;
-  std::vector<uint64_t> hr_dst, hr_src;
-  std::vector<int32_t> hr_hour;
-  std::vector<uint32_t> hr_kord;
-  if (n_main && main_named)
-    for (auto& h : kh)
+  if (q->n_main && q->main_named)
+    for (size_t i = 0; i < q->kh.size(); i++) {
+      const FindHostPair& h = q->kh[i];
       if (h.member->size() <= CTMR_MAX_SERIAL) {
-        hr_dst.push_back(hr_src.size());
-        hr_src.push_back(hr_src.size());
-        hr_hour.push_back(h.hour);
-        hr_kord.push_back(h.kord);
-        known_put_record(*h.member, &hr_rec);
+        q->hr_dst.push_back(q->hr_src.size());
+        q->hr_src.push_back(q->hr_src.size());
+        q->hr_of.push_back(i);
+        q->hr_hour.push_back(h.hour);
+        q->hr_kord.push_back(h.kord);
+        known_put_record(*h.member, &q->hr_rec);
       }
-  const uint64_t n_hr = hr_src.size();
-  hr_dst.push_back(n_hr);
+    }
+  q->hr_dst.push_back(q->hr_src.size());
+  return CTMR_OK;
+}
+
+// The tables of a FindPrep packed for one upload, and what the kernels are given of them once they lie at t8.
+struct FindTabs {
+  FindPack pk;
+  size_t o_pfirst, o_pkord, o_xrec, o_xkord, o_dst, o_src, o_hour, o_kord, o_hrec, o_hdst, o_hsrc, o_hhour, o_hkord, o_err;
+  void pack(const FindPrep& q, const KnownMeta& p) {
+    const uint64_t K = q.x.set_range.size();
+    std::vector<uint64_t> dst(K + 1);
+    for (uint64_t s = 0; s <= K; s++) dst[s] = q.x.first(s);
+    o_pfirst = pk.put(p.set_first); o_pkord = pk.put(q.p_set_kord); o_xrec = pk.put(q.extra_rec); o_xkord = pk.put(q.extra_kord);
+    o_dst = pk.put(dst); o_src = pk.put(q.seg_src); o_hour = pk.put(q.seg_hour); o_kord = pk.put(q.seg_kord);
+    o_hrec = pk.put(q.hr_rec); o_hdst = pk.put(q.hr_dst); o_hsrc = pk.put(q.hr_src); o_hhour = pk.put(q.hr_hour); o_hkord = pk.put(q.hr_kord);
+    o_err = pk.put(nullptr, 0);
+    pk.b.resize(o_err + 16, 0);
+  }
+  FindProbes probes(const FindPrep& q, const KnownMeta& p, const uint8_t* t8, const uint8_t* d_p) const {
+    FindProbes fp{};
+    fp.recs = d_p; fp.extra = t8 + o_xrec; fp.extra_kord = (const uint32_t*)(t8 + o_xkord);
+    fp.set_first = (const uint64_t*)(t8 + o_pfirst); fp.set_kord = (const uint32_t*)(t8 + o_pkord);
+    fp.n_main = q.n_main; fp.n_extra = q.n_extra(); fp.n_sets = (uint32_t)p.n_sets;
+    return fp;
+  }
+  // the kept sets [s_lo, s_hi) of K as one run
+  FindSegs run(const uint8_t* t8, const uint8_t* d_k, size_t s_lo, size_t s_hi) const {
+    return FindSegs{d_k, (const uint64_t*)(t8 + o_dst) + s_lo, (const uint64_t*)(t8 + o_src) + s_lo, (const int32_t*)(t8 + o_hour) + s_lo,
+                    (const uint32_t*)(t8 + o_kord) + s_lo, (uint32_t)(s_hi - s_lo)};
+  }
+  // the host pairs' run
+  FindSegs host_run(const FindPrep& q, const uint8_t* t8) const {
+    return FindSegs{t8 + o_hrec, (const uint64_t*)(t8 + o_hdst), (const uint64_t*)(t8 + o_hsrc), (const int32_t*)(t8 + o_hhour),
+                    (const uint32_t*)(t8 + o_hkord), (uint32_t)q.n_hr()};
+  }
+};
+
+// Both metas are parsed and the member records of both images are on the device.  d_hits: device memory for
+// p.n_members hits (the device variant's buffer), or null: then the hits of P's member records go to `hits` on the host.
+int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const KnownMeta& p, const uint8_t* d_p, int64_t now,
+              ctmr_known_find_hit* hits, uint8_t* d_hits, uint64_t hits_cap, ctmr_known_find_hit* host_hits, size_t host_hits_cap,
+              ctmr_known_find_info* info) {
+  const char* what = "known image find";
+  int r;
+  FindPrep q;
+  if ((r = find_prepare(e, k, d_k, p, d_p, now, d_hits, nullptr, what, &q))) return r;
+  const KnownExport& x = q.x;
+  const uint64_t kept_records = q.kept_records, n_main = q.n_main, n_hostp = q.n_hostp;
+  const uint64_t n_extra = q.n_extra(), n_probes = q.n_probes(), n_hr = q.n_hr();
+  const std::vector<uint64_t>& extra_of = q.extra_of;
+  // ---- the two host sections matched here: K's kept pairs by (K ordinal, member)
+  std::map<std::pair<uint32_t, std::string>, FindAcc> kh_by;
+  for (auto& h : q.kh) kh_by[{h.kord, *h.member}].add(1, h.hour, h.hour);
+  std::vector<FindAcc> host_acc(n_hostp);
+  for (size_t j = 0; j < n_hostp; j++) {
+    if (q.p_host_kord[j] == FIND_NO_ISSUER) continue;
+    auto it = kh_by.find({q.p_host_kord[j], p.host[j].second});
+    if (it != kh_by.end()) host_acc[j] = it->second;
+  }
   // ---- sizing
   memset(info, 0, sizeof *info);
   info->probes = n_main;
   info->host_probes = n_hostp;
-  info->sets_kept = sets_kept;
+  info->sets_kept = q.sets_kept;
   info->members_read = kept_records;
   if (hits_cap < n_main || host_hits_cap < n_hostp || (n_main && !hits && !d_hits) || (n_hostp && !host_hits))
     return fail(e, CTMR_E_RANGE, "%s: %llu hits and %llu host hits needed", what, (unsigned long long)n_main, (unsigned long long)n_hostp);
@@ -168,14 +238,9 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
   const uint64_t forced_slots = env_u64("CTMR_KNOWN_FIND_SLOTS");  // tests only: the smallest table, so that chains are long
   const uint64_t slots = forced_slots ? pow2_at_least(n_probes + 1) : pow2_at_least(std::max<uint64_t>(2 * n_probes, 64));
   const uint64_t nb_fin = (n_probes + 255) / 256;
-  std::vector<uint64_t> dst(K + 1);
-  for (uint64_t s = 0; s <= K; s++) dst[s] = x.first(s);
-  FindPack pk;
-  const size_t o_pfirst = pk.put(p.set_first), o_pkord = pk.put(p_set_kord), o_xrec = pk.put(extra_rec), o_xkord = pk.put(extra_kord);
-  const size_t o_dst = pk.put(dst), o_src = pk.put(seg_src), o_hour = pk.put(seg_hour), o_kord = pk.put(seg_kord);
-  const size_t o_hrec = pk.put(hr_rec), o_hdst = pk.put(hr_dst), o_hsrc = pk.put(hr_src), o_hhour = pk.put(hr_hour), o_hkord = pk.put(hr_kord);
-  const size_t o_err = pk.put(nullptr, 0);
-  pk.b.resize(o_err + 16, 0);
+  FindTabs tb;
+  tb.pack(q, p);
+  const FindPack& pk = tb.pk;
   DevMem tabs, work;
   const size_t off_hits = slots * 8, off_cnt = off_hits + (size_t)n_probes * 16;
   if (tabs.alloc(pk.b.size()) != hipSuccess || work.alloc(off_cnt + (nb_fin + 1) * 8) != hipSuccess)
@@ -185,13 +250,10 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
   HIPCHK(e, hipMemcpyAsync(tabs.p, pk.b.data(), pk.b.size(), hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, hipMemsetAsync(work.p, 0, off_hits, e->stream));
   const uint8_t* t8 = tabs.u8();
-  uint32_t* d_err = (uint32_t*)(t8 + o_err);
+  uint32_t* d_err = (uint32_t*)(t8 + tb.o_err);
   uint4* d_work = (uint4*)(work.u8() + off_hits);
   unsigned long long* d_cnt = (unsigned long long*)(work.u8() + off_cnt);
-  FindProbes fp{};
-  fp.recs = d_p; fp.extra = t8 + o_xrec; fp.extra_kord = (const uint32_t*)(t8 + o_xkord);
-  fp.set_first = (const uint64_t*)(t8 + o_pfirst); fp.set_kord = (const uint32_t*)(t8 + o_pkord);
-  fp.n_main = n_main; fp.n_extra = n_extra; fp.n_sets = (uint32_t)p.n_sets;
+  const FindProbes fp = tb.probes(q, p, t8, d_p);
   const FindTable ft{(unsigned long long*)work.p, slots - 1};
   // ---- build, then the runs of K: whole kept sets of at most FIND_CHUNK records, the host pairs' run last
   if (n_probes) hipLaunchKernelGGL(k_find_build, dim3((unsigned)nb_fin), dim3(256), 0, e->stream, fp, ft, d_work, d_err);
@@ -200,14 +262,12 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
     const std::vector<size_t> cut = known_cut_sets(x, forced ? forced : FIND_CHUNK);
     for (size_t c = 0; c + 1 < cut.size(); c++) {
       const uint64_t n = x.first(cut[c + 1]) - x.first(cut[c]);
-      const FindSegs g{d_k, (const uint64_t*)(t8 + o_dst) + cut[c], (const uint64_t*)(t8 + o_src) + cut[c],
-                       (const int32_t*)(t8 + o_hour) + cut[c], (const uint32_t*)(t8 + o_kord) + cut[c], (uint32_t)(cut[c + 1] - cut[c])};
+      const FindSegs g = tb.run(t8, d_k, cut[c], cut[c + 1]);
       hipLaunchKernelGGL(k_find_scan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, g, n, ft, fp, n_probes, d_work, d_err);
     }
   }
   if (n_hr) {
-    const FindSegs g{t8 + o_hrec, (const uint64_t*)(t8 + o_hdst), (const uint64_t*)(t8 + o_hsrc), (const int32_t*)(t8 + o_hhour),
-                     (const uint32_t*)(t8 + o_hkord), (uint32_t)n_hr};
+    const FindSegs g = tb.host_run(q, t8);
     hipLaunchKernelGGL(k_find_scan, dim3((unsigned)((n_hr + 255) / 256)), dim3(256), 0, e->stream, g, n_hr, ft, fp, n_main, d_work, d_err);
   }
   uint32_t err = 0;

@@ -43,6 +43,8 @@
 //                       (set algebra on known-certificate images: union, minus, intersect of canonical member records)
 //   kernels/find.h      k_find_build / k_find_scan / k_find_finish (serials looked up in a known image whatever their
 //                       expiration date: the probes in a hash table, the image streamed once against it)
+//   kernels/split.h     k_split_mark / k_split_place / k_split_sets (a known image partitioned by a probe image: a flag
+//                       per record against the find's table, then one stable compaction into the two results)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once
 #include "kernels/readers.h"
@@ -70,3 +72,4 @@
 #include "kernels/sort.h"
 #include "kernels/merge.h"
 #include "kernels/find.h"
+#include "kernels/split.h"

@@ -1230,6 +1230,66 @@ class Engine:
         hits, host_hits, info = self.known_image_find_device(k_meta, d_k, probes[:at], d_p, now)
         return hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits, info
 
+    # ---- an image partitioned by a probe image, the hour as wildcard (include/ctmr.h ctmr_known_image_split*, DESIGN.md
+    # §28; CPU twin: known_image.split)
+    @staticmethod
+    def _split_info(info) -> dict:
+        out = {f: getattr(info, f) for f in ("probes", "host_probes", "sets_kept", "members_read")}
+        out["hit"], out["miss"] = Engine._stats_dict(info.hit), Engine._stats_dict(info.miss)
+        return out
+
+    @staticmethod
+    def _split_want(want):
+        want = tuple(want)
+        if set(want) - {"hit", "miss"}:
+            raise ValueError("want: \"hit\" and / or \"miss\", not %r" % (want,))
+        return "hit" in want, "miss" in want
+
+    def known_image_split(self, known, probes, now, want=("hit", "miss")):
+        """`known` partitioned by the probe image `probes` with the hour as wildcard → (hit, miss, info dict): two images
+        (bytes; None for a side `want` leaves out).  hit holds every member record and host pair of a set of `known`
+        kept at `now` that equals a probe — same Issuer.ID, same serial —, miss every other one of a kept set; both in
+        the order of `known`, nothing sorted, deduplicated or moved between the sections.  One call, the buffers sized by
+        the bound (each result is at most as large as `known`).  The engine's own sets and issuers play no part."""
+        known, probes = bytes(known), bytes(probes)
+        sides = [np.empty(len(known), np.uint8) if w else None for w in self._split_want(want)]
+        info = N.KnownSplitInfo()
+        args = [a for s in sides for a in ((s.ctypes.data, s.nbytes) if s is not None else (None, 0))]
+        self._ck(self._lib.ctmr_known_image_split(self._h, known, len(known), probes, len(probes), int(now), *args, C.byref(info)))
+        hit, miss = (s[:i.image_bytes].tobytes() if s is not None else None for s, i in zip(sides, (info.hit, info.miss)))
+        return hit, miss, self._split_info(info)
+
+    def known_image_split_device(self, k_meta, d_k_members, p_meta, d_p_members, now, want=("hit", "miss")):
+        """known_image_split with the member records of both operands in device memory (torch uint8 tensors) →
+        ((hit meta bytes, torch uint8 tensor of hit's member records on this engine's device; a view), the same for miss,
+        info dict); None for a side `want` leaves out.  One call, the buffers sized by the bound."""
+        import torch
+        k_meta, p_meta = bytes(k_meta), bytes(p_meta)
+        nk, kptr = self._members_ptr(d_k_members)
+        n, pptr = self._members_ptr(d_p_members)
+        dev = "cuda:%d" % self.device
+        sides = [(np.empty(len(k_meta), np.uint8), torch.empty(max(nk, 1) * 48, dtype=torch.uint8, device=dev)) if w else None
+                 for w in self._split_want(want)]
+        info = N.KnownSplitInfo()
+        args = [a for s in sides for a in ((s[0].ctypes.data, s[0].nbytes, C.c_void_p(s[1].data_ptr()), nk) if s else (None, 0, None, 0))]
+        self._ck(self._lib.ctmr_known_image_split_device(self._h, k_meta, len(k_meta), kptr, nk, p_meta, len(p_meta), pptr, n, int(now),
+                                                         *args, C.byref(info)))
+        hit, miss = ((s[0][:i.meta_bytes].tobytes(), s[1][:i.members * 48]) if s else None for s, i in zip(sides, (info.hit, info.miss)))
+        return hit, miss, self._split_info(info)
+
+    def known_split(self, probes, now, want=("hit", "miss")):
+        """known_image_split over the engine's own sets: known_export_device followed by known_image_split_device, as
+        known_find does.  → (hit, miss, info dict): images as bytes."""
+        import torch
+        probes = bytes(probes)
+        n = self._header_counts(probes)[0]
+        k_meta, d_k = self.known_export_device()
+        at = len(probes) - 48 * n
+        d_p = torch.frombuffer(bytearray(probes[at:]), dtype=torch.uint8).to("cuda:%d" % self.device) if n else \
+            torch.empty(0, dtype=torch.uint8, device="cuda:%d" % self.device)
+        hit, miss, info = self.known_image_split_device(k_meta, d_k, probes[:at], d_p, now, want)
+        return tuple(s[0] + s[1].cpu().numpy().tobytes() if s else None for s in (hit, miss)) + (info,)
+
     # ---- the Redis protocol stream of an image (include/ctmr.h ctmr_known_image_resp*, DESIGN.md §18; CPU twin:
     # known_image.image_resp)
     def _sized_call(self, call, cap, need, check=None):
@@ -1463,6 +1523,29 @@ class Engine:
         k_meta, d_k = self.known_export_device()
         hits, host_hits, _ = self.known_image_find_device(k_meta, d_k, p_meta, d_p, now)
         out = (p_meta, hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits)
+        return out + (verdicts,) if each else out
+
+    def known_revoked_split(self, crls, digests, now, each=False):
+        """The engine's known certificates in two images, the revoked and the others: crl_probes_device →
+        known_export_device → known_image_split_device, with no probe image and no member record in host memory.  crls,
+        digests, each: as for known_revoked.  → ((hit meta, hit's member records on the device), (miss meta, miss's
+        member records), info dict[, verdicts]).  The per-issuer lists of a revocation filter are two more calls:
+
+            (hit_meta, d_hit), (miss_meta, d_miss), info = e.known_revoked_split(crls, digests, now)
+            ids, offs, text = e.known_image_lists_device(hit_meta, d_hit, now)      # revoked/<Issuer.ID>
+            ids, offs, text = e.known_image_lists_device(miss_meta, d_miss, now)    # known/<Issuer.ID>
+        """
+        import torch
+        if not isinstance(crls, tuple):
+            blob, _, offsets, _, digests = self._crl_args(crls, digests)
+            raw = np.frombuffer(blob, np.uint8)
+            crls = (torch.from_numpy(raw.copy()).to("cuda:%d" % self.device), offsets)
+        if each:
+            p_meta, d_p, _, verdicts = self.crl_probes_each_device(crls[0], crls[1], digests)
+        else:
+            p_meta, d_p, _ = self.crl_probes_device(crls[0], crls[1], digests)
+        k_meta, d_k = self.known_export_device()
+        out = self.known_image_split_device(k_meta, d_k, p_meta, d_p, now)
         return out + (verdicts,) if each else out
 
     def known_import_resp(self, stream, world=1, rank=0) -> dict:

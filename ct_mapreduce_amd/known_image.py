@@ -8,7 +8,8 @@ checks before it applies an image; `build` is the canonical writer; `sort` is th
 `Engine.known_query` / `Engine.known_remove` over a dict of sets; `union` / `minus` / `intersect` are the twins of
 `Engine.known_merge` (set algebra on images, key by key); `image_lists` is the twin of `Engine.known_image_lists`
 (per-issuer lists straight from an image, in the image's order); `find` is the twin of `Engine.known_image_find`
-(serials looked up whatever their expiration date) and `probes` builds its probe image; `image_resp` is the twin of `Engine.known_image_resp`
+(serials looked up whatever their expiration date) and `probes` builds its probe image; `split` is the twin of
+`Engine.known_image_split` (an image partitioned by a probe image: the records that equal a probe, and the others); `image_resp` is the twin of `Engine.known_image_resp`
 (the SADD + EXPIREAT stream of an image as it lies, key by key) and `resp_image` its inverse, the twin of
 `Engine.known_resp_image` (a SADD / EXPIREAT stream as it lies → an image, members in stream order); `to_resp` /
 `from_resp` turn an image into the SADD + EXPIREAT stream `redis_dump` writes for the same sets and back (a warm start
@@ -527,6 +528,61 @@ def find(known, probes, now):
                 h[i] = (len(hours) % 2 ** 32, min(hours), max(hours), 0)
         out.append(h)
     return tuple(out)
+
+
+# ---- an image partitioned by a probe image, the hour as wildcard (include/ctmr.h ctmr_known_image_split),
+# without a GPU
+
+def _image_as_given(sets, rec, host) -> bytes:
+    """The image of sets [(exp hour, digest, [indices into rec])] in the order given and host pairs [(key, member)] in
+    the order given: the issuer table is the distinct digests ascending, nothing else is sorted or dropped."""
+    digests = sorted({dg for _, dg, _ in sets})
+    ordinal = {dg: i for i, dg in enumerate(digests)}
+    set_part, first, take = [], 0, []
+    for eh, dg, idx in sets:
+        set_part.append(_SET.pack(eh, ordinal[dg], first, len(idx)))
+        first += len(idx)
+        take += idx
+    host_part = b"".join(struct.pack("<I", len(k)) + k + struct.pack("<I", len(m)) + m for k, m in host)
+    meta = _HEADER.pack(MAGIC, VERSION, HEADER_BYTES, len(digests), 0, len(sets), first, len(host_part), len(host), 0)
+    meta += b"".join(digests) + b"".join(set_part) + host_part
+    meta += b"\0" * (-len(meta) % 64)
+    return meta + rec[np.asarray(take, np.int64)].tobytes()
+
+
+def split(known, probes, now):
+    """Engine.known_image_split(known, probes, now) without a GPU → (hit, miss): two images.  A probe is (Issuer.ID,
+    serial) — the member records and host-section members of `probes`, their hours ignored.  hit holds every member
+    record and host pair of a set of `known` kept at `now` that equals a probe, miss every other one of a kept set; sets
+    that are not kept are in neither.  Both keep the order of `known`: the set records with their hour, those left
+    empty dropped, the records of a set and the host pairs as they lie, repeats carried, nothing moved between the
+    sections; the issuer table is the distinct digests the surviving set records name, ascending.  A canonical `known`
+    gives canonical results.  Raises ImageError / ListsError where `find` does."""
+    _, k_host = _sections(known)
+    p_dev, p_host = _sections(probes)
+    wanted = {(ident, m) for _, ident, m in p_dev + p_host}
+    b = bytes(known)
+    _, _, _, n_iss, _, n_sets, n_mem, _, _, _ = _HEADER.unpack_from(b, 0)
+    so = HEADER_BYTES + 32 * n_iss
+    rec = np.frombuffer(b, MEMBER_DTYPE, count=n_mem, offset=len(b) - n_mem * MEMBER_BYTES)
+    sets, host = ([], []), ([], [])
+    for s in range(n_sets):
+        eh, ordinal, first, count = _SET.unpack_from(b, so + SET_BYTES * s)
+        if not _HOUR_LO <= eh < _HOUR_HI or now >= (eh + 1) * 3600:
+            continue
+        dg = b[HEADER_BYTES + 32 * ordinal:HEADER_BYTES + 32 * (ordinal + 1)]
+        ident = issuer_id(dg)
+        r = rec[first:first + count]
+        idx = ([], [])
+        for i, (l, m) in enumerate(zip(r["len"], r["serial"])):
+            idx[(ident, bytes(m[:int(l)])) not in wanted].append(first + i)
+        for side in (0, 1):
+            if idx[side]:
+                sets[side].append((eh, dg, idx[side]))
+    for (key, member), (span, ident, _) in zip(records(known)[1], k_host):
+        if span is not None and now < span[1]:
+            host[(ident, member) not in wanted].append((key, member))
+    return _image_as_given(sets[0], rec, host[0]), _image_as_given(sets[1], rec, host[1])
 
 
 def merge_hits(per_rank):

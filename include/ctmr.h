@@ -567,6 +567,61 @@ int ctmr_known_image_find_device(ctmr_engine* e, const uint8_t* k_meta, size_t k
                                  uint64_t p_members, int64_t now_unix, void* d_hits, uint64_t hits_cap,
                                  ctmr_known_find_hit* host_hits, size_t host_hits_cap, ctmr_known_find_info* info);
 
+/* ---- an image v1 partitioned by a probe image, the hour as wildcard: the known certificates that are revoked and those
+ *      that are not, each with its expDate — the revoked/<Issuer.ID> and known/<Issuer.ID> lists of a revocation filter.
+ *      The semi-join of ctmr_known_image_find* that keeps K's records instead of counting them.  DESIGN.md §28.
+ *
+ * Operands, probes, kept sets, sections.  Word for word those of ctmr_known_image_find*: K is any image
+ *   ctmr_known_import accepts; P's member records and host-section members are the probes (Issuer.ID string, serial
+ *   octets), P's hours are ignored; K's kept sets are exactly those ctmr_known_image_lists keeps at now_unix (INT64_MIN
+ *   keeps all that parse, hours outside the years 0000..9999 are skipped, a host date that does not parse is skipped); a
+ *   host key of other than three "::" parts is CTMR_E_INVAL in either operand; a member matches wherever it lies (a
+ *   pair of K's host section of at most CTMR_MAX_SERIAL octets meets P's member records, P's host members of at most
+ *   CTMR_MAX_SERIAL octets meet K's member records, longer members meet in the two host sections only); a probe whose
+ *   Issuer.ID K does not name matches nothing.
+ * Results.  Two images v1.  HIT holds every member record and every host pair of a kept set of K that equals at least
+ *   one probe, MISS every other member record and host pair of a kept set.  Sets that are not kept appear in neither and
+ *   their records are not read.  A record repeated in K is carried each time; repeated probes change nothing.
+ * Layout.  The call is stable: it does not sort, deduplicate or move anything between the sections.  The set records of
+ *   a result are K's kept sets in K's order with K's hour, the new count and the new first_member, a set left empty
+ *   dropped; inside a set the surviving records keep K's order.  The issuer table holds the distinct digests the
+ *   surviving set records name, ascending, each once, and the set records' ordinals are renumbered to it.  The host
+ *   section holds the surviving kept pairs in K's order.
+ * Consequence.  If K is canonical (a sorted export, any ctmr_known_merge result) both results are canonical byte for
+ *   byte, and ctmr_known_merge(CTMR_KNOWN_UNION, HIT, MISS) is the canonical image of K's kept sets.  A caller with
+ *   another K normalises a result with ctmr_known_merge(CTMR_KNOWN_UNION, x, NULL).
+ * Declining.  Either result may be declined — host variant: hit_out == NULL with hit_cap == 0; device variant:
+ *   hit_meta == NULL, hit_meta_cap == 0, d_hit == NULL, hit_members_cap == 0; the same for MISS.  A declined image is
+ *   not written and its part of *info is still filled.  Declining both is allowed: the call then only sizes.  A null
+ *   buffer with a capacity is CTMR_E_INVAL.
+ * Sizing.  The two-call convention: a wanted buffer that is too small gives CTMR_E_RANGE with *info filled and nothing
+ *   written to any buffer.  A caller can size without a first call: each result has at most K's member records and at
+ *   most K's meta bytes.
+ * Validation.  Both metas are checked as ctmr_known_import checks them.  On the device, before the first output byte,
+ *   every record of P and every record of a kept set of K is checked for serial_len <= 40 and zero padding.
+ *   CTMR_E_INVAL and CTMR_E_NOMEM leave all four output buffers as they were; every working buffer is allocated before
+ *   the first output byte.  Device pointers are 16-byte aligned, else CTMR_E_INVAL.
+ * Read-only.  Nothing of the engine's state is read or changed, as for ctmr_known_image_find*: the issuers need not be
+ *   registered, the operands are const and stay byte for byte.
+ * K's kept member records are read twice where they lie (a pass that flags them against a hash table of the probes, a
+ *   pass that copies them), in runs of whole kept sets of at most 2^27 records.  ctmr_known_image_split takes whole
+ *   images in host memory (both member sections staged on the device once, the results staged there and copied out as
+ *   meta ‖ members); ctmr_known_image_split_device takes each operand's meta and member records apart and leaves the
+ *   results' member records in device memory.  Both return after the engine's stream has drained. */
+typedef struct {
+  ctmr_known_image_info hit, miss;   /* the two results, as ctmr_known_export fills them */
+  uint64_t probes, host_probes;      /* P's member records, P's host-section members */
+  uint64_t sets_kept, members_read;  /* as in ctmr_known_find_info */
+} ctmr_known_split_info;
+int ctmr_known_image_split(ctmr_engine* e, const uint8_t* known, size_t known_len, const uint8_t* probes, size_t probes_len,
+                           int64_t now_unix, uint8_t* hit_out, size_t hit_cap, uint8_t* miss_out, size_t miss_cap,
+                           ctmr_known_split_info* info);
+int ctmr_known_image_split_device(ctmr_engine* e, const uint8_t* k_meta, size_t k_meta_len, const void* d_k_members, uint64_t k_members,
+                                  const uint8_t* p_meta, size_t p_meta_len, const void* d_p_members, uint64_t p_members, int64_t now_unix,
+                                  uint8_t* hit_meta, size_t hit_meta_cap, void* d_hit, uint64_t hit_members_cap,
+                                  uint8_t* miss_meta, size_t miss_meta_cap, void* d_miss, uint64_t miss_members_cap,
+                                  ctmr_known_split_info* info);
+
 /* ---- the Redis protocol stream of an image v1: the SADD commands of every serials:: key and the EXPIREAT
  *      KnownCertificates.setExpiryFlag puts on it (storage/knowncertificates.go:98-104), as `redis-cli --pipe` loads them
  *      into the Redis of a reference deployment.  DESIGN.md §18.
