@@ -15,15 +15,10 @@ static int xchg_round_check(ctmr_engine* e, const char* what) {
   return CTMR_OK;
 }
 
-int ctmr_xchg_map_device(ctmr_engine* e, const ctmr_shard* sh, uint32_t world, uint32_t rank, uint32_t ord_base,
-                         uint64_t* counts32, uint64_t* n_long) {
-  if (!e || !sh || !counts32 || !n_long || world == 0 || world > MAX_WORLD || rank >= world ||
-      (sh->n && (!sh->d_payload || !sh->d_offsets || !sh->d_issuer_idx || !sh->d_records)))
-    return CTMR_E_INVAL;
-  std::lock_guard<std::mutex> g(e->mu);
-  HIPCHK(e, hipSetDevice(e->device));
-  for (uint32_t w = 0; w < world; w++) counts32[w] = 0;
-  *n_long = 0;
+// Opens the round of one shard: fills the RoundCtx, makes room, and leaves it in e->rd with `valid` false — a round that
+// fails before its last range has run is never taken for an open one.  An empty shard still owns keys: its round (the one
+// its received records are inserted in) is complete at once.
+static int xchg_round_open(ctmr_engine* e, const ctmr_shard* sh, uint32_t world, uint32_t rank, uint32_t ord_base, bool chunked) {
   e->rd.valid = false;
   RoundCtx rc;
   rc.mode = XM_OWNER; rc.world = world; rc.rank = rank; rc.ord_base = ord_base;
@@ -31,9 +26,10 @@ int ctmr_xchg_map_device(ctmr_engine* e, const ctmr_shard* sh, uint32_t world, u
   rc.d_entry_type = sh->d_entry_type; rc.n = sh->n; rc.blob_bytes = sh->blob_bytes;
   rc.d_records = sh->d_records; rc.d_new_idx = sh->d_new_idx;
   rc.counts32.assign(world, 0);
+  rc.chunked = chunked;
   const uint64_t n = sh->n;
   if ((uint64_t)ord_base + n > 0xffffffffull) return fail(e, CTMR_E_INVAL, "a round holds fewer than 2^32 entries over all ranks");
-  if (n == 0) {  // an empty shard still owns keys: the round its received records are inserted in
+  if (n == 0) {
     e->epoch++;
     rc.ref0 = e->arena_used;
     e->pairs_dirty = true;
@@ -44,42 +40,95 @@ int ctmr_xchg_map_device(ctmr_engine* e, const ctmr_shard* sh, uint32_t world, u
     return CTMR_OK;
   }
   int r;
-  const uint64_t nb = (n + 1023) / 1024, n_waves = (n + 63) / 64;
-  const uint64_t ncnt = (uint64_t)world * nb;
-  XchgArgs xa{};
-  xa.world = world; xa.rank = rank;
   if (world > 1) {
+    const uint64_t nb = (n + 1023) / 1024, n_waves = (n + 63) / 64, ncnt = (uint64_t)world * nb;
     if ((r = ensure(e, SC_XSTAGE, n_waves * 64 * sizeof(KeyRec32)))) return r;
     if ((r = ensure(e, SC_XWCNT, n_waves * MAX_WORLD + 16))) return r;
     if ((r = ensure(e, SC_XCNT, (ncnt + 1) * 4))) return r;
     if ((r = ensure(e, SC_XBASE, (ncnt + 1) * 8))) return r;
+  }
+  if ((r = round_prepare(e, rc))) return r;
+  e->rd = rc;
+  return CTMR_OK;
+}
+
+// The key records that entries [lo, hi) export, counted per owner: per-block counts, their scan into partition bases
+// (SC_XBASE, on the device), and the W + 1 bases on their way to the host — in `base` once the stream has been drained.
+// With `deliver` the records are gathered at once into d_keys32_out (the gather needs the bases on the device only).
+static int xchg_count_range(ctmr_engine* e, uint32_t world, uint64_t lo, uint64_t hi, bool deliver, void* d_keys32_out,
+                            std::vector<uint64_t>& base) {
+  const uint64_t cn = hi - lo, nb = (cn + 1023) / 1024, n_waves = (cn + 63) / 64, ncnt = (uint64_t)world * nb;
+  uint32_t* d_cnt = (uint32_t*)e->d_scratch[SC_XCNT];
+  uint64_t* d_base = (uint64_t*)e->d_scratch[SC_XBASE];
+  const uint8_t* wc = (const uint8_t*)e->d_scratch[SC_XWCNT] + (lo / 64) * MAX_WORLD;
+  HIPCHK(e, hipMemsetAsync(d_cnt, 0, (ncnt + 1) * 4, e->stream));
+  hipLaunchKernelGGL(k_key_blockcount, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream, wc, n_waves, nb, world, d_cnt);
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, e->stream, d_cnt, ncnt + 1, d_base);
+  if (deliver) {
+    if (!d_keys32_out) return fail(e, CTMR_E_INVAL, "ctmr_xchg_map_chunk_device: null output buffer");
+    hipLaunchKernelGGL(k_key_gather, dim3((unsigned)nb), dim3(1024), 0, e->stream, (const KeyRec32*)e->d_scratch[SC_XSTAGE] + lo, wc,
+                       n_waves, nb, world, (const uint64_t*)d_base, (KeyRec32*)d_keys32_out);
+  }
+  // the W + 1 partition bases lie nb words apart: ONE strided copy (each small copy of its own costs ≈ 20 µs on the stream)
+  base.resize(world + 1);
+  HIPCHK(e, hipMemcpy2DAsync(base.data(), 8, d_base, nb * 8, 8, world + 1, hipMemcpyDeviceToHost, e->stream));
+  return CTMR_OK;
+}
+
+// Both forms of the map: entries [lo, hi) of the shard are mapped, their own duplicates settled, and the key records they
+// export counted per owner.  lo == 0 opens the round, hi == n completes it.  `chunked` says who delivers the 32-byte
+// records: this call, range by range, into d_keys32_out — or ctmr_xchg_keys_device afterwards, for the whole shard.
+// ONE stream synchronisation: the bases and n_xl are read behind it (and, chunked, the gather has finished: the caller may
+// hand the buffer to the transport).
+static int xchg_map_range(ctmr_engine* e, const ctmr_shard* sh, uint32_t world, uint32_t rank, uint32_t ord_base, uint64_t lo,
+                          uint64_t hi, bool chunked, void* d_keys32_out, uint64_t* counts32, uint64_t* n_long) {
+  std::lock_guard<std::mutex> g(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  for (uint32_t w = 0; w < world; w++) counts32[w] = 0;
+  *n_long = 0;
+  const uint64_t n = sh->n;
+  int r;
+  if (lo == 0) {
+    if ((r = xchg_round_open(e, sh, world, rank, ord_base, chunked))) return r;
+    if (n == 0) return CTMR_OK;
+  }
+  RoundCtx& rc = e->rd;
+  // (a later chunk continues the round its first chunk opened, and no other)
+  if (lo && (!rc.chunked || rc.mode != XM_OWNER || rc.valid || rc.chunk_next != lo || rc.n != n || rc.world != world || rc.rank != rank))
+    return fail(e, CTMR_E_INVAL, "ctmr_xchg_map_chunk_device: chunks must cover the shard in ascending order, starting at 0");
+  XchgArgs xa{};
+  xa.world = world; xa.rank = rank;
+  if (world > 1) {
     xa.stage = (KeyRec32*)e->d_scratch[SC_XSTAGE];
     xa.wave_cnt = (uint8_t*)e->d_scratch[SC_XWCNT];
   }
-  if ((r = round_begin(e, rc, &xa))) return r;
-  if (world > 1) {
-    uint32_t* d_cnt = (uint32_t*)e->d_scratch[SC_XCNT];
-    uint64_t* d_base = (uint64_t*)e->d_scratch[SC_XBASE];
-    HIPCHK(e, hipMemsetAsync(d_cnt, 0, (ncnt + 1) * 4, e->stream));
-    hipLaunchKernelGGL(k_key_blockcount, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream,
-                       (const uint8_t*)xa.wave_cnt, n_waves, nb, world, d_cnt);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, e->stream, d_cnt, ncnt + 1, d_base);
-    std::vector<uint64_t> base(world + 1);
-    unsigned long long nxl = 0;
-    // the W + 1 partition bases lie nb words apart: ONE strided copy (each small copy of its own costs ≈ 20 µs on the stream)
-    HIPCHK(e, hipMemcpy2DAsync(base.data(), 8, d_base, nb * 8, 8, world + 1, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipMemcpyAsync(&nxl, &e->d_stats->n_xl, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipGetLastError());
-    for (uint32_t w = 0; w < world; w++) rc.counts32[w] = counts32[w] = base[w + 1] - base[w];
+  if ((r = round_launch_range(e, rc, &xa, lo, hi))) return r;
+  std::vector<uint64_t> base;
+  if (world > 1 && hi > lo && (r = xchg_count_range(e, world, lo, hi, chunked, d_keys32_out, base))) return r;
+  const bool last = hi == n;
+  unsigned long long nxl = 0;
+  if (last && world > 1) HIPCHK(e, hipMemcpyAsync(&nxl, &e->d_stats->n_xl, 8, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));  // (world 1 too: so that a caller's phase clock sees the map where it ran)
+  HIPCHK(e, hipGetLastError());
+  if (!base.empty())
+    for (uint32_t w = 0; w < world; w++) {
+      counts32[w] = base[w + 1] - base[w];
+      rc.counts32[w] += counts32[w];
+    }
+  rc.chunk_next = hi;
+  if (last) {  // the round is complete
     rc.n_xl = *n_long = nxl;
-  } else {
-    HIPCHK(e, hipStreamSynchronize(e->stream));  // (so that a caller's phase clock sees the map where it ran)
-    HIPCHK(e, hipGetLastError());
+    rc.valid = true;
   }
-  e->rd = rc;
-  e->rd.valid = true;
   return CTMR_OK;
+}
+
+int ctmr_xchg_map_device(ctmr_engine* e, const ctmr_shard* sh, uint32_t world, uint32_t rank, uint32_t ord_base,
+                         uint64_t* counts32, uint64_t* n_long) {
+  if (!e || !sh || !counts32 || !n_long || world == 0 || world > MAX_WORLD || rank >= world ||
+      (sh->n && (!sh->d_payload || !sh->d_offsets || !sh->d_issuer_idx || !sh->d_records)))
+    return CTMR_E_INVAL;
+  return xchg_map_range(e, sh, world, rank, ord_base, 0, sh->n, false, nullptr, counts32, n_long);
 }
 
 // The same map in CHUNKS (ctmr_group_set_chunks): entries [lo, hi) of the shard — lo a multiple of 1024, chunks in ascending
@@ -94,88 +143,7 @@ int ctmr_xchg_map_chunk_device(ctmr_engine* e, const ctmr_shard* sh, uint32_t wo
   if (!e || !sh || !counts32 || !n_long || world == 0 || world > MAX_WORLD || rank >= world || lo > hi || hi > sh->n ||
       (lo & 1023) || (sh->n && (!sh->d_payload || !sh->d_offsets || !sh->d_issuer_idx || !sh->d_records)))
     return CTMR_E_INVAL;
-  std::lock_guard<std::mutex> g(e->mu);
-  HIPCHK(e, hipSetDevice(e->device));
-  for (uint32_t w = 0; w < world; w++) counts32[w] = 0;
-  *n_long = 0;
-  const uint64_t n = sh->n;
-  int r;
-  if (lo == 0) {  // the first chunk opens the round
-    e->rd.valid = false;
-    RoundCtx rc;
-    rc.mode = XM_OWNER; rc.world = world; rc.rank = rank; rc.ord_base = ord_base;
-    rc.d_payload = sh->d_payload; rc.d_offsets = sh->d_offsets; rc.d_ends = sh->d_ends; rc.d_issuer_idx = sh->d_issuer_idx;
-    rc.d_entry_type = sh->d_entry_type; rc.n = n; rc.blob_bytes = sh->blob_bytes;
-    rc.d_records = sh->d_records; rc.d_new_idx = sh->d_new_idx;
-    rc.counts32.assign(world, 0);
-    rc.chunked = true;
-    if ((uint64_t)ord_base + n > 0xffffffffull) return fail(e, CTMR_E_INVAL, "a round holds fewer than 2^32 entries over all ranks");
-    if (n == 0) {  // an empty shard still owns keys: the round its received records are inserted in
-      e->epoch++;
-      rc.ref0 = e->arena_used;
-      e->pairs_dirty = true;
-      HIPCHK(e, hipMemsetAsync(e->d_stats, 0, 2 * sizeof(DevStats), e->stream));
-      HIPCHK(e, hipStreamSynchronize(e->stream));
-      e->rd = rc;
-      e->rd.valid = true;
-      return CTMR_OK;
-    }
-    if (world > 1) {
-      const uint64_t nb = (n + 1023) / 1024, n_waves = (n + 63) / 64;
-      if ((r = ensure(e, SC_XSTAGE, n_waves * 64 * sizeof(KeyRec32)))) return r;
-      if ((r = ensure(e, SC_XWCNT, n_waves * MAX_WORLD + 16))) return r;
-      if ((r = ensure(e, SC_XCNT, ((uint64_t)world * nb + 1) * 4))) return r;
-      if ((r = ensure(e, SC_XBASE, ((uint64_t)world * nb + 1) * 8))) return r;
-    }
-    if ((r = round_prepare(e, rc))) return r;
-    e->rd = rc;  // open: valid stays false until the last chunk has run
-  }
-  RoundCtx& rc = e->rd;
-  if (!rc.chunked || rc.mode != XM_OWNER || rc.valid || rc.chunk_next != lo || rc.n != n || rc.world != world || rc.rank != rank)
-    return fail(e, CTMR_E_INVAL, "ctmr_xchg_map_chunk_device: chunks must cover the shard in ascending order, starting at 0");
-  XchgArgs xa{};
-  xa.world = world; xa.rank = rank;
-  if (world > 1) {
-    xa.stage = (KeyRec32*)e->d_scratch[SC_XSTAGE];
-    xa.wave_cnt = (uint8_t*)e->d_scratch[SC_XWCNT];
-  }
-  if ((r = round_launch_range(e, rc, &xa, lo, hi))) return r;
-  const uint64_t cn = hi - lo;
-  if (world > 1 && cn) {  // this chunk's records → per-owner partitions in the caller's buffer
-    const uint64_t nb = (cn + 1023) / 1024, n_waves = (cn + 63) / 64, ncnt = (uint64_t)world * nb;
-    uint32_t* d_cnt = (uint32_t*)e->d_scratch[SC_XCNT];
-    uint64_t* d_base = (uint64_t*)e->d_scratch[SC_XBASE];
-    const uint8_t* wc = (const uint8_t*)e->d_scratch[SC_XWCNT] + (lo / 64) * MAX_WORLD;
-    HIPCHK(e, hipMemsetAsync(d_cnt, 0, (ncnt + 1) * 4, e->stream));
-    hipLaunchKernelGGL(k_key_blockcount, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, e->stream, wc, n_waves, nb, world, d_cnt);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, e->stream, d_cnt, ncnt + 1, d_base);
-    // the gather needs the bases on the DEVICE only: it is queued at once, and the host reads the per-owner counts with one
-    // strided copy behind it — one synchronisation per chunk
-    if (!d_keys32_out) return fail(e, CTMR_E_INVAL, "ctmr_xchg_map_chunk_device: null output buffer");
-    hipLaunchKernelGGL(k_key_gather, dim3((unsigned)nb), dim3(1024), 0, e->stream, (const KeyRec32*)e->d_scratch[SC_XSTAGE] + lo, wc,
-                       n_waves, nb, world, (const uint64_t*)d_base, (KeyRec32*)d_keys32_out);
-    std::vector<uint64_t> base(world + 1);
-    HIPCHK(e, hipMemcpy2DAsync(base.data(), 8, d_base, nb * 8, 8, world + 1, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipGetLastError());
-    for (uint32_t w = 0; w < world; w++) {
-      counts32[w] = base[w + 1] - base[w];
-      rc.counts32[w] += counts32[w];
-    }
-  }
-  rc.chunk_next = hi;
-  if (hi == n) {  // the last chunk: the round is complete
-    unsigned long long nxl = 0;
-    HIPCHK(e, hipMemcpyAsync(&nxl, &e->d_stats->n_xl, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    HIPCHK(e, hipGetLastError());
-    rc.n_xl = *n_long = world > 1 ? nxl : 0;
-    rc.valid = true;
-  } else {
-    HIPCHK(e, hipStreamSynchronize(e->stream));  // (the gather has finished: the caller may hand the buffer to the transport)
-    HIPCHK(e, hipGetLastError());
-  }
-  return CTMR_OK;
+  return xchg_map_range(e, sh, world, rank, ord_base, lo, hi, true, d_keys32_out, counts32, n_long);
 }
 
 int ctmr_xchg_keys_device(ctmr_engine* e, void* d_keys32_out, void* d_keys64_out, uint64_t* counts64) {

@@ -607,20 +607,22 @@ int round_finish(ctmr_group* g, ctmr_batch_stats* stats) {
   return round_agree(g);
 }
 
+// A shard through the engine's plain map, as a packed batch or as an entry view.  No collective.
+int map_shard(GroupRank& r, const ctmr_shard& s, uint64_t* d_new_idx, ctmr_batch_stats* st) {
+  if (s.d_ends) {
+    const ctmr_entry_view v = shard_view(s);
+    return ctmr_map_view_device(r.e, s.d_payload, s.blob_bytes, &v, s.n, s.d_records, d_new_idx, st);
+  }
+  return ctmr_map_batch_device(r.e, s.d_payload, s.d_offsets, s.d_issuer_idx, s.d_entry_type, s.n, s.d_records, d_new_idx, st);
+}
+
 int group_map_local(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats) {
   PhaseClock clk{g};
   par_ranks(g, [&](size_t k) -> int {
     GroupRank& r = g->local[k];
-    const ctmr_shard& s = sh[k];
     memset(&r.st, 0, sizeof r.st);
-    if (!s.n) return CTMR_OK;
-    int rc;
-    if (s.d_ends) {
-      const ctmr_entry_view v = shard_view(s);
-      rc = ctmr_map_view_device(r.e, s.d_payload, s.blob_bytes, &v, s.n, s.d_records, s.d_new_idx, &r.st);
-    } else {
-      rc = ctmr_map_batch_device(r.e, s.d_payload, s.d_offsets, s.d_issuer_idx, s.d_entry_type, s.n, s.d_records, s.d_new_idx, &r.st);
-    }
+    if (!sh[k].n) return CTMR_OK;
+    const int rc = map_shard(r, sh[k], sh[k].d_new_idx, &r.st);
     return rc ? rank_fail(g, r, rc) : CTMR_OK;
   });
   clk.lap(0);
@@ -674,33 +676,183 @@ int round_header(ctmr_group* g, int mode, const ctmr_shard* sh) {
   return CTMR_OK;
 }
 
+// ------------------------------------------------------------------ the steps the exact rounds share
+// One copy of each, so that the invariant of a round — a rank that has failed still enters every collective its peers
+// enter, in the same order and with the same sizes — is kept in one place per step.  The drivers below only say which
+// steps a mode runs, in which order, and where the phase clock laps.
+
+// The round's log order, from the opening row (round_header, already gathered): Σ n over all ranks, and for every local
+// rank where its shard begins — Σ n of the lower ranks.  No collective; every rank reads the same row, so all return here
+// or none does.
+int round_log_order(ctmr_group* g, uint64_t* total_n) {
+  const uint32_t W = g->world;
+  *total_n = 0;
+  for (uint32_t w = 0; w < W; w++) *total_n += g->local[0].ctl_in[(size_t)w * KH + 4];
+  if (*total_n > 0xffffffffull) return gfail(g, CTMR_E_INVAL, "a round holds fewer than 2^32 entries over all ranks");
+  for (auto& r : g->local) {
+    r.ord_base = 0;
+    for (uint32_t w = 0; w < r.rank; w++) r.ord_base += r.ctl_in[(size_t)w * KH + 4];
+  }
+  return CTMR_OK;
+}
+
+// The buffers and count vectors of one record stream of a rank: what leaves (keys, send), what arrives (recv, got), and
+// the one byte per record that comes back (flags_out at the owner → flags_mine at the sender).
+struct Chan {
+  DevBuf GroupRank::*keys, GroupRank::*recv, GroupRank::*flags_out, GroupRank::*flags_mine;
+  std::vector<uint64_t> GroupRank::*send, GroupRank::*got;
+};
+constexpr Chan MAIN{&GroupRank::keys, &GroupRank::recv, &GroupRank::flags_out, &GroupRank::flags_mine,
+                    &GroupRank::send_counts, &GroupRank::recv_counts};
+// … and the side channel of the owner-computes rounds: the rare 64-byte records (21..40-octet serials)
+constexpr Chan SIDE64{&GroupRank::keys64, &GroupRank::recv64, &GroupRank::flags_out64, &GroupRank::flags_mine64,
+                      &GroupRank::send_counts64, &GroupRank::recv_counts64};
+
+struct CountCols {  // one set of W columns of a counts row: what the rank sends to each peer, what each peer sends it
+  const std::vector<uint64_t>* send;
+  std::vector<uint64_t>* got;
+};
+CountCols counts_of(GroupRank& r, const Chan& c) { return {&(r.*c.send), &(r.*c.got)}; }
+
+// A counts row: every rank publishes status | ncol x W send counts (cols(r, j) names rank r's vectors of column set j),
+// the row is gathered and its status column judged, and every rank reads its own column of each set: what every peer will
+// send it.  totals[j] (optional) = Σ of set j over all senders and owners.  A failed rank enters the gather like its peers,
+// with its code and zero counts; the verdict is the same on every rank, so all return here or none does — before any
+// exchange whose sizes the row told.
+template <class Cols>
+int counts_row(ctmr_group* g, uint32_t ncol, Cols cols, uint64_t* totals = nullptr) {
+  const uint32_t W = g->world, K = 1 + ncol * W;
+  for (auto& r : g->local) {
+    r.ctl_out.assign(K, 0);
+    r.ctl_out[0] = (uint64_t)(int64_t)r.rc;
+    if (r.rc != CTMR_OK) continue;
+    for (uint32_t j = 0; j < ncol; j++)
+      for (uint32_t w = 0; w < W; w++) r.ctl_out[1 + j * W + w] = (*cols(r, j).send)[w];
+  }
+  int rc;
+  if ((rc = control_gather(g, K))) return rc;
+  if ((rc = control_status(g, K))) return rc;
+  for (auto& r : g->local)
+    for (uint32_t j = 0; j < ncol; j++) {
+      std::vector<uint64_t>& got = *cols(r, j).got;
+      got.assign(W, 0);
+      for (uint32_t s = 0; s < W; s++) got[s] = r.ctl_in[(size_t)s * K + 1 + j * W + r.rank];
+    }
+  if (totals)
+    for (uint32_t j = 0; j < ncol; j++) {
+      totals[j] = 0;
+      for (uint32_t s = 0; s < W; s++)
+        for (uint32_t w = 0; w < W; w++) totals[j] += g->local[0].ctl_in[(size_t)s * K + 1 + j * W + w];
+    }
+  return CTMR_OK;
+}
+
+// Room on rank r for what an exchange of `unit`-byte records brings: nrecv records in, a byte for each of them out, and a
+// byte back for each of the nsend records that leave.  The first failure is returned, for note_failure: the status row
+// that follows tells every rank, and all leave the round together.
+int recv_buffers(ctmr_group* g, GroupRank& r, const Chan& c, size_t unit, uint64_t nsend, uint64_t nrecv) {
+  int e1 = gbuf(g, r, r.*c.recv, (size_t)(nrecv ? nrecv : 1) * unit);
+  if (!e1) e1 = gbuf(g, r, r.*c.flags_out, nrecv ? nrecv : 1);
+  if (!e1) e1 = gbuf(g, r, r.*c.flags_mine, nsend ? nsend : 1);
+  return e1;
+}
+void note_failure(GroupRank& r, int e1) {
+  if (e1 && r.rc == CTMR_OK) r.rc = e1;
+}
+
+// One all-to-all: ends(r) names the buffer and the count vector rank r sends from and those it receives into.  A
+// collective: every rank calls it, also one that failed after the status row before it (its buffers exist, what they
+// hold is not used).
+struct Ends {
+  void* send;
+  const std::vector<uint64_t>* send_cnt;
+  void* recv;
+  const std::vector<uint64_t>* recv_cnt;
+};
+template <class F>
+int exchange(ctmr_group* g, size_t unit, F ends) {
+  return all_to_all_v(g, unit, [&](GroupRank& r) { return ends(r).send; },
+                      [&](GroupRank& r) -> const std::vector<uint64_t>& { return *ends(r).send_cnt; },
+                      [&](GroupRank& r) { return ends(r).recv; },
+                      [&](GroupRank& r) -> const std::vector<uint64_t>& { return *ends(r).recv_cnt; });
+}
+// key records → the ranks that answer for them …
+int keys_there(ctmr_group* g, size_t unit, const Chan& c) {
+  return exchange(g, unit, [&](GroupRank& r) { return Ends{(r.*c.keys).p, &(r.*c.send), (r.*c.recv).p, &(r.*c.got)}; });
+}
+// … and one byte per record back the way the keys came: the roles of the count vectors swapped
+int flags_back(ctmr_group* g, const Chan& c) {
+  return exchange(g, 1, [&](GroupRank& r) { return Ends{(r.*c.flags_out).p, &(r.*c.got), (r.*c.flags_mine).p, &(r.*c.send)}; });
+}
+
+// The 64-byte side channel of both owner-computes drivers.  any64 = Σ of the 64-byte counts over ALL ranks, from a counts
+// row: the same on every rank, so either every rank enters the side channel's status row and exchanges or none does —
+// whatever a rank's own counts are, and whether it has failed or not.
+int side64_buffers(ctmr_group* g, GroupRank& r) {
+  const int e1 = gbuf(g, r, r.keys64, (size_t)(r.n_keys64 ? r.n_keys64 : 1) * 64);
+  return e1 ? e1 : recv_buffers(g, r, SIDE64, 64, r.n_keys64, prefix(r.recv_counts64, g->world));
+}
+int side64_there(ctmr_group* g, uint64_t any64) { return any64 ? keys_there(g, 64, SIDE64) : CTMR_OK; }
+int side64_back(ctmr_group* g, uint64_t any64) { return any64 ? flags_back(g, SIDE64) : CTMR_OK; }
+
+// The owner side of both owner-computes drivers: every rank inserts the records it received (r.recv_counts / 64 say how
+// many, over all chunks), one "was unknown" byte per record, then resolves its own shard; and the round's traffic is
+// counted.  No collective: a rank that fails here goes on into the exchange back with whatever its buffers hold.
+void owner_insert(ctmr_group* g) {
+  const uint32_t W = g->world;
+  const bool alone = W == 1;  // one rank: it owns every key, nothing was exported
+  g->last_keys_sent = g->last_keys_received = 0;
+  par_ranks(g, [&](size_t k) -> int {
+    GroupRank& r = g->local[k];
+    const uint64_t nrecv = alone ? 0 : prefix(r.recv_counts, W), nrecv64 = alone ? 0 : prefix(r.recv_counts64, W);
+    int e1 = ctmr_xchg_insert_device(r.e, r.recv.p, nrecv, r.recv64.p, nrecv64, (uint8_t*)r.flags_out.p, (uint8_t*)r.flags_out64.p);
+    return e1 ? rank_fail(g, r, e1) : CTMR_OK;
+  });
+  for (auto& r : g->local) {
+    g->last_keys_sent += r.n_keys + r.n_keys64 - r.send_counts[r.rank] - r.send_counts64[r.rank];
+    g->last_keys_received += prefix(r.recv_counts, W) + prefix(r.recv_counts64, W) - r.recv_counts[r.rank] - r.recv_counts64[r.rank];
+  }
+}
+// … and the sender side afterwards: the returned bytes → records, NEW list, stats.  No collective.
+void owner_apply(ctmr_group* g, uint64_t any64) {
+  const bool alone = g->world == 1;
+  par_ranks(g, [&](size_t k) -> int {
+    GroupRank& r = g->local[k];
+    memset(&r.st, 0, sizeof r.st);
+    int e1 = ctmr_xchg_apply_device(r.e, r.keys.p, (const uint8_t*)r.flags_mine.p, alone ? 0 : r.n_keys, r.keys64.p,
+                                    (const uint8_t*)r.flags_mine64.p, (alone || !any64) ? 0 : r.n_keys64, &r.st);
+    return e1 ? rank_fail(g, r, e1) : CTMR_OK;
+  });
+}
+
+// The end of every exact round: the statistics out, then round_finish — the long-serial settlement and the closing row,
+// collectives that every rank enters, failed or not — and the clock's last lap.
+int round_tail(ctmr_group* g, ctmr_batch_stats* stats, PhaseClock& clk) {
+  if (stats)
+    for (size_t k = 0; k < g->local.size(); k++) stats[k] = g->local[k].st;
+  const int rc = round_finish(g, stats);
+  clk.lap(6);
+  return rc;
+}
+
 // Owner-computes key exchange (SURVEY.md §8(e)(ii)): map (+ insert of the keys the rank owns) → key records all-to-all →
 // owner insert → flags back → apply.
 int group_map_owner(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats) {
   const uint32_t W = g->world;
-  const uint32_t K0 = KH, K1 = 1 + 2 * W;
   int rc;
   PhaseClock clk{g};
   round_open(g);
-  // ---- control: the opening row (round_header, already gathered) says where every shard lies in the round's log order:
-  // Σ n of the lower ranks
-  uint64_t total_n = 0;
-  for (uint32_t w = 0; w < W; w++) total_n += g->local[0].ctl_in[(size_t)w * K0 + 4];
-  if (total_n > 0xffffffffull) return gfail(g, CTMR_E_INVAL, "a round holds fewer than 2^32 entries over all ranks");
+  uint64_t total_n;
+  if ((rc = round_log_order(g, &total_n))) return rc;
   clk.lap(6);
   // ---- phase 1: map + insert of the locally owned keys + the other keys as records, partitioned by owner
   par_ranks(g, [&](size_t k) -> int {
     GroupRank& r = g->local[k];
-    const ctmr_shard& s = sh[k];
-    uint64_t ord_base = 0;
-    for (uint32_t w = 0; w < r.rank; w++) ord_base += r.ctl_in[(size_t)w * K0 + 4];
-    r.ord_base = ord_base;
     r.send_counts.assign(W, 0);
     r.send_counts64.assign(W, 0);
     r.n_keys64 = 0;
-    int e1 = ctmr_xchg_map_device(r.e, &s, W, r.rank, (uint32_t)ord_base, r.send_counts.data(), &r.n_keys64);
-    if (e1) return rank_fail(g, r, e1);
-    return CTMR_OK;
+    int e1 = ctmr_xchg_map_device(r.e, &sh[k], W, r.rank, (uint32_t)r.ord_base, r.send_counts.data(), &r.n_keys64);
+    return e1 ? rank_fail(g, r, e1) : CTMR_OK;
   });
   clk.lap(0);
   par_ranks(g, [&](size_t k) -> int {
@@ -714,97 +866,40 @@ int group_map_owner(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats
     return CTMR_OK;
   });
   clk.lap(1);
-  // ---- control: who sends how much to whom (and: is everybody still there)
-  for (auto& r : g->local) {
-    r.ctl_out.assign(K1, 0);
-    r.ctl_out[0] = (uint64_t)(int64_t)r.rc;
-    if (r.rc == CTMR_OK)
-      for (uint32_t w = 0; w < W; w++) {
-        r.ctl_out[1 + w] = r.send_counts[w];
-        r.ctl_out[1 + W + w] = r.send_counts64[w];
-      }
-  }
-  if ((rc = control_gather(g, K1))) return rc;
-  if ((rc = control_status(g, K1))) return rc;  // a rank failed before anything was exchanged: every rank stops here
-  uint64_t any64 = 0;
-  for (auto& r : g->local) {
-    r.recv_counts.assign(W, 0);
-    r.recv_counts64.assign(W, 0);
-    for (uint32_t s = 0; s < W; s++) {
-      r.recv_counts[s] = r.ctl_in[(size_t)s * K1 + 1 + r.rank];
-      r.recv_counts64[s] = r.ctl_in[(size_t)s * K1 + 1 + W + r.rank];
-      for (uint32_t w = 0; w < W; w++) any64 += r.ctl_in[(size_t)s * K1 + 1 + W + w];
-    }
-  }
+  // ---- control: who sends how much to whom (and: is everybody still there — a rank failed before anything was
+  // exchanged: every rank stops here)
+  uint64_t tot[2];
+  if ((rc = counts_row(g, 2, [](GroupRank& r, uint32_t j) { return counts_of(r, j ? SIDE64 : MAIN); }, tot))) return rc;
+  const uint64_t any64 = tot[1];
   clk.lap(6);
   const bool alone = W == 1;  // one rank: it owns every key, nothing was exported
   // from here on a failed rank still takes part in every collective (with whatever its buffers hold)
   for (auto& r : g->local) {
-    const uint64_t nrecv = prefix(r.recv_counts, W), nrecv64 = prefix(r.recv_counts64, W);
     int e1 = CTMR_OK;
     if (!alone) {
-      if (!e1) e1 = gbuf(g, r, r.recv, (size_t)(nrecv ? nrecv : 1) * 32);
-      if (!e1) e1 = gbuf(g, r, r.flags_out, nrecv ? nrecv : 1);
-      if (!e1) e1 = gbuf(g, r, r.flags_mine, r.n_keys ? r.n_keys : 1);
-      if (any64) {
-        if (!e1) e1 = gbuf(g, r, r.keys64, (size_t)(r.n_keys64 ? r.n_keys64 : 1) * 64);
-        if (!e1) e1 = gbuf(g, r, r.recv64, (size_t)(nrecv64 ? nrecv64 : 1) * 64);
-        if (!e1) e1 = gbuf(g, r, r.flags_out64, nrecv64 ? nrecv64 : 1);
-        if (!e1) e1 = gbuf(g, r, r.flags_mine64, r.n_keys64 ? r.n_keys64 : 1);
-      }
+      e1 = recv_buffers(g, r, MAIN, 32, r.n_keys, prefix(r.recv_counts, W));
+      if (any64 && !e1) e1 = side64_buffers(g, r);
     }
-    if (e1 && r.rc == CTMR_OK) r.rc = e1;  // no memory for the receive buffers: said in the row below
+    note_failure(r, e1);  // no memory for the receive buffers: said in the row below
   }
   if (!alone && (rc = status_row(g))) return rc;
   // ---- exchange A: key partitions → owners
   if (!alone) {
-    if ((rc = all_to_all_v(g, 32, [](GroupRank& r) { return r.keys.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts; },
-                           [](GroupRank& r) { return r.recv.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts; })))
-      return rc;
-    if (any64 &&
-        (rc = all_to_all_v(g, 64, [](GroupRank& r) { return r.keys64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts64; },
-                           [](GroupRank& r) { return r.recv64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts64; })))
-      return rc;
+    if ((rc = keys_there(g, 32, MAIN))) return rc;
+    if ((rc = side64_there(g, any64))) return rc;
   }
   clk.lap(2);
-  g->last_keys_sent = g->last_keys_received = 0;
-  // ---- phase 2: the owner inserts what it received, one "was unknown" byte per record; then its own shard's resolve
-  par_ranks(g, [&](size_t k) -> int {
-    GroupRank& r = g->local[k];
-    const uint64_t nrecv = alone ? 0 : prefix(r.recv_counts, W), nrecv64 = alone ? 0 : prefix(r.recv_counts64, W);
-    int e1 = ctmr_xchg_insert_device(r.e, r.recv.p, nrecv, r.recv64.p, nrecv64, (uint8_t*)r.flags_out.p, (uint8_t*)r.flags_out64.p);
-    return e1 ? rank_fail(g, r, e1) : CTMR_OK;
-  });
-  for (auto& r : g->local) {
-    g->last_keys_sent += r.n_keys + r.n_keys64 - r.send_counts[r.rank] - r.send_counts64[r.rank];
-    g->last_keys_received += prefix(r.recv_counts, W) + prefix(r.recv_counts64, W) - r.recv_counts[r.rank] - r.recv_counts64[r.rank];
-  }
+  owner_insert(g);  // ---- phase 2
   clk.lap(3);
-  // ---- exchange B: the bytes go back the way the keys came (roles of the count vectors swapped)
+  // ---- exchange B: the bytes go back the way the keys came
   if (!alone) {
-    if ((rc = all_to_all_v(g, 1, [](GroupRank& r) { return r.flags_out.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts; },
-                           [](GroupRank& r) { return r.flags_mine.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts; })))
-      return rc;
-    if (any64 &&
-        (rc = all_to_all_v(g, 1, [](GroupRank& r) { return r.flags_out64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts64; },
-                           [](GroupRank& r) { return r.flags_mine64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts64; })))
-      return rc;
+    if ((rc = flags_back(g, MAIN))) return rc;
+    if ((rc = side64_back(g, any64))) return rc;
   }
   clk.lap(4);
-  // ---- phase 3: the returned bytes → records, NEW list, stats
-  par_ranks(g, [&](size_t k) -> int {
-    GroupRank& r = g->local[k];
-    memset(&r.st, 0, sizeof r.st);
-    int e1 = ctmr_xchg_apply_device(r.e, r.keys.p, (const uint8_t*)r.flags_mine.p, alone ? 0 : r.n_keys, r.keys64.p,
-                                    (const uint8_t*)r.flags_mine64.p, (alone || !any64) ? 0 : r.n_keys64, &r.st);
-    return e1 ? rank_fail(g, r, e1) : CTMR_OK;
-  });
+  owner_apply(g, any64);  // ---- phase 3
   clk.lap(5);
-  if (stats)
-    for (size_t k = 0; k < g->local.size(); k++) stats[k] = g->local[k].st;
-  rc = round_finish(g, stats);
-  clk.lap(6);
-  return rc;
+  return round_tail(g, stats, clk);
 }
 
 // The owner-computes round with every shard mapped in K CHUNKS (ctmr_group_set_chunks): chunk c's key records travel — on
@@ -815,36 +910,35 @@ int group_map_owner(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats
 // worst case before the first chunk is mapped (every key of the shard may leave, every key of the other shards may arrive).
 int group_map_owner_chunked(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats) {
   const uint32_t W = g->world, K = g->chunks;
-  const uint32_t K0 = KH, K1 = 1 + W;
   int rc;
   PhaseClock clk{g};
   round_open(g);
   if ((rc = xfer_streams(g))) return rc;
-  uint64_t total_n = 0;
-  for (uint32_t w = 0; w < W; w++) total_n += g->local[0].ctl_in[(size_t)w * K0 + 4];
-  if (total_n > 0xffffffffull) return gfail(g, CTMR_E_INVAL, "a round holds fewer than 2^32 entries over all ranks");
-  std::vector<uint64_t> send_tot(g->local.size(), 0), recv_tot(g->local.size(), 0);
+  uint64_t total_n;
+  if ((rc = round_log_order(g, &total_n))) return rc;
   for (size_t k = 0; k < g->local.size(); k++) {
     GroupRank& r = g->local[k];
     const uint64_t n = sh[k].n, others = total_n - n;
-    uint64_t ord_base = 0;
-    for (uint32_t w = 0; w < r.rank; w++) ord_base += r.ctl_in[(size_t)w * K0 + 4];
-    r.ord_base = ord_base;
     r.csend.assign(K, std::vector<uint64_t>(W, 0));
     r.crecv.assign(K, std::vector<uint64_t>(W, 0));
     r.csend_off.assign(K, 0);
     r.crecv_off.assign(K, 0);
+    r.send_counts.assign(W, 0);  // Σ over the chunks so far; r.n_keys = how many records that is
+    r.recv_counts.assign(W, 0);
     r.send_counts64.assign(W, 0);
     r.recv_counts64.assign(W, 0);
     r.n_keys = r.n_keys64 = 0;
     int e1 = gbuf(g, r, r.keys, (size_t)(n ? n : 1) * 32);
-    if (!e1) e1 = gbuf(g, r, r.recv, (size_t)(others ? others : 1) * 32);
-    if (!e1) e1 = gbuf(g, r, r.flags_out, others ? others : 1);
-    if (!e1) e1 = gbuf(g, r, r.flags_mine, n ? n : 1);
-    if (e1 && r.rc == CTMR_OK) r.rc = e1;
+    if (!e1) e1 = recv_buffers(g, r, MAIN, 32, n, others);
+    note_failure(r, e1);
   }
   if ((rc = status_row(g))) return rc;
   clk.lap(6);
+  // once a chunk may be on the wire, a round that stops early stops behind the transfers already in flight
+  auto stop = [&](int code) {
+    (void)xfer_wait(g);
+    return code;
+  };
   // ---- the chunks: map c, tell the counts, put c on the wire, go on with c + 1
   for (uint32_t c = 0; c < K; c++) {
     par_ranks(g, [&](size_t k) -> int {
@@ -855,37 +949,25 @@ int group_map_owner_chunked(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stat
       const uint64_t hi = (c + 1 == K || (uint64_t)(c + 1) * cs > s.n) ? s.n : (uint64_t)(c + 1) * cs;
       if (lo == hi && !(s.n == 0 && c == 0)) return CTMR_OK;  // nothing of this shard in this chunk
       uint64_t n_long = 0;
-      int e1 = ctmr_xchg_map_chunk_device(r.e, &s, W, r.rank, (uint32_t)r.ord_base, lo, hi, (uint8_t*)r.keys.p + send_tot[k] * 32,
+      int e1 = ctmr_xchg_map_chunk_device(r.e, &s, W, r.rank, (uint32_t)r.ord_base, lo, hi, (uint8_t*)r.keys.p + r.n_keys * 32,
                                           r.csend[c].data(), &n_long);
       if (e1) return rank_fail(g, r, e1);
       if (hi == s.n) r.n_keys64 = n_long;
       return CTMR_OK;
     });
     clk.lap(0);
-    for (auto& r : g->local) {
-      r.ctl_out.assign(K1, 0);
-      r.ctl_out[0] = (uint64_t)(int64_t)r.rc;
-      if (r.rc == CTMR_OK)
-        for (uint32_t w = 0; w < W; w++) r.ctl_out[1 + w] = r.csend[c][w];
-    }
-    if (!(rc = control_gather(g, K1))) rc = control_status(g, K1);
-    if (rc) {  // some rank failed: every rank stops here — behind the transfers already in flight
-      (void)xfer_wait(g);
-      return rc;
-    }
-    for (size_t k = 0; k < g->local.size(); k++) {
-      GroupRank& r = g->local[k];
-      for (uint32_t s = 0; s < W; s++) r.crecv[c][s] = r.ctl_in[(size_t)s * K1 + 1 + r.rank];
-      r.csend_off[c] = send_tot[k];
-      r.crecv_off[c] = recv_tot[k];
-      send_tot[k] += prefix(r.csend[c], W);
-      recv_tot[k] += prefix(r.crecv[c], W);
+    if ((rc = counts_row(g, 1, [c](GroupRank& r, uint32_t) { return CountCols{&r.csend[c], &r.crecv[c]}; }))) return stop(rc);
+    for (auto& r : g->local) {  // where chunk c lies in the send / receive buffers: behind the chunks before it
+      r.csend_off[c] = r.n_keys;
+      r.crecv_off[c] = prefix(r.recv_counts, W);
+      for (uint32_t w = 0; w < W; w++) {
+        r.send_counts[w] += r.csend[c][w];
+        r.recv_counts[w] += r.crecv[c][w];
+      }
+      r.n_keys = prefix(r.send_counts, W);
     }
     clk.lap(6);
-    if ((rc = chunk_all_to_all_async(g, c))) {
-      (void)xfer_wait(g);
-      return rc;
-    }
+    if ((rc = chunk_all_to_all_async(g, c))) return stop(rc);
   }
   // ---- the rare 64-byte records (21..40-octet serials) of the whole shard, after the last chunk: one more row, one exchange
   par_ranks(g, [&](size_t k) -> int {
@@ -896,90 +978,28 @@ int group_map_owner_chunked(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stat
     if ((e1 = ctmr_xchg_keys_device(r.e, nullptr, r.keys64.p, r.send_counts64.data()))) return rank_fail(g, r, e1);
     return CTMR_OK;
   });
-  for (auto& r : g->local) {
-    r.ctl_out.assign(K1, 0);
-    r.ctl_out[0] = (uint64_t)(int64_t)r.rc;
-    if (r.rc == CTMR_OK)
-      for (uint32_t w = 0; w < W; w++) r.ctl_out[1 + w] = r.send_counts64[w];
-  }
-  if (!(rc = control_gather(g, K1))) rc = control_status(g, K1);
-  if (rc) {
-    (void)xfer_wait(g);
-    return rc;
-  }
   uint64_t any64 = 0;
-  for (auto& r : g->local)
-    for (uint32_t s = 0; s < W; s++) {
-      r.recv_counts64[s] = r.ctl_in[(size_t)s * K1 + 1 + r.rank];
-      for (uint32_t w = 0; w < W; w++) any64 += r.ctl_in[(size_t)s * K1 + 1 + w];
-    }
+  if ((rc = counts_row(g, 1, [](GroupRank& r, uint32_t) { return counts_of(r, SIDE64); }, &any64))) return stop(rc);
   if (any64) {
-    for (auto& r : g->local) {
-      const uint64_t nrecv64 = prefix(r.recv_counts64, W);
-      int e1 = gbuf(g, r, r.keys64, (size_t)(r.n_keys64 ? r.n_keys64 : 1) * 64);
-      if (!e1) e1 = gbuf(g, r, r.recv64, (size_t)(nrecv64 ? nrecv64 : 1) * 64);
-      if (!e1) e1 = gbuf(g, r, r.flags_out64, nrecv64 ? nrecv64 : 1);
-      if (!e1) e1 = gbuf(g, r, r.flags_mine64, r.n_keys64 ? r.n_keys64 : 1);
-      if (e1 && r.rc == CTMR_OK) r.rc = e1;
-    }
-    if ((rc = status_row(g))) {
-      (void)xfer_wait(g);
-      return rc;
-    }
-    if ((rc = all_to_all_v(g, 64, [](GroupRank& r) { return r.keys64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts64; },
-                           [](GroupRank& r) { return r.recv64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts64; }))) {
-      (void)xfer_wait(g);
-      return rc;
-    }
+    for (auto& r : g->local) note_failure(r, side64_buffers(g, r));
+    if ((rc = status_row(g))) return stop(rc);
+    if ((rc = side64_there(g, any64))) return stop(rc);
   }
   if ((rc = xfer_wait(g))) return rc;  // every chunk has arrived
   clk.lap(2);
-  // ---- the owner inserts what it received (all chunks at once), one "was unknown" byte per record; then its own shard's resolve
-  g->last_keys_sent = g->last_keys_received = 0;
-  par_ranks(g, [&](size_t k) -> int {
-    GroupRank& r = g->local[k];
-    const uint64_t nrecv64 = any64 ? prefix(r.recv_counts64, W) : 0;
-    int e1 = ctmr_xchg_insert_device(r.e, r.recv.p, recv_tot[k], r.recv64.p, nrecv64, (uint8_t*)r.flags_out.p, (uint8_t*)r.flags_out64.p);
-    return e1 ? rank_fail(g, r, e1) : CTMR_OK;
-  });
-  for (size_t k = 0; k < g->local.size(); k++) {
-    GroupRank& r = g->local[k];
-    r.n_keys = send_tot[k];
-    uint64_t own_s = 0, own_r = 0;
-    for (uint32_t c = 0; c < K; c++) {
-      own_s += r.csend[c][r.rank];
-      own_r += r.crecv[c][r.rank];
-    }
-    g->last_keys_sent += send_tot[k] + r.n_keys64 - own_s - r.send_counts64[r.rank];
-    g->last_keys_received += recv_tot[k] + prefix(r.recv_counts64, W) - own_r - r.recv_counts64[r.rank];
-  }
+  owner_insert(g);  // ---- all chunks at once
   clk.lap(3);
-  // ---- the bytes go back the way the keys came, chunk by chunk (roles of the count vectors swapped)
+  // ---- the bytes go back the way the keys came, chunk by chunk: flags_back, with each chunk where it lies in the buffers
   for (uint32_t c = 0; c < K; c++)
-    if ((rc = all_to_all_v(g, 1, [c](GroupRank& r) { return (void*)((uint8_t*)r.flags_out.p + r.crecv_off[c]); },
-                           [c](GroupRank& r) -> const std::vector<uint64_t>& { return r.crecv[c]; },
-                           [c](GroupRank& r) { return (void*)((uint8_t*)r.flags_mine.p + r.csend_off[c]); },
-                           [c](GroupRank& r) -> const std::vector<uint64_t>& { return r.csend[c]; })))
+    if ((rc = exchange(g, 1, [c](GroupRank& r) {
+           return Ends{(uint8_t*)r.flags_out.p + r.crecv_off[c], &r.crecv[c], (uint8_t*)r.flags_mine.p + r.csend_off[c], &r.csend[c]};
+         })))
       return rc;
-  if (any64 &&
-      (rc = all_to_all_v(g, 1, [](GroupRank& r) { return r.flags_out64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts64; },
-                         [](GroupRank& r) { return r.flags_mine64.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts64; })))
-    return rc;
+  if ((rc = side64_back(g, any64))) return rc;
   clk.lap(4);
-  // ---- the returned bytes → records, NEW list, stats
-  par_ranks(g, [&](size_t k) -> int {
-    GroupRank& r = g->local[k];
-    memset(&r.st, 0, sizeof r.st);
-    int e1 = ctmr_xchg_apply_device(r.e, r.keys.p, (const uint8_t*)r.flags_mine.p, send_tot[k], r.keys64.p,
-                                    (const uint8_t*)r.flags_mine64.p, any64 ? r.n_keys64 : 0, &r.st);
-    return e1 ? rank_fail(g, r, e1) : CTMR_OK;
-  });
+  owner_apply(g, any64);
   clk.lap(5);
-  if (stats)
-    for (size_t k = 0; k < g->local.size(); k++) stats[k] = g->local[k].st;
-  rc = round_finish(g, stats);
-  clk.lap(6);
-  return rc;
+  return round_tail(g, stats, clk);
 }
 
 // Bloom pre-filter variant (north_star: "all-gather of per-GPU Bloom fingerprints"; SURVEY.md §8(e)(i)), exact:
@@ -987,7 +1007,6 @@ int group_map_owner_chunked(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stat
 // → exact lookup there → flags back → apply.
 int group_map_bloom(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats) {
   const uint32_t W = g->world;
-  const uint32_t K1 = 1 + W;
   int rc;
   PhaseClock clk{g};
   round_open(g);
@@ -995,15 +1014,7 @@ int group_map_bloom(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats
     GroupRank& r = g->local[k];
     const ctmr_shard& s = sh[k];
     r.ord_base = s.order_base;
-    int e1 = CTMR_OK;
-    if (s.n) {
-      if (s.d_ends) {
-        const ctmr_entry_view v = shard_view(s);
-        e1 = ctmr_map_view_device(r.e, s.d_payload, s.blob_bytes, &v, s.n, s.d_records, nullptr, nullptr);
-      } else {
-        e1 = ctmr_map_batch_device(r.e, s.d_payload, s.d_offsets, s.d_issuer_idx, s.d_entry_type, s.n, s.d_records, nullptr, nullptr);
-      }
-    }
+    int e1 = s.n ? map_shard(r, s, nullptr, nullptr) : CTMR_OK;
     if (!e1 && W > 1) e1 = ctmr_bloom_add_device(r.e, s.d_payload, s.d_offsets, s.d_ends, s.n, s.d_records);
     return e1 ? rank_fail(g, r, e1) : CTMR_OK;
   });
@@ -1034,32 +1045,15 @@ int group_map_bloom(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats
     return CTMR_OK;
   });
   clk.lap(1);
-  for (auto& r : g->local) {
-    r.ctl_out.assign(K1, 0);
-    r.ctl_out[0] = (uint64_t)(int64_t)r.rc;
-    if (r.rc == CTMR_OK)
-      for (uint32_t w = 0; w < W; w++) r.ctl_out[1 + w] = r.send_counts[w];
-  }
-  if ((rc = control_gather(g, K1))) return rc;
-  if ((rc = control_status(g, K1))) return rc;
-  for (auto& r : g->local) {
-    r.recv_counts.assign(W, 0);
-    for (uint32_t s = 0; s < W; s++) r.recv_counts[s] = r.ctl_in[(size_t)s * K1 + 1 + r.rank];
-  }
+  if ((rc = counts_row(g, 1, [](GroupRank& r, uint32_t) { return counts_of(r, MAIN); }))) return rc;
   clk.lap(6);
   for (auto& r : g->local) {
-    const uint64_t nrecv = prefix(r.recv_counts, W);
     int e1 = gbuf(g, r, r.keys, 64);
-    if (!e1) e1 = gbuf(g, r, r.recv, (size_t)(nrecv ? nrecv : 1) * 64);
-    if (!e1) e1 = gbuf(g, r, r.flags_out, nrecv ? nrecv : 1);
-    if (!e1) e1 = gbuf(g, r, r.flags_mine, r.n_keys ? r.n_keys : 1);
-    if (e1 && r.rc == CTMR_OK) r.rc = e1;  // said in the row below: every rank leaves together
+    if (!e1) e1 = recv_buffers(g, r, MAIN, 64, r.n_keys, prefix(r.recv_counts, W));
+    note_failure(r, e1);  // said in the row below: every rank leaves together
   }
   if (W > 1 && (rc = status_row(g))) return rc;
-  if (W > 1 &&
-      (rc = all_to_all_v(g, 64, [](GroupRank& r) { return r.keys.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts; },
-                         [](GroupRank& r) { return r.recv.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts; })))
-    return rc;
+  if (W > 1 && (rc = keys_there(g, 64, MAIN))) return rc;
   clk.lap(2);
   g->last_keys_sent = g->last_keys_received = 0;
   par_ranks(g, [&](size_t k) -> int {  // phase 4: exact, read-only lookup at the peer
@@ -1074,10 +1068,7 @@ int group_map_bloom(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats
     g->last_keys_received += prefix(r.recv_counts, W);
   }
   clk.lap(3);
-  if (W > 1 &&
-      (rc = all_to_all_v(g, 1, [](GroupRank& r) { return r.flags_out.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.recv_counts; },
-                         [](GroupRank& r) { return r.flags_mine.p; }, [](GroupRank& r) -> const std::vector<uint64_t>& { return r.send_counts; })))
-    return rc;
+  if (W > 1 && (rc = flags_back(g, MAIN))) return rc;
   clk.lap(4);
   par_ranks(g, [&](size_t k) -> int {  // phase 5
     GroupRank& r = g->local[k];
@@ -1087,11 +1078,7 @@ int group_map_bloom(ctmr_group* g, const ctmr_shard* sh, ctmr_batch_stats* stats
     return e1 ? rank_fail(g, r, e1) : CTMR_OK;
   });
   clk.lap(5);
-  if (stats)
-    for (size_t k = 0; k < g->local.size(); k++) stats[k] = g->local[k].st;
-  rc = round_finish(g, stats);
-  clk.lap(6);
-  return rc;
+  return round_tail(g, stats, clk);
 }
 
 }  // namespace

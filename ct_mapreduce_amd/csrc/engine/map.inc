@@ -148,9 +148,10 @@ static void round_insert_args(ctmr_engine* e, const RoundCtx& rc, InsertArgs& ia
 }
 
 // round_begin = round_prepare (capacity, the batch's key cells, scratch — no kernel) + round_launch_range over the whole
-// batch.  The owner-computes exchange may launch the range in CHUNKS instead (ctmr_xchg_map_chunk_device): inside one round
-// that is free — pass-1 claims commute and pass 2 settles by order, whatever ran first (DESIGN.md §6) — and it lets chunk
-// c's key records travel while chunk c + 1 is being walked.
+// batch.  The owner-computes exchange calls the two halves itself (engine/exchange.inc: xchg_map_range), so that it may
+// launch the range in CHUNKS (ctmr_xchg_map_chunk_device): inside one round that is free — pass-1 claims commute and pass 2
+// settles by order, whatever ran first (DESIGN.md §6) — and it lets chunk c's key records travel while chunk c + 1 is
+// being walked.
 static int round_prepare(ctmr_engine* e, RoundCtx& rc) {
   HIPCHK(e, hipSetDevice(e->device));
   e->rd.valid = false;
