@@ -217,6 +217,22 @@ def walk_window_noreach(der: bytes, phase: int = 0, wbytes: int = 224, flavour: 
     return o, tuple(st)
 
 
+def walk_window_stale(der: bytes, phase: int = 0, wbytes: int = 224, slack: int = 4, strings: bool = True, ext: bool = True,
+                      fill: int = 0xA5):
+    """The walk through a simulated window with CONTENTS of its own: refills copy the payload's octets, a partial cooperative
+    refill (kernels/readers.h coop_refill_lines_to: up to the value's end + `slack`) leaves the rows behind its chunks as they
+    were, reads are clamped into the window and counted as WinReaderS does, ld2 is not; after a miss or a deferral the exact
+    reader decides.  Returns (HarnessOut, stats) with stats = (per-lane refills, misses, cooperative refills, defer_exact
+    calls, partial cooperative refills, unclamped reads outside the window)."""
+    product_walk(b"\x30\x00")
+    fn = _walk.harness_walk_window_stale
+    fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int, C.c_int, C.c_uint8, C.POINTER(HarnessOut),
+                   C.POINTER(C.c_uint32)]
+    o, st = HarnessOut(), (C.c_uint32 * 6)()
+    fn(der, len(der), phase, wbytes, slack, int(strings), int(ext), fill, C.byref(o), st)
+    return o, tuple(st)
+
+
 def ossl_extract(der: bytes):
     global _ossl
     if _ossl is None:

@@ -288,6 +288,87 @@ extern "C" int harness_walk_window_skip(const uint8_t* der, uint32_t len, uint32
   return ok;
 }
 
+// The same window with CONTENTS of its own (tests/test_ext_corpus_cpu.py): what WindowSim leaves out is that the device's
+// reads are served from the window whatever it holds.  Here every refill copies the payload's octets into a buffer, a
+// partial cooperative refill (readers.h coop_refill_lines_to: as far as the value's end + `slack`, in 16-octet chunks)
+// copies only its chunks and leaves the rows behind them as they were, ld4 / ld2c are clamped into the window and counted
+// (WinReaderS), ld2 reads the buffer wherever it is asked to, and the octets nobody loaded are poison (0xee).  A walk that
+// looks at an octet it did not ask for — without a miss — gets the wrong octet, as on the device.
+struct StaleSim : WindowSim {
+  uint8_t fill = 0;
+  uint32_t len = 0;
+  int32_t slack = 4;
+  mutable std::vector<uint8_t> win;
+  mutable uint32_t partial = 0, stray = 0;
+  uint8_t octet(int64_t pos) const { return pos < 0 ? fill : (uint64_t)pos < size ? p[pos] : 0; }  // (zeros behind the payload's pad)
+  void load(uint32_t nbytes) const {
+    for (uint32_t i = 0; i < nbytes && i < wbytes; i++) win[i] = octet(grel + (int64_t)i);
+  }
+  uint32_t from_win(uint32_t rel) const {
+    uint32_t v;
+    memcpy(&v, win.data() + rel, 4);
+    return v;
+  }
+  uint32_t ld4(uint32_t pos) const {
+    int64_t rel = (int64_t)pos - grel;
+    if (rel < 0 || rel > (int64_t)wbytes - 4) {
+      if (!misses) first_miss_pos = pos;
+      misses++;
+      rel = (int64_t)wbytes - 4;
+    }
+    return from_win((uint32_t)rel);
+  }
+  uint32_t ld2c(uint32_t pos) const {
+    int64_t rel = (int64_t)pos - grel;
+    if (rel < 0 || rel > (int64_t)wbytes - 2) {
+      if (!misses) first_miss_pos = pos;
+      misses++;
+      rel = (int64_t)wbytes - 2;
+    }
+    return from_win((uint32_t)rel) & 0xffffu;
+  }
+  uint32_t ld2(uint32_t pos) const {  // unclamped: the caller knows (holds) that the octets lie in the window
+    const int64_t rel = (int64_t)pos - grel;
+    if (rel < 0 || rel > (int64_t)wbytes - 2) {
+      stray++;
+      return 0xeeeeu;
+    }
+    return from_win((uint32_t)rel) & 0xffffu;
+  }
+  void touch(uint32_t pos, uint32_t need) const {
+    const uint32_t before = refills;
+    WindowSim::touch(pos, need);
+    if (refills != before) load(wbytes);
+  }
+  void touch_tail(uint32_t pos, uint32_t t) const {
+    WindowSim::touch_tail(pos, t);
+    load(wbytes);
+  }
+  void coop_refill(uint32_t pos, bool want) const {
+    WindowSim::coop_refill(pos, want);
+    if (want) load(wbytes);
+  }
+  void coop_refill_lines(uint32_t pos, bool want) const {
+    WindowSim::coop_refill_lines(pos, want);
+    if (want) load(wbytes);
+  }
+  void coop_refill_lines_to(uint32_t pos, bool want, uint32_t end) const {
+    WindowSim::coop_refill_lines(pos, want);
+    if (!want) return;
+    const int64_t need = (int64_t)end + slack - grel;
+    uint32_t n = need > 0 ? (uint32_t)((need + 15) >> 4) : 0u;
+    n = n > wbytes / 16u ? wbytes / 16u : n;
+    partial += n < wbytes / 16u;
+    load(16u * n);
+  }
+};
+// returns 1; out = the verdict and fields of the walk through that window — or, after a miss or a deferral, of the exact
+// reader, as in k_map_fused; stats = {per-lane refills, misses, cooperative refills, defer_exact calls, partial cooperative
+// refills, unclamped reads outside the window}; fill = the octets around the certificate; slack: see above (readers.h: 4;
+// negative: the refill stops short of the value's end — a defect the simulation must notice)
+extern "C" int harness_walk_window_stale(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, int32_t slack,
+                                         int strings, int ext, uint8_t fill, HarnessOut* out, uint32_t* stats);
+
 // An OUT-OF-REACH lane (kernels/readers.h: lrel == REL_NONE — the certificate lies below the base of its wave's buffer
 // descriptor, or REL_SPAN or more beyond it: an entry view in no order), for a wave of one lane.  What the device readers do
 // for such a lane: the cooperative refills do NOTHING (window and grel stay as they are), touch() — WinReader::refill, the
@@ -417,6 +498,32 @@ extern "C" int harness_walk_window_noreach(const uint8_t* der, uint32_t len, uin
   } catch (const DidNotTerminate&) {
     return 0;
   }
+  return 1;
+}
+
+extern "C" int harness_walk_window_stale(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, int32_t slack,
+                                         int strings, int ext, uint8_t fill, HarnessOut* out, uint32_t* stats) {
+  std::vector<uint8_t> buf((size_t)len + 64, fill);
+  memcpy(buf.data(), der, len);
+  StaleSim r;
+  r.p = buf.data();
+  r.base_phase = phase & 127u;
+  r.wbytes = wbytes;
+  r.grel = -(int64_t)(phase & 3u);
+  r.size = (uint32_t)buf.size();
+  r.fill = fill;
+  r.len = len;
+  r.slack = slack;
+  r.win.assign((size_t)wbytes + 8, 0xee);
+  r.load(wbytes);
+  ctmr::Walk w;
+  bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
+  stats[0] = r.refills; stats[1] = r.misses; stats[2] = r.coop; stats[3] = r.deferred; stats[4] = r.partial; stats[5] = r.stray;
+  if (r.misses || r.deferred) {
+    PaddedReader g{buf.data()};
+    ok = ctmr::walk_cert(g, len, w, nullptr, true, strings != 0, ext != 0);
+  }
+  put_walk(out, ok, w);
   return 1;
 }
 
