@@ -18,9 +18,17 @@ RECORD_DTYPE = np.dtype([("status", "u1"), ("flags", "u1"), ("serial_len", "<u2"
 assert RECORD_DTYPE.itemsize == 32
 
 
+NONE = 2**64 - 1   # no index: bad_response, bad_file, bad_crl, a good item's word in a `bad` array
+
+
 def _addr(a):
-    """an array's address; a raw address (an int: e.g. a pinned buffer) or None as it is"""
-    return a.ctypes.data if hasattr(a, "ctypes") else a
+    """an array's or a torch tensor's address; a raw address (an int: e.g. a pinned buffer) or None as it is"""
+    return a.ctypes.data if hasattr(a, "ctypes") else a.data_ptr() if hasattr(a, "data_ptr") else a
+
+
+def _bad_list(bad, n):
+    """the `bad` array of an _each call or a text wait → per item None, or the offset that puts it outside the grammar"""
+    return [None if int(b) == NONE else int(b) for b in bad[:n]]
 
 
 def _text_arg(bodies, join):
@@ -186,12 +194,78 @@ class Engine:
         if rc != 0:
             raise CtmrError(rc, self._lib.ctmr_last_error(self._h).decode(errors="replace"))
 
+    def _ck_at(self, rc, index, error):
+        """_ck, but CTMR_E_INVAL with an index that is not NONE — the input item outside the grammar — raises
+        error(the library's message): the typed error of the call."""
+        if rc == N.E_INVAL and index != NONE:
+            raise error(self._lib.ctmr_last_error(self._h).decode(errors="replace"))
+        self._ck(rc)
+
     @property
     def handle(self):
         return self._h
 
+    # ---- the sizing convention (include/ctmr.h): a call whose buffers are short fails with CTMR_E_RANGE and leaves the
+    # sizes in its `info`.  The wrappers of such calls go through one of these two.
+    def _sized_call(self, call, caps, need, check=None):
+        """A first guess, and a second call only when it was short: call(*caps) → (rc, the buffers it made of `caps`),
+        once with the caller's guess and once more with need() — the caps the call's `info` asks for after
+        CTMR_E_RANGE.  check(rc) raises for any other failure (default: _ck).  → (the buffers, the caps they were made of)"""
+        for _ in range(2):
+            rc, bufs = call(*caps)
+            if rc != N.E_RANGE:
+                break
+            caps = need()
+        (check or self._ck)(rc)
+        return bufs, caps
+
+    def _sizes_first(self, call, nothing, alloc, check=None):
+        """The sizes first, then the exact call: call(*nothing) → rc without buffers, alloc() → the arguments made of
+        what `info` says then, call(*those) to collect.  A first call that returns 0 had nothing to hand over: alloc()
+        makes the empty result and there is no second call.  → what alloc() gave"""
+        check = check or self._ck
+        rc = call(*nothing)
+        if rc != N.E_RANGE:
+            check(rc)
+        args = alloc()
+        if rc == N.E_RANGE:
+            check(call(*args))
+        return args
+
+    # ---- what the device wrappers share
+    @property
+    def _dev(self):
+        return "cuda:%d" % self.device
+
+    def _empty(self, n, device, dtype=np.uint8):
+        """n uninitialised uint8 or uint64: a numpy array, or (device) a torch tensor on this engine's device, u64 as int64"""
+        if not device:
+            return np.empty(n, dtype)
+        import torch
+        return torch.empty(n, dtype=torch.int64 if dtype is np.uint64 else torch.uint8, device=self._dev)
+
+    def _upload(self, data, floor=0):
+        """bytes → a torch uint8 tensor on this engine's device (of `floor` zero bytes when there are none)"""
+        import torch
+        return torch.from_numpy(np.frombuffer(data, np.uint8).copy() if data else np.zeros(floor, np.uint8)).to(self._dev)
+
+    @staticmethod
+    def _tensor(t, name):
+        if not hasattr(t, "data_ptr"):
+            raise TypeError(name + ": a torch tensor on this engine's device")
+
+    @staticmethod
+    def _text_bounds(d_text, bounds, name):
+        """The text of a device decoder and where its n items lie in it → (bounds u64[n + 1], the bytes they span)"""
+        Engine._tensor(d_text, "d_text")
+        b = np.ascontiguousarray(bounds, dtype=np.uint64)
+        n = len(b) - 1
+        if n < 0 or (n and ((b[1:] < b[:-1]).any() or int(b[n]) > d_text.numel())):
+            raise ValueError(name + " do not ascend or reach beyond the text")
+        return b, int(b[n] - b[0]) if n else 0
+
     def set_stream(self, hip_stream):
-        self._ck(self._lib.ctmr_set_stream(self._h, C.c_void_p(hip_stream)))
+        self._ck(self._lib.ctmr_set_stream(self._h, hip_stream))
 
     def synchronize(self):
         self._ck(self._lib.ctmr_synchronize(self._h))
@@ -209,7 +283,7 @@ class Engine:
 
     def free_pinned(self):
         for p in getattr(self, "_pinned", []):
-            self._lib.ctmr_free_pinned(self._h, C.c_void_p(p))
+            self._lib.ctmr_free_pinned(self._h, p)
         self._pinned = []
 
     # ---- issuers / filter
@@ -305,16 +379,15 @@ class Engine:
             raise CtmrError(N.E_NOTFOUND, f"not a ticket of {name}, or already collected")
         first = np.zeros(B + 1, np.uint64)
         bad = np.zeros(max(B, 1), np.uint64)
-        rc = call(0, None, None, None, first, bad)
-        n = items() if rc == N.E_RANGE else 0
-        records = np.zeros(n, dtype=RECORD_DTYPE)
-        new_idx = np.zeros(max(n, 1), dtype=np.uint64)
-        ts = np.zeros(max(n, 1), dtype=np.uint64)
-        if rc == N.E_RANGE:
-            rc = call(n, records, new_idx, ts, first, bad)
-        del self._text_tickets[ticket]   # collected, or failed with its super-batch: either way it is gone
-        self._ck(rc)
-        return records, new_idx, ts[:n], first, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:B]]
+
+        def alloc():
+            n = items()
+            return n, np.zeros(n, dtype=RECORD_DTYPE), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        try:
+            n, records, new_idx, ts = self._sizes_first(lambda *bufs: call(*bufs, first, bad), (0, None, None, None), alloc)
+        finally:
+            del self._text_tickets[ticket]   # collected, or failed with its super-batch: either way it is gone
+        return records, new_idx, ts[:n], first, _bad_list(bad, B)
 
     def submit_entries_json(self, bodies) -> int:
         """get-entries HTTP bodies as they lie (a list of bytes — a downloader submits one; or (text, resp_bounds) with
@@ -373,16 +446,15 @@ class Engine:
         """The ticket's slice of its super-batch's write-back (the size query is done here).  Call it BEFORE the ticket's
         wait, any number of times; afterwards it raises CtmrError(E_NOTFOUND)."""
         info = N.WritebackInfo()
-        rc = self._lib.ctmr_ticket_writeback(self._h, ticket, None, 0, None, None, 0, None, 0, C.byref(info))
-        if rc not in (0, N.E_RANGE):
-            self._ck(rc)
-        pem = np.zeros(max(int(info.pem_bytes), 1), np.uint8)
-        offs = np.zeros(int(info.n_new) + 1, np.uint64)
-        items = (N.MetaItem * max(int(info.n_items), 1))()
-        buf = np.zeros(max(int(info.item_bytes), 1), np.uint8)
-        if rc == N.E_RANGE:
-            self._ck(self._lib.ctmr_ticket_writeback(self._h, ticket, pem.ctypes.data, pem.size, offs.ctypes.data, items, int(info.n_items),
-                                                     buf.ctypes.data, buf.size, C.byref(info)))
+
+        def alloc():
+            pem, buf = np.zeros(max(int(info.pem_bytes), 1), np.uint8), np.zeros(max(int(info.item_bytes), 1), np.uint8)
+            return (pem, pem.size, np.zeros(int(info.n_new) + 1, np.uint64), (N.MetaItem * max(int(info.n_items), 1))(), int(info.n_items),
+                    buf, buf.size)
+        pem, _, offs, items, _, buf, _ = self._sizes_first(
+            lambda pem, pem_cap, offs, items, n_items, buf, buf_cap: self._lib.ctmr_ticket_writeback(
+                self._h, ticket, _addr(pem), pem_cap, _addr(offs), items, n_items, _addr(buf), buf_cap, C.byref(info)),
+            (None, 0, None, None, 0, None, 0), alloc)
         raw, at, out = buf.tobytes(), 0, []
         for it in items[:int(info.n_items)]:
             out.append((it.kind, int(it.entry), it.issuer_idx, it.exp_hour, raw[at:at + it.len]))
@@ -394,11 +466,8 @@ class Engine:
                          d_new_idx=0) -> N.BatchStats:
         """All pointers are device addresses (ints), e.g. torch tensors' data_ptr()."""
         st = N.BatchStats()
-        self._ck(self._lib.ctmr_map_batch_device(
-            self._h, C.c_void_p(d_payload), C.c_void_p(d_offsets), C.c_void_p(d_issuer_idx),
-            C.c_void_p(d_entry_type) if d_entry_type else None, n,
-            C.c_void_p(d_records) if d_records else None,
-            C.c_void_p(d_new_idx) if d_new_idx else None, C.byref(st)))
+        self._ck(self._lib.ctmr_map_batch_device(self._h, d_payload, d_offsets, d_issuer_idx, d_entry_type, n, d_records, d_new_idx,
+                                                 C.byref(st)))
         return st
 
     # ---- raw get-entries input (N2): ct.LogEntryFromLeaf + the choice of certificate and Chain[0] on the GPU
@@ -421,113 +490,76 @@ class Engine:
 
     def decode_entries_device(self, d_blob, d_bounds, n, view: N.EntryView) -> N.DecodeStats:
         ds = N.DecodeStats()
-        self._ck(self._lib.ctmr_decode_entries_device(self._h, C.c_void_p(d_blob), C.c_void_p(d_bounds), n,
-                                                      C.byref(view), C.byref(ds)))
+        self._ck(self._lib.ctmr_decode_entries_device(self._h, d_blob, d_bounds, n, C.byref(view), C.byref(ds)))
         return ds
 
     def map_view_device(self, d_blob, blob_bytes, view: N.EntryView, n, d_records=0, d_new_idx=0) -> N.BatchStats:
         st = N.BatchStats()
-        self._ck(self._lib.ctmr_map_view_device(self._h, C.c_void_p(d_blob), blob_bytes, C.byref(view), n,
-                                                C.c_void_p(d_records) if d_records else None,
-                                                C.c_void_p(d_new_idx) if d_new_idx else None, C.byref(st)))
+        self._ck(self._lib.ctmr_map_view_device(self._h, d_blob, blob_bytes, C.byref(view), n, d_records, d_new_idx, C.byref(st)))
         return st
 
     def map_entries_device(self, d_blob, d_bounds, n, d_records=0, d_new_idx=0, d_timestamp=0):
         st, ds = N.BatchStats(), N.DecodeStats()
-        self._ck(self._lib.ctmr_map_entries_device(
-            self._h, C.c_void_p(d_blob), C.c_void_p(d_bounds), n, C.c_void_p(d_records) if d_records else None,
-            C.c_void_p(d_new_idx) if d_new_idx else None, C.c_void_p(d_timestamp) if d_timestamp else None,
-            C.byref(ds), C.byref(st)))
+        self._ck(self._lib.ctmr_map_entries_device(self._h, d_blob, d_bounds, n, d_records, d_new_idx, d_timestamp, C.byref(ds),
+                                                   C.byref(st)))
         return st, ds
 
     # ---- get-entries HTTP bodies as they lie (include/ctmr.h ctmr_entries_json*; CPU twin: get_entries.parse)
     def _ej_ck(self, rc, info):
-        if rc == N.E_INVAL and info.bad_response != 2**64 - 1:
-            raise EntriesJsonError(rc, self._lib.ctmr_last_error(self._h).decode(errors="replace"), info.bad_response,
-                                   info.bad_offset)
-        self._ck(rc)
+        self._ck_at(rc, info.bad_response, lambda msg: EntriesJsonError(rc, msg, info.bad_response, info.bad_offset))
+
+    def _entries_json(self, text, text_bytes, rb, device, each):
+        """The one call of the four entries_json forms, its buffers sized by the bounds 3/4 text_bytes and
+        text_bytes / 34.  text: the address rb counts from.  → (blob, bounds, resp_first, bad or None, info)"""
+        R = len(rb) - 1
+        blob_cap, entries_cap = text_bytes * 3 // 4 + N.PAYLOAD_PAD, text_bytes // 34
+        blob, bounds = self._empty(blob_cap, device), self._empty(2 * entries_cap + 1, device, np.uint64)
+        first = np.empty(R + 1, np.uint64)
+        bad = np.empty(max(R, 1), np.uint64) if each else None
+        info = N.EntriesJsonInfo()
+        fn = getattr(self._lib, "ctmr_entries_json" + ("_each" if each else "") + ("_device" if device else ""))
+        rc = fn(self._h, text, rb.ctypes.data, R, _addr(blob), blob_cap, _addr(bounds), entries_cap, first.ctypes.data,
+                *((bad.ctypes.data,) if each else ()), C.byref(info))
+        if each:   # (every body is judged alone: no typed error)
+            self._ck(rc)
+        else:
+            self._ej_ck(rc, info)
+        return blob[:info.blob_bytes + N.PAYLOAD_PAD], bounds[:2 * info.entries + 1], first, _bad_list(bad, R) if each else None, info
+
+    def _entries_json_host(self, bodies, each) -> RawEntries:
+        from . import get_entries
+        text, rb = get_entries.join(bodies)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        return RawEntries(*self._entries_json(buf.ctypes.data, len(text), rb, False, each)[:4])
+
+    def _entries_json_device(self, d_text, resp_bounds, each):
+        rb, text_bytes = self._text_bounds(d_text, resp_bounds, "resp_bounds")
+        return self._entries_json(d_text.data_ptr() if text_bytes else None, text_bytes, rb, True, each)
 
     def entries_json(self, bodies) -> RawEntries:
         """The raw entries of get-entries bodies (a list of bytes, in log order): JSON and base64 decoded on the GPU,
         text and result in host memory; the blob keeps the PAYLOAD_PAD zero bytes behind bounds[2n], as
         synth.host_entries' does.  A body outside the grammar raises EntriesJsonError with its number."""
-        from . import get_entries
-        text, rb = get_entries.join(bodies)
-        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
-        info = N.EntriesJsonInfo()
-        blob_cap, entries_cap = len(text) * 3 // 4 + N.PAYLOAD_PAD, len(text) // 34
-        blob = np.empty(blob_cap, np.uint8)
-        bounds = np.empty(2 * entries_cap + 1, np.uint64)
-        first = np.empty(len(bodies) + 1, np.uint64)
-        self._ej_ck(self._lib.ctmr_entries_json(self._h, buf.ctypes.data, rb.ctypes.data, len(bodies), blob.ctypes.data, blob_cap,
-                                                bounds.ctypes.data, entries_cap, first.ctypes.data, C.byref(info)), info)
-        return RawEntries(blob[:info.blob_bytes + N.PAYLOAD_PAD], bounds[:2 * info.entries + 1], first)
+        return self._entries_json_host(bodies, False)
 
     def entries_json_device(self, d_text, resp_bounds):
         """entries_json of a torch uint8 tensor on this engine's device (any alignment; body r at
         d_text[resp_bounds[r]:resp_bounds[r + 1]]) → (d_blob, d_bounds, resp_first, info): torch tensors on the device —
         blob_bytes + PAYLOAD_PAD bytes and u64[2n + 1] as int64, views of buffers sized in one call by the bounds
         3/4 text_bytes and text_bytes / 34 — and the host array u64[R + 1]."""
-        import torch
-        if not hasattr(d_text, "data_ptr"):
-            raise TypeError("d_text: a torch tensor on this engine's device")
-        rb = np.ascontiguousarray(resp_bounds, dtype=np.uint64)
-        R = len(rb) - 1
-        if R < 0 or (R and ((rb[1:] < rb[:-1]).any() or int(rb[R]) > d_text.numel())):
-            raise ValueError("resp_bounds do not ascend or reach beyond the text")
-        text_bytes = int(rb[R] - rb[0]) if R else 0
-        blob_cap, entries_cap = text_bytes * 3 // 4 + N.PAYLOAD_PAD, text_bytes // 34
-        dev = "cuda:%d" % self.device
-        d_blob = torch.empty(blob_cap, dtype=torch.uint8, device=dev)
-        d_bounds = torch.empty(2 * entries_cap + 1, dtype=torch.int64, device=dev)
-        first = np.empty(R + 1, np.uint64)
-        info = N.EntriesJsonInfo()
-        self._ej_ck(self._lib.ctmr_entries_json_device(self._h, C.c_void_p(d_text.data_ptr()) if text_bytes else None, rb.ctypes.data, R,
-                                                       C.c_void_p(d_blob.data_ptr()), blob_cap, C.c_void_p(d_bounds.data_ptr()),
-                                                       entries_cap, first.ctypes.data, C.byref(info)), info)
-        return d_blob[:info.blob_bytes + N.PAYLOAD_PAD], d_bounds[:2 * info.entries + 1], first, info
+        d_blob, d_bounds, first, _, info = self._entries_json_device(d_text, resp_bounds, False)
+        return d_blob, d_bounds, first, info
 
     def entries_json_each(self, bodies) -> RawEntries:
         """entries_json with every body judged on its own (ctmr_entries_json_each; CPU twin:
         get_entries.parse_each): nothing is raised for a body outside the grammar — it has no entries, and .bad[r] holds
         its offset (None for the others)."""
-        from . import get_entries
-        text, rb = get_entries.join(bodies)
-        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
-        info = N.EntriesJsonInfo()
-        blob_cap, entries_cap = len(text) * 3 // 4 + N.PAYLOAD_PAD, len(text) // 34
-        blob = np.empty(blob_cap, np.uint8)
-        bounds = np.empty(2 * entries_cap + 1, np.uint64)
-        first = np.empty(len(bodies) + 1, np.uint64)
-        bad = np.empty(max(len(bodies), 1), np.uint64)
-        self._ck(self._lib.ctmr_entries_json_each(self._h, buf.ctypes.data, rb.ctypes.data, len(bodies), blob.ctypes.data, blob_cap,
-                                                  bounds.ctypes.data, entries_cap, first.ctypes.data, bad.ctypes.data, C.byref(info)))
-        return RawEntries(blob[:info.blob_bytes + N.PAYLOAD_PAD], bounds[:2 * info.entries + 1], first,
-                          [None if int(b) == 2**64 - 1 else int(b) for b in bad[:len(bodies)]])
+        return self._entries_json_host(bodies, True)
 
     def entries_json_each_device(self, d_text, resp_bounds):
         """entries_json_device with every body judged on its own → (d_blob, d_bounds, resp_first, bad, info); bad as in
         entries_json_each, offsets counted as resp_bounds counts."""
-        import torch
-        if not hasattr(d_text, "data_ptr"):
-            raise TypeError("d_text: a torch tensor on this engine's device")
-        rb = np.ascontiguousarray(resp_bounds, dtype=np.uint64)
-        R = len(rb) - 1
-        if R < 0 or (R and ((rb[1:] < rb[:-1]).any() or int(rb[R]) > d_text.numel())):
-            raise ValueError("resp_bounds do not ascend or reach beyond the text")
-        text_bytes = int(rb[R] - rb[0]) if R else 0
-        blob_cap, entries_cap = text_bytes * 3 // 4 + N.PAYLOAD_PAD, text_bytes // 34
-        dev = "cuda:%d" % self.device
-        d_blob = torch.empty(blob_cap, dtype=torch.uint8, device=dev)
-        d_bounds = torch.empty(2 * entries_cap + 1, dtype=torch.int64, device=dev)
-        first = np.empty(R + 1, np.uint64)
-        bad = np.empty(max(R, 1), np.uint64)
-        info = N.EntriesJsonInfo()
-        self._ck(self._lib.ctmr_entries_json_each_device(self._h, C.c_void_p(d_text.data_ptr()) if text_bytes else None, rb.ctypes.data, R,
-                                                         C.c_void_p(d_blob.data_ptr()), blob_cap, C.c_void_p(d_bounds.data_ptr()),
-                                                         entries_cap, first.ctypes.data, bad.ctypes.data, C.byref(info)))
-        return (d_blob[:info.blob_bytes + N.PAYLOAD_PAD], d_bounds[:2 * info.entries + 1], first,
-                [None if int(b) == 2**64 - 1 else int(b) for b in bad[:R]], info)
+        return self._entries_json_device(d_text, resp_bounds, True)
 
     def map_entries_json(self, bodies) -> EntriesResult:
         """map_entries over get-entries bodies (a list of bytes): text → raw entries on the device → map_entries_device,
@@ -535,8 +567,8 @@ class Engine:
         import torch
         from . import get_entries
         text, rb = get_entries.join(bodies)
-        dev = "cuda:%d" % self.device
-        d_text = torch.from_numpy(np.frombuffer(text, np.uint8).copy() if text else np.zeros(1, np.uint8)).to(dev)
+        dev = self._dev
+        d_text = self._upload(text, 1)
         d_blob, d_bounds, _, info = self.entries_json_device(d_text, rb)
         n = int(info.entries)
         if not n:   # nothing to map
@@ -552,92 +584,64 @@ class Engine:
                              d_ts.cpu().numpy().view(np.uint64)[:n].copy(), st, ds)
 
     # ---- PEM certificate files as they lie (include/ctmr.h ctmr_pem_decode*; CPU twin: pem_text.parse)
-    def _pd_call(self, fn, alloc):
-        """The two calls of the sizing convention: one without buffers for the sizes (CTMR_E_RANGE fills `info`), one
-        into buffers of exactly that size.  A file outside the grammar raises PemDecodeError with its number."""
+    def _pem_decode(self, text, fb, device, each):
+        """The two calls of the four pem_decode forms (sizes first: CTMR_E_RANGE fills `info`, then into buffers of
+        exactly that size).  text: the address fb counts from.  A file outside the grammar raises PemDecodeError with
+        its number.  → (payload, offsets, file_first, info[, bad])"""
+        F = len(fb) - 1
+        bad = np.empty(max(F, 1), np.uint64) if each else None
         info = N.PemDecodeInfo()
-        rc = fn(None, 0, None, 0, None, info)
-        bufs = None
-        if rc == N.E_RANGE:
-            bufs = alloc(info.payload_bytes + N.PAYLOAD_PAD, info.certificates + 1, info.files + 1)
-            rc = fn(bufs[0], info.payload_bytes + N.PAYLOAD_PAD, bufs[1], info.certificates, bufs[2], info)
-        if rc == N.E_INVAL and info.bad_file != 2**64 - 1:
-            raise PemDecodeError(rc, self._lib.ctmr_last_error(self._h).decode(errors="replace"), info.bad_file, info.bad_offset)
-        self._ck(rc)
-        return bufs, info
+        fn = getattr(self._lib, "ctmr_pem_decode" + ("_each" if each else "") + ("_device" if device else ""))
+
+        def call(payload, payload_cap, offsets, n, first):
+            return fn(self._h, text, fb.ctypes.data, F, _addr(payload), payload_cap, _addr(offsets), n, _addr(first),
+                      *((bad.ctypes.data,) if each else ()), C.byref(info))
+
+        def alloc():
+            cap = info.payload_bytes + N.PAYLOAD_PAD
+            return (self._empty(cap, device), cap, self._empty(info.certificates + 1, device, np.uint64), info.certificates,
+                    np.empty(info.files + 1, np.uint64))
+
+        def check(rc):
+            self._ck_at(rc, info.bad_file, lambda msg: PemDecodeError(rc, msg, info.bad_file, info.bad_offset))
+        payload, _, offsets, _, first = self._sizes_first(call, (None, 0, None, 0, None), alloc, check)
+        return (payload, offsets, first, info) + ((_bad_list(bad, F),) if each else ())
+
+    def _pem_decode_host(self, files, each):
+        from . import pem_text
+        text, fb = pem_text.join(files)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        return self._pem_decode(buf.ctypes.data, fb, False, each)
+
+    def _pem_decode_device(self, d_text, file_bounds, each):
+        import torch
+        fb, text_bytes = self._text_bounds(d_text, file_bounds, "file_bounds")
+        torch.cuda.synchronize(self.device)     # the engine runs on a stream of its own: what was queued to write d_text is done first
+        return self._pem_decode(d_text.data_ptr() if text_bytes else None, fb, True, each)
 
     def pem_decode(self, files):
         """The certificates of PEM files (a list of bytes: concatenated CERTIFICATE blocks each), armor and base64
         decoded on the GPU, text and result in host memory → (payload: numpy uint8 of payload_bytes + PAYLOAD_PAD, the
         padding zeroed; offsets u64[n + 1]; file_first u64[F + 1]; info).  With issuer indices and entry types this is a
         Batch."""
-        from . import pem_text
-        text, fb = pem_text.join(files)
-        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
-        (payload, offsets, first), info = self._pd_call(
-            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode(self._h, buf.ctypes.data, fb.ctypes.data, len(files), _addr(p), pc,
-                                                                     _addr(o), oc, _addr(ff), C.byref(info)),
-            lambda pb, no, nf: (np.empty(pb, np.uint8), np.empty(no, np.uint64), np.empty(nf, np.uint64)))
-        return payload, offsets, first, info
+        return self._pem_decode_host(files, False)
 
     def pem_decode_device(self, d_text, file_bounds):
         """pem_decode of a torch uint8 tensor on this engine's device (any alignment; file f at
         d_text[file_bounds[f]:file_bounds[f + 1]]) → (d_payload, d_offsets, file_first, info): torch tensors on the
         device — payload_bytes + PAYLOAD_PAD bytes and u64[n + 1] as int64 — and the host array u64[F + 1]."""
-        import torch
-        if not hasattr(d_text, "data_ptr"):
-            raise TypeError("d_text: a torch tensor on this engine's device")
-        fb = np.ascontiguousarray(file_bounds, dtype=np.uint64)
-        F = len(fb) - 1
-        if F < 0 or (F and ((fb[1:] < fb[:-1]).any() or int(fb[F]) > d_text.numel())):
-            raise ValueError("file_bounds do not ascend or reach beyond the text")
-        dev = "cuda:%d" % self.device
-        torch.cuda.synchronize(self.device)     # the engine runs on a stream of its own: what was queued to write d_text is done first
-        text = C.c_void_p(d_text.data_ptr()) if F and fb[F] > fb[0] else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        (d_payload, d_offsets, first), info = self._pd_call(
-            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_device(self._h, text, fb.ctypes.data, F, ptr(p), pc, ptr(o), oc,
-                                                                            ff.ctypes.data if ff is not None else None, C.byref(info)),
-            lambda pb, no, nf: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(no, dtype=torch.int64, device=dev),
-                                np.empty(nf, np.uint64)))
-        return d_payload, d_offsets, first, info
+        return self._pem_decode_device(d_text, file_bounds, False)
 
     def pem_decode_each(self, files):
         """pem_decode with every file judged on its own (ctmr_pem_decode_each; CPU twin:
         pem_text.parse_each) → (payload, offsets, file_first, info, bad): nothing is raised for a file outside the
         grammar — it has no certificates, and bad[f] holds its offset (None for the others)."""
-        from . import pem_text
-        text, fb = pem_text.join(files)
-        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
-        bad = np.empty(max(len(files), 1), np.uint64)
-        (payload, offsets, first), info = self._pd_call(
-            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_each(self._h, buf.ctypes.data, fb.ctypes.data, len(files), _addr(p), pc,
-                                                                          _addr(o), oc, _addr(ff), bad.ctypes.data, C.byref(info)),
-            lambda pb, no, nf: (np.empty(pb, np.uint8), np.empty(no, np.uint64), np.empty(nf, np.uint64)))
-        return payload, offsets, first, info, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:len(files)]]
+        return self._pem_decode_host(files, True)
 
     def pem_decode_each_device(self, d_text, file_bounds):
         """pem_decode_device with every file judged on its own → (d_payload, d_offsets, file_first, info, bad); bad as in
         pem_decode_each, offsets counted as file_bounds counts."""
-        import torch
-        if not hasattr(d_text, "data_ptr"):
-            raise TypeError("d_text: a torch tensor on this engine's device")
-        fb = np.ascontiguousarray(file_bounds, dtype=np.uint64)
-        F = len(fb) - 1
-        if F < 0 or (F and ((fb[1:] < fb[:-1]).any() or int(fb[F]) > d_text.numel())):
-            raise ValueError("file_bounds do not ascend or reach beyond the text")
-        dev = "cuda:%d" % self.device
-        torch.cuda.synchronize(self.device)     # the engine runs on a stream of its own: what was queued to write d_text is done first
-        text = C.c_void_p(d_text.data_ptr()) if F and fb[F] > fb[0] else None
-        bad = np.empty(max(F, 1), np.uint64)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        (d_payload, d_offsets, first), info = self._pd_call(
-            lambda p, pc, o, oc, ff, info: self._lib.ctmr_pem_decode_each_device(self._h, text, fb.ctypes.data, F, ptr(p), pc, ptr(o), oc,
-                                                                                 ff.ctypes.data if ff is not None else None,
-                                                                                 bad.ctypes.data, C.byref(info)),
-            lambda pb, no, nf: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(no, dtype=torch.int64, device=dev),
-                                np.empty(nf, np.uint64)))
-        return d_payload, d_offsets, first, info, [None if int(b) == 2**64 - 1 else int(b) for b in bad[:F]]
+        return self._pem_decode_device(d_text, file_bounds, True)
 
     def map_pem(self, files, issuer_idx, want_records=True, want_new=True) -> BatchResult:
         """map_batch over PEM files (a list of bytes): text → packed batch on the device → map_batch_device, no DER in
@@ -650,8 +654,8 @@ class Engine:
         iss = np.ascontiguousarray(issuer_idx, dtype=np.uint32)
         if iss.shape != (len(files),):
             raise ValueError("issuer_idx: one per file")
-        dev = "cuda:%d" % self.device
-        d_text = torch.from_numpy(np.frombuffer(text, np.uint8).copy() if text else np.zeros(1, np.uint8)).to(dev)
+        dev = self._dev
+        d_text = self._upload(text, 1)
         d_payload, d_offsets, first, info = self.pem_decode_device(d_text, fb)
         n = int(info.certificates)
         if not n:   # nothing to map
@@ -670,8 +674,7 @@ class Engine:
 
     def synth_entries_device(self, cfg: N.SynthConfig, first, n, d_bounds, d_blob, blob_cap) -> int:
         out = C.c_uint64()
-        self._ck(self._lib.ctmr_synth_entries_device(self._h, C.byref(cfg), first, n, C.c_void_p(d_bounds),
-                                                     C.c_void_p(d_blob) if d_blob else None, blob_cap, C.byref(out)))
+        self._ck(self._lib.ctmr_synth_entries_device(self._h, C.byref(cfg), first, n, d_bounds, d_blob, blob_cap, C.byref(out)))
         return out.value
 
     # ---- IssuerMetadata on device (N3): first sightings among the new certificates of the last host batch
@@ -696,9 +699,8 @@ class Engine:
 
     def meta_new_device(self, d_payload, d_offsets, d_ends, d_records, d_new_idx, n_new, d_items, items_cap) -> int:
         n = C.c_uint64(0)
-        self._ck(self._lib.ctmr_meta_new_device(
-            self._h, C.c_void_p(d_payload), C.c_void_p(d_offsets), C.c_void_p(d_ends) if d_ends else None,
-            C.c_void_p(d_records), C.c_void_p(d_new_idx), n_new, C.c_void_p(d_items), items_cap, C.byref(n)))
+        self._ck(self._lib.ctmr_meta_new_device(self._h, d_payload, d_offsets, d_ends, d_records, d_new_idx, n_new, d_items, items_cap,
+                                                C.byref(n)))
         return n.value
 
     def meta_reset(self):
@@ -708,9 +710,7 @@ class Engine:
     def fingerprint_device(self, d_payload, d_offsets, d_ends, n, d_digests) -> float:
         """n × 32-byte SHA-256 digests of the certificates into d_digests; returns the kernel time in ms."""
         ms = C.c_float(0)
-        self._ck(self._lib.ctmr_fingerprint_device(self._h, C.c_void_p(d_payload), C.c_void_p(d_offsets),
-                                                   C.c_void_p(d_ends) if d_ends else None, n, C.c_void_p(d_digests),
-                                                   C.byref(ms)))
+        self._ck(self._lib.ctmr_fingerprint_device(self._h, d_payload, d_offsets, d_ends, n, d_digests, C.byref(ms)))
         return ms.value
 
     # ---- PEM write-back (N1): pem.EncodeToMemory of the newly unknown certificates, on the GPU
@@ -731,16 +731,14 @@ class Engine:
 
     def pem_encode_device(self, d_payload, d_offsets, d_idx, n_idx, d_pem, pem_cap, d_pem_offsets) -> int:
         total = C.c_uint64(0)
-        self._ck(self._lib.ctmr_pem_encode_device(
-            self._h, C.c_void_p(d_payload), C.c_void_p(d_offsets), C.c_void_p(d_idx), n_idx,
-            C.c_void_p(d_pem) if d_pem else None, pem_cap, C.c_void_p(d_pem_offsets), C.byref(total)))
+        self._ck(self._lib.ctmr_pem_encode_device(self._h, d_payload, d_offsets, d_idx, n_idx, d_pem, pem_cap, d_pem_offsets,
+                                                  C.byref(total)))
         return int(total.value)
 
     def pem_encode_view_device(self, d_blob, view: N.EntryView, d_idx, n_idx, d_pem, pem_cap, d_pem_offsets) -> int:
         total = C.c_uint64(0)
-        self._ck(self._lib.ctmr_pem_encode_view_device(
-            self._h, C.c_void_p(d_blob), C.byref(view), C.c_void_p(d_idx), n_idx,
-            C.c_void_p(d_pem) if d_pem else None, pem_cap, C.c_void_p(d_pem_offsets), C.byref(total)))
+        self._ck(self._lib.ctmr_pem_encode_view_device(self._h, d_blob, C.byref(view), d_idx, n_idx, d_pem, pem_cap, d_pem_offsets,
+                                                       C.byref(total)))
         return int(total.value)
 
     # ---- cross-GPU key exchange, owner-computes (ctmr.h: ctmr_xchg_*): one round on this rank, device pointers as ints.
@@ -759,20 +757,19 @@ class Engine:
     def xchg_keys(self, world: int, d_keys32_out=0, d_keys64_out=0):
         """Partitioned key records into the caller's buffers → 64-byte records per owner."""
         counts64 = (C.c_uint64 * world)()
-        self._ck(self._lib.ctmr_xchg_keys_device(self._h, C.c_void_p(d_keys32_out) if d_keys32_out else None,
-                                                 C.c_void_p(d_keys64_out) if d_keys64_out else None, counts64))
+        self._ck(self._lib.ctmr_xchg_keys_device(self._h, d_keys32_out, d_keys64_out, counts64))
         return [int(c) for c in counts64]
 
     def xchg_insert(self, d_keys32=0, n32=0, d_flags32=0, d_keys64=0, n64=0, d_flags64=0):
         self._ck(self._lib.ctmr_xchg_insert_device(
-            self._h, C.c_void_p(d_keys32) if n32 else None, n32, C.c_void_p(d_keys64) if n64 else None, n64,
-            C.c_void_p(d_flags32) if n32 else None, C.c_void_p(d_flags64) if n64 else None))
+            self._h, d_keys32 if n32 else None, n32, d_keys64 if n64 else None, n64,
+            d_flags32 if n32 else None, d_flags64 if n64 else None))
 
     def xchg_apply(self, d_sent32=0, d_flags32=0, n32=0, d_sent64=0, d_flags64=0, n64=0) -> N.BatchStats:
         st = N.BatchStats()
         self._ck(self._lib.ctmr_xchg_apply_device(
-            self._h, C.c_void_p(d_sent32) if n32 else None, C.c_void_p(d_flags32) if n32 else None, n32,
-            C.c_void_p(d_sent64) if n64 else None, C.c_void_p(d_flags64) if n64 else None, n64, C.byref(st)))
+            self._h, d_sent32 if n32 else None, d_flags32 if n32 else None, n32,
+            d_sent64 if n64 else None, d_flags64 if n64 else None, n64, C.byref(st)))
         return st
 
     def set_issuer_autoregister(self, on: bool):
@@ -827,7 +824,7 @@ class Engine:
     # ---- cross-GPU global dedup, Bloom pre-filter variant (ctmr.h: ctmr_bloom_*), device pointers as ints
     def bloom_config(self, bits: int, d_words=0):
         """d_words: caller-owned device buffer of bits/8 bytes (0 = the library allocates the filter)."""
-        self._ck(self._lib.ctmr_bloom_config(self._h, bits, C.c_void_p(d_words) if d_words else None))
+        self._ck(self._lib.ctmr_bloom_config(self._h, bits, d_words))
 
     def bloom_device(self):
         """(device pointer, n_words) of this rank's cumulative filter (u64 words)."""
@@ -836,34 +833,26 @@ class Engine:
         return int(p.value), int(nw.value)
 
     def bloom_add(self, d_payload, d_offsets, d_ends, n, d_records=0):
-        self._ck(self._lib.ctmr_bloom_add_device(
-            self._h, C.c_void_p(d_payload) if n else None, C.c_void_p(d_offsets) if n else None,
-            C.c_void_p(d_ends) if d_ends else None, n, C.c_void_p(d_records) if d_records else None))
+        self._ck(self._lib.ctmr_bloom_add_device(self._h, d_payload if n else None, d_offsets if n else None, d_ends, n, d_records))
 
     def bloom_probe(self, d_payload, d_offsets, d_ends, n, d_records, d_filters, world, rank, order_base,
                     d_keys_out, keys_cap):
         """→ (counts per peer, fits): fits False = keys_cap too small, nothing written, call again."""
         counts = (C.c_uint64 * world)()
-        rc = self._lib.ctmr_bloom_probe_device(
-            self._h, C.c_void_p(d_payload) if n else None, C.c_void_p(d_offsets) if n else None,
-            C.c_void_p(d_ends) if d_ends else None, n, C.c_void_p(d_records) if d_records else None,
-            C.c_void_p(d_filters), world, rank, order_base, C.c_void_p(d_keys_out) if keys_cap else None,
-            keys_cap, counts)
+        rc = self._lib.ctmr_bloom_probe_device(self._h, d_payload if n else None, d_offsets if n else None, d_ends, n, d_records, d_filters,
+                                               world, rank, order_base, d_keys_out if keys_cap else None, keys_cap, counts)
         if rc == N.E_RANGE:
             return [int(c) for c in counts], False
         self._ck(rc)
         return [int(c) for c in counts], True
 
     def bloom_lookup(self, d_keys, n_keys, order_base, d_flags):
-        self._ck(self._lib.ctmr_bloom_lookup_device(self._h, C.c_void_p(d_keys) if n_keys else None, n_keys,
-                                                    order_base, C.c_void_p(d_flags) if n_keys else None))
+        self._ck(self._lib.ctmr_bloom_lookup_device(self._h, d_keys if n_keys else None, n_keys, order_base, d_flags if n_keys else None))
 
     def bloom_apply(self, d_records, n, d_keys_sent, d_flags, n_keys, d_new_idx=0) -> N.BatchStats:
         st = N.BatchStats()
-        self._ck(self._lib.ctmr_bloom_apply_device(
-            self._h, C.c_void_p(d_records) if d_records else None, n,
-            C.c_void_p(d_keys_sent) if n_keys else None, C.c_void_p(d_flags) if n_keys else None, n_keys,
-            C.c_void_p(d_new_idx) if d_new_idx else None, C.byref(st)))
+        self._ck(self._lib.ctmr_bloom_apply_device(self._h, d_records, n, d_keys_sent if n_keys else None, d_flags if n_keys else None,
+                                                   n_keys, d_new_idx, C.byref(st)))
         return st
 
     # ---- storage.RemoteCache set methods (storage/types.go:83-102)
@@ -968,23 +957,20 @@ class Engine:
 
     @staticmethod
     def _members_ptr(d_members):
-        if not hasattr(d_members, "data_ptr"):
-            raise TypeError("d_members: a torch tensor on this engine's device")
+        Engine._tensor(d_members, "d_members")
         n = d_members.numel() // 48
-        return n, (C.c_void_p(d_members.data_ptr()) if n else None)
+        return n, (d_members.data_ptr() if n else None)
 
     def _known_export_call(self, fn, alloc):
         """One export call sized up front — the live members are at most table_info().occupied, the meta part as large
         as last time — and a second one only when that was short (CTMR_E_RANGE fills `info` with the sizes)."""
         info = N.KnownImageInfo()
-        meta_cap, members_cap = getattr(self, "_known_meta_cap", 1 << 16), max(self.table_info().occupied, 1)
-        for _ in range(2):
+
+        def call(meta_cap, members_cap):
             bufs = alloc(meta_cap, members_cap)
-            rc = fn(bufs, meta_cap, members_cap, info)
-            if rc != N.E_RANGE:
-                break
-            meta_cap, members_cap = max(info.meta_bytes, 64), max(info.members, 1)
-        self._ck(rc)
+            return fn(bufs, meta_cap, members_cap, info), bufs
+        bufs, (meta_cap, _) = self._sized_call(call, (getattr(self, "_known_meta_cap", 1 << 16), max(self.table_info().occupied, 1)),
+                                               lambda: (max(info.meta_bytes, 64), max(info.members, 1)))
         self._known_meta_cap = max(meta_cap, info.meta_bytes)
         return bufs, info
 
@@ -997,11 +983,9 @@ class Engine:
 
     def known_export_device(self):
         """→ (meta bytes, torch uint8 tensor of the 48-byte member records on this engine's device; a view)."""
-        import torch
         (meta, members), info = self._known_export_call(
-            lambda b, mc, nc, info: self._lib.ctmr_known_export_device(self._h, b[0].ctypes.data, mc,
-                                                                       C.c_void_p(b[1].data_ptr()), nc, C.byref(info)),
-            lambda mc, nc: (np.empty(mc, np.uint8), torch.empty(nc * 48, dtype=torch.uint8, device="cuda:%d" % self.device)))
+            lambda b, mc, nc, info: self._lib.ctmr_known_export_device(self._h, b[0].ctypes.data, mc, b[1].data_ptr(), nc, C.byref(info)),
+            lambda mc, nc: (np.empty(mc, np.uint8), self._empty(nc * 48, True)))
         return meta[:info.meta_bytes].tobytes(), members[:info.members * 48]
 
     def known_import(self, image, world=1, rank=0) -> dict:
@@ -1045,16 +1029,14 @@ class Engine:
     def known_query_device(self, meta, d_members, world=1, rank=0):
         """known_query with the member records in device memory (a torch uint8 tensor) → (flags: torch uint8 tensor on
         this engine's device, host_flags: numpy uint8, stats dict)."""
-        import torch
         meta = bytes(meta)
         n, ptr = self._members_ptr(d_members)
         n_host = self._header_counts(meta)[1]
-        flags = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda:%d" % self.device)
+        flags = self._empty(max(n, 1), True)
         host_flags = np.empty(max(n_host, 1), np.uint8)
         st = N.KnownProbeStats()
-        self._ck(self._lib.ctmr_known_query_device(self._h, meta, len(meta), ptr, n, world, rank,
-                                                   C.c_void_p(flags.data_ptr()), n, host_flags.ctypes.data, n_host,
-                                                   C.byref(st)))
+        self._ck(self._lib.ctmr_known_query_device(self._h, meta, len(meta), ptr, n, world, rank, flags.data_ptr(), n,
+                                                   host_flags.ctypes.data, n_host, C.byref(st)))
         return flags[:n], host_flags[:n_host], self._stats_dict(st)
 
     def known_remove(self, image, world=1, rank=0) -> dict:
@@ -1074,48 +1056,53 @@ class Engine:
         return self._stats_dict(st)
 
     # ---- per-issuer known-serial lists (include/ctmr.h ctmr_known_lists*; CPU twin: known_image.known_lists)
-    def _known_lists_call(self, fn, alloc, now):
-        """One call sized by the bound (81 B per live member, the host-store text as large as last time), which writes
-        without a separate count pass, and a second, exact one only when that was short (CTMR_E_RANGE fills `info`)."""
+    def _lists_call(self, fn, device, caps):
+        """The call of the four list writers: fn(text address, text_cap, ids address, ids_cap, offsets address, n_offs,
+        info), first with the caller's guess caps = (text_cap, ids_cap, n_offs), and a second, exact time only when
+        that was short (CTMR_E_RANGE fills `info`).  → (text: numpy uint8 or (device) a torch tensor, ids: bytes, text
+        offsets, ID offsets (u64, issuers + 1 each), info, the caps of the last call)"""
         info = N.KnownListsInfo()
-        occ = self.table_info().occupied
-        text_cap = 81 * occ + getattr(self, "_known_lists_host", 1 << 12)
-        ids_cap, n_offs = getattr(self, "_known_lists_ids", 1 << 12), getattr(self, "_known_lists_offs", 256)
-        for _ in range(2):
-            text = alloc(text_cap)
-            ids, offs = np.empty(max(ids_cap, 1), np.uint8), np.empty(max(n_offs, 2), np.uint64)
-            rc = fn(int(now), text, text_cap, ids.ctypes.data, ids_cap, offs.ctypes.data, n_offs, C.byref(info))
-            if rc != N.E_RANGE:
-                break
-            text_cap, ids_cap, n_offs = info.text_bytes, info.ids_bytes, 2 * (info.issuers + 1)
-        self._ck(rc)
+
+        def call(text_cap, ids_cap, n_offs):
+            bufs = self._empty(max(text_cap, 1), device), np.empty(max(ids_cap, 1), np.uint8), np.empty(max(n_offs, 2), np.uint64)
+            return fn(_addr(bufs[0]), text_cap, bufs[1].ctypes.data, ids_cap, bufs[2].ctypes.data, n_offs, C.byref(info)), bufs
+        (text, ids, offs), caps = self._sized_call(call, caps, lambda: (info.text_bytes, info.ids_bytes, 2 * (info.issuers + 1)))
+        g = info.issuers
+        return text[:info.text_bytes], ids[:info.ids_bytes].tobytes(), offs[:g + 1].copy(), offs[g + 1:2 * g + 2].copy(), info, caps
+
+    @staticmethod
+    def _list_ids(ids, ioff, info):
+        return [ids[ioff[k]:ioff[k + 1]] for k in range(info.issuers)]
+
+    @staticmethod
+    def _list_pairs(text, ids, toff, ioff, info):
+        return [(i, text[toff[k]:toff[k + 1]].tobytes()) for k, i in enumerate(Engine._list_ids(ids, ioff, info))]
+
+    def _known_lists_call(self, device, now):
+        """One call sized by the bound (81 B per live member, the host-store text as large as last time), which writes
+        without a separate count pass, and a second, exact one only when that was short."""
+        fn = self._lib.ctmr_known_lists_device if device else self._lib.ctmr_known_lists
+        caps = (81 * self.table_info().occupied + getattr(self, "_known_lists_host", 1 << 12),
+                getattr(self, "_known_lists_ids", 1 << 12), getattr(self, "_known_lists_offs", 256))
+        *out, info, (_, ids_cap, n_offs) = self._lists_call(lambda *args: fn(self._h, int(now), *args), device, caps)
         self._known_lists_host = max(info.text_bytes - 81 * info.members, 1 << 12)
         self._known_lists_ids, self._known_lists_offs = max(ids_cap, info.ids_bytes), max(n_offs, 2 * (info.issuers + 1))
-        g = info.issuers
-        return text, ids[:info.ids_bytes].tobytes(), offs[:g + 1].copy(), offs[g + 1:2 * g + 2].copy(), info
+        return (*out, info)
 
     def known_lists_raw(self, now):
         """→ (text: numpy uint8 of info.text_bytes, ids: bytes, text offsets, ID offsets (u64, issuers + 1 each), info)."""
-        text, ids, toff, ioff, info = self._known_lists_call(
-            lambda now, t, tc, *rest: self._lib.ctmr_known_lists(self._h, now, t.ctypes.data, tc, *rest),
-            lambda cap: np.empty(max(cap, 1), np.uint8), now)
-        return text[:info.text_bytes], ids, toff, ioff, info
+        return self._known_lists_call(False, now)
 
     def known_lists(self, now) -> list:
         """[(Issuer.ID bytes, list text bytes)] in ID order: the serials of every set not expired at `now` (unix seconds),
         one lowercase hex line each — what LocalDiskBackend.StoreKnownCertificateList writes per issuer."""
-        text, ids, toff, ioff, info = self.known_lists_raw(now)
-        return [(ids[ioff[k]:ioff[k + 1]], text[toff[k]:toff[k + 1]].tobytes()) for k in range(info.issuers)]
+        return self._list_pairs(*self.known_lists_raw(now))
 
     def known_lists_device(self, now):
         """→ ([Issuer.ID bytes], text offsets (numpy u64, issuers + 1), torch uint8 tensor of the text on this engine's
         device; a view)."""
-        import torch
-        dev = "cuda:%d" % self.device
-        text, ids, toff, ioff, info = self._known_lists_call(
-            lambda now, t, tc, *rest: self._lib.ctmr_known_lists_device(self._h, now, C.c_void_p(t.data_ptr()), tc, *rest),
-            lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), now)
-        return [ids[ioff[k]:ioff[k + 1]] for k in range(info.issuers)], toff, text[:info.text_bytes]
+        text, ids, toff, ioff, info = self._known_lists_call(True, now)
+        return self._list_ids(ids, ioff, info), toff, text
 
     def store_known_lists(self, writer, now) -> int:
         """StoreKnownCertificateList for every list at `now` through a host_writeback.HostWriter (LocalDiskBackend: one
@@ -1126,55 +1113,34 @@ class Engine:
 
     # ---- the same lists straight from an image, with no table behind them (include/ctmr.h ctmr_known_image_lists*,
     # DESIGN.md §17; CPU twin: known_image.image_lists)
-    def _known_image_lists_call(self, fn, alloc, n, host_bytes):
+    def _known_image_lists_call(self, fn, device, n, buf):
         """One call sized by the bound — 81 B per member record, the host section's lines at most 2 B per octet of the
-        section — and a second, exact one only for IDs or offsets beyond the guess (CTMR_E_RANGE fills `info`)."""
-        info = N.KnownListsInfo()
-        text_cap, ids_cap, n_offs = 81 * n + 2 * host_bytes + 1, 1 << 12, 256
-        for _ in range(2):
-            text = alloc(text_cap)
-            ids, offs = np.empty(max(ids_cap, 1), np.uint8), np.empty(max(n_offs, 2), np.uint64)
-            rc = fn(text, text_cap, ids.ctypes.data, ids_cap, offs.ctypes.data, n_offs, C.byref(info))
-            if rc != N.E_RANGE:
-                break
-            text_cap, ids_cap, n_offs = info.text_bytes, info.ids_bytes, 2 * (info.issuers + 1)
-        self._ck(rc)
-        g = info.issuers
-        return text, ids[:info.ids_bytes].tobytes(), offs[:g + 1].copy(), offs[g + 1:2 * g + 2].copy(), info
-
-    @staticmethod
-    def _host_bytes(buf):
-        """The host section's bytes as the header of an image or its meta part has them, held to what `buf` could carry."""
+        section, as the header of the image or meta part `buf` has it, held to what `buf` could carry — and a second,
+        exact one only for IDs or offsets beyond the guess."""
         from .known_image import _HEADER
-        return min(_HEADER.unpack_from(buf, 0)[7], len(buf)) if len(buf) >= 64 else 0
+        host_bytes = min(_HEADER.unpack_from(buf, 0)[7], len(buf)) if len(buf) >= 64 else 0
+        return self._lists_call(fn, device, (81 * n + 2 * host_bytes + 1, 1 << 12, 256))[:5]
 
     def known_image_lists_raw(self, image, now):
         """known_lists_raw of the sets `image` holds, read where they lie: one line per member record in the image's
         order (a canonical image gives sorted lists).  The engine's own sets and issuers play no part.
         → (text: numpy uint8, ids: bytes, text offsets, ID offsets (u64, issuers + 1 each), info)."""
         image = bytes(image)
-        text, ids, toff, ioff, info = self._known_image_lists_call(
-            lambda t, tc, *rest: self._lib.ctmr_known_image_lists(self._h, image, len(image), int(now), t.ctypes.data, tc, *rest),
-            lambda cap: np.empty(max(cap, 1), np.uint8), self._header_counts(image)[0], self._host_bytes(image))
-        return text[:info.text_bytes], ids, toff, ioff, info
+        return self._known_image_lists_call(lambda *args: self._lib.ctmr_known_image_lists(self._h, image, len(image), int(now), *args),
+                                            False, self._header_counts(image)[0], image)
 
     def known_image_lists(self, image, now) -> list:
         """[(Issuer.ID bytes, list text bytes)] in ID order of the sets `image` holds that are not expired at `now`."""
-        text, ids, toff, ioff, info = self.known_image_lists_raw(image, now)
-        return [(ids[ioff[k]:ioff[k + 1]], text[toff[k]:toff[k + 1]].tobytes()) for k in range(info.issuers)]
+        return self._list_pairs(*self.known_image_lists_raw(image, now))
 
     def known_image_lists_device(self, meta, d_members, now):
         """known_image_lists with the member records in device memory (a torch uint8 tensor) → ([Issuer.ID bytes], text
         offsets (numpy u64, issuers + 1), torch uint8 tensor of the text on this engine's device; a view)."""
-        import torch
         meta = bytes(meta)
         n, ptr = self._members_ptr(d_members)
-        dev = "cuda:%d" % self.device
         text, ids, toff, ioff, info = self._known_image_lists_call(
-            lambda t, tc, *rest: self._lib.ctmr_known_image_lists_device(self._h, meta, len(meta), ptr, n, int(now),
-                                                                         C.c_void_p(t.data_ptr()), tc, *rest),
-            lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), n, self._host_bytes(meta))
-        return [ids[ioff[k]:ioff[k + 1]] for k in range(info.issuers)], toff, text[:info.text_bytes]
+            lambda *args: self._lib.ctmr_known_image_lists_device(self._h, meta, len(meta), ptr, n, int(now), *args), True, n, meta)
+        return self._list_ids(ids, ioff, info), toff, text
 
     def store_image_lists(self, writer, image, now) -> int:
         """store_known_lists for the lists of `image` at `now`.  → the lists handed to the backend."""
@@ -1208,27 +1174,28 @@ class Engine:
         nk, kptr = self._members_ptr(d_k_members)
         n, pptr = self._members_ptr(d_p_members)
         n_host = self._header_counts(p_meta)[1]
-        hits = torch.empty((max(n, 1), 4), dtype=torch.int32, device="cuda:%d" % self.device)
+        hits = torch.empty((max(n, 1), 4), dtype=torch.int32, device=self._dev)
         host_hits = np.zeros(max(n_host, 1), HIT_DTYPE)
         info = N.KnownFindInfo()
         self._ck(self._lib.ctmr_known_image_find_device(self._h, k_meta, len(k_meta), kptr, nk, p_meta, len(p_meta), pptr, n,
-                                                        int(now), C.c_void_p(hits.data_ptr()), n, host_hits.ctypes.data, n_host,
+                                                        int(now), hits.data_ptr(), n, host_hits.ctypes.data, n_host,
                                                         C.byref(info)))
         return hits[:n], host_hits[:n_host], self._stats_dict(info)
 
     def known_find(self, probes, now):
         """known_image_find over the engine's own sets: known_export_device followed by known_image_find_device, nothing
         cleverer.  → (hits, host_hits: numpy known_image.HIT_DTYPE; info dict)."""
-        import torch
         from .known_image import HIT_DTYPE
-        probes = bytes(probes)
-        n = self._header_counts(probes)[0]
-        k_meta, d_k = self.known_export_device()
-        at = len(probes) - 48 * n
-        d_p = torch.frombuffer(bytearray(probes[at:]), dtype=torch.uint8).to("cuda:%d" % self.device) if n else \
-            torch.empty(0, dtype=torch.uint8, device="cuda:%d" % self.device)
-        hits, host_hits, info = self.known_image_find_device(k_meta, d_k, probes[:at], d_p, now)
+        hits, host_hits, info = self.known_image_find_device(*self._own_and_probes(probes), now)
         return hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits, info
+
+    def _own_and_probes(self, probes):
+        """The operands of known_find and known_split: the engine's own sets exported to the device, and the probe image
+        cut into its meta part and its member records on the device → (k_meta, d_k, p_meta, d_p)"""
+        probes = bytes(probes)
+        at = len(probes) - 48 * self._header_counts(probes)[0]
+        k_meta, d_k = self.known_export_device()
+        return k_meta, d_k, probes[:at], self._upload(probes[at:])
 
     # ---- an image partitioned by a probe image, the hour as wildcard (include/ctmr.h ctmr_known_image_split*, DESIGN.md
     # §28; CPU twin: known_image.split)
@@ -1263,15 +1230,12 @@ class Engine:
         """known_image_split with the member records of both operands in device memory (torch uint8 tensors) →
         ((hit meta bytes, torch uint8 tensor of hit's member records on this engine's device; a view), the same for miss,
         info dict); None for a side `want` leaves out.  One call, the buffers sized by the bound."""
-        import torch
         k_meta, p_meta = bytes(k_meta), bytes(p_meta)
         nk, kptr = self._members_ptr(d_k_members)
         n, pptr = self._members_ptr(d_p_members)
-        dev = "cuda:%d" % self.device
-        sides = [(np.empty(len(k_meta), np.uint8), torch.empty(max(nk, 1) * 48, dtype=torch.uint8, device=dev)) if w else None
-                 for w in self._split_want(want)]
+        sides = [(np.empty(len(k_meta), np.uint8), self._empty(max(nk, 1) * 48, True)) if w else None for w in self._split_want(want)]
         info = N.KnownSplitInfo()
-        args = [a for s in sides for a in ((s[0].ctypes.data, s[0].nbytes, C.c_void_p(s[1].data_ptr()), nk) if s else (None, 0, None, 0))]
+        args = [a for s in sides for a in ((s[0].ctypes.data, s[0].nbytes, s[1].data_ptr(), nk) if s else (None, 0, None, 0))]
         self._ck(self._lib.ctmr_known_image_split_device(self._h, k_meta, len(k_meta), kptr, nk, p_meta, len(p_meta), pptr, n, int(now),
                                                          *args, C.byref(info)))
         hit, miss = ((s[0][:i.meta_bytes].tobytes(), s[1][:i.members * 48]) if s else None for s, i in zip(sides, (info.hit, info.miss)))
@@ -1280,73 +1244,42 @@ class Engine:
     def known_split(self, probes, now, want=("hit", "miss")):
         """known_image_split over the engine's own sets: known_export_device followed by known_image_split_device, as
         known_find does.  → (hit, miss, info dict): images as bytes."""
-        import torch
-        probes = bytes(probes)
-        n = self._header_counts(probes)[0]
-        k_meta, d_k = self.known_export_device()
-        at = len(probes) - 48 * n
-        d_p = torch.frombuffer(bytearray(probes[at:]), dtype=torch.uint8).to("cuda:%d" % self.device) if n else \
-            torch.empty(0, dtype=torch.uint8, device="cuda:%d" % self.device)
-        hit, miss, info = self.known_image_split_device(k_meta, d_k, probes[:at], d_p, now, want)
+        hit, miss, info = self.known_image_split_device(*self._own_and_probes(probes), now, want)
         return tuple(s[0] + s[1].cpu().numpy().tobytes() if s else None for s in (hit, miss)) + (info,)
 
     # ---- the Redis protocol stream of an image (include/ctmr.h ctmr_known_image_resp*, DESIGN.md §18; CPU twin:
     # known_image.image_resp)
-    def _sized_call(self, call, cap, need, check=None):
-        """The sizing convention's loop: call(cap) → (rc, the buffer it made of `cap`), once with the first guess and a
-        second time, with need() — what the call's `info` says after CTMR_E_RANGE —, only when that was short.  check(rc)
-        raises for any other failure (default: _ck).  → (the buffer, the cap it was made of)."""
-        for _ in range(2):
-            rc, buf = call(cap)
-            if rc != N.E_RANGE:
-                break
-            cap = need()
-        (check or self._ck)(rc)
-        return buf, cap
-
-    def _known_resp_call(self, fn, alloc, buf, n):
-        """One call sized by the header's bound (include/ctmr.h) and a second, exact one only when the header understated
-        the image (CTMR_E_RANGE fills `info`)."""
+    def _known_resp_call(self, fn, device, buf, n, members_per_command):
+        """One call sized by the bound the header of the image or meta part `buf` gives (include/ctmr.h) and a second,
+        exact one only when the header understated the image: fn(per, text address, text_cap, info).  → the stream"""
         from .known_image import _HEADER, resp_bound
+        per = int(members_per_command)
+        if not 0 <= per < 1 << 32:
+            raise ValueError("members_per_command %r" % (members_per_command,))
         h = _HEADER.unpack_from(buf, 0) if len(buf) >= 64 else (0,) * 10
-        per = min(max(int(fn.per), 1), 1 << 20)
-        text_cap = resp_bound(n, min(h[5], len(buf) // 24), min(h[7], len(buf)), min(h[8], len(buf) // 8), per)
+        bound = resp_bound(n, min(h[5], len(buf) // 24), min(h[7], len(buf)), min(h[8], len(buf) // 8), min(max(per, 1), 1 << 20))
         info = N.KnownRespInfo()
 
         def call(cap):
-            text = alloc(cap)
-            return fn(text, cap, C.byref(info)), text
-        return self._sized_call(call, text_cap, lambda: info.text_bytes)[0], info
+            text = self._empty(max(cap, 1), device)
+            return fn(per, _addr(text), cap, C.byref(info)), text
+        return self._sized_call(call, (bound,), lambda: (info.text_bytes,))[0][:info.text_bytes]
 
     def known_image_resp(self, image, members_per_command=512) -> bytes:
         """The SADD + EXPIREAT stream of the sets `image` holds, as `redis-cli --pipe` loads it: the keys in order, the
         member records in the image's order, at most `members_per_command` members per SADD.  The engine's own sets and
         issuers play no part."""
         image = bytes(image)
-
-        def fn(t, tc, info):
-            return self._lib.ctmr_known_image_resp(self._h, image, len(image), fn.per, t.ctypes.data, tc, info)
-        fn.per = int(members_per_command)
-        if not 0 <= fn.per < 1 << 32:
-            raise ValueError("members_per_command %r" % (members_per_command,))
-        text, info = self._known_resp_call(fn, lambda cap: np.empty(max(cap, 1), np.uint8), image, self._header_counts(image)[0])
-        return text[:info.text_bytes].tobytes()
+        return self._known_resp_call(lambda per, *args: self._lib.ctmr_known_image_resp(self._h, image, len(image), per, *args),
+                                     False, image, self._header_counts(image)[0], members_per_command).tobytes()
 
     def known_image_resp_device(self, meta, d_members, members_per_command=512):
         """known_image_resp with the member records in device memory (a torch uint8 tensor) → torch uint8 tensor of the
         stream on this engine's device; a view."""
-        import torch
         meta = bytes(meta)
         n, ptr = self._members_ptr(d_members)
-        dev = "cuda:%d" % self.device
-
-        def fn(t, tc, info):
-            return self._lib.ctmr_known_image_resp_device(self._h, meta, len(meta), ptr, n, fn.per, C.c_void_p(t.data_ptr()), tc, info)
-        fn.per = int(members_per_command)
-        if not 0 <= fn.per < 1 << 32:
-            raise ValueError("members_per_command %r" % (members_per_command,))
-        text, info = self._known_resp_call(fn, lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev), meta, n)
-        return text[:info.text_bytes]
+        return self._known_resp_call(lambda per, *args: self._lib.ctmr_known_image_resp_device(self._h, meta, len(meta), ptr, n, per, *args),
+                                     True, meta, n, members_per_command)
 
     def known_resp(self, members_per_command=512) -> bytes:
         """The stream of the engine's own sets: known_image_resp of its sorted export.  The order setting
@@ -1371,29 +1304,27 @@ class Engine:
         def call(cap):
             out = np.empty(cap, np.uint8)
             return self._lib.ctmr_known_resp_image(self._h, stream, len(stream), out.ctypes.data, cap, C.byref(info)), out
-        out, _ = self._sized_call(call, 1 << 16, lambda: info.image_bytes)
+        out, _ = self._sized_call(call, (1 << 16,), lambda: (info.image_bytes,))
         return out[:info.image_bytes].tobytes()
 
     def known_resp_image_device(self, d_stream, n=None):
         """known_resp_image of the first n bytes of a torch uint8 tensor on this engine's device (all of it by default;
         any alignment) → (meta bytes, torch uint8 tensor of the member records on the device; a view).  The records are
         sized by their bound (n / 6), the meta by a second call when 64 KiB were short."""
-        import torch
-        if not hasattr(d_stream, "data_ptr"):
-            raise TypeError("d_stream: a torch tensor on this engine's device")
+        self._tensor(d_stream, "d_stream")
         n = d_stream.numel() if n is None else int(n)
         if not 0 <= n <= d_stream.numel():
             raise ValueError("n = %r of %d bytes" % (n, d_stream.numel()))
-        ptr = C.c_void_p(d_stream.data_ptr()) if n else None
+        ptr = d_stream.data_ptr() if n else None
         info = N.KnownRespImageInfo()
         members_cap = max(n // 6, 1)
-        out = torch.empty(members_cap * 48, dtype=torch.uint8, device="cuda:%d" % self.device)
+        out = self._empty(members_cap * 48, True)
 
         def call(meta_cap):
             meta = np.empty(meta_cap, np.uint8)
-            return self._lib.ctmr_known_resp_image_device(self._h, ptr, n, meta.ctypes.data, meta_cap, C.c_void_p(out.data_ptr()),
-                                                          members_cap, C.byref(info)), meta
-        meta, meta_cap = self._sized_call(call, getattr(self, "_resp_meta_cap", 1 << 16), lambda: info.meta_bytes)
+            return self._lib.ctmr_known_resp_image_device(self._h, ptr, n, meta.ctypes.data, meta_cap, out.data_ptr(), members_cap,
+                                                          C.byref(info)), meta
+        meta, (meta_cap,) = self._sized_call(call, (getattr(self, "_resp_meta_cap", 1 << 16),), lambda: (info.meta_bytes,))
         self._resp_meta_cap = max(meta_cap, info.meta_bytes)
         return meta[:info.meta_bytes].tobytes(), out[:info.members * 48]
 
@@ -1419,10 +1350,10 @@ class Engine:
         return blob, total, offsets, n, digests
 
     def _crl_fail(self, rc, cinfo):
-        if rc == N.E_INVAL and cinfo.bad_crl != (1 << 64) - 1:
+        def error(msg):
             from .crl import CrlError
-            raise CrlError(cinfo.bad_offset, self._lib.ctmr_last_error(self._h).decode(errors="replace"), cinfo.bad_crl)
-        self._ck(rc)
+            return CrlError(cinfo.bad_offset, msg, cinfo.bad_crl)
+        self._ck_at(rc, cinfo.bad_crl, error)
 
     def crl_probes(self, crls, digests):
         """The probe image of the revoked serials of `crls` — a list of DER CRLs, or (blob bytes, offsets) — whose
@@ -1455,7 +1386,7 @@ class Engine:
             out = np.empty(max(cap, 64), np.uint8)
             args = (self._h, blob, total, offsets.ctypes.data, n, digests, out.ctypes.data, out.nbytes, C.byref(info), C.byref(cinfo))
             return (self._lib.ctmr_crl_probes_each(*args, C.byref(verdicts)) if each else self._lib.ctmr_crl_probes(*args)), out
-        out, _ = self._sized_call(call, 64 + 56 * n + 48 * (total // 6), lambda: info.image_bytes, lambda rc: self._crl_fail(rc, cinfo))
+        out, _ = self._sized_call(call, (64 + 56 * n + 48 * (total // 6),), lambda: (info.image_bytes,), lambda rc: self._crl_fail(rc, cinfo))
         return out[:info.image_bytes].tobytes(), self._stats_dict(cinfo), read()
 
     def crl_probes_device(self, d_crls, offsets, digests, exact=None):
@@ -1476,31 +1407,32 @@ class Engine:
 
     def _crl_probes_device(self, d_crls, offsets, digests, exact, each):
         import torch
-        if not hasattr(d_crls, "data_ptr"):
-            raise TypeError("d_crls: a torch tensor on this engine's device")
+        self._tensor(d_crls, "d_crls")
         _, total, offsets, n, digests = self._crl_args((d_crls, offsets), digests)
-        ptr = C.c_void_p(d_crls.data_ptr()) if total else None
+        ptr = d_crls.data_ptr() if total else None
         info, cinfo = N.KnownImageInfo(), N.CrlInfo()
         verdicts, read = self._crl_verdicts(n, each)
-        dev = "cuda:%d" % self.device
-        meta_cap, members_cap = 64 + 56 * n + (1 << 12), max(total // 6, 1)
+        members_cap = max(total // 6, 1)
         if exact is None:
             exact = 48 * members_cap > torch.cuda.mem_get_info(self.device)[0] // 4
 
         def fn(meta, meta_cap, d_out, members_cap):
-            args = (self._h, ptr, total, offsets.ctypes.data, n, digests, meta, meta_cap, d_out, members_cap, C.byref(info), C.byref(cinfo))
+            args = (self._h, ptr, total, offsets.ctypes.data, n, digests, _addr(meta), meta_cap, _addr(d_out), members_cap, C.byref(info),
+                    C.byref(cinfo))
             return self._lib.ctmr_crl_probes_each_device(*args, C.byref(verdicts)) if each else self._lib.ctmr_crl_probes_device(*args)
-        if exact:
-            rc = fn(None, 0, None, 0)
-            if rc != N.E_RANGE:
-                self._crl_fail(rc, cinfo)
-            meta_cap, members_cap = info.meta_bytes, max(info.members, 1)
-        out = torch.empty(members_cap * 48, dtype=torch.uint8, device=dev)
 
-        def call(meta_cap):
-            meta = np.empty(meta_cap, np.uint8)
-            return fn(meta.ctypes.data, meta_cap, C.c_void_p(out.data_ptr()), members_cap), meta
-        meta, _ = self._sized_call(call, meta_cap, lambda: info.meta_bytes, lambda rc: self._crl_fail(rc, cinfo))
+        def check(rc):
+            self._crl_fail(rc, cinfo)
+        if exact:
+            meta, _, out, _ = self._sizes_first(fn, (None, 0, None, 0), lambda: (
+                np.empty(info.meta_bytes, np.uint8), info.meta_bytes, self._empty(max(info.members, 1) * 48, True), max(info.members, 1)), check)
+        else:
+            out = self._empty(members_cap * 48, True)
+
+            def call(meta_cap):
+                meta = np.empty(meta_cap, np.uint8)
+                return fn(meta, meta_cap, out, members_cap), meta
+            meta, _ = self._sized_call(call, (64 + 56 * n + (1 << 12),), lambda: (info.meta_bytes,), check)
         return meta[:info.meta_bytes].tobytes(), out[:info.members * 48], self._stats_dict(cinfo), read()
 
     def known_revoked(self, crls, digests, now, each=False):
@@ -1510,20 +1442,21 @@ class Engine:
         record of the probe image in its order, host_hits per host-section pair).  each=True: every CRL is judged on its
         own (crl_probes_each_device): the CRLs outside the grammar are left out instead of failing the call, and the
         verdicts of all CRLs are a fourth element."""
-        import torch
         from .known_image import HIT_DTYPE
-        if not isinstance(crls, tuple):
-            blob, _, offsets, _, digests = self._crl_args(crls, digests)
-            raw = np.frombuffer(blob, np.uint8)
-            crls = (torch.from_numpy(raw.copy()).to("cuda:%d" % self.device), offsets)
-        if each:
-            p_meta, d_p, _, verdicts = self.crl_probes_each_device(crls[0], crls[1], digests)
-        else:
-            p_meta, d_p, _ = self.crl_probes_device(crls[0], crls[1], digests)
+        p_meta, d_p, verdicts = self._crl_probes_staged(crls, digests, each)
         k_meta, d_k = self.known_export_device()
         hits, host_hits, _ = self.known_image_find_device(k_meta, d_k, p_meta, d_p, now)
         out = (p_meta, hits.cpu().numpy().view(HIT_DTYPE).reshape(-1), host_hits)
         return out + (verdicts,) if each else out
+
+    def _crl_probes_staged(self, crls, digests, each):
+        """The probe image of known_revoked and known_revoked_split: a list of CRLs goes to the device as one blob first
+        → (the probe image's meta, its member records on the device, the verdicts (each) or None)"""
+        if not isinstance(crls, tuple):
+            blob, _, offsets, _, digests = self._crl_args(crls, digests)
+            crls = (self._upload(blob), offsets)
+        p_meta, d_p, _, verdicts = self._crl_probes_device(crls[0], crls[1], digests, None, each)
+        return p_meta, d_p, verdicts
 
     def known_revoked_split(self, crls, digests, now, each=False):
         """The engine's known certificates in two images, the revoked and the others: crl_probes_device →
@@ -1535,15 +1468,7 @@ class Engine:
             ids, offs, text = e.known_image_lists_device(hit_meta, d_hit, now)      # revoked/<Issuer.ID>
             ids, offs, text = e.known_image_lists_device(miss_meta, d_miss, now)    # known/<Issuer.ID>
         """
-        import torch
-        if not isinstance(crls, tuple):
-            blob, _, offsets, _, digests = self._crl_args(crls, digests)
-            raw = np.frombuffer(blob, np.uint8)
-            crls = (torch.from_numpy(raw.copy()).to("cuda:%d" % self.device), offsets)
-        if each:
-            p_meta, d_p, _, verdicts = self.crl_probes_each_device(crls[0], crls[1], digests)
-        else:
-            p_meta, d_p, _ = self.crl_probes_device(crls[0], crls[1], digests)
+        p_meta, d_p, verdicts = self._crl_probes_staged(crls, digests, each)
         k_meta, d_k = self.known_export_device()
         out = self.known_image_split_device(k_meta, d_k, p_meta, d_p, now)
         return out + (verdicts,) if each else out
@@ -1552,10 +1477,8 @@ class Engine:
         """The warm start from a reference deployment's Redis contents: every serials:: member of the stream (bytes, or
         a torch uint8 tensor on this engine's device) this rank takes, as SetInsert would add it.  Stream → member
         records on the device → known_import_device: no image in host memory."""
-        import torch
         if not hasattr(stream, "data_ptr"):
-            raw = np.frombuffer(bytes(stream), np.uint8)
-            stream = torch.from_numpy(raw.copy()).to("cuda:%d" % self.device)
+            stream = self._upload(bytes(stream))
         meta, d_members = self.known_resp_image_device(stream)
         return self.known_import_device(meta, d_members, world, rank)
 
@@ -1591,22 +1514,19 @@ class Engine:
         play no part.  Sized by the bounds (|a| + |b| members, the two metas), so one call."""
         a = bytes(a)
         b = None if b is None else bytes(b)
-        cap = len(a) + (len(b) if b is not None else 0) + 64
+        len_b = len(b) if b is not None else 0
         info = N.KnownImageInfo()
-        for _ in range(2):   # (a second call only when host-section pairs moved into sets and issuers of their own)
+
+        def call(cap):
             out = np.empty(cap, np.uint8)
-            rc = self._lib.ctmr_known_merge(self._h, int(op), a, len(a), b, len(b) if b is not None else 0,
-                                            out.ctypes.data, cap, C.byref(info))
-            if rc != N.E_RANGE:
-                break
-            cap = info.image_bytes
-        self._ck(rc)
+            return self._lib.ctmr_known_merge(self._h, int(op), a, len(a), b, len_b, out.ctypes.data, cap, C.byref(info)), out
+        # (a second call only when host-section pairs moved into sets and issuers of their own)
+        out, _ = self._sized_call(call, (len(a) + len_b + 64,), lambda: (info.image_bytes,))
         return out[:info.image_bytes].tobytes()
 
     def known_merge_device(self, op, a_meta, d_a, b_meta=None, d_b=None):
         """known_merge with the member records in device memory (torch uint8 tensors on this engine's device)
         → (meta bytes, torch uint8 tensor of the result's member records; a view)."""
-        import torch
         a_meta = bytes(a_meta)
         na, pa = self._members_ptr(d_a)
         nb, pb = (0, None) if b_meta is None else self._members_ptr(d_b)
@@ -1615,11 +1535,11 @@ class Engine:
         meta_cap = len(a_meta) + (len(b_meta) if b_meta is not None else 0) + 64
         cap = (na + nb if op == N.KNOWN_UNION else na) + hosts
         meta = np.empty(meta_cap, np.uint8)
-        out = torch.empty(max(cap, 1) * 48, dtype=torch.uint8, device="cuda:%d" % self.device)
+        out = self._empty(max(cap, 1) * 48, True)
         info = N.KnownImageInfo()
         self._ck(self._lib.ctmr_known_merge_device(self._h, int(op), a_meta, len(a_meta), pa, na, b_meta,
-                                                   len(b_meta) if b_meta is not None else 0, pb, nb, meta.ctypes.data,
-                                                   meta_cap, C.c_void_p(out.data_ptr()), cap, C.byref(info)))
+                                                   len(b_meta) if b_meta is not None else 0, pb, nb, meta.ctypes.data, meta_cap,
+                                                   out.data_ptr(), cap, C.byref(info)))
         return meta[:info.meta_bytes].tobytes(), out[:info.members * 48]
 
     # ---- synthetic input (bench / tests)
@@ -1627,19 +1547,13 @@ class Engine:
                           d_issuer_idx, d_entry_type) -> int:
         """The synthetic certificates as an entry view, every certificate at a multiple of `align` bytes."""
         out = C.c_uint64()
-        self._ck(self._lib.ctmr_synth_view_device(
-            self._h, C.byref(cfg), first, n, align, C.c_void_p(d_starts), C.c_void_p(d_ends),
-            C.c_void_p(d_payload) if d_payload else None, payload_cap,
-            C.c_void_p(d_issuer_idx) if d_issuer_idx else None,
-            C.c_void_p(d_entry_type) if d_entry_type else None, C.byref(out)))
+        self._ck(self._lib.ctmr_synth_view_device(self._h, C.byref(cfg), first, n, align, d_starts, d_ends, d_payload, payload_cap,
+                                                  d_issuer_idx, d_entry_type, C.byref(out)))
         return out.value
 
     def synth_device(self, cfg: N.SynthConfig, first, n, d_offsets, d_payload, payload_cap,
                      d_issuer_idx, d_entry_type) -> int:
         out = C.c_uint64()
-        self._ck(self._lib.ctmr_synth_device(
-            self._h, C.byref(cfg), first, n, C.c_void_p(d_offsets),
-            C.c_void_p(d_payload) if d_payload else None, payload_cap,
-            C.c_void_p(d_issuer_idx) if d_issuer_idx else None,
-            C.c_void_p(d_entry_type) if d_entry_type else None, C.byref(out)))
+        self._ck(self._lib.ctmr_synth_device(self._h, C.byref(cfg), first, n, d_offsets, d_payload, payload_cap, d_issuer_idx, d_entry_type,
+                                             C.byref(out)))
         return out.value
