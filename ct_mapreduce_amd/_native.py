@@ -157,6 +157,29 @@ class KnownSplitInfo(C.Structure):
                 ("sets_kept", C.c_uint64), ("members_read", C.c_uint64)]
 
 
+CASCADE_MAX_LAYERS = 255
+
+
+class CascadeParams(C.Structure):
+    _fields_ = [("k_first", C.c_uint32), ("bpk_first_q8", C.c_uint32), ("k_rest", C.c_uint32), ("bpk_rest_q8", C.c_uint32),
+                ("max_layers", C.c_uint32), ("salt_len", C.c_uint32), ("salt", C.c_uint8 * 16)]
+
+
+class CascadeLayer(C.Structure):
+    _fields_ = [("level", C.c_uint32), ("k", C.c_uint32), ("m_bits", C.c_uint64), ("offset", C.c_uint64), ("n_held", C.c_uint64)]
+
+
+class CascadeInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("layers", C.c_uint32), ("syncs", C.c_uint32), ("r_records", C.c_uint64),
+                ("s_records", C.c_uint64), ("r_sets_kept", C.c_uint64), ("s_sets_kept", C.c_uint64),
+                ("r_host_skipped", C.c_uint64), ("s_host_skipped", C.c_uint64), ("left", C.c_uint64),
+                ("layer", CascadeLayer * CASCADE_MAX_LAYERS)]
+
+
+class CascadeQueryInfo(C.Structure):
+    _fields_ = [("probes", C.c_uint64), ("host_probes", C.c_uint64), ("layers", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_issuers", C.c_uint32), ("zipf", C.c_uint32),
                 ("dup_permille", C.c_uint32), ("ca_permille", C.c_uint32),
@@ -232,6 +255,13 @@ SIGNATURES = {
     "ctmr_known_image_split_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, C.c_int64,
                                                 _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64,
                                                 C.POINTER(KnownSplitInfo)]),
+    "ctmr_cascade_build": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int64, C.POINTER(CascadeParams), _P, C.c_size_t,
+                                     C.POINTER(CascadeInfo)]),
+    "ctmr_cascade_build_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, _P, C.c_size_t, _P, C.c_uint64, C.c_int64,
+                                            C.POINTER(CascadeParams), _P, C.c_size_t, C.POINTER(CascadeInfo)]),
+    "ctmr_cascade_query": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(CascadeQueryInfo)]),
+    "ctmr_cascade_query_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_uint64, _P, C.c_uint64,
+                                            C.POINTER(CascadeQueryInfo)]),
     "ctmr_known_image_resp": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, C.c_size_t, C.POINTER(KnownRespInfo)]),
     "ctmr_known_image_resp_device": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint64, C.c_uint32, _P, C.c_size_t,
                                                C.POINTER(KnownRespInfo)]),

@@ -737,6 +737,7 @@ extern "C" {
 #include "engine/merge.inc"
 #include "engine/find.inc"
 #include "engine/split.inc"
+#include "engine/cascade.inc"
 #include "engine/resp_parse.inc"
 #include "engine/crl.inc"
 #include "engine/text_decode.inc"

@@ -45,6 +45,8 @@
 //                       expiration date: the probes in a hash table, the image streamed once against it)
 //   kernels/split.h     k_split_mark / k_split_place / k_split_sets (a known image partitioned by a probe image: a flag
 //                       per record against the find's table, then one stable compaction into the two results)
+//   kernels/cascade.h   k_casc_insert / k_casc_test / k_casc_compact / k_casc_query (the CRLite filter cascade of a revoked /
+//                       not-revoked image pair: Bloom layers hashed with SHA-256, the false positives compacted into lists)
 // der_walk.h is the TBSCertificate walk every kernel above shares; spki_key.h the key inside SubjectPublicKeyInfo.
 #pragma once
 #include "kernels/readers.h"
@@ -73,3 +75,4 @@
 #include "kernels/merge.h"
 #include "kernels/find.h"
 #include "kernels/split.h"
+#include "kernels/cascade.h"

@@ -1247,6 +1247,96 @@ class Engine:
         hit, miss, info = self.known_image_split_device(*self._own_and_probes(probes), now, want)
         return tuple(s[0] + s[1].cpu().numpy().tobytes() if s else None for s in (hit, miss)) + (info,)
 
+    # ---- the filter cascade of a revoked / not-revoked image pair (include/ctmr.h ctmr_cascade_*; CPU
+    # twin: cascade.build / cascade.query)
+    @staticmethod
+    def _cascade_params(params):
+        salt = bytes(params.salt)
+        if len(salt) > 16:
+            raise ValueError("a salt of at most 16 octets")
+        return N.CascadeParams(params.k_first, params.bpk_first_q8, params.k_rest, params.bpk_rest_q8, params.max_layers, len(salt),
+                               (C.c_uint8 * 16)(*salt))
+
+    @staticmethod
+    def _cascade_info(info) -> dict:
+        out = {f: getattr(info, f) for f, _ in info._fields_ if f != "layer"}
+        out["layer"] = [(l.level, l.k, l.m_bits, l.offset, l.n_held) for l in info.layer[:info.layers]]
+        return out
+
+    def _cascade_build(self, fn, n_revoked, params, device):
+        """The first guess — twice the first layer of n_revoked records, plus the tables — and one exact second call
+        when it was short: fn(params, out address, cap, info).  A call that is short has still built every layer (the
+        size is known only then), so the second call builds the cascade again: the guess is made generous for that
+        reason.  → (the buffer, info)"""
+        from .cascade import HEADER_BYTES, LAYER_BYTES, layer_bits
+        p, info = self._cascade_params(params), N.CascadeInfo()
+        first = ((layer_bits(n_revoked, params.bpk_first_q8) + 7) // 8 + 63) & ~63
+
+        def call(cap):
+            out = self._empty(cap, device)
+            return fn(C.byref(p), _addr(out), cap, C.byref(info)), out
+        out, _ = self._sized_call(call, (2 * first + ((HEADER_BYTES + LAYER_BYTES * params.max_layers + 63) & ~63),),
+                                  lambda: (max(info.bytes, 64),))
+        return out[:info.bytes], self._cascade_info(info)
+
+    def cascade_build(self, revoked, known, now, params):
+        """The filter cascade (cascade.py, format CTMRCASC v1) that answers 1 for every member record of the sets of the
+        image `revoked` kept at `now` and 0 for every one of `known`; params: cascade.Params (cascade.crlite_params
+        makes CRLite's choice).  → (cascade bytes, info dict).  Raises CtmrError (CTMR_E_INVAL) when max_layers layers do
+        not finish it — the operands share a key.  The engine's own sets and issuers play no part."""
+        revoked, known = bytes(revoked), bytes(known)
+        out, info = self._cascade_build(
+            lambda p, out, cap, info: self._lib.ctmr_cascade_build(self._h, revoked, len(revoked), known, len(known), int(now), p, out, cap, info),
+            self._header_counts(revoked)[0], params, False)
+        return out.tobytes(), info
+
+    def cascade_build_device(self, r_meta, d_r_members, s_meta, d_s_members, now, params):
+        """cascade_build with the member records of both operands in device memory (torch uint8 tensors) → (the cascade:
+        a torch uint8 tensor on this engine's device; a view, info dict)."""
+        r_meta, s_meta = bytes(r_meta), bytes(s_meta)
+        nr, rptr = self._members_ptr(d_r_members)
+        ns, sptr = self._members_ptr(d_s_members)
+        return self._cascade_build(
+            lambda p, out, cap, info: self._lib.ctmr_cascade_build_device(self._h, r_meta, len(r_meta), rptr, nr, s_meta, len(s_meta), sptr, ns,
+                                                                          int(now), p, out, cap, info),
+            nr, params, True)
+
+    def cascade_query(self, cascade, probes):
+        """One byte per member record of the image `probes`, all sets, in record order: 1 = `cascade` says revoked.
+        → (numpy uint8, info dict)"""
+        cascade, probes = bytes(cascade), bytes(probes)
+        n = self._header_counts(probes)[0]
+        out, info = np.zeros(max(n, 1), np.uint8), N.CascadeQueryInfo()
+        self._ck(self._lib.ctmr_cascade_query(self._h, cascade, len(cascade), probes, len(probes), out.ctypes.data, n, C.byref(info)))
+        return out[:n], self._stats_dict(info)
+
+    def cascade_query_device(self, d_cascade, p_meta, d_p_members):
+        """cascade_query with the cascade and the member records of the probe image in device memory (torch uint8
+        tensors) → (torch uint8 tensor of the answers on this engine's device, info dict)."""
+        self._tensor(d_cascade, "d_cascade")
+        p_meta = bytes(p_meta)
+        n, pptr = self._members_ptr(d_p_members)
+        out, info = self._empty(max(n, 1), True), N.CascadeQueryInfo()
+        self._ck(self._lib.ctmr_cascade_query_device(self._h, d_cascade.data_ptr(), d_cascade.numel(), p_meta, len(p_meta), pptr, n,
+                                                     out.data_ptr(), n, C.byref(info)))
+        return out[:n], self._stats_dict(info)
+
+    def known_revoked_cascade(self, crls, digests, now, params=None, each=False):
+        """The filter cascade of the engine's known certificates against `crls`: crl_probes[_each]_device →
+        known_export_device → known_image_split_device → cascade_build_device, with no member record in host memory.
+        crls, digests, each: as for known_revoked.  params: cascade.Params; None: cascade.crlite_params of the two
+        results' record counts, no salt.  → (the cascade on the device, info dict with the split's under "split"[,
+        verdicts])."""
+        from .cascade import crlite_params
+        p_meta, d_p, verdicts = self._crl_probes_staged(crls, digests, each)
+        k_meta, d_k = self.known_export_device()
+        (hit_meta, d_hit), (miss_meta, d_miss), split = self.known_image_split_device(k_meta, d_k, p_meta, d_p, now)
+        if params is None:
+            params = crlite_params(split["hit"]["members"], split["miss"]["members"])
+        d_cascade, info = self.cascade_build_device(hit_meta, d_hit, miss_meta, d_miss, now, params)
+        info["split"] = split
+        return (d_cascade, info, verdicts) if each else (d_cascade, info)
+
     # ---- the Redis protocol stream of an image (include/ctmr.h ctmr_known_image_resp*, DESIGN.md §18; CPU twin:
     # known_image.image_resp)
     def _known_resp_call(self, fn, device, buf, n, members_per_command):

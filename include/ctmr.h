@@ -622,6 +622,100 @@ int ctmr_known_image_split_device(ctmr_engine* e, const uint8_t* k_meta, size_t 
                                   uint8_t* miss_meta, size_t miss_meta_cap, void* d_miss, uint64_t miss_members_cap,
                                   ctmr_known_split_info* info);
 
+/* ---- the filter cascade of a revoked / not-revoked image pair: the CRLite filter the two results of
+ *      ctmr_known_image_split* are the lists of.  A stack of Bloom filter layers that answers "revoked" for every record
+ *      of R and "not revoked" for every record of S, with no error on either.  DESIGN.md §29.
+ *
+ * Operands.  R (revoked) and S (not revoked) are images v1, canonical or not, each any image ctmr_known_import accepts.
+ *   Only the member records of KEPT sets take part: exactly the sets ctmr_known_image_lists keeps at now_unix (a set of
+ *   exp hour h is kept iff now_unix < (h + 1) × 3600, hours outside the years 0000..9999 are skipped, INT64_MIN keeps
+ *   all of those).  The records of sets that are not kept are not read.
+ * Key.  The key of a member record is the 32-byte SPKI digest its set's issuer ordinal names in that image's own issuer
+ *   table, followed by the record's serial_len serial octets: 32 to 72 octets.  The hour is not part of the key, and the
+ *   issuer tables of the two images are not joined.
+ * Hash.  Hash function i (0-based) of layer `level` (1-based) of an m-bit layer is
+ *       u32le(SHA-256(salt ‖ u32le(i) ‖ u8(level) ‖ key)[0:4]) mod m
+ *   with the caller's salt of 0 to 16 octets: a message of 37 to 93 octets.  This is the construction filtercascade's
+ *   format 2 with hash algorithm 2 (rust-cascade's SHA-256/32) is understood to use; neither is available to this
+ *   project and no golden vector exists, so compatibility with them is UNPINNED (as DESIGN.md §2 says of the CT
+ *   parser).  What is pinned is this text, which the tests hold against hashlib.
+ * Layers.  Layer 1 holds every kept record of R; the kept records of S that pass it (all k bits set) are its false
+ *   positives F1.  Layer 2 holds F1; the kept records of R that pass it are F2.  Layer 3 holds F2 and is tested with F1,
+ *   and so on: layer l is tested with the list layer l − 1 holds.  The build ends at the first layer whose list of false
+ *   positives is empty.  No kept record in R: no layer.  No kept record in S: one layer, no test.  A key that occurs
+ *   twice on a side is inserted and counted twice: nothing is deduplicated.
+ * Sizes.  Integer arithmetic only.  A layer that holds n records has m = max(1, ceil(n × bpk_q8 / 256)) bits and k hash
+ *   functions: (k_first, bpk_first_q8) for layer 1, (k_rest, bpk_rest_q8) for the others.  k lies in 1..32, bpk_q8 in
+ *   1..65536, max_layers in 1..255, salt_len in 0..16 (the octets of salt[] behind it are ignored), else CTMR_E_INVAL;
+ *   m must be below 2^32 and each side must have fewer than 2^32 member records, else CTMR_E_INVAL.
+ * Non-convergence.  If layer max_layers still has false positives the operands share a key or the sizes are degenerate:
+ *   CTMR_E_INVAL, info.left = how many records were left, nothing written.
+ * Host sections.  Members of more than 40 octets, and every other pair of a host section, are NOT in the filter:
+ *   info.r_host_skipped / s_host_skipped count the pairs under keys kept at now_unix (a key's date parsed as
+ *   ctmr_known_image_find* parses it; a key of other than three "::" parts is CTMR_E_INVAL).  A caller answers them
+ *   from the lists.
+ * Format CTMRCASC v1, little-endian.  A 64-byte header: "CTMRCASC", u32 version = 1, u32 hash algorithm = 2, u32 layer
+ *   count, u32 salt_len, salt[16] (zeros behind salt_len), u64 total length, u64 kept records of R, u64 of S.  Then one
+ *   32-byte ctmr_cascade_layer per layer, levels 1, 2, ….  Each layer's bits start at the next multiple of 64 bytes
+ *   (layer.offset, from the start of the cascade); bit b is byte b >> 3, mask 1 << (b & 7); the bits at and above m and
+ *   all padding are zero; the total length is a multiple of 64.  A filtercascade format 2 file is a re-framing of the
+ *   same bit arrays (not written here).
+ * Build.  ctmr_cascade_build takes whole images in host memory and writes the cascade to host memory;
+ *   ctmr_cascade_build_device takes each operand's meta and its member records in device memory and writes the cascade
+ *   to device memory (all device pointers 16-byte aligned, else CTMR_E_INVAL).  The two-call convention: out == NULL or
+ *   out_cap < info.bytes fills *info (layers, bytes, the layer table, the counts) and returns CTMR_E_RANGE with nothing
+ *   written.  The layers are built in working memory and copied out only when they fit, so a call that only sizes costs
+ *   a whole build: a caller who can bound the size (layer 1 is ceil(n × bpk_first_q8 / 256) bits, the others together
+ *   are usually smaller) does better with one call and a generous buffer.  Every failure leaves `out` as it was.  Before the first output byte every record of a kept set of either operand is checked for serial_len <= 40
+ *   and zero padding (CTMR_E_INVAL).  Nothing of the engine's state is read or changed; the operands stay byte for byte.
+ *   info.syncs counts the times the host waited for the device: one per tested layer and one at the end.
+ * Query.  For every member record of the probe image P — all its sets, whatever their hour, in record order — one byte:
+ *   1 = the cascade says revoked, 0 = not.  A record that fails layer 1 is not revoked; one that passes layers 1..j and
+ *   fails layer j + 1 is revoked iff j is odd; one that passes every layer is revoked iff the layer count is odd (no
+ *   layer: not revoked).  The answer is exact for the kept records of R and S the cascade was built from and a guess
+ *   for anything else.  The cascade is validated before anything is launched: magic, version, hash algorithm, the total
+ *   length against the buffer's, salt_len, strictly ascending levels in 1..255, k in 1..32, m in 1..2^32 − 1, offsets
+ *   that are multiples of 64 with the bits inside the buffer, else CTMR_E_INVAL.  P's host section is counted
+ *   (info.host_probes), not answered.  out_cap < P's member records: CTMR_E_RANGE with *info filled, nothing written.
+ *   ctmr_cascade_query takes everything in host memory; ctmr_cascade_query_device takes the cascade and P's member
+ *   records in device memory (16-byte aligned) and leaves the answers there.
+ * All four return after the engine's stream has drained. */
+#define CTMR_CASCADE_MAX_LAYERS 255
+typedef struct {
+  uint32_t k_first, bpk_first_q8;  /* layer 1: hash functions, bits per held record × 256 */
+  uint32_t k_rest, bpk_rest_q8;    /* the other layers */
+  uint32_t max_layers;
+  uint32_t salt_len;
+  uint8_t salt[16];
+} ctmr_cascade_params;
+typedef struct {
+  uint32_t level, k;
+  uint64_t m_bits, offset, n_held;
+} ctmr_cascade_layer;
+typedef struct {
+  uint64_t bytes;                           /* the cascade's total length */
+  uint32_t layers, syncs;
+  uint64_t r_records, s_records;            /* the member records of kept sets */
+  uint64_t r_sets_kept, s_sets_kept;
+  uint64_t r_host_skipped, s_host_skipped;
+  uint64_t left;                            /* CTMR_E_INVAL by max_layers: the false positives of the last layer */
+  ctmr_cascade_layer layer[CTMR_CASCADE_MAX_LAYERS];
+} ctmr_cascade_info;
+typedef struct {
+  uint64_t probes, host_probes;  /* P's member records, P's host-section members */
+  uint32_t layers, reserved;
+} ctmr_cascade_query_info;
+int ctmr_cascade_build(ctmr_engine* e, const uint8_t* revoked, size_t revoked_len, const uint8_t* known, size_t known_len,
+                       int64_t now_unix, const ctmr_cascade_params* params, uint8_t* out, size_t out_cap, ctmr_cascade_info* info);
+int ctmr_cascade_build_device(ctmr_engine* e, const uint8_t* r_meta, size_t r_meta_len, const void* d_r_members, uint64_t r_members,
+                              const uint8_t* s_meta, size_t s_meta_len, const void* d_s_members, uint64_t s_members, int64_t now_unix,
+                              const ctmr_cascade_params* params, void* d_out, size_t out_cap, ctmr_cascade_info* info);
+int ctmr_cascade_query(ctmr_engine* e, const uint8_t* cascade, size_t cascade_len, const uint8_t* probes, size_t probes_len,
+                       uint8_t* out, size_t out_cap, ctmr_cascade_query_info* info);
+int ctmr_cascade_query_device(ctmr_engine* e, const void* d_cascade, size_t cascade_len, const uint8_t* p_meta, size_t p_meta_len,
+                              const void* d_p_members, uint64_t p_members, void* d_out, uint64_t out_cap,
+                              ctmr_cascade_query_info* info);
+
 /* ---- the Redis protocol stream of an image v1: the SADD commands of every serials:: key and the EXPIREAT
  *      KnownCertificates.setExpiryFlag puts on it (storage/knowncertificates.go:98-104), as `redis-cli --pipe` loads them
  *      into the Redis of a reference deployment.  DESIGN.md §18.
