@@ -1,7 +1,7 @@
 // engine/cascade.inc — the CRLite filter cascade of a revoked / not-revoked image pair (include/ctmr.h ctmr_cascade_*,
 // DESIGN.md §29).  Host side: both metas opened, each side's kept sets chosen by the rule of ctmr_known_image_lists
 // (engine/lists.inc: lists_hour_kept, lists_parse_date) and laid out as the segments of a virtual record sequence
-// (engine/find.inc: FindSegs, FindPack), then layer by layer: the bits of the records the layer holds, the flags of the
+// (kernels/find.h: FindSegs; engine/image.inc: KnownPack), then layer by layer: the bits of the records the layer holds, the flags of the
 // records it is tested with, one scan of the block counts and one count read by the host, the survivors compacted into
 // the list the next layers read (kernels/cascade.h).  The query validates a cascade and walks it for a probe image.
 // Part of ctmr_engine.hip (one translation unit): included inside its extern "C" block, after engine/split.inc.
@@ -13,10 +13,7 @@ constexpr char CASC_MAGIC[8] = {'C', 'T', 'M', 'R', 'C', 'A', 'S', 'C'};
 constexpr uint32_t CASC_VERSION = 1, CASC_HASH_SHA256_32 = 2, CASC_HEADER = 64, CASC_LAYER_BYTES = 32;
 constexpr uint64_t CASC_CHUNK = 1ull << 27;  // records per launch
 
-uint64_t casc_chunk() {
-  const uint64_t v = env_u64("CTMR_CASCADE_CHUNK");  // tests only: several runs
-  return v ? v : CASC_CHUNK;
-}
+uint64_t casc_chunk() { return known_chunk("CTMR_CASCADE_CHUNK", CASC_CHUNK); }
 
 // One operand before anything is launched: its kept sets in image order as segments, its kept host pairs counted.
 struct CascSide {
@@ -44,22 +41,10 @@ int casc_side(ctmr_engine* e, const KnownMeta& k, const uint8_t* d, int64_t now,
   }
   s->dst.push_back(s->kept);
   s->x.info.members = s->kept;
-  const std::string* prev = nullptr;
-  bool prev_kept = false;
-  for (auto& hm : k.host) {
-    if (!prev || *prev != hm.first) {  // (the section is in key order: a key's date is parsed once)
-      std::string date, id;
-      if (!known_split_key(hm.first, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, hm.first.c_str());
-      int64_t start, end;
-      prev_kept = lists_parse_date(date, &start, &end) && now < end;
-      prev = &hm.first;
-    }
-    s->host_skipped += prev_kept;
-  }
-  return CTMR_OK;
+  return known_kept_host_pairs(e, k, now, what, [&](size_t, bool, const std::string&, int64_t) { s->host_skipped++; });
 }
 
-void casc_pack_side(FindPack* pk, CascSide* s) {
+void casc_pack_side(KnownPack* pk, CascSide* s) {
   s->o_dst = pk->put(s->dst);
   s->o_src = pk->put(s->src);
   s->o_ord = pk->put(s->ord);
@@ -68,8 +53,8 @@ void casc_pack_side(FindPack* pk, CascSide* s) {
 
 // the kept sets [lo, hi) of a side as one run
 CascSrc casc_run(const CascSide& s, const uint8_t* t8, size_t lo, size_t hi) {
-  return CascSrc{FindSegs{s.d, (const uint64_t*)(t8 + s.o_dst) + lo, (const uint64_t*)(t8 + s.o_src) + lo, nullptr,
-                          (const uint32_t*)(t8 + s.o_ord) + lo, (uint32_t)(hi - lo)},
+  return CascSrc{FindSegs{{s.d, (const uint64_t*)(t8 + s.o_dst) + lo, (const uint64_t*)(t8 + s.o_src) + lo, (uint32_t)(hi - lo)},
+                          nullptr, (const uint32_t*)(t8 + s.o_ord) + lo},
                  nullptr, (const uint32_t*)(t8 + s.o_dig)};
 }
 
@@ -80,28 +65,23 @@ struct CascSeq {
   uint64_t n = 0;
 };
 
-// fn(src, records of the run, the blocks in front of it) for every run of the sequence → the blocks of all runs
-template <class F>
-uint64_t casc_runs(const CascSeq& q, const uint8_t* t8, uint64_t chunk, F fn, bool launch = true) {
-  uint64_t blk = 0;
-  if (!q.n) return 0;
-  if (q.list) {
-    for (uint64_t at = 0; at < q.n; at += chunk) {
-      const uint64_t n = std::min(chunk, q.n - at);
-      CascSrc c = casc_run(*q.side, t8, 0, 0);
-      c.list = q.list + at;
-      if (launch) fn(c, n, blk);
-      blk += (n + 255) / 256;
-    }
-  } else {
-    const std::vector<size_t> cut = known_cut_sets(q.side->x, chunk);
-    for (size_t c = 0; c + 1 < cut.size(); c++) {
-      const uint64_t n = q.side->x.first(cut[c + 1]) - q.side->x.first(cut[c]);
-      if (launch) fn(casc_run(*q.side, t8, cut[c], cut[c + 1]), n, blk);
-      blk += (n + 255) / 256;
-    }
+// The runs of a sequence: a side's kept sets as known_cut_sets cuts them, or — the cascade's own — a survivor list cut
+// into runs of `chunk` records, not into whole sets (lo: the run's first entry of the list; no sets).
+std::vector<KnownRun> casc_runs(const CascSeq& q, uint64_t chunk) {
+  if (!q.list) return q.n ? known_cut_sets(q.side->x, chunk) : std::vector<KnownRun>();
+  std::vector<KnownRun> runs;
+  for (uint64_t at = 0; at < q.n; at += chunk) {
+    const uint64_t n = std::min(chunk, q.n - at);
+    runs.push_back(KnownRun{0, 0, at, n, known_runs_blocks(runs)});
   }
-  return blk;
+  return runs;
+}
+
+// where the records of a run of the sequence lie
+CascSrc casc_src(const CascSeq& q, const uint8_t* t8, const KnownRun& run) {
+  CascSrc c = casc_run(*q.side, t8, run.s_lo, run.s_hi);
+  if (q.list) c.list = q.list + run.lo;
+  return c;
 }
 
 CascHash casc_prefix(const uint8_t* salt, uint32_t salt_len) {
@@ -131,8 +111,7 @@ int cascade_core(ctmr_engine* e, const KnownMeta& rm, const uint8_t* d_r, const 
   memset(info, 0, sizeof *info);
   if ((r = casc_params_check(e, p))) return r;
   if ((r = known_bind(e, rm, d_r, what)) || (r = known_bind(e, sm, d_s, what))) return r;
-  if (((uintptr_t)d_r | (uintptr_t)d_s | (host ? 0 : (uintptr_t)out)) & 15u)
-    return fail(e, CTMR_E_INVAL, "%s: device memory that is not 16-byte aligned", what);
+  if ((r = known_aligned16(e, (uintptr_t)d_r | (uintptr_t)d_s | (host ? 0 : (uintptr_t)out), what))) return r;
   CascSide R, S;
   if ((r = casc_side(e, rm, d_r, now, "cascade build (R)", &R)) || (r = casc_side(e, sm, d_s, now, "cascade build (S)", &S))) return r;
   info->r_records = R.kept;
@@ -142,11 +121,10 @@ int cascade_core(ctmr_engine* e, const KnownMeta& rm, const uint8_t* d_r, const 
   info->r_host_skipped = R.host_skipped;
   info->s_host_skipped = S.host_skipped;
   // ---- the tables of both sides in one upload, the error word behind them
-  FindPack pk;
+  KnownPack pk;
   casc_pack_side(&pk, &R);
   casc_pack_side(&pk, &S);
-  const size_t o_err = pk.put(nullptr, 0);
-  pk.b.resize(o_err + 16, 0);
+  const size_t o_err = pk.put_err();
   DevMem tabs;
   if (tabs.alloc(pk.b.size()) != hipSuccess) return fail(e, CTMR_E_NOMEM, "%s: no device memory for the tables", what);
   HIPCHK(e, hipMemcpyAsync(tabs.p, pk.b.data(), pk.b.size(), hipMemcpyHostToDevice, e->stream));
@@ -161,23 +139,23 @@ int cascade_core(ctmr_engine* e, const KnownMeta& rm, const uint8_t* d_r, const 
   // The flags of every test pass, allocated once for the pass with the most blocks: a side where it lies, or all of
   // it as a list (a list is cut into runs of `chunk` records, whole sets are not: either can have more blocks).  No
   // buffer is released before the end of the call: a release would wait for the device in front of every layer.
-  const auto no_launch = [](const CascSrc&, uint64_t, uint64_t) {};
   uint64_t NB_max = 0;
   for (const CascSide* side : {&R, &S}) {
-    NB_max = std::max(NB_max, casc_runs(CascSeq{side, nullptr, side->kept}, t8, chunk, no_launch, false));
-    NB_max = std::max(NB_max, casc_runs(CascSeq{side, (const uint2*)t8, side->kept}, t8, chunk, no_launch, false));
+    NB_max = std::max(NB_max, known_runs_blocks(casc_runs(CascSeq{side, nullptr, side->kept}, chunk)));
+    NB_max = std::max(NB_max, known_runs_blocks(casc_runs(CascSeq{side, (const uint2*)t8, side->kept}, chunk)));
   }
   DevMem flags;
   if (NB_max && flags.alloc((NB_max + 1) * 8 + NB_max * 32) != hipSuccess)
     return fail(e, CTMR_E_NOMEM, "%s: no device memory for the flags of %llu blocks", what, (unsigned long long)NB_max);
-  const SplitFlags fl{(unsigned long long*)(flags.u8() + (NB_max + 1) * 8), (unsigned long long*)flags.p};
+  const KnownFlags fl{(unsigned long long*)(flags.u8() + (NB_max + 1) * 8), (unsigned long long*)flags.p};
   // a test pass over `q`, its scan, and the one count the host reads: how many records passed
   auto tested = [&](const CascSeq& q, const CascLayer& ly, uint64_t* passed) -> int {
-    const uint64_t NB = casc_runs(q, t8, chunk, no_launch, false);
+    const std::vector<KnownRun> runs = casc_runs(q, chunk);
+    const uint64_t NB = known_runs_blocks(runs);
     HIPCHK(e, hipMemsetAsync(flags.p, 0, (NB + 1) * 8, e->stream));
-    casc_runs(q, t8, chunk, [&](const CascSrc& c, uint64_t n, uint64_t blk0) {
-      hipLaunchKernelGGL(k_casc_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, c, n, hp, ly, fl, blk0, d_err);
-    });
+    for (const KnownRun& run : runs)
+      hipLaunchKernelGGL(k_casc_test, dim3((unsigned)run.blocks()), dim3(256), 0, e->stream, casc_src(q, t8, run), run.n, hp, ly, fl,
+                         run.blk0, d_err);
     HIPCHK(e, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, e->stream));
     int rr;
     if ((rr = scan_total(e, (uint64_t*)fl.cnt, NB + 1, false, SC_MISC, passed))) return rr;
@@ -200,9 +178,8 @@ int cascade_core(ctmr_engine* e, const KnownMeta& rm, const uint8_t* d_r, const 
     HIPCHK(e, hipMemsetAsync(bits.back()->p, 0, bytes, e->stream));
     const CascLayer ly{(uint32_t*)bits.back()->p, (uint32_t)m, k, level};
     table.push_back(ctmr_cascade_layer{level, k, m, 0, hold.n});
-    casc_runs(hold, t8, chunk, [&](const CascSrc& c, uint64_t n, uint64_t) {
-      hipLaunchKernelGGL(k_casc_insert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, c, n, hp, ly, d_err);
-    });
+    for (const KnownRun& run : casc_runs(hold, chunk))
+      hipLaunchKernelGGL(k_casc_insert, dim3((unsigned)run.blocks()), dim3(256), 0, e->stream, casc_src(hold, t8, run), run.n, hp, ly, d_err);
     if (!test.n) break;
     uint64_t passed = 0;
     if ((r = tested(test, ly, &passed))) return r;
@@ -216,9 +193,9 @@ int cascade_core(ctmr_engine* e, const KnownMeta& rm, const uint8_t* d_r, const 
     lists.emplace_back(new DevMem);
     if (lists.back()->alloc(passed * 8) != hipSuccess) return fail(e, CTMR_E_NOMEM, "%s: no device memory for %llu survivors", what, (unsigned long long)passed);
     uint2* d_list = (uint2*)lists.back()->p;
-    casc_runs(test, t8, chunk, [&](const CascSrc& c, uint64_t n, uint64_t blk0) {
-      hipLaunchKernelGGL(k_casc_compact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, c, n, fl, blk0, d_list);
-    });
+    for (const KnownRun& run : casc_runs(test, chunk))
+      hipLaunchKernelGGL(k_casc_compact, dim3((unsigned)run.blocks()), dim3(256), 0, e->stream, casc_src(test, t8, run), run.n, fl, run.blk0,
+                         d_list);
     const CascSeq next{test.side, d_list, passed};
     test = hold;
     hold = next;
@@ -317,12 +294,11 @@ int cascade_query_core(ctmr_engine* e, const uint8_t* d_c, const CascHash& hp, c
   for (uint64_t s = 0; s < pm.n_sets; s++) P.x.set_range.push_back({pm.set_first[s], pm.set_first[s + 1] - pm.set_first[s]});
   P.kept = P.x.info.members = pm.n_members;
   if (!P.kept) return CTMR_OK;
-  FindPack pk;
+  KnownPack pk;
   casc_pack_side(&pk, &P);
   std::vector<CascLayer> ls;
   for (auto& l : table) ls.push_back(CascLayer{(uint32_t*)(d_c + l.offset), (uint32_t)l.m_bits, l.k, l.level});
-  const size_t o_ls = pk.put(ls), o_err = pk.put(nullptr, 0);
-  pk.b.resize(o_err + 16, 0);
+  const size_t o_ls = pk.put(ls), o_err = pk.put_err();
   DevMem tabs, stage;
   if (tabs.alloc(pk.b.size()) != hipSuccess || stage.alloc(P.kept) != hipSuccess)
     return fail(e, CTMR_E_NOMEM, "%s: no device memory for the tables and %llu answers", what, (unsigned long long)P.kept);
@@ -330,10 +306,9 @@ int cascade_query_core(ctmr_engine* e, const uint8_t* d_c, const CascHash& hp, c
   const uint8_t* t8 = tabs.u8();
   uint32_t* d_err = (uint32_t*)(t8 + o_err);
   const CascSeq all{&P, nullptr, P.kept};
-  casc_runs(all, t8, casc_chunk(), [&](const CascSrc& c, uint64_t n, uint64_t) {
-    hipLaunchKernelGGL(k_casc_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, c, n, hp, (const CascLayer*)(t8 + o_ls),
-                       (uint32_t)ls.size(), stage.u8(), d_err);
-  });
+  for (const KnownRun& run : casc_runs(all, casc_chunk()))
+    hipLaunchKernelGGL(k_casc_query, dim3((unsigned)run.blocks()), dim3(256), 0, e->stream, casc_src(all, t8, run), run.n, hp,
+                       (const CascLayer*)(t8 + o_ls), (uint32_t)ls.size(), stage.u8(), d_err);
   uint32_t err = 0;
   HIPCHK(e, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -408,15 +383,14 @@ int ctmr_cascade_query_device(ctmr_engine* e, const void* d_cascade, size_t casc
   std::lock_guard<std::mutex> g(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   memset(info, 0, sizeof *info);
-  if (((uintptr_t)d_cascade | (uintptr_t)d_p_members | (uintptr_t)d_out) & 15u)
-    return fail(e, CTMR_E_INVAL, "cascade query: device memory that is not 16-byte aligned");
+  int r;
+  if ((r = known_aligned16(e, (uintptr_t)d_cascade | (uintptr_t)d_p_members | (uintptr_t)d_out, "cascade query"))) return r;
   if (cascade_len < CASC_HEADER) return fail(e, CTMR_E_INVAL, "cascade query: a cascade shorter than its header");
   // ---- the header, then the layer table it announces, to the host
   std::vector<uint8_t> head(CASC_HEADER);
   HIPCHK(e, hipMemcpy(head.data(), d_cascade, CASC_HEADER, hipMemcpyDeviceToHost));
   CascHash hp;
   std::vector<ctmr_cascade_layer> table;
-  int r;
   if ((r = casc_parse(e, head.data(), head.size(), cascade_len, &info->layers, &hp, &table))) return r;
   if (info->layers) {
     head.resize(CASC_HEADER + (size_t)info->layers * CASC_LAYER_BYTES);

@@ -23,18 +23,6 @@ struct FindAcc {
   }
 };
 
-// device tables of one call, packed into one upload: every piece 16-byte aligned
-struct FindPack {
-  std::vector<uint8_t> b;
-  size_t put(const void* p, size_t n) {
-    const size_t at = (b.size() + 15) & ~(size_t)15;
-    b.resize(at + n);
-    if (n) memcpy(&b[at], p, n);
-    return at;
-  }
-  template <class T> size_t put(const std::vector<T>& v) { return put(v.data(), v.size() * sizeof(T)); }
-};
-
 // What a call knows of its two operands before anything is launched — shared with engine/split.inc.  K: the Issuer.IDs
 // it names (K ordinals, per ID string: a digest the image lists twice is one ID), its kept sets in image order as the
 // segments of a virtual record sequence, its kept host pairs.  P: the K ordinal of every set's issuer and of every
@@ -69,8 +57,7 @@ int find_prepare(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const K
                  const void* d_out0, const void* d_out1, const char* what, FindPrep* q) {
   int r;
   if ((r = known_bind(e, k, d_k, what)) || (r = known_bind(e, p, d_p, what))) return r;
-  if (((uintptr_t)d_k | (uintptr_t)d_p | (uintptr_t)d_out0 | (uintptr_t)d_out1) & 15u)
-    return fail(e, CTMR_E_INVAL, "%s: device memory that is not 16-byte aligned", what);
+  if ((r = known_aligned16(e, (uintptr_t)d_k | (uintptr_t)d_p | (uintptr_t)d_out0 | (uintptr_t)d_out1, what))) return r;
   // ---- K: the Issuer.IDs it names (K ordinals), its kept sets in image order, its kept host pairs
   auto kord = [&](const std::string& id) {
     return q->kord_of.emplace(id, (uint32_t)q->kord_of.size()).first->second;
@@ -94,29 +81,15 @@ int find_prepare(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const K
   }
   q->x.info.members = q->kept_records;
   q->sets_kept = q->x.set_range.size();
-  {
-    const std::string* prev = nullptr;
-    bool prev_kept = false;
-    uint32_t ko = 0;
-    int32_t hour = 0;
-    for (size_t j = 0; j < k.host.size(); j++) {
-      auto& hm = k.host[j];
-      if (!prev || *prev != hm.first) {  // (the section is in key order: a key's date is parsed once)
-        std::string date, id;
-        if (!known_split_key(hm.first, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, hm.first.c_str());
-        int64_t start, end;
-        prev_kept = lists_parse_date(date, &start, &end) && now < end;
-        prev = &hm.first;
-        if (prev_kept) {
+  uint32_t ko = 0;
+  if ((r = known_kept_host_pairs(e, k, now, what, [&](size_t j, bool new_key, const std::string& id, int64_t start) {
+        if (new_key) {
           ko = kord(id);
-          hour = (int32_t)(start / 3600);
           q->sets_kept++;
         }
-      }
-      if (!prev_kept) continue;
-      q->kh.push_back({ko, hour, &hm.second, j});
-    }
-  }
+        q->kh.push_back({ko, (int32_t)(start / 3600), &k.host[j].second, j});
+      })))
+    return r;
   // ---- P: the K ordinal of every set's issuer; its host-section members, and those a member record of K can equal as
   // probes of their own
   auto find_kord = [&](const std::string& id) {
@@ -170,7 +143,7 @@ int find_prepare(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const K
 
 // The tables of a FindPrep packed for one upload, and what the kernels are given of them once they lie at t8.
 struct FindTabs {
-  FindPack pk;
+  KnownPack pk;
   size_t o_pfirst, o_pkord, o_xrec, o_xkord, o_dst, o_src, o_hour, o_kord, o_hrec, o_hdst, o_hsrc, o_hhour, o_hkord, o_err;
   void pack(const FindPrep& q, const KnownMeta& p) {
     const uint64_t K = q.x.set_range.size();
@@ -179,8 +152,7 @@ struct FindTabs {
     o_pfirst = pk.put(p.set_first); o_pkord = pk.put(q.p_set_kord); o_xrec = pk.put(q.extra_rec); o_xkord = pk.put(q.extra_kord);
     o_dst = pk.put(dst); o_src = pk.put(q.seg_src); o_hour = pk.put(q.seg_hour); o_kord = pk.put(q.seg_kord);
     o_hrec = pk.put(q.hr_rec); o_hdst = pk.put(q.hr_dst); o_hsrc = pk.put(q.hr_src); o_hhour = pk.put(q.hr_hour); o_hkord = pk.put(q.hr_kord);
-    o_err = pk.put(nullptr, 0);
-    pk.b.resize(o_err + 16, 0);
+    o_err = pk.put_err();
   }
   FindProbes probes(const FindPrep& q, const KnownMeta& p, const uint8_t* t8, const uint8_t* d_p) const {
     FindProbes fp{};
@@ -191,13 +163,13 @@ struct FindTabs {
   }
   // the kept sets [s_lo, s_hi) of K as one run
   FindSegs run(const uint8_t* t8, const uint8_t* d_k, size_t s_lo, size_t s_hi) const {
-    return FindSegs{d_k, (const uint64_t*)(t8 + o_dst) + s_lo, (const uint64_t*)(t8 + o_src) + s_lo, (const int32_t*)(t8 + o_hour) + s_lo,
-                    (const uint32_t*)(t8 + o_kord) + s_lo, (uint32_t)(s_hi - s_lo)};
+    return FindSegs{{d_k, (const uint64_t*)(t8 + o_dst) + s_lo, (const uint64_t*)(t8 + o_src) + s_lo, (uint32_t)(s_hi - s_lo)},
+                    (const int32_t*)(t8 + o_hour) + s_lo, (const uint32_t*)(t8 + o_kord) + s_lo};
   }
   // the host pairs' run
   FindSegs host_run(const FindPrep& q, const uint8_t* t8) const {
-    return FindSegs{t8 + o_hrec, (const uint64_t*)(t8 + o_hdst), (const uint64_t*)(t8 + o_hsrc), (const int32_t*)(t8 + o_hhour),
-                    (const uint32_t*)(t8 + o_hkord), (uint32_t)q.n_hr()};
+    return FindSegs{{t8 + o_hrec, (const uint64_t*)(t8 + o_hdst), (const uint64_t*)(t8 + o_hsrc), (uint32_t)q.n_hr()},
+                    (const int32_t*)(t8 + o_hhour), (const uint32_t*)(t8 + o_hkord)};
   }
 };
 
@@ -240,7 +212,7 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
   const uint64_t nb_fin = (n_probes + 255) / 256;
   FindTabs tb;
   tb.pack(q, p);
-  const FindPack& pk = tb.pk;
+  const KnownPack& pk = tb.pk;
   DevMem tabs, work;
   const size_t off_hits = slots * 8, off_cnt = off_hits + (size_t)n_probes * 16;
   if (tabs.alloc(pk.b.size()) != hipSuccess || work.alloc(off_cnt + (nb_fin + 1) * 8) != hipSuccess)
@@ -257,15 +229,10 @@ int find_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Know
   const FindTable ft{(unsigned long long*)work.p, slots - 1};
   // ---- build, then the runs of K: whole kept sets of at most FIND_CHUNK records, the host pairs' run last
   if (n_probes) hipLaunchKernelGGL(k_find_build, dim3((unsigned)nb_fin), dim3(256), 0, e->stream, fp, ft, d_work, d_err);
-  if (n_probes && kept_records) {
-    const uint64_t forced = env_u64("CTMR_KNOWN_FIND_CHUNK");  // tests only: several runs
-    const std::vector<size_t> cut = known_cut_sets(x, forced ? forced : FIND_CHUNK);
-    for (size_t c = 0; c + 1 < cut.size(); c++) {
-      const uint64_t n = x.first(cut[c + 1]) - x.first(cut[c]);
-      const FindSegs g = tb.run(t8, d_k, cut[c], cut[c + 1]);
-      hipLaunchKernelGGL(k_find_scan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, g, n, ft, fp, n_probes, d_work, d_err);
-    }
-  }
+  if (n_probes && kept_records)
+    for (const KnownRun& run : known_cut_sets(x, known_chunk("CTMR_KNOWN_FIND_CHUNK", FIND_CHUNK)))
+      hipLaunchKernelGGL(k_find_scan, dim3((unsigned)run.blocks()), dim3(256), 0, e->stream, tb.run(t8, d_k, run.s_lo, run.s_hi), run.n, ft,
+                         fp, n_probes, d_work, d_err);
   if (n_hr) {
     const FindSegs g = tb.host_run(q, t8);
     hipLaunchKernelGGL(k_find_scan, dim3((unsigned)((n_hr + 255) / 256)), dim3(256), 0, e->stream, g, n_hr, ft, fp, n_main, d_work, d_err);

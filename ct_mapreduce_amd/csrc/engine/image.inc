@@ -217,17 +217,62 @@ struct KnownExport {
   uint64_t first(size_t s) const { return s < set_range.size() ? set_range[s].first : info.members; }
 };
 
-// The sets cut into runs of whole sets of at most `limit` records, a larger set standing alone: the set index at which
-// each run starts, then the number of sets.
-std::vector<size_t> known_cut_sets(const KnownExport& x, uint64_t limit) {
-  std::vector<size_t> cut{0};
+// The runs of a call, the one copy of the image's calls (DESIGN.md §12): the sets cut into runs of whole sets of at most
+// `limit` records, a larger set standing alone.  A run is the sets [s_lo, s_hi): n records from record `lo` on, which
+// a launch of one lane per record takes as blocks() blocks of 256 — blk0 of them lie in front of it in the runs before
+// (where a call numbers its blocks through all its runs: kernels/image.h, KnownFlags).
+struct KnownRun {
+  size_t s_lo, s_hi;
+  uint64_t lo, n, blk0;
+  uint64_t blocks() const { return (n + 255) / 256; }
+};
+
+std::vector<KnownRun> known_cut_sets(const KnownExport& x, uint64_t limit) {
+  std::vector<KnownRun> runs;
+  uint64_t blk0 = 0;
   for (size_t s = 0; s < x.set_range.size();) {
     size_t t = s + 1;
     while (t < x.set_range.size() && x.first(t + 1) - x.first(s) <= limit) t++;
-    cut.push_back(t);
+    runs.push_back(KnownRun{s, t, x.first(s), x.first(t) - x.first(s), blk0});
+    blk0 += runs.back().blocks();
     s = t;
   }
-  return cut;
+  return runs;
+}
+
+// the blocks of all runs
+uint64_t known_runs_blocks(const std::vector<KnownRun>& runs) { return runs.empty() ? 0 : runs.back().blk0 + runs.back().blocks(); }
+
+// The call's chunk, records per run: the override `name` (a CTMR_*_CHUNK variable, tests only: it forces several small
+// runs), else the call's default.
+uint64_t known_chunk(const char* name, uint64_t dflt) {
+  const uint64_t v = env_u64(name);
+  return v && v < dflt ? v : dflt;
+}
+
+// The device tables of one call, packed into one upload: every piece 16-byte aligned.
+struct KnownPack {
+  std::vector<uint8_t> b;
+  size_t put(const void* p, size_t n) {
+    const size_t at = (b.size() + 15) & ~(size_t)15;
+    b.resize(at + n);
+    if (n) memcpy(&b[at], p, n);
+    return at;
+  }
+  template <class T> size_t put(const std::vector<T>& v) { return put(v.data(), v.size() * sizeof(T)); }
+  // the error word of the call's kernels (kernels/image.h: known_report_bad), zeroed, behind what was put so far
+  size_t put_err() {
+    const size_t at = put(nullptr, 0);
+    b.resize(at + 16, 0);
+    return at;
+  }
+};
+
+// The calls that read member records with 16-byte loads from wherever the caller has them refuse other addresses
+// (ptrs: the call's device pointers or-ed together).
+int known_aligned16(ctmr_engine* e, uintptr_t ptrs, const char* what) {
+  if (ptrs & 15u) return fail(e, CTMR_E_INVAL, "%s: device memory that is not 16-byte aligned", what);
+  return CTMR_OK;
 }
 
 int known_export_prepare(ctmr_engine* e, KnownExport* x) {
@@ -549,11 +594,8 @@ int known_import_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_memb
 // ---- bulk SetContains / SetRemove over an image's member records (include/ctmr.h ctmr_known_query* / ctmr_known_remove*,
 // DESIGN.md §14)
 
-// records per pass, as import's; CTMR_KNOWN_PROBE_CHUNK (tests only) forces small passes
-uint64_t known_probe_chunk() {
-  const uint64_t v = env_u64("CTMR_KNOWN_PROBE_CHUNK");
-  return v && v < KNOWN_CHUNK ? v : KNOWN_CHUNK;
-}
+// records per pass, as import's
+uint64_t known_probe_chunk() { return known_chunk("CTMR_KNOWN_PROBE_CHUNK", KNOWN_CHUNK); }
 
 // records per lane of k_known_query / k_known_remove: KNOWN_PROBE_RPL was the fastest of 1, 2, 4, 8 (DESIGN.md §14);
 // CTMR_KNOWN_PROBE_RPL selects another for scripts/bench_known_query.py's sweep and the tests of every instantiation
@@ -693,15 +735,14 @@ int ctmr_known_export(ctmr_engine* e, uint8_t* out, size_t cap, ctmr_known_image
       if (stage <= (1ull << 20)) return fail(e, CTMR_E_NOMEM, "known export: no device memory to stage the member records");
       stage /= 2;
     }
-    const std::vector<size_t> cut = known_cut_sets(x, stage);
-    for (size_t c = 0; c + 1 < cut.size(); c++) {
-      const uint64_t lo = x.first(cut[c]), n = x.first(cut[c + 1]) - lo;
+    for (const KnownRun& run : known_cut_sets(x, stage)) {
+      const uint64_t n = run.n;
       DevMem big;  // one set larger than the staging buffer: staged alone
       if (n > stage && big.alloc(n * KNOWN_REC_BYTES) != hipSuccess)
         return fail(e, CTMR_E_NOMEM, "known export: no device memory to stage a set of %llu members", (unsigned long long)n);
       uint8_t* buf = n > stage ? big.u8() : d.u8();
-      if ((r = known_export_members(e, x, cut[c], cut[c + 1], buf))) return r;
-      HIPCHK(e, hipMemcpy(out + x.info.meta_bytes + lo * KNOWN_REC_BYTES, buf, n * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
+      if ((r = known_export_members(e, x, run.s_lo, run.s_hi, buf))) return r;
+      HIPCHK(e, hipMemcpy(out + x.info.meta_bytes + run.lo * KNOWN_REC_BYTES, buf, n * KNOWN_REC_BYTES, hipMemcpyDeviceToHost));
     }
   }
   memcpy(out, x.meta.data(), x.meta.size());

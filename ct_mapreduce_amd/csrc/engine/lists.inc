@@ -68,6 +68,29 @@ bool known_split_key(const std::string& k, std::string* date, std::string* id) {
   return true;
 }
 
+// The kept host pairs of a meta: f(j, new_key, id, start) for every pair j of km.host, in order, whose key's expDate has
+// not ended at `now` (id, start: the key's Issuer.ID and the first second of its expDate; new_key: the pair is the
+// first kept one of its key).  The section is in key order, so a key is split and its date parsed once; a key that
+// does not split is an error where it is met.
+template <class F>
+int known_kept_host_pairs(ctmr_engine* e, const KnownMeta& km, int64_t now, const char* what, F f) {
+  const std::string* prev = nullptr;
+  bool kept = false;
+  std::string date, id;
+  int64_t start = 0, end = 0;
+  for (size_t j = 0; j < km.host.size(); j++) {
+    const std::string& key = km.host[j].first;
+    const bool new_key = !prev || *prev != key;
+    if (new_key) {
+      if (!known_split_key(key, &date, &id)) return fail(e, CTMR_E_INVAL, "%s: unexpected key format: %s", what, key.c_str());
+      kept = lists_parse_date(date, &start, &end) && now < end;
+      prev = &key;
+    }
+    if (kept) f(j, new_key, id, start);
+  }
+  return CTMR_OK;
+}
+
 // Which sets, grouped and ordered: the device sets `dev` (kept ones only; ids[rank] = the Issuer.ID of a rank, ascending)
 // and the serials:: keys of `store`, kept while now < the end of their expDate; per Issuer.ID ascending, expDates
 // ascending (by their first second, then as strings).
@@ -206,17 +229,17 @@ int image_lists_upload(ctmr_engine* e, const KnownLists& L, ListSource* src) {
   return CTMR_OK;
 }
 
-// Device records [lo, hi) of the list order, staged and counted: *bytes = their text, cnt[] their block offsets.
+// The device records of a run of the list order, staged and counted: *bytes = their text, cnt[] their block offsets.
 // ordered: as known_export_members takes it (the text's size does not depend on the order).
 // An image's segments are counted where they lie, and every record read is validated.
-int known_lists_count(ctmr_engine* e, KnownLists& L, const ListSource& src, size_t s_lo, size_t s_hi, uint8_t* d_rec,
+int known_lists_count(ctmr_engine* e, KnownLists& L, const ListSource& src, const KnownRun& run, uint8_t* d_rec,
                       unsigned long long* cnt, uint64_t* bytes, bool ordered) {
   int r;
-  if (!src.segments && (r = known_export_members(e, L.x, s_lo, s_hi, d_rec, ordered))) return r;
-  const uint64_t n = L.x.first(s_hi) - L.x.first(s_lo), nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
+  if (!src.segments && (r = known_export_members(e, L.x, run.s_lo, run.s_hi, d_rec, ordered))) return r;
+  const uint64_t n = run.n, nb = run.blocks();
   HIPCHK(e, hipMemsetAsync(cnt + nb, 0, 8, e->stream));
   if (!src.segments) hipLaunchKernelGGL(k_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec, n, cnt);
-  else if (n) hipLaunchKernelGGL(k_image_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, src.segs(s_lo, s_hi), n, cnt, src.err());
+  else if (n) hipLaunchKernelGGL(k_image_lists_count, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, src.segs(run.s_lo, run.s_hi), n, cnt, src.err());
   if ((r = scan_u64(e, (uint64_t*)cnt, nb + 1, false, SC_MISC))) return r;
   unsigned long long b;
   uint32_t err = 0;
@@ -241,10 +264,9 @@ int known_lists_emit(ctmr_engine* e, KnownLists& L, const ListSource& src, bool 
   info->members = N;
   info->host_members = L.host_members;
   info->ids_bytes = ids_bytes;
-  // chunks: runs of whole sets of at most `chunk` records (a larger set alone); the test-only override forces small ones
-  const uint64_t forced = env_u64("CTMR_KNOWN_LISTS_CHUNK");
-  const std::vector<size_t> cut = known_cut_sets(L.x, forced ? forced : LISTS_CHUNK);  // set index at each chunk start, then the end
-  const size_t nch = cut.size() - 1;
+  // chunks: the runs of whole sets (known_cut_sets)
+  const std::vector<KnownRun> runs = known_cut_sets(L.x, known_chunk("CTMR_KNOWN_LISTS_CHUNK", LISTS_CHUNK));
+  const size_t nch = runs.size();
   // points: the device record at which each list starts and each host-store piece goes in (ascending, unique)
   std::vector<uint64_t> pts;
   {
@@ -257,8 +279,8 @@ int known_lists_emit(ctmr_engine* e, KnownLists& L, const ListSource& src, bool 
   size_t max_pts = 0;
   uint64_t max_n = 0;
   for (size_t c = 0; c < nch; c++) {
-    const uint64_t lo = L.x.first(cut[c]), hi = L.x.first(cut[c + 1]);
-    max_n = std::max(max_n, hi - lo);
+    const uint64_t lo = runs[c].lo, hi = lo + runs[c].n;
+    max_n = std::max(max_n, runs[c].n);
     max_pts = std::max(max_pts, (size_t)(std::lower_bound(pts.begin(), pts.end(), hi) - std::lower_bound(pts.begin(), pts.end(), lo)));
   }
   DevMem d_rec, tmp, d_text;
@@ -276,7 +298,7 @@ int known_lists_emit(ctmr_engine* e, KnownLists& L, const ListSource& src, bool 
   if (sized) {
     uint64_t dev_bytes = 0;
     for (size_t c = 0; c < nch; c++) {
-      if ((r = known_lists_count(e, L, src, cut[c], cut[c + 1], d_rec.u8(), cnt, &chunk_bytes[c], nch <= 1))) return r;
+      if ((r = known_lists_count(e, L, src, runs[c], d_rec.u8(), cnt, &chunk_bytes[c], nch <= 1))) return r;
       dev_bytes += chunk_bytes[c];
     }
     info->text_bytes = dev_bytes + L.host_bytes;
@@ -294,7 +316,7 @@ int known_lists_emit(ctmr_engine* e, KnownLists& L, const ListSource& src, bool 
   };
   if (src.segments) {  // every buffer before the first text byte: the largest chunk that is staged as text
     for (size_t c = 0; c < nch; c++)
-      if (!device || splits(L.x.first(cut[c]), L.x.first(cut[c + 1]))) text_cap_dev = std::max<size_t>(text_cap_dev, chunk_bytes[c]);
+      if (!device || splits(runs[c].lo, runs[c].lo + runs[c].n)) text_cap_dev = std::max<size_t>(text_cap_dev, chunk_bytes[c]);
     if (text_cap_dev && d_text.alloc(text_cap_dev) != hipSuccess)
       return fail(e, CTMR_E_NOMEM, "%s: no device memory to stage %llu text bytes", src.what, (unsigned long long)text_cap_dev);
   }
@@ -303,10 +325,10 @@ int known_lists_emit(ctmr_engine* e, KnownLists& L, const ListSource& src, bool 
     return k ? L.host[k - 1].hb + L.host[k - 1].text.size() : 0ull;
   };
   for (size_t c = 0; c < nch; c++) {
-    const uint64_t lo = L.x.first(cut[c]), hi = L.x.first(cut[c + 1]);
+    const uint64_t lo = runs[c].lo, n = runs[c].n, hi = lo + n, nb = runs[c].blocks();
     uint64_t bytes = chunk_bytes[c];
     if (nch > 1)  // (one chunk: still staged and scanned from the sizing pass)
-      if ((r = known_lists_count(e, L, src, cut[c], cut[c + 1], d_rec.u8(), cnt, &bytes, true))) return r;
+      if ((r = known_lists_count(e, L, src, runs[c], d_rec.u8(), cnt, &bytes, true))) return r;
     const size_t p0 = std::lower_bound(pts.begin(), pts.end(), lo) - pts.begin();
     const size_t p1 = std::lower_bound(pts.begin(), pts.end(), hi) - pts.begin();
     std::vector<uint64_t> rel(p1 - p0);
@@ -328,12 +350,11 @@ int known_lists_emit(ctmr_engine* e, KnownLists& L, const ListSource& src, bool 
     uint64_t* d_pts = (uint64_t*)(tmp.u8() + off_pts);
     unsigned long long* d_po = (unsigned long long*)(tmp.u8() + off_po);
     if (!rel.empty()) HIPCHK(e, hipMemcpyAsync(d_pts, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, e->stream));
-    const uint64_t n = hi - lo, nb = (n + LIST_BLOCK - 1) / LIST_BLOCK;
     if (!src.segments)
       hipLaunchKernelGGL(k_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, (const uint8_t*)d_rec.p, n,
                          (const unsigned long long*)cnt, dest, (const uint64_t*)d_pts, (uint64_t)rel.size(), d_po);
     else if (n)
-      hipLaunchKernelGGL(k_image_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, src.segs(cut[c], cut[c + 1]), n,
+      hipLaunchKernelGGL(k_image_lists_write, dim3((unsigned)nb), dim3(LIST_BLOCK), 0, e->stream, src.segs(runs[c].s_lo, runs[c].s_hi), n,
                          (const unsigned long long*)cnt, dest, (const uint64_t*)d_pts, (uint64_t)rel.size(), d_po);
     if (!rel.empty()) HIPCHK(e, hipMemcpyAsync(&D[p0], d_po, rel.size() * 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));

@@ -110,21 +110,20 @@ struct RespDev {
   unsigned long long* cnt() const { return (unsigned long long*)(t8() + off_cnt); }
   uint64_t* pts() const { return (uint64_t*)(t8() + off_pts); }
   unsigned long long* pt_off() const { return (unsigned long long*)(t8() + off_po); }
-  RespArgs args(const KnownResp& R, size_t s_lo, size_t s_hi) const {
-    return RespArgs{members + R.x.first(s_lo) * KNOWN_REC_BYTES, (const uint64_t*)t8() + s_lo,
-                    (const unsigned long long*)(t8() + off_meta) + s_lo, t8() + off_ids, (uint32_t)(s_hi - s_lo), per};
+  RespArgs args(const KnownRun& run) const {
+    return RespArgs{members + run.lo * KNOWN_REC_BYTES, (const uint64_t*)t8() + run.s_lo,
+                    (const unsigned long long*)(t8() + off_meta) + run.s_lo, t8() + off_ids, (uint32_t)(run.s_hi - run.s_lo), per};
   }
 };
 
-// The count pass over sets [s_lo, s_hi) and its scan: cnt[] = the block offsets, *bytes = the text of the chunk,
+// The count pass over a run and its scan: cnt[] = the block offsets, *bytes = the text of the chunk,
 // *max_block = the text of its largest block.
-int known_resp_count(ctmr_engine* e, const KnownResp& R, const RespDev& d, size_t s_lo, size_t s_hi, uint64_t* bytes,
-                     uint32_t* max_block) {
-  const uint64_t n = R.x.first(s_hi) - R.x.first(s_lo), nb = (n + RESP_BLOCK - 1) / RESP_BLOCK;
+int known_resp_count(ctmr_engine* e, const RespDev& d, const KnownRun& run, uint64_t* bytes, uint32_t* max_block) {
+  const uint64_t n = run.n, nb = run.blocks();
   int r;
   HIPCHK(e, hipMemsetAsync(d.cnt() + nb, 0, 8, e->stream));
   HIPCHK(e, hipMemsetAsync(d.err() + 1, 0, 4, e->stream));
-  hipLaunchKernelGGL(k_image_resp_count, dim3((unsigned)nb), dim3(RESP_BLOCK), 0, e->stream, d.args(R, s_lo, s_hi), n, d.cnt(), d.err());
+  hipLaunchKernelGGL(k_image_resp_count, dim3((unsigned)nb), dim3(RESP_BLOCK), 0, e->stream, d.args(run), n, d.cnt(), d.err());
   if ((r = scan_u64(e, (uint64_t*)d.cnt(), nb + 1, false, SC_MISC))) return r;
   unsigned long long b = 0;
   uint32_t err[2] = {0u, 0u};  // the error bits, the largest block
@@ -155,10 +154,9 @@ int known_resp_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_member
   info->commands = R.host_commands;
   for (uint64_t s = 0; s < S; s++)
     info->commands += (R.x.set_range[s].second + per - 1) / per + ((R.meta[s] & RESP_NO_EXPIRE) ? 0 : 1);
-  // chunks: runs of whole sets of at most `chunk` records (a larger set alone); the test-only override forces small ones
-  const uint64_t forced = env_u64("CTMR_KNOWN_RESP_CHUNK");
-  const std::vector<size_t> cut = known_cut_sets(R.x, forced ? forced : RESP_CHUNK);
-  const size_t nch = cut.size() - 1;
+  // chunks: the runs of whole sets (known_cut_sets)
+  const std::vector<KnownRun> runs = known_cut_sets(R.x, known_chunk("CTMR_KNOWN_RESP_CHUNK", RESP_CHUNK));
+  const size_t nch = runs.size();
   // points: the records in front of which host pieces go (ascending, unique); those strictly inside a chunk split its text
   std::vector<uint64_t> pts;
   for (auto& p : R.pieces)
@@ -170,10 +168,9 @@ int known_resp_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_member
   uint64_t max_n = 0;
   size_t max_pts = 0;
   for (size_t c = 0; c < nch; c++) {
-    const uint64_t lo = R.x.first(cut[c]), hi = R.x.first(cut[c + 1]);
     size_t p0, p1;
-    inner(lo, hi, &p0, &p1);
-    max_n = std::max(max_n, hi - lo);
+    inner(runs[c].lo, runs[c].lo + runs[c].n, &p0, &p1);
+    max_n = std::max(max_n, runs[c].n);
     max_pts = std::max(max_pts, p1 - p0);
   }
   RespDev d;
@@ -202,7 +199,7 @@ int known_resp_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_member
   uint64_t dev_bytes = 0;
   uint32_t max_block = 0;
   for (size_t c = 0; c < nch; c++) {
-    if ((r = known_resp_count(e, R, d, cut[c], cut[c + 1], &chunk_bytes[c], &max_block))) return r;
+    if ((r = known_resp_count(e, d, runs[c], &chunk_bytes[c], &max_block))) return r;
     dev_bytes += chunk_bytes[c];
   }
   info->text_bytes = dev_bytes + R.host_bytes;
@@ -213,7 +210,7 @@ int known_resp_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_member
   size_t stage = 0;
   for (size_t c = 0; c < nch; c++) {
     size_t p0, p1;
-    inner(R.x.first(cut[c]), R.x.first(cut[c + 1]), &p0, &p1);
+    inner(runs[c].lo, runs[c].lo + runs[c].n, &p0, &p1);
     if (!device || p1 > p0) stage = std::max<size_t>(stage, chunk_bytes[c]);
   }
   if (stage && d_text.alloc(stage) != hipSuccess)
@@ -227,10 +224,10 @@ int known_resp_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_member
   std::vector<uint64_t> D(pts.size(), 0);  // the device text in front of each point
   uint64_t base = 0;
   for (size_t c = 0; c < nch; c++) {
-    const uint64_t lo = R.x.first(cut[c]), hi = R.x.first(cut[c + 1]), n = hi - lo, nb = (n + RESP_BLOCK - 1) / RESP_BLOCK;
+    const uint64_t lo = runs[c].lo, n = runs[c].n, hi = lo + n, nb = runs[c].blocks();
     uint64_t bytes = chunk_bytes[c];
     if (nch > 1)  // (one chunk: cnt[] still holds the sizing pass's scan)
-      if ((r = known_resp_count(e, R, d, cut[c], cut[c + 1], &bytes, &max_block))) return r;
+      if ((r = known_resp_count(e, d, runs[c], &bytes, &max_block))) return r;
     size_t p0, p1;
     inner(lo, hi, &p0, &p1);
     const bool split = p1 > p0;
@@ -238,7 +235,7 @@ int known_resp_core(ctmr_engine* e, const KnownMeta& km, const uint8_t* d_member
     for (size_t k = p0; k < p1; k++) rel[k - p0] = pts[k] - lo;
     if (split) HIPCHK(e, hipMemcpyAsync(d.pts(), rel.data(), rel.size() * 8, hipMemcpyHostToDevice, e->stream));
     uint8_t* dest = device && !split ? text + base + hb_le(lo) : d_text.u8();
-    hipLaunchKernelGGL(k_image_resp_write, dim3((unsigned)nb), dim3(RESP_BLOCK), resp_lds_bytes(max_block), e->stream, d.args(R, cut[c], cut[c + 1]), n,
+    hipLaunchKernelGGL(k_image_resp_write, dim3((unsigned)nb), dim3(RESP_BLOCK), resp_lds_bytes(max_block), e->stream, d.args(runs[c]), n,
                        (const unsigned long long*)d.cnt(), dest, (const uint64_t*)d.pts(), (uint64_t)rel.size(), d.pt_off());
     if (split) HIPCHK(e, hipMemcpyAsync(&D[p0], d.pt_off(), rel.size() * 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));

@@ -9,11 +9,7 @@ namespace {
 
 constexpr uint64_t SORT_CHUNK = 1ull << 27;  // records per run (32-bit perm and group, bounded working memory)
 
-// records per run; CTMR_KNOWN_SORT_CHUNK (tests only) forces small runs
-uint64_t known_sort_chunk() {
-  const uint64_t v = env_u64("CTMR_KNOWN_SORT_CHUNK");
-  return v && v < SORT_CHUNK ? v : SORT_CHUNK;
-}
+uint64_t known_sort_chunk() { return known_chunk("CTMR_KNOWN_SORT_CHUNK", SORT_CHUNK); }
 
 uint32_t bits_of(uint64_t v) {  // bits needed for the values 0..v
   uint32_t b = 0;
@@ -45,15 +41,17 @@ struct SortWork {
 
 struct SortInfo { uint64_t records = 0, runs = 0; uint32_t rounds = 0, passes = 0; };
 
-// One run: records [lo, lo + n) of d_rec, sets [s0, s1) of first[] (host) / d_first[] (device), both in records of d_rec.
-int known_sort_run(ctmr_engine* e, uint8_t* d_rec, uint64_t lo, uint64_t n, const std::vector<uint64_t>& first,
-                   const uint64_t* d_first, size_t s0, size_t s1, SortWork& w, SortInfo* si) {
+// One run of d_rec's records: its sets are those of first[] (host) / d_first[] (device), both in records of d_rec.
+int known_sort_run(ctmr_engine* e, uint8_t* d_rec, const KnownRun& run, const std::vector<uint64_t>& first,
+                   const uint64_t* d_first, SortWork& w, SortInfo* si) {
+  const size_t s0 = run.s_lo, s1 = run.s_hi;
+  const uint64_t lo = run.lo, n = run.n;
   uint64_t tied = 0;  // records that share their set with another
   for (size_t s = s0; s < s1; s++)
     if (first[s + 1] - first[s] > 1) tied += first[s + 1] - first[s];
   si->runs++;
   if (!tied) return CTMR_OK;
-  const uint64_t nb = (n + SORT_TILE - 1) / SORT_TILE, nb2 = (n + 255) / 256;
+  const uint64_t nb = (n + SORT_TILE - 1) / SORT_TILE, nb2 = run.blocks();
   int r;
   hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)nb2), dim3(256), 0, e->stream, (const uint8_t*)d_rec, lo, n,
                      d_first + s0, (uint32_t)(s1 - s0), w.a);
@@ -110,9 +108,9 @@ int known_sort_sets(ctmr_engine* e, uint8_t* d_rec, const std::vector<uint64_t>&
     KnownExport x;  // (known_cut_sets reads the set ranges alone)
     for (size_t s = 0; s < ns; s++) x.set_range.push_back({first[s], first[s + 1] - first[s]});
     x.info.members = N;
-    const std::vector<size_t> cut = known_cut_sets(x, known_sort_chunk());
+    const std::vector<KnownRun> runs = known_cut_sets(x, known_sort_chunk());
     uint64_t max_n = 0;
-    for (size_t c = 0; c + 1 < cut.size(); c++) max_n = std::max(max_n, first[cut[c + 1]] - first[cut[c]]);
+    for (const KnownRun& run : runs) max_n = std::max(max_n, run.n);
     if (max_n > 0xffffffffull) return fail(e, CTMR_E_NOMEM, "known sort: a set of %llu members", (unsigned long long)max_n);
     SortWork w;
     DevMem d_first;
@@ -121,10 +119,8 @@ int known_sort_sets(ctmr_engine* e, uint8_t* d_rec, const std::vector<uint64_t>&
       return fail(e, CTMR_E_NOMEM, "known sort: no device memory for the working buffers of %llu member records", (unsigned long long)max_n);
     if ((r = ensure(e, SC_TMP, ((256 * ((max_n + SORT_TILE - 1) / SORT_TILE) + SCAN_TILE - 1) / SCAN_TILE) * 8))) return r;
     HIPCHK(e, hipMemcpyAsync(d_first.p, first.data(), (ns + 1) * 8, hipMemcpyHostToDevice, e->stream));
-    for (size_t c = 0; c + 1 < cut.size(); c++)
-      if ((r = known_sort_run(e, d_rec, first[cut[c]], first[cut[c + 1]] - first[cut[c]], first, (const uint64_t*)d_first.p,
-                              cut[c], cut[c + 1], w, &si)))
-        return r;
+    for (const KnownRun& run : runs)
+      if ((r = known_sort_run(e, d_rec, run, first, (const uint64_t*)d_first.p, w, &si))) return r;
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
   if (env_u64("CTMR_KNOWN_SORT_INFO"))  // tests and scripts/bench_known_sort.py read the round count here

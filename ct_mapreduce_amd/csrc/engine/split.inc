@@ -69,11 +69,8 @@ int split_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Kno
     return fail(e, CTMR_E_NOMEM, "%s: %llu kept sets, %llu probes", what, (unsigned long long)K, (unsigned long long)n_probes);
   // ---- the runs: whole kept sets of at most FIND_CHUNK records; blocks are numbered through all of them, the host
   // pairs' run behind the last
-  const uint64_t forced = env_u64("CTMR_KNOWN_SPLIT_CHUNK");  // tests only: several runs
-  const std::vector<size_t> cut = q.kept_records ? known_cut_sets(x, forced ? forced : FIND_CHUNK) : std::vector<size_t>{0};
-  std::vector<uint64_t> blk0(cut.size(), 0);
-  for (size_t c = 0; c + 1 < cut.size(); c++) blk0[c + 1] = blk0[c] + (x.first(cut[c + 1]) - x.first(cut[c]) + 255) / 256;
-  const uint64_t NB = blk0.back(), nb_hr = (n_hr + 255) / 256, nb_build = (n_probes + 255) / 256;
+  const std::vector<KnownRun> runs = known_cut_sets(x, known_chunk("CTMR_KNOWN_SPLIT_CHUNK", FIND_CHUNK));
+  const uint64_t NB = known_runs_blocks(runs), nb_hr = (n_hr + 255) / 256, nb_build = (n_probes + 255) / 256;
   // ---- every working buffer but the host variant's staged results: the tables in one upload, the probe table and the
   // working hits (the probes' K ordinals), the flags
   const uint64_t forced_slots = env_u64("CTMR_KNOWN_FIND_SLOTS");  // tests only: the smallest table, so that chains are long
@@ -96,29 +93,25 @@ int split_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Kno
   uint4* d_work = (uint4*)(work.u8() + off_hits);
   unsigned long long* d_cnt = (unsigned long long*)flags.p;
   unsigned long long* d_before = (unsigned long long*)(flags.u8() + off_before);
-  const SplitFlags sf{(unsigned long long*)(flags.u8() + off_ball), d_cnt};
-  const SplitFlags sf_hr{sf.ball + NB * 4, (unsigned long long*)(flags.u8() + off_hcnt)};
+  const KnownFlags sf{(unsigned long long*)(flags.u8() + off_ball), d_cnt};
+  const KnownFlags sf_hr{sf.ball + NB * 4, (unsigned long long*)(flags.u8() + off_hcnt)};
   const FindProbes fp = tb.probes(q, p, t8, d_p);
   const FindTable ft{(unsigned long long*)work.p, slots - 1};
   // ---- build, then the mark pass over the runs of K and over the host pairs' run: every record of P and of a kept set
   // of K is validated here, before anything is written
   if (n_probes) hipLaunchKernelGGL(k_find_build, dim3((unsigned)nb_build), dim3(256), 0, e->stream, fp, ft, d_work, d_err);
-  for (size_t c = 0; c + 1 < cut.size(); c++) {
-    const uint64_t n = x.first(cut[c + 1]) - x.first(cut[c]);
-    hipLaunchKernelGGL(k_split_mark, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, tb.run(t8, d_k, cut[c], cut[c + 1]), n, ft,
-                       fp, n_probes, (const uint4*)d_work, sf, blk0[c], d_err);
-  }
+  for (const KnownRun& run : runs)
+    hipLaunchKernelGGL(k_split_mark, dim3((unsigned)run.blocks()), dim3(256), 0, e->stream, tb.run(t8, d_k, run.s_lo, run.s_hi), run.n, ft,
+                       fp, n_probes, (const uint4*)d_work, sf, run.blk0, d_err);
   if (n_hr)
     hipLaunchKernelGGL(k_split_mark, dim3((unsigned)nb_hr), dim3(256), 0, e->stream, tb.host_run(q, t8), n_hr, ft, fp, q.n_main,
                        (const uint4*)d_work, sf_hr, (uint64_t)0, d_err);
   // ---- the hits in front of every block (one scan through all runs: the base carries from run to run in cnt[]) and
   // in front of every kept set
   if ((r = scan_u64(e, (uint64_t*)d_cnt, NB + 1, false, SC_MISC))) return r;
-  for (size_t c = 0; c + 1 < cut.size(); c++) {
-    const uint64_t ns = cut[c + 1] - cut[c];
-    hipLaunchKernelGGL(k_split_sets, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, e->stream, tb.run(t8, d_k, cut[c], cut[c + 1]), sf,
-                       blk0[c], d_before + cut[c]);
-  }
+  for (const KnownRun& run : runs)
+    hipLaunchKernelGGL(k_split_sets, dim3((unsigned)((run.s_hi - run.s_lo + 255) / 256)), dim3(256), 0, e->stream,
+                       tb.run(t8, d_k, run.s_lo, run.s_hi), sf, run.blk0, d_before + run.s_lo);
   uint32_t err = 0;
   std::vector<unsigned long long> before(K + 1, 0ull), hr_ball(nb_hr * 4);
   HIPCHK(e, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, e->stream));
@@ -167,11 +160,9 @@ int split_core(ctmr_engine* e, const KnownMeta& k, const uint8_t* d_k, const Kno
   uint8_t* to_hit = hit.want && info->hit.members ? hit.d_rec : nullptr;
   uint8_t* to_miss = miss.want && info->miss.members ? miss.d_rec : nullptr;
   if (to_hit || to_miss)
-    for (size_t c = 0; c + 1 < cut.size(); c++) {
-      const uint64_t n = x.first(cut[c + 1]) - x.first(cut[c]);
-      hipLaunchKernelGGL(k_split_place, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, tb.run(t8, d_k, cut[c], cut[c + 1]), n, sf,
-                         blk0[c], to_hit, to_miss);
-    }
+    for (const KnownRun& run : runs)
+      hipLaunchKernelGGL(k_split_place, dim3((unsigned)run.blocks()), dim3(256), 0, e->stream, tb.run(t8, d_k, run.s_lo, run.s_hi), run.n, sf,
+                         run.blk0, to_hit, to_miss);
   // ---- each wanted image out: its meta, and for the host variant the staged records behind it
   auto deliver = [&](const SplitSide& s, const std::vector<uint8_t>& m, uint64_t members) -> int {
     if (!s.want) return CTMR_OK;

@@ -1,9 +1,9 @@
 // kernels/cascade.h — the CRLite filter cascade of a revoked / not-revoked image pair (include/ctmr.h ctmr_cascade_*,
 // DESIGN.md §29): Bloom filter layers whose hash functions are SHA-256 over salt ‖ u32le(i) ‖ u8(level) ‖ key, the key a
 // member record's 32-byte issuer digest and its serial octets.  k_casc_insert sets the bits of the records a layer
-// holds, k_casc_test leaves one flag bit per record that passes the layer (a ballot word per wave) and one count per
-// block, as k_split_mark does; after a scan of the counts k_casc_compact writes the survivors as (record index, issuer
-// ordinal) pairs at their ranks (split_rank), the list the next layers read instead of the image.  k_casc_query walks a
+// holds, k_casc_test leaves the flags of the pass (KnownFlags, kernels/image.h): one bit per record that passes the
+// layer; after a scan of the counts k_casc_compact writes the survivors as (record index, issuer ordinal) pairs at
+// their ranks (known_flags_before), the list the next layers read instead of the image.  k_casc_query walks a
 // finished cascade for every member record of a probe image.
 // One lane per record; the message is assembled in registers and hashed in one or two sha256_compress per hash function.
 // No cross-workgroup publish, no spin-wait; the global atomics are the bits' atomicOr (no return value used) and the
@@ -14,8 +14,8 @@
 
 namespace ctmr {
 
-// Where the records of a launch lie.  list == null: the run of whole kept sets g, addressed as k_find_scan addresses it
-// (g.kord: the issuer ordinal of each set in the image's own issuer table).  Otherwise record i of the launch is member
+// Where the records of a launch lie.  list == null: the run of whole kept sets g (KnownSegs, kernels/image.h; g.kord:
+// the issuer ordinal of each set in the image's own issuer table, g.hour: null).  Otherwise record i of the launch is member
 // record list[i].x of g.recs under issuer ordinal list[i].y — a survivor list k_casc_compact wrote.
 struct CascSrc {
   FindSegs g;
@@ -37,25 +37,22 @@ struct CascLayer {
 };
 
 // Record i of a launch of n: its index in the image and its issuer ordinal — the list's pair, or the segment search.
-__device__ __forceinline__ void casc_locate(const CascSrc& c, uint64_t i, uint64_t n, uint32_t lane, uint32_t& idx, uint32_t& ord) {
+__device__ __forceinline__ void casc_locate(const CascSrc& c, uint64_t i, uint64_t n, uint32_t& idx, uint32_t& ord) {
   if (c.list) {
     const uint2 e = c.list[i];
     idx = e.x;
     ord = e.y;
   } else {
-    const FindSegs& g = c.g;
-    const uint64_t v0 = g.dst[0], wi = i - lane;
-    const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-    const uint32_t set = known_set_in_wave(g.dst, g.k, v, wfirst, wlast);
-    idx = (uint32_t)(g.src[set] + (v - g.dst[set]));
-    ord = g.kord[set];
+    uint32_t set;
+    idx = (uint32_t)c.g.index(i, n, &set);
+    ord = c.g.kord[set];
   }
 }
 
 // … and the record itself, validated (known_load).
-__device__ __forceinline__ uint32_t casc_fetch(const CascSrc& c, uint64_t i, uint64_t n, uint32_t lane, uint32_t& idx, uint32_t& ord,
+__device__ __forceinline__ uint32_t casc_fetch(const CascSrc& c, uint64_t i, uint64_t n, uint32_t& idx, uint32_t& ord,
                                                unsigned long long& len, unsigned long long s[5]) {
-  casc_locate(c, i, n, lane, idx, ord);
+  casc_locate(c, i, n, idx, ord);
   return known_load((const uint4*)(c.g.recs + (uint64_t)idx * KNOWN_REC_BYTES), len, s);
 }
 
@@ -138,12 +135,11 @@ __global__ void __launch_bounds__(256) k_casc_insert(CascSrc c, uint64_t n, Casc
   __shared__ uint32_t kc[64];
   casc_constants(kc);
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
   uint32_t bad = 0u;
   if (i < n) {
     uint32_t idx, ord;
     unsigned long long len, s[5];
-    bad = casc_fetch(c, i, n, lane, idx, ord, len, s);
+    bad = casc_fetch(c, i, n, idx, ord, len, s);
     if (!bad) {
       uint32_t M[32];
       const bool two = casc_message(hp, c.dig + (uint64_t)ord * 8u, len, s, M);
@@ -157,21 +153,19 @@ __global__ void __launch_bounds__(256) k_casc_insert(CascSrc c, uint64_t n, Casc
 }
 
 // One lane per record the layer is tested with: hash function f is computed only while all earlier bits were set; the
-// record passes when all k are (k = 0: every valid record passes — the pass that only validates).  The flags as
-// k_split_mark leaves them: block blk0 + blockIdx.x owns four ballot words and one count.
-__global__ void __launch_bounds__(256) k_casc_test(CascSrc c, uint64_t n, CascHash hp, CascLayer ly, SplitFlags fl, uint64_t blk0,
+// record passes when all k are (k = 0: every valid record passes — the pass that only validates).  The flags go to
+// block blk0 + blockIdx.x (known_flags_out).
+__global__ void __launch_bounds__(256) k_casc_test(CascSrc c, uint64_t n, CascHash hp, CascLayer ly, KnownFlags fl, uint64_t blk0,
                                                    uint32_t* err) {
   __shared__ uint32_t kc[64];
-  __shared__ uint32_t ws[4];
   casc_constants(kc);
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
   uint32_t bad = 0u;
   bool pass = false;
   if (i < n) {
     uint32_t idx, ord;
     unsigned long long len, s[5];
-    bad = casc_fetch(c, i, n, lane, idx, ord, len, s);
+    bad = casc_fetch(c, i, n, idx, ord, len, s);
     if (!bad) {
       uint32_t M[32];
       const bool two = casc_message(hp, c.dig + (uint64_t)ord * 8u, len, s, M);
@@ -183,26 +177,19 @@ __global__ void __launch_bounds__(256) k_casc_test(CascSrc c, uint64_t n, CascHa
     }
   }
   known_report_bad(bad, err);
-  const unsigned long long mask = __ballot(pass);
-  const uint64_t blk = blk0 + blockIdx.x;
-  if (lane == 0) {
-    fl.ball[blk * 4 + (threadIdx.x >> 6)] = mask;
-    ws[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) fl.cnt[blk] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
+  known_flags_out(pass, fl, blk0 + blockIdx.x);
 }
 
 // One lane per record of the run again, after the scan: a record whose flag is set goes to out[rank] as (record index,
 // issuer ordinal).  No record is read.
-__global__ void __launch_bounds__(256) k_casc_compact(CascSrc c, uint64_t n, SplitFlags fl, uint64_t blk0, uint2* out) {
+__global__ void __launch_bounds__(256) k_casc_compact(CascSrc c, uint64_t n, KnownFlags fl, uint64_t blk0, uint2* out) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   bool flag;
-  const unsigned long long rank = split_rank(fl, blk0 + blockIdx.x, threadIdx.x, &flag);
+  const unsigned long long rank = known_flags_before(fl.ball, fl.cnt, (blk0 + blockIdx.x) * 256 + threadIdx.x, &flag);
   if (!flag) return;
   uint2 e;
-  casc_locate(c, i, n, threadIdx.x & 63u, e.x, e.y);
+  casc_locate(c, i, n, e.x, e.y);
   out[rank] = e;
 }
 
@@ -215,14 +202,13 @@ __global__ void __launch_bounds__(256) k_casc_query(CascSrc c, uint64_t n, CascH
   __shared__ uint32_t kc[64];
   casc_constants(kc);
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
   uint32_t bad = 0u, passed = 0u;
   uint32_t M[32];
   bool two = false, alive = false;
   if (i < n) {
     uint32_t idx, ord;
     unsigned long long len, s[5];
-    bad = casc_fetch(c, i, n, lane, idx, ord, len, s);
+    bad = casc_fetch(c, i, n, idx, ord, len, s);
     if (!bad) {
       two = casc_message(hp, c.dig + (uint64_t)ord * 8u, len, s, M);
       alive = true;

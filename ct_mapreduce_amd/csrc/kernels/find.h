@@ -47,15 +47,13 @@ struct FindTable {
 __global__ void __launch_bounds__(256) k_find_build(FindProbes p, FindTable t, uint4* hits, uint32_t* err) {
   const uint64_t n = p.n_main + p.n_extra;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
   uint32_t bad = 0u;
   if (i < n) {
     unsigned long long len, s[5];
     bad = known_load(p.rec(i), len, s);
     uint32_t kord = FIND_NO_ISSUER;
     if (i < p.n_main) {
-      const uint64_t wfirst = i - lane, wlast = wfirst + 63u < p.n_main ? wfirst + 63u : p.n_main - 1u;
-      kord = p.set_kord[known_set_in_wave(p.set_first, p.n_sets, i, wfirst, wlast)];
+      kord = p.set_kord[known_run_set(p.set_first, p.n_sets, i, p.n_main)];
     } else {
       kord = p.extra_kord[i - p.n_main];
     }
@@ -74,15 +72,11 @@ __global__ void __launch_bounds__(256) k_find_build(FindProbes p, FindTable t, u
   known_report_bad(bad, err);
 }
 
-// A run of k whole kept sets of K as segments of a virtual record sequence (ListSegs): segment s holds the virtual
-// records [dst[s], dst[s + 1]) and lies at records [src[s], …) of recs; hour[s] and kord[s] are its set's.
-struct FindSegs {
-  const uint8_t* recs;
-  const uint64_t* dst;  // k + 1
-  const uint64_t* src;  // k
-  const int32_t* hour;
-  const uint32_t* kord;
-  uint32_t k;
+// A run of k whole kept sets of K: the segment table (KnownSegs, kernels/image.h) and per segment its set's hour and
+// K ordinal.
+struct FindSegs : KnownSegs {
+  const int32_t* hour;   // k
+  const uint32_t* kord;  // k
 };
 
 // One lane per member record of the run: three 16-byte loads (a wave reads 3 KiB in a row), the record validated
@@ -92,14 +86,11 @@ struct FindSegs {
 __global__ void __launch_bounds__(256) k_find_scan(FindSegs g, uint64_t n, FindTable t, FindProbes p, uint64_t limit, uint4* hits,
                                                    uint32_t* err) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
   uint32_t bad = 0u;
   if (i < n) {
-    const uint64_t v0 = g.dst[0], wi = i - lane;
-    const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-    const uint32_t set = known_set_in_wave(g.dst, g.k, v, wfirst, wlast);
+    uint32_t set;
     unsigned long long len, s[5];
-    bad = known_load((const uint4*)(g.recs + (g.src[set] + (v - g.dst[set])) * KNOWN_REC_BYTES), len, s);
+    bad = known_load(g.at(i, n, &set), len, s);
     if (!bad) {
       const uint32_t kord = g.kord[set];
       const int32_t hour = g.hour[set];
@@ -131,7 +122,6 @@ __global__ void __launch_bounds__(256) k_find_scan(FindSegs g, uint64_t n, FindT
 // The working hits → the caller's (in place when out == in): the hours of a probe without a record become 0, the
 // reserved word 0; cnt[blk] = the block's probes with records > 0.
 __global__ void __launch_bounds__(256) k_find_finish(const uint4* in, uint4* out, uint64_t n, unsigned long long* cnt) {
-  __shared__ uint32_t ws[4];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   bool found = false;
   if (i < n) {
@@ -139,10 +129,7 @@ __global__ void __launch_bounds__(256) k_find_finish(const uint4* in, uint4* out
     found = h.x != 0u;
     out[i] = found ? make_uint4(h.x, h.y, h.z, 0u) : make_uint4(0u, 0u, 0u, 0u);
   }
-  const unsigned long long m = __ballot(found);
-  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
+  known_block_count((uint32_t)__popcll(__ballot(found)), cnt, blockIdx.x);
 }
 
 }  // namespace ctmr

@@ -107,6 +107,79 @@ __device__ __forceinline__ uint32_t known_set_in_wave(const uint64_t* first, uin
   return known_set_of(first, s_lo, s_hi, v);
 }
 
+// The run walk, the one copy of the image's kernels.  A launch of 256-thread blocks, one lane per
+// record, covers the n records of k whole sets: first[0..k] ascending, first[0] = the run's first virtual record,
+// first[k] = first[0] + n.  → the set of record i of the launch, which is virtual record first[0] + i: the wave's first
+// and last record (the last wave of the launch ends at record n − 1), then known_set_in_wave.  Call with i < n.
+__device__ __forceinline__ uint32_t known_run_set(const uint64_t* first, uint32_t k, uint64_t i, uint64_t n) {
+  const uint64_t v0 = first[0], wi = i - (threadIdx.x & 63u);
+  const uint64_t wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
+  return known_set_in_wave(first, k, v0 + i, wfirst, wlast);
+}
+
+// The segment table of a run: segment s holds the virtual records [dst[s], dst[s + 1]) (every segment non-empty) and
+// lies at records [src[s], src[s] + dst[s + 1] − dst[s]) of recs — whole sets of an image where they lie, in another
+// order or with sets left out in between.  A plain aggregate, passed by value as a kernel argument.
+struct KnownSegs {
+  const uint8_t* recs;
+  const uint64_t* dst;  // k + 1
+  const uint64_t* src;  // k
+  uint32_t k;
+  // record i of a launch of n (known_run_set) → its index in recs and, where the caller wants it, its segment
+  __device__ __forceinline__ uint64_t index(uint64_t i, uint64_t n, uint32_t* set = nullptr) const {
+    const uint32_t s = known_run_set(dst, k, i, n);
+    if (set) *set = s;
+    return src[s] + (dst[0] + i - dst[s]);
+  }
+  // … → the record
+  __device__ __forceinline__ const uint4* at(uint64_t i, uint64_t n, uint32_t* set = nullptr) const {
+    return (const uint4*)(recs + index(i, n, set) * KNOWN_REC_BYTES);
+  }
+};
+
+// The flags of a pass, the one copy of the image's kernels: one bit per record and one count per block
+// of 256 records.  Block b owns the four ballot words ball[4 b ..] and cnt[b] — its flagged records after the pass, the
+// flagged records in front of it after the exclusive scan of cnt[].  A call of several runs numbers its blocks through
+// all of them: a run of n records takes (n + 255) / 256 blocks from the blocks in front of it on.
+struct KnownFlags {
+  unsigned long long* ball;
+  unsigned long long* cnt;
+};
+
+// v, a wave's total (lane 0's counts) → cnt[blk] = the sum over the block's four waves; → that sum, in thread 0 alone.
+// Every thread of the block calls.
+__device__ __forceinline__ uint32_t known_block_count(uint32_t v, unsigned long long* cnt, uint64_t blk) {
+  __shared__ uint32_t ws[4];
+  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint32_t total = 0u;
+  if (threadIdx.x == 0) {
+    total = ws[0] + ws[1] + ws[2] + ws[3];
+    cnt[blk] = (unsigned long long)total;
+  }
+  return total;
+}
+
+// Leaves this wave's ballot and this block's count at block blk.  Every thread of the block calls.
+__device__ __forceinline__ void known_flags_out(bool flag, const KnownFlags& f, uint64_t blk) {
+  const unsigned long long m = __ballot(flag);
+  if ((threadIdx.x & 63u) == 0) f.ball[blk * 4 + (threadIdx.x >> 6)] = m;
+  known_block_count((uint32_t)__popcll(m), f.cnt, blk);
+}
+
+// The flagged records in front of record q (block q >> 8), after the scan: the block's base, the popcounts of the
+// block's earlier words, and the bits of q's word below q.  *flag: q's own bit.  (q = all records may be asked about
+// where ball has four words and cnt one entry more than the blocks.)
+__device__ __forceinline__ unsigned long long known_flags_before(const unsigned long long* ball, const unsigned long long* cnt,
+                                                                 uint64_t q, bool* flag) {
+  const uint64_t blk = q >> 8, w = q >> 6;
+  unsigned long long r = cnt[blk];
+  for (uint64_t k = blk * 4u; k < w; k++) r += (unsigned long long)__popcll(ball[k]);
+  const unsigned long long m = ball[w];
+  *flag = (m >> (q & 63u)) & 1ull;
+  return r + (unsigned long long)__popcll(m & ((1ull << (q & 63u)) - 1ull));
+}
+
 // A member record loaded (three 16-byte loads) and held to the rule that makes it valid: serial_len is
 // at most 40 and the octets behind it are zero.  → 0 with len and the five serial words, or 1 for a serial_len above
 // 40, 2 for padding that is not zero — the bits of the error word the calls report (known_report_bad).

@@ -3,8 +3,7 @@
 // line hex(serial) "\n" per record.  A count pass (per-block byte totals, then scan_u64) and a write pass that stages
 // each block's text in LDS and stores it with 16-byte stores between two ragged ends.
 // ctmr_known_image_lists*  runs the same two passes over the member records of an image where they lie:
-// the kept sets are SEGMENTS of a virtual record sequence in list order (ListSegs), and virtual record v is read at
-// seg_src[s] + v − seg_dst[s].  Its count pass (k_image_lists_count) also validates every record it reads.
+// the kept sets are the segments of a virtual record sequence in list order (KnownSegs, kernels/image.h).  Its count pass (k_image_lists_count) also validates every record it reads.
 // gfx950 (CDNA4, wave64) only; part of kernels.h, which includes the pieces in dependency order.
 #pragma once
 #include "image.h"
@@ -22,14 +21,11 @@ __device__ __forceinline__ uint32_t list_rec_len(const uint8_t* recs, uint64_t i
 
 // Count pass: cnt[blk] = the text bytes of records [256 blk, 256 blk + 256).
 __global__ void __launch_bounds__(LIST_BLOCK) k_lists_count(const uint8_t* recs, uint64_t n, unsigned long long* cnt) {
-  __shared__ uint32_t ws[LIST_BLOCK / 64];
   const uint64_t i = (uint64_t)blockIdx.x * LIST_BLOCK + threadIdx.x;
   uint32_t b = i < n ? 2u * list_rec_len(recs, i) + 1u : 0u;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d);
-  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = b;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
+  known_block_count(b, cnt, blockIdx.x);
 }
 
 __device__ __forceinline__ uint8_t list_hex(uint32_t v) { return (uint8_t)(v < 10u ? '0' + v : 'a' - 10u + v); }
@@ -39,7 +35,7 @@ __device__ __forceinline__ uint8_t list_hex(uint32_t v) { return (uint8_t)(v < 1
 // phase of its first global byte, so that every 16-byte aligned global chunk is one aligned 16-byte LDS word.
 // pts[0..npts) (ascending record indices of the chunk): pt_off[k] = the text offset of record pts[k] — where the host
 // needs the text position of a record (an issuer's first line, host-store lines that go in between).
-// src(i, n): where record i of the n the launch covers lies (called with i < n by every such lane of a wave).
+// src.at(i, n): where record i of the n the launch covers lies (called with i < n by every such lane of a wave).
 template <class Src>
 __device__ __forceinline__ void lists_write_body(const Src& src, uint64_t n, const unsigned long long* base, uint8_t* out,
                                                  const uint64_t* pts, uint64_t npts, unsigned long long* pt_off) {
@@ -49,7 +45,7 @@ __device__ __forceinline__ void lists_write_body(const Src& src, uint64_t n, con
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   uint4 c0 = make_uint4(0u, 0u, 0u, 0u), c1 = c0, c2 = c0;
   if (i < n) {
-    const uint4* rec = src(i, n);
+    const uint4* rec = src.at(i, n);
     c0 = rec[0];
     c1 = rec[1];
     c2 = rec[2];
@@ -124,7 +120,7 @@ __device__ __forceinline__ void lists_write_body(const Src& src, uint64_t n, con
 // the records where they were staged: record i is the i-th of recs
 struct ListStaged {
   const uint8_t* recs;
-  __device__ __forceinline__ const uint4* operator()(uint64_t i, uint64_t) const { return (const uint4*)(recs + i * KNOWN_REC_BYTES); }
+  __device__ __forceinline__ const uint4* at(uint64_t i, uint64_t) const { return (const uint4*)(recs + i * KNOWN_REC_BYTES); }
 };
 
 __global__ void __launch_bounds__(LIST_BLOCK) k_lists_write(const uint8_t* recs, uint64_t n, const unsigned long long* base,
@@ -133,40 +129,24 @@ __global__ void __launch_bounds__(LIST_BLOCK) k_lists_write(const uint8_t* recs,
   lists_write_body(ListStaged{recs}, n, base, out, pts, npts, pt_off);
 }
 
-// ---- the lists of an image (ctmr_known_image_lists*).  A launch covers n virtual records of k whole segments: segment s
-// holds the virtual records [dst[s], dst[s + 1]) (dst ascending, every segment non-empty, dst[0] = the launch's first
-// virtual record, dst[k] = dst[0] + n) and lies at records [src[s], src[s] + dst[s + 1] − dst[s]) of the image.  Record i
-// of the launch is virtual record dst[0] + i; its segment comes from known_set_in_wave over dst (kernels/image.h).
-struct ListSegs {
-  const uint8_t* recs;  // the image's member records
-  const uint64_t* dst;  // k + 1
-  const uint64_t* src;  // k
-  uint32_t k;
-  __device__ __forceinline__ const uint4* operator()(uint64_t i, uint64_t n) const {
-    const uint64_t v0 = dst[0], wi = i - (threadIdx.x & 63u);
-    const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-    const uint32_t s = known_set_in_wave(dst, k, v, wfirst, wlast);
-    return (const uint4*)(recs + (src[s] + (v - dst[s])) * KNOWN_REC_BYTES);
-  }
-};
+// ---- the lists of an image (ctmr_known_image_lists*).  A launch covers n virtual records of k whole segments — the
+// kept sets in list order — and reads record i where KnownSegs::at finds it (kernels/image.h).
+using ListSegs = KnownSegs;
 
 // Count pass over the segments: cnt[blk] = the text bytes of the launch's records [256 blk, 256 blk + 256), and every
 // record read is validated (known_load) and a bad one reported in *err (known_report_bad).
 __global__ void __launch_bounds__(LIST_BLOCK) k_image_lists_count(ListSegs g, uint64_t n, unsigned long long* cnt, uint32_t* err) {
-  __shared__ uint32_t ws[LIST_BLOCK / 64];
   const uint64_t i = (uint64_t)blockIdx.x * LIST_BLOCK + threadIdx.x;
   uint32_t b = 0u, bad = 0u;
   if (i < n) {
     unsigned long long len, s[5];
-    bad = known_load(g(i, n), len, s);
+    bad = known_load(g.at(i, n), len, s);
     b = 2u * (uint32_t)(len < (unsigned long long)CTMR_MAX_SERIAL ? len : (unsigned long long)CTMR_MAX_SERIAL) + 1u;
   }
   known_report_bad(bad, err);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d);
-  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = b;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
+  known_block_count(b, cnt, blockIdx.x);
 }
 
 // Write pass over the segments: k_lists_write with the indirect source (pts / pt_off in the launch's record indices).

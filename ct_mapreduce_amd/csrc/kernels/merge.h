@@ -10,8 +10,8 @@
 //                      record and a count per 256-record block
 //   k_merge_sets       per pair of sets the members the result holds
 //   k_merge_place      the kept records to their places in the result (three 16-byte loads and stores)
-// "Kept records before position q of an operand" is everywhere merge_kept_before: the scanned block counts, the bit
-// words of q's block in front of q's, and the bits of q's word below q.
+// The kept records are the flags of a pass (KnownFlags, kernels/image.h), blocks numbered by blockIdx.x: "kept records
+// before position q of an operand" is everywhere known_flags_before.
 // gfx950 (CDNA4, wave64) only; plain vector loads and stores, LDS and global atomics.
 #pragma once
 #include "sort.h"
@@ -37,17 +37,12 @@ struct MergeSide {
 // bits[i >> 6] bit (i & 63) = record i is kept; base[blk] = kept records before block blk (256 records), base[nb] = all.
 // bits has 4 (nb + 1) words and base nb + 1 entries, so q = n may be asked about.
 __device__ __forceinline__ uint64_t merge_kept_before(const unsigned long long* bits, const unsigned long long* base, uint64_t q) {
-  const uint64_t blk = q >> 8, w = q >> 6;
-  uint64_t r = base[blk];
-  for (uint64_t k = blk * 4u; k < w; k++) r += (uint64_t)__popcll(bits[k]);
-  return r + (uint64_t)__popcll(bits[w] & ((1ull << (q & 63u)) - 1ull));
+  bool flag;
+  return known_flags_before(bits, base, q, &flag);
 }
 
-// the set of record i of a side (known_set_in_wave, kernels/image.h)
-__device__ __forceinline__ uint32_t merge_set_of(const MergeSide& s, uint64_t i) {
-  const uint64_t wfirst = i - (threadIdx.x & 63u), wlast = wfirst + 63u < s.n ? wfirst + 63u : s.n - 1u;
-  return known_set_in_wave(s.first, s.ns, i, wfirst, wlast);
-}
+// the set of record i of a side: its sets are one run from record 0 on (known_run_set, kernels/image.h)
+__device__ __forceinline__ uint32_t merge_set_of(const MergeSide& s, uint64_t i) { return known_run_set(s.first, s.ns, i, s.n); }
 
 // A record as the order compares it: the five octet words as big-endian numbers, then serial_len.
 struct MergeKey {
@@ -88,20 +83,6 @@ __device__ __forceinline__ int merge_compare(const uint8_t* rec, uint64_t j, con
   return len == k.len ? 0 : (len < k.len ? -1 : 1);
 }
 
-// The kept records of a 256-record block: the wave's ballot is its bit word, the block's count goes to cnt[blockIdx.x].
-// Every thread of the block calls.
-__device__ __forceinline__ void merge_keep_out(bool keep, unsigned long long* bits, unsigned long long* cnt) {
-  __shared__ uint32_t wc[4];
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) {
-    wc[wv] = (uint32_t)__popcll(m);
-    bits[(uint64_t)blockIdx.x * 4u + wv] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)(wc[0] + wc[1] + wc[2] + wc[3]);
-}
-
 // Canonical check: *flag |= 1 when a record is not strictly above its predecessor in its set.  One atomicOr per wave
 // that found one, like the bad-record report of k_known_count.
 __global__ void __launch_bounds__(256) k_merge_ascending(MergeSide s, uint32_t* flag) {
@@ -123,7 +104,7 @@ __global__ void __launch_bounds__(256) k_merge_unique(MergeSide s, unsigned long
     const uint32_t set = merge_set_of(s, i);
     head = i == s.first[set] || merge_compare(s.rec, i - 1u, merge_key(s.rec, i)) != 0;
   }
-  merge_keep_out(head, bits, cnt);
+  known_flags_out(head, KnownFlags{bits, cnt}, blockIdx.x);
 }
 
 // … and the first record of every set once the repeats are gone (behind the exclusive scan of cnt[]); first[ns] too.
@@ -164,7 +145,7 @@ __global__ void __launch_bounds__(256) k_merge_rank(MergeSide s, const MergePair
     if (lb) lb[i] = (uint32_t)lo;
     keep = found == (keep_found != 0u);
   }
-  if (bits) merge_keep_out(keep, bits, cnt);
+  if (bits) known_flags_out(keep, KnownFlags{bits, cnt}, blockIdx.x);
 }
 
 // The members the result holds per pair (behind the exclusive scan of the block counts): UNION all of A's and B's kept

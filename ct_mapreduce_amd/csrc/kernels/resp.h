@@ -29,7 +29,7 @@ __host__ __device__ constexpr uint32_t resp_lds_bytes(uint32_t max_block_text) {
 constexpr unsigned long long RESP_NO_EXPIRE = 1ull << 63;
 
 // A launch covers the n records of k whole sets: set s holds the image's records [first[s], first[s + 1]) (first[0] = the
-// launch's first record, recs points at it), meta[s] = (uint32_t)hour | ordinal << 32 | RESP_NO_EXPIRE.
+// launch's first record, recs points at it; the set of record i: known_run_set, kernels/image.h), meta[s] = (uint32_t)hour | ordinal << 32 | RESP_NO_EXPIRE.
 struct RespArgs {
   const uint8_t* recs;
   const uint64_t* first;            // k + 1
@@ -37,13 +37,6 @@ struct RespArgs {
   const uint8_t* ids;               // RESP_ID_ROW bytes per ordinal: the 44 characters of its Issuer.ID, then zeros
   uint32_t k, per;
 };
-
-// the set of record i of the launch (known_set_in_wave, kernels/image.h)
-__device__ __forceinline__ uint32_t resp_set_of(const RespArgs& a, uint64_t i, uint64_t n) {
-  const uint64_t v0 = a.first[0], wi = i - (threadIdx.x & 63u);
-  const uint64_t wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-  return known_set_in_wave(a.first, a.k, v0 + i, wfirst, wlast);
-}
 
 // decimal digits of v (at most 12: |hour × 3600| of the years 0000..9999)
 __device__ __forceinline__ uint32_t resp_digits(unsigned long long v) {
@@ -99,26 +92,20 @@ __device__ __forceinline__ uint32_t resp_rec_bytes(const RespRec& r, uint32_t le
 // (known_load) and a bad one reported in err[0] (known_report_bad).  err[1] = the largest cnt[blk] of the launch (the
 // write pass's LDS): an atomicMax by the blocks that raise it.
 __global__ void __launch_bounds__(RESP_BLOCK) k_image_resp_count(RespArgs a, uint64_t n, unsigned long long* cnt, uint32_t* err) {
-  __shared__ uint32_t ws[RESP_BLOCK / 64];
   const uint64_t i = (uint64_t)blockIdx.x * RESP_BLOCK + threadIdx.x;
   uint32_t b = 0u, bad = 0u;
   if (i < n) {
     unsigned long long len, s[5];
     bad = known_load((const uint4*)(a.recs + i * KNOWN_REC_BYTES), len, s);
     const uint32_t l = (uint32_t)(len < (unsigned long long)CTMR_MAX_SERIAL ? len : (unsigned long long)CTMR_MAX_SERIAL);
-    b = resp_rec_bytes(resp_rec(a, resp_set_of(a, i, n), i), l);
+    b = resp_rec_bytes(resp_rec(a, known_run_set(a.first, a.k, i, n), i), l);
   }
   known_report_bad(bad, err);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d);
-  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = b;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t total = ws[0] + ws[1] + ws[2] + ws[3];
-    cnt[blockIdx.x] = (unsigned long long)total;
-    // (every block's atomic on the one word would serialise: only a block above what the word held a moment ago tries)
-    if (total > __hip_atomic_load(err + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(err + 1, total);
-  }
+  const uint32_t total = known_block_count(b, cnt, blockIdx.x);
+  // (every block's atomic on the one word would serialise: only a block above what the word held a moment ago tries)
+  if (threadIdx.x == 0 && total > __hip_atomic_load(err + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(err + 1, total);
 }
 
 // v in decimal, nd = resp_digits(v) of them → behind the last
@@ -209,7 +196,7 @@ __global__ void __launch_bounds__(RESP_BLOCK) k_image_resp_write(RespArgs a, uin
     c0 = rec[0];
     c1 = rec[1];
     c2 = rec[2];
-    r = resp_rec(a, resp_set_of(a, i, n), i);
+    r = resp_rec(a, known_run_set(a.first, a.k, i, n), i);
   }
   const uint32_t len = c0.x < (uint32_t)CTMR_MAX_SERIAL ? c0.x : (uint32_t)CTMR_MAX_SERIAL;
   const uint32_t bytes = i < n ? resp_rec_bytes(r, len) : 0u;

@@ -46,13 +46,12 @@ __device__ __forceinline__ unsigned long long sort_word(const uint8_t* rec, uint
 }
 
 // Keys of round 1 for records [lo, lo + n) of rec: first[0..ns] = the first record of each set of the run (first[0] = lo,
-// first[ns] = lo + n); the set of a record comes from known_set_in_wave (kernels/image.h).
+// first[ns] = lo + n); the set of a record comes from known_run_set (kernels/image.h).
 __global__ void __launch_bounds__(256) k_sort_keys(const uint8_t* rec, uint64_t lo, uint64_t n, const uint64_t* first,
                                                    uint32_t ns, uint4* keys) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const uint64_t wfirst = i - (threadIdx.x & 63u), wlast = wfirst + 63u < n ? wfirst + 63u : n - 1u;
-  const uint32_t set = known_set_in_wave(first, ns, lo + i, lo + wfirst, lo + wlast);
+  const uint32_t set = known_run_set(first, ns, i, n);
   const unsigned long long w = sort_word(rec, lo + i, 0u);
   keys[i] = make_uint4((uint32_t)w, (uint32_t)(w >> 32), set, (uint32_t)i);
 }

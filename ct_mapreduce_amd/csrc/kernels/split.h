@@ -1,8 +1,8 @@
 // kernels/split.h — a known image partitioned by a probe image, the hour as wildcard (include/ctmr.h
 // ctmr_known_image_split*): the member records of K's kept sets that equal a probe go to one image, the
 // others to a second one, both in K's order.  The probes are find.h's table (k_find_build, unchanged); the records are
-// streamed twice: k_split_mark walks each against the table and leaves one flag bit per record (a ballot word per wave)
-// and one count per block; after a scan of the counts k_split_place copies each record to its rank among the hits or
+// streamed twice: k_split_mark walks each against the table and leaves the flags of the pass (KnownFlags,
+// kernels/image.h); after a scan of the counts k_split_place copies each record to its rank among the hits or
 // among the misses, and k_split_sets says how many hits lie in front of every kept set.  One stable compaction over the
 // virtual sequence of the kept sets is the per-set layout, because kept sets are contiguous there.
 // No cross-workgroup publish, no spin-wait; the only global atomic is the bad-record report (known_report_bad).
@@ -12,31 +12,19 @@
 
 namespace ctmr {
 
-// The flags of the call: blocks are numbered through all its runs (a run of n records takes (n + 255) / 256 blocks from
-// its blk0 on), block b owns the four ballot words ball[4 b ..] and cnt[b] — its hits after k_split_mark, the hits in
-// front of it after the exclusive scan.
-struct SplitFlags {
-  unsigned long long* ball;
-  unsigned long long* cnt;
-};
-
-// One lane per member record of the run, addressed as k_find_scan addresses it: three 16-byte loads, the record
+// One lane per member record of the run (KnownSegs::at): three 16-byte loads, the record
 // validated (known_load), then the walk from its home slot to the first empty word.  At the first probe below `limit`
 // that is equal in full (48 bytes and K ordinal) the flag is set and the walk stops.  A record that matches nothing
 // reads one table word.  hits: the working hits k_find_build wrote, read for the probes' K ordinals only.
 __global__ void __launch_bounds__(256) k_split_mark(FindSegs g, uint64_t n, FindTable t, FindProbes p, uint64_t limit, const uint4* hits,
-                                                    SplitFlags f, uint64_t blk0, uint32_t* err) {
-  __shared__ uint32_t ws[4];
+                                                    KnownFlags f, uint64_t blk0, uint32_t* err) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
   uint32_t bad = 0u;
   bool found = false;
   if (i < n) {
-    const uint64_t v0 = g.dst[0], wi = i - lane;
-    const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-    const uint32_t set = known_set_in_wave(g.dst, g.k, v, wfirst, wlast);
+    uint32_t set;
     unsigned long long len, s[5];
-    bad = known_load((const uint4*)(g.recs + (g.src[set] + (v - g.dst[set])) * KNOWN_REC_BYTES), len, s);
+    bad = known_load(g.at(i, n, &set), len, s);
     if (!bad) {
       const uint32_t kord = g.kord[set];
       const unsigned long long h = key_hash(find_meta(kord, len), s);
@@ -57,44 +45,21 @@ __global__ void __launch_bounds__(256) k_split_mark(FindSegs g, uint64_t n, Find
     }
   }
   known_report_bad(bad, err);
-  const unsigned long long m = __ballot(found);
-  const uint64_t blk = blk0 + blockIdx.x;
-  if (lane == 0) {
-    f.ball[blk * 4 + (threadIdx.x >> 6)] = m;
-    ws[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) f.cnt[blk] = (unsigned long long)(ws[0] + ws[1] + ws[2] + ws[3]);
-}
-
-// The hits in front of record `at` (0..255) of block blk, after the scan: the block's base, the popcounts of the earlier
-// waves of the block, and the bits of its own wave's word below its lane.  *flag: the record's own bit.
-__device__ __forceinline__ unsigned long long split_rank(const SplitFlags& f, uint64_t blk, uint32_t at, bool* flag) {
-  const unsigned long long* b = f.ball + blk * 4;
-  const uint32_t wave = at >> 6, lane = at & 63u;
-  unsigned long long r = f.cnt[blk];
-  for (uint32_t w = 0; w < wave; w++) r += (unsigned long long)__popcll(b[w]);
-  const unsigned long long m = b[wave];
-  *flag = (m >> lane) & 1ull;
-  return r + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+  known_flags_out(found, f, blk0 + blockIdx.x);
 }
 
 // One lane per record of the run again: virtual record v with `rank` hits in front of it goes to hit[rank] when its
 // flag is set, else to miss[v − rank], as three 16-byte stores.  A side that is null is not stored.
-__global__ void __launch_bounds__(256) k_split_place(FindSegs g, uint64_t n, SplitFlags f, uint64_t blk0, uint8_t* hit, uint8_t* miss) {
+__global__ void __launch_bounds__(256) k_split_place(FindSegs g, uint64_t n, KnownFlags f, uint64_t blk0, uint8_t* hit, uint8_t* miss) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t v0 = g.dst[0], wi = i - lane;
-  const uint64_t v = v0 + i, wfirst = v0 + wi, wlast = wi + 63u < n ? wfirst + 63u : v0 + n - 1u;
-  const uint32_t set = known_set_in_wave(g.dst, g.k, v, wfirst, wlast);
+  const uint4* src = g.at(i, n);
   bool flag;
-  const unsigned long long rank = split_rank(f, blk0 + blockIdx.x, threadIdx.x, &flag);
+  const unsigned long long rank = known_flags_before(f.ball, f.cnt, (blk0 + blockIdx.x) * 256 + threadIdx.x, &flag);
   uint8_t* side = flag ? hit : miss;
   if (!side) return;
-  const uint4* src = (const uint4*)(g.recs + (g.src[set] + (v - g.dst[set])) * KNOWN_REC_BYTES);
   const uint4 c0 = src[0], c1 = src[1], c2 = src[2];
-  uint4* o = (uint4*)(side + (flag ? rank : v - rank) * KNOWN_REC_BYTES);
+  uint4* o = (uint4*)(side + (flag ? rank : g.dst[0] + i - rank) * KNOWN_REC_BYTES);
   o[0] = c0;
   o[1] = c1;
   o[2] = c2;
@@ -102,12 +67,11 @@ __global__ void __launch_bounds__(256) k_split_place(FindSegs g, uint64_t n, Spl
 
 // One lane per kept set of the run: before[s] = the hits in front of the set's first virtual record.  The host takes
 // both results' counts and first members from these and the total.
-__global__ void __launch_bounds__(256) k_split_sets(FindSegs g, SplitFlags f, uint64_t blk0, unsigned long long* before) {
+__global__ void __launch_bounds__(256) k_split_sets(FindSegs g, KnownFlags f, uint64_t blk0, unsigned long long* before) {
   const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (s >= g.k) return;
-  const uint64_t i = g.dst[s] - g.dst[0];
   bool flag;
-  before[s] = split_rank(f, blk0 + (i >> 8), (uint32_t)(i & 255u), &flag);
+  before[s] = known_flags_before(f.ball, f.cnt, blk0 * 256 + (g.dst[s] - g.dst[0]), &flag);
 }
 
 }  // namespace ctmr

@@ -10,7 +10,7 @@ warm-up, medians of --reps, one process, of
   query_miss  Engine.cascade_query_device(cascade, MISS)  — every answer must be 0.
 The build is reported as a ratio to the split of the same run and to the rate of the CPU twin cascade.build on a sample
 of --python-members records (a tenth of them from HIT, the rest from MISS; whole sets), where the device's cascade is held
-to the twin's byte for byte.  No threshold: the numbers are recorded, not gated."""
+to the twin's byte for byte.  No threshold: the numbers are recorded, not gated.  --kernels-only leaves the twin out."""
 import argparse
 import json
 import os
@@ -29,6 +29,19 @@ from bench_known_image import build_table, timed  # noqa: E402
 from bench_known_image_resp import head_image  # noqa: E402
 
 
+def twin_sample(e, args, line, hit_meta, d_hit, miss_meta, d_miss):
+    """The twin on a sample, and the device held to it there."""
+    small_r, small_s = head_image(hit_meta, d_hit, args.python_members // 10), head_image(miss_meta, d_miss, args.python_members * 9 // 10)
+    sample = CA.crlite_params(KI._HEADER.unpack_from(small_r, 0)[6], KI._HEADER.unpack_from(small_s, 0)[6], b"bench")
+    t0 = time.perf_counter()
+    want = CA.build(small_r, small_s, 0, sample)
+    py_s = time.perf_counter() - t0
+    got, sinfo = e.cascade_build(small_r, small_s, 0, sample)
+    assert got == want, "the device differs from the twin"
+    n_sample = sinfo["r_records"] + sinfo["s_records"]
+    line["python"] = {"records": n_sample, "layers": sinfo["layers"], "s": round(py_s, 3), "records_per_s": n_sample / py_s}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--members", type=int, default=120_000_000)
@@ -37,6 +50,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--slots", type=int, default=1 << 28)
     ap.add_argument("--python-members", type=int, default=100_000)
+    ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_cascade.json"))
     args = ap.parse_args()
     stream = torch.cuda.current_stream().cuda_stream
@@ -73,16 +87,8 @@ def main():
     line = {"metric": "cascade_build", "members": M, "probes": d_probes.numel() // 48, "entries_mapped": entries, "revoked": n_hit,
             "not_revoked": n_miss, "params": [params.k_first, params.bpk_first_q8, params.k_rest, params.bpk_rest_q8, params.max_layers],
             "split": leg(s_ms, M)}
-    # the twin on a sample, and the device held to it there
-    small_r, small_s = head_image(hit_meta, d_hit, args.python_members // 10), head_image(miss_meta, d_miss, args.python_members * 9 // 10)
-    sample = CA.crlite_params(KI._HEADER.unpack_from(small_r, 0)[6], KI._HEADER.unpack_from(small_s, 0)[6], b"bench")
-    t0 = time.perf_counter()
-    want = CA.build(small_r, small_s, 0, sample)
-    py_s = time.perf_counter() - t0
-    got, sinfo = e.cascade_build(small_r, small_s, 0, sample)
-    assert got == want, "the device differs from the twin"
-    n_sample = sinfo["r_records"] + sinfo["s_records"]
-    line["python"] = {"records": n_sample, "layers": sinfo["layers"], "s": round(py_s, 3), "records_per_s": n_sample / py_s}
+    if not args.kernels_only:
+        twin_sample(e, args, line, hit_meta, d_hit, miss_meta, d_miss)
 
     def build():
         keep["c"] = None
@@ -111,7 +117,8 @@ def main():
     line["query_hit"] = leg(qh_ms, n_hit)
     line["query_miss"] = leg(qm_ms, n_miss)
     line["ratio_build_over_split"] = round(line["build"]["ms_median"] / line["split"]["ms_median"], 3)
-    line["ratio_build_rate_over_python"] = round(line["build"]["records_per_s"] / line["python"]["records_per_s"], 1)
+    if not args.kernels_only:
+        line["ratio_build_rate_over_python"] = round(line["build"]["records_per_s"] / line["python"]["records_per_s"], 1)
     text = json.dumps(line)
     print(text)
     if args.out:
