@@ -152,7 +152,8 @@ int ctmr_sha256(ctmr_engine* e, const uint8_t* data, size_t len, uint8_t out[32]
 int ctmr_issuer_info_get(ctmr_engine* e, uint32_t idx, ctmr_issuer_info* out);
 
 /* ---- filter configuration: *ctconfig.IssuerCNFilter, *ctconfig.LogExpiredEntries and the
- *      time.Now() of certIsFilteredOut (ct-fetch.go:44-70; config/config.go:194-196) ---- */
+ *      time.Now() of certIsFilteredOut (ct-fetch.go:44-70; config/config.go:194-196).  A refused call
+ *      (CTMR_E_INVAL: more than 64 pieces or 1024 words) leaves the earlier filter in force. ---- */
 int ctmr_set_filter(ctmr_engine* e, const char* issuer_cn_filter, size_t len, int log_expired,
                     int64_t now_unix);
 

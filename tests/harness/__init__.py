@@ -106,8 +106,7 @@ def product_walk(der: bytes, fill=0xA5, cn_filter=None) -> HarnessOut:
         _walk.harness_walk_f.argtypes = [C.c_char_p, C.c_uint32, C.c_uint8, C.c_char_p, C.c_uint32,
                                          C.c_int, C.POINTER(HarnessOut)]
     o = HarnessOut()
-    f = cn_filter if cn_filter is not None else b""
-    _walk.harness_walk_f(der, len(der), fill, f, len(f), int(cn_filter is not None), C.byref(o))
+    _walk.harness_walk_f(der, len(der), fill, *_filter_args(cn_filter), C.byref(o))
     return o
 
 
@@ -178,22 +177,31 @@ def walk_touched(der: bytes, phase: int = 0, cn_filter: bytes = b"", reference_p
     return bool(ok), nb.value, nl.value
 
 
-def walk_window(der: bytes, phase: int = 0, wbytes: int = 224, strings: bool = False, ext: bool = False, skip: int = 0):
+def _filter_args(cn_filter):
+    f = cn_filter if cn_filter is not None else b""
+    return f, len(f), int(cn_filter is not None)
+
+
+def walk_window(der: bytes, phase: int = 0, wbytes: int = 224, strings: bool = False, ext: bool = False, skip: int = 0,
+                cn_filter=None):
     """The walk through a SIMULATED per-lane window of `wbytes` bytes (kernels/readers.h geometry) for a certificate that
     starts at byte `phase` of its 128-byte line: (accepted, per-lane refills the hints asked for, reads that missed the
     window, position of the first refill, position of the first miss, cooperative refills of the subjectAltName walk,
-    defer_exact calls)."""
+    defer_exact calls).  cn_filter (bytes: the raw issuerCNFilter): three more — cn_match as THIS walk saw it, and how many
+    reads of cn_prefix_match lay inside and outside the window."""
     product_walk(b"\x30\x00")
-    out = (C.c_uint32 * 6)()
+    out = (C.c_uint32 * 9)()
     if skip:    # the first window begins `skip` octets in, the outer headers come from sixteen octets held apart (WinGeo::SKIP)
         fn = _walk.harness_walk_window_skip
-        fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
-        ok = fn(der, len(der), phase, wbytes, skip, int(strings), int(ext), out)
-        return bool(ok), out[0], out[1], out[2], out[3], out[4], out[5]
-    fn = _walk.harness_walk_window
-    fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
-    ok = fn(der, len(der), phase, wbytes, int(strings), int(ext), out)
-    return bool(ok), out[0], out[1], out[2], out[3], out[4], out[5]
+        fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_int,
+                       C.POINTER(C.c_uint32)]
+        ok = fn(der, len(der), phase, wbytes, skip, int(strings), int(ext), *_filter_args(cn_filter), out)
+    else:
+        fn = _walk.harness_walk_window
+        fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_int,
+                       C.POINTER(C.c_uint32)]
+        ok = fn(der, len(der), phase, wbytes, int(strings), int(ext), *_filter_args(cn_filter), out)
+    return (bool(ok),) + tuple(out)[:6 if cn_filter is None else 9]
 
 
 class DidNotTerminate(Exception):
@@ -201,36 +209,41 @@ class DidNotTerminate(Exception):
 
 
 def walk_window_noreach(der: bytes, phase: int = 0, wbytes: int = 224, flavour: str = "C", strings: bool = True, ext: bool = True,
-                        cap: int = 10_000, fill: int = 0xA5):
+                        cap: int = 10_000, fill: int = 0xA5, cn_filter=None):
     """The walk as a lane OUT OF REACH of its wave's buffer descriptor runs it (kernels/readers.h lrel == REL_NONE: an entry
     view in no order): cooperative refills do nothing, the lane's own refills work; flavour "C" = WinReaderC (reads outside
     the window are global reads), "S" = WinReaderS (clamped and counted; the exact reader then decides).  Returns
     (HarnessOut, stats) with stats = (per-lane refills, misses, cooperative refills asked for in vain, defer_exact calls,
-    exact rerun, window reads outside the window); raises DidNotTerminate past `cap` calls of holds / coop_refill_lines_to."""
+    exact rerun, window reads outside the window); raises DidNotTerminate past `cap` calls of holds / coop_refill_lines_to.
+    cn_filter (bytes): the walk runs under that issuerCNFilter, and stats gains the reads of cn_prefix_match inside and
+    outside the window (flavour "S": of the clamped walk)."""
     product_walk(b"\x30\x00")
     fn = _walk.harness_walk_window_noreach
     fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint8,
-                   C.POINTER(HarnessOut), C.POINTER(C.c_uint32)]
-    o, st = HarnessOut(), (C.c_uint32 * 6)()
-    if not fn(der, len(der), phase, wbytes, {"C": 0, "S": 1}[flavour], int(strings), int(ext), cap, fill, C.byref(o), st):
+                   C.c_char_p, C.c_uint32, C.c_int, C.POINTER(HarnessOut), C.POINTER(C.c_uint32)]
+    o, st = HarnessOut(), (C.c_uint32 * 8)()
+    if not fn(der, len(der), phase, wbytes, {"C": 0, "S": 1}[flavour], int(strings), int(ext), cap, fill, *_filter_args(cn_filter),
+              C.byref(o), st):
         raise DidNotTerminate(f"phase {phase}, window {wbytes}, flavour {flavour}: more than {cap} rounds")
-    return o, tuple(st)
+    return o, tuple(st)[:6 if cn_filter is None else 8]
 
 
 def walk_window_stale(der: bytes, phase: int = 0, wbytes: int = 224, slack: int = 4, strings: bool = True, ext: bool = True,
-                      fill: int = 0xA5):
+                      fill: int = 0xA5, cn_filter=None, skip: int = 0):
     """The walk through a simulated window with CONTENTS of its own: refills copy the payload's octets, a partial cooperative
     refill (kernels/readers.h coop_refill_lines_to: up to the value's end + `slack`) leaves the rows behind its chunks as they
     were, reads are clamped into the window and counted as WinReaderS does, ld2 is not; after a miss or a deferral the exact
     reader decides.  Returns (HarnessOut, stats) with stats = (per-lane refills, misses, cooperative refills, defer_exact
-    calls, partial cooperative refills, unclamped reads outside the window)."""
+    calls, partial cooperative refills, unclamped reads outside the window).  cn_filter (bytes): the walk runs under that
+    issuerCNFilter, and stats gains the reads of cn_prefix_match inside and outside the window.  skip: the first window begins
+    that many octets into the certificate, the outer headers come from sixteen octets held apart (WinGeo::SKIP)."""
     product_walk(b"\x30\x00")
     fn = _walk.harness_walk_window_stale
-    fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int, C.c_int, C.c_uint8, C.POINTER(HarnessOut),
-                   C.POINTER(C.c_uint32)]
-    o, st = HarnessOut(), (C.c_uint32 * 6)()
-    fn(der, len(der), phase, wbytes, slack, int(strings), int(ext), fill, C.byref(o), st)
-    return o, tuple(st)
+    fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int, C.c_int, C.c_uint8, C.c_char_p,
+                   C.c_uint32, C.c_int, C.POINTER(HarnessOut), C.POINTER(C.c_uint32)]
+    o, st = HarnessOut(), (C.c_uint32 * 8)()
+    fn(der, len(der), phase, wbytes, skip, slack, int(strings), int(ext), fill, *_filter_args(cn_filter), C.byref(o), st)
+    return o, tuple(st)[:6 if cn_filter is None else 8]
 
 
 def ossl_extract(der: bytes):

@@ -42,6 +42,27 @@ extern "C" void harness_set_ext(int on) { g_ext = on; }
 static int g_strings = 0;
 extern "C" void harness_set_strings(int on) { g_strings = on; }
 
+// strings.Split(filter, ",") laid out exactly as ctmr_set_filter does: at most 64 pieces, zero padded to words, 1024 words in
+// all (the callers stay within that; what ctmr_set_filter refuses is tests/test_gpu_filter_corpus.py's business)
+struct Pieces {
+  uint32_t piece_len[64], piece_word[64], words[1024], np = 0, nw = 0;
+  Pieces(const char* filter, uint32_t flen) {
+    memset(words, 0, sizeof words);
+    for (uint32_t s = 0;;) {
+      uint32_t t = s;
+      while (t < flen && filter[t] != ',') t++;
+      piece_len[np] = t - s;
+      piece_word[np] = nw;
+      memcpy((uint8_t*)(words + nw), filter + s, t - s);
+      nw += (t - s + 3) / 4;
+      np++;
+      if (t >= flen) break;
+      s = t + 1;
+    }
+  }
+  ctmr::FilterView view() const { return ctmr::FilterView{np, piece_len, piece_word, words}; }
+};
+
 extern "C" void harness_walk_f(const uint8_t* der, uint32_t len, uint8_t fill, const char* filter,
                                uint32_t flen, int use_filter, HarnessOut* out);
 
@@ -65,20 +86,8 @@ extern "C" void harness_walk(const uint8_t* der, uint32_t len, uint8_t fill, Har
 
 extern "C" void harness_walk_f(const uint8_t* der, uint32_t len, uint8_t fill, const char* filter,
                                uint32_t flen, int use_filter, HarnessOut* out) {
-  // strings.Split(filter, ",") laid out exactly as ctmr_set_filter does
-  uint32_t piece_len[64], piece_word[64], words[1024] = {0}, np = 0, nw = 0;
-  for (uint32_t s = 0;;) {
-    uint32_t t = s;
-    while (t < flen && filter[t] != ',') t++;
-    piece_len[np] = t - s;
-    piece_word[np] = nw;
-    memcpy((uint8_t*)(words + nw), filter + s, t - s);
-    nw += (t - s + 3) / 4;
-    np++;
-    if (t >= flen) break;
-    s = t + 1;
-  }
-  ctmr::FilterView fv{np, piece_len, piece_word, words};
+  const Pieces pc(filter, flen);
+  const ctmr::FilterView fv = pc.view();
   // bytes past the certificate are garbage the walk must never depend on
   std::vector<uint8_t> buf((size_t)len + 64, fill);
   memcpy(buf.data(), der, len);
@@ -151,19 +160,8 @@ static int g_touched_strict = 0;  // harness_walk_touched under the reference pr
 extern "C" void harness_touched_profile(int strict) { g_touched_strict = strict; }
 extern "C" int harness_walk_touched(const uint8_t* der, uint32_t len, uint32_t phase, const char* filter, uint32_t flen,
                                     uint32_t* bytes, uint32_t* lines128) {
-  uint32_t piece_len[64], piece_word[64], words[1024] = {0}, np = 0, nw = 0;
-  for (uint32_t s = 0;;) {
-    uint32_t t = s;
-    while (t < flen && filter[t] != ',') t++;
-    piece_len[np] = t - s;
-    piece_word[np] = nw;
-    memcpy((uint8_t*)(words + nw), filter + s, t - s);
-    nw += (t - s + 3) / 4;
-    np++;
-    if (t >= flen) break;
-    s = t + 1;
-  }
-  ctmr::FilterView fv{np, piece_len, piece_word, words};
+  const Pieces pc(filter, flen);
+  const ctmr::FilterView fv = pc.view();
   std::vector<uint8_t> buf((size_t)len + 64, 0);
   memcpy(buf.data(), der, len);
   std::vector<uint8_t> mark(len, 0);
@@ -199,6 +197,14 @@ struct WindowSimT {
   uint32_t wbytes;
   mutable int64_t grel;
   mutable uint32_t refills = 0, misses = 0, first_refill_pos = 0, first_miss_pos = 0;
+  // cn_prefix_match's reads, told apart by where they run: der_walk.h calls note_issuer() right in front of the compare and
+  // touch() right behind it.  cmp_in / cmp_out: reads of the compare inside / outside the window.
+  mutable bool in_cmp = false;
+  mutable uint32_t cmp_in = 0, cmp_out = 0;
+  void note_issuer(uint32_t, uint32_t) const { in_cmp = true; }
+  void cmp_read(bool outside) const {
+    if (in_cmp) (outside ? cmp_out : cmp_in)++;
+  }
   uint32_t size = 0xffffffffu;  // of the buffer behind p (set by the caller: damaged lengths ask for octets far outside)
   uint32_t at(uint32_t pos) const {
     uint32_t v = 0;
@@ -207,7 +213,9 @@ struct WindowSimT {
   }
   uint32_t ld4(uint32_t pos) const {
     const int64_t rel = (int64_t)pos - grel;
-    if (rel < 0 || rel > (int64_t)wbytes - 4) {
+    const bool outside = rel < 0 || rel > (int64_t)wbytes - 4;
+    cmp_read(outside);
+    if (outside) {
       if (!misses) first_miss_pos = pos;
       misses++;
     }
@@ -223,6 +231,7 @@ struct WindowSimT {
   }
   uint32_t ldg(uint32_t pos) const { return at(pos); }  // the tail registers
   void touch(uint32_t pos, uint32_t need) const {
+    in_cmp = false;
     if (need > wbytes - 16u) need = wbytes - 16u;
     const int64_t rel = (int64_t)pos - grel;
     if (rel < 0 || rel > (int64_t)(wbytes - need)) {
@@ -262,29 +271,37 @@ struct WindowSimT {
 using WindowSim = WindowSimT<false>;
 // returns ok; out = {per-lane refills, misses, position of the first refill, position of the first miss, cooperative
 // refills of the subjectAltName walk, defer_exact calls}; phase = the certificate's offset within a 128-byte line
+// use_filter: under that issuerCNFilter — out[6..8] = cn_match of THIS walk (what the window's bytes say; after a miss the
+// device asks the exact reader), reads of cn_prefix_match inside the window, reads of it outside
 extern "C" int harness_walk_window(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, int strings, int ext,
-                                   uint32_t* out) {
+                                   const char* filter, uint32_t flen, int use_filter, uint32_t* out) {
+  const Pieces pc(filter, flen);
+  const ctmr::FilterView fv = pc.view();
   std::vector<uint8_t> buf((size_t)len + 64, 0);
   memcpy(buf.data(), der, len);
   WindowSim r{{0, 0, 0, 0}, false, buf.data(), phase & 127u, wbytes, -(int64_t)(phase & 3u)};
   r.size = (uint32_t)buf.size();
   ctmr::Walk w;
-  const bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
+  const bool ok = ctmr::walk_cert(r, len, w, use_filter ? &fv : nullptr, true, strings != 0, ext != 0);
   out[0] = r.refills; out[1] = r.misses; out[2] = r.first_refill_pos; out[3] = r.first_miss_pos; out[4] = r.coop; out[5] = r.deferred;
+  out[6] = w.cn_match; out[7] = r.cmp_in; out[8] = r.cmp_out;
   return ok;
 }
 // … with the first window beginning `skip` octets into the certificate (dword-aligned down in the payload) and the outer
 // headers read from the certificate's first sixteen octets (kernels/readers.h WinGeo::SKIP, der_walk.h HeadView)
 extern "C" int harness_walk_window_skip(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, uint32_t skip, int strings,
-                                        int ext, uint32_t* out) {
+                                        int ext, const char* filter, uint32_t flen, int use_filter, uint32_t* out) {
+  const Pieces pc(filter, flen);
+  const ctmr::FilterView fv = pc.view();
   std::vector<uint8_t> buf((size_t)len + 64, 0);
   memcpy(buf.data(), der, len);
   WindowSimT<true> r{{0, 0, 0, 0}, true, buf.data(), phase & 127u, wbytes, (int64_t)skip - (int64_t)((phase + skip) & 3u)};
   memcpy(r.hd, buf.data(), 16);
   r.size = (uint32_t)buf.size();
   ctmr::Walk w;
-  const bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
+  const bool ok = ctmr::walk_cert(r, len, w, use_filter ? &fv : nullptr, true, strings != 0, ext != 0);
   out[0] = r.refills; out[1] = r.misses; out[2] = r.first_refill_pos; out[3] = r.first_miss_pos; out[4] = r.coop; out[5] = r.deferred;
+  out[6] = w.cn_match; out[7] = r.cmp_in; out[8] = r.cmp_out;
   return ok;
 }
 
@@ -311,7 +328,9 @@ struct StaleSim : WindowSim {
   }
   uint32_t ld4(uint32_t pos) const {
     int64_t rel = (int64_t)pos - grel;
-    if (rel < 0 || rel > (int64_t)wbytes - 4) {
+    const bool outside = rel < 0 || rel > (int64_t)wbytes - 4;
+    cmp_read(outside);
+    if (outside) {
       if (!misses) first_miss_pos = pos;
       misses++;
       rel = (int64_t)wbytes - 4;
@@ -366,8 +385,13 @@ struct StaleSim : WindowSim {
 // reader, as in k_map_fused; stats = {per-lane refills, misses, cooperative refills, defer_exact calls, partial cooperative
 // refills, unclamped reads outside the window}; fill = the octets around the certificate; slack: see above (readers.h: 4;
 // negative: the refill stops short of the value's end — a defect the simulation must notice)
-extern "C" int harness_walk_window_stale(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, int32_t slack,
-                                         int strings, int ext, uint8_t fill, HarnessOut* out, uint32_t* stats);
+// cn_filter (use_filter): the walk runs under that issuerCNFilter; stats[6], stats[7] = reads of cn_prefix_match inside /
+// outside the window
+// skip: the first window begins that many octets into the certificate and the outer headers come from sixteen octets held
+// apart (WinGeo::SKIP; 0: the window begins at the certificate)
+extern "C" int harness_walk_window_stale(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, uint32_t skip,
+                                         int32_t slack, int strings, int ext, uint8_t fill, const char* filter, uint32_t flen,
+                                         int use_filter, HarnessOut* out, uint32_t* stats);
 
 // An OUT-OF-REACH lane (kernels/readers.h: lrel == REL_NONE — the certificate lies below the base of its wave's buffer
 // descriptor, or REL_SPAN or more beyond it: an entry view in no order), for a wave of one lane.  What the device readers do
@@ -393,6 +417,12 @@ struct NoReachSimC {
   mutable int64_t grel = 0;
   mutable uint64_t rounds = 0;
   mutable uint32_t refills = 0, misses = 0, coop_asked = 0, stray = 0;
+  mutable bool in_cmp = false;  // cn_prefix_match's reads, as in WindowSimT
+  mutable uint32_t cmp_in = 0, cmp_out = 0;
+  void note_issuer(uint32_t, uint32_t) const { in_cmp = true; }
+  void cmp_read(bool outside) const {
+    if (in_cmp) (outside ? cmp_out : cmp_in)++;
+  }
   uint32_t at(uint32_t pos) const {
     uint32_t v = 0;
     if ((uint64_t)pos + 4u <= size) memcpy(&v, p + pos, 4);
@@ -405,10 +435,14 @@ struct NoReachSimC {
   void tick() const {
     if (++rounds > cap) throw DidNotTerminate{};
   }
-  uint32_t ld4(uint32_t pos) const { return at(pos); }  // window or global memory: the same bytes
+  uint32_t ld4(uint32_t pos) const {  // window or global memory: the same bytes
+    cmp_read(!inside(pos, 4u));
+    return at(pos);
+  }
   uint32_t ldg(uint32_t pos) const { return at(pos); }
   ctmr::RawCert raw() const { return ctmr::RawCert{(const uint32_t*)p, 0}; }
   void touch(uint32_t pos, uint32_t need) const {
+    in_cmp = false;
     if (need > wbytes - 16u) need = wbytes - 16u;
     if (!inside(pos, need)) {
       refills++;
@@ -440,6 +474,7 @@ struct NoReachSimC {
 struct NoReachSimS : NoReachSimC {
   mutable uint32_t deferred = 0;
   uint32_t clamped(uint32_t pos, uint32_t need) const {
+    cmp_read(!inside(pos, need));
     if (inside(pos, need)) return at(pos);
     misses++;
     return have ? at((uint32_t)(grel + wbytes - need)) : 0u;  // the window's last octets, or the zeros of no window
@@ -471,26 +506,32 @@ static void put_walk(HarnessOut* out, bool ok, const ctmr::Walk& w) {
 // `cap` rounds; flavour 0 = C, 1 = S (a miss or a deferral: the verdict is the exact reader's, as in k_map_fused);
 // stats = {per-lane refills, misses, cooperative refills asked for in vain, defer_exact calls, exact rerun, window reads
 // outside the window}; fill = the octets behind the certificate
+// use_filter: under that issuerCNFilter; stats[6], stats[7] = reads of cn_prefix_match inside / outside the window
 extern "C" int harness_walk_window_noreach(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, int flavour,
-                                           int strings, int ext, uint64_t cap, uint8_t fill, HarnessOut* out, uint32_t* stats) {
+                                           int strings, int ext, uint64_t cap, uint8_t fill, const char* filter, uint32_t flen,
+                                           int use_filter, HarnessOut* out, uint32_t* stats) {
+  const Pieces pc(filter, flen);
+  const ctmr::FilterView fv = pc.view();
+  const ctmr::FilterView* const f = use_filter ? &fv : nullptr;
   std::vector<uint8_t> buf((size_t)len + 64, fill);
   memcpy(buf.data(), der, len);
   ctmr::Walk w;
   memset(out, 0, sizeof *out);
-  for (int k = 0; k < 6; k++) stats[k] = 0;
+  for (int k = 0; k < 8; k++) stats[k] = 0;
   try {
     if (flavour == 0) {
       NoReachSimC r{buf.data(), phase & 127u, wbytes, (uint32_t)buf.size(), cap};
-      const bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
-      stats[0] = r.refills; stats[2] = r.coop_asked; stats[5] = r.stray;
+      const bool ok = ctmr::walk_cert(r, len, w, f, true, strings != 0, ext != 0);
+      stats[0] = r.refills; stats[2] = r.coop_asked; stats[5] = r.stray; stats[6] = r.cmp_in; stats[7] = r.cmp_out;
       put_walk(out, ok, w);
     } else {
       NoReachSimS r{{buf.data(), phase & 127u, wbytes, (uint32_t)buf.size(), cap}};
-      bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
+      bool ok = ctmr::walk_cert(r, len, w, f, true, strings != 0, ext != 0);
       stats[0] = r.refills; stats[1] = r.misses; stats[2] = r.coop_asked; stats[3] = r.deferred; stats[5] = r.stray;
+      stats[6] = r.cmp_in; stats[7] = r.cmp_out;
       if (r.misses || r.deferred) {
         PaddedReader g{buf.data()};
-        ok = ctmr::walk_cert(g, len, w, nullptr, true, strings != 0, ext != 0);
+        ok = ctmr::walk_cert(g, len, w, f, true, strings != 0, ext != 0);
         stats[4] = 1;
       }
       put_walk(out, ok, w);
@@ -501,15 +542,24 @@ extern "C" int harness_walk_window_noreach(const uint8_t* der, uint32_t len, uin
   return 1;
 }
 
-extern "C" int harness_walk_window_stale(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, int32_t slack,
-                                         int strings, int ext, uint8_t fill, HarnessOut* out, uint32_t* stats) {
+// (StaleSim with the first window behind the outer headers: der_walk.h asks R::kHead)
+struct StaleSimHead : StaleSim {
+  static constexpr bool kHead = true;
+};
+template <class SIM>
+static int walk_stale(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, uint32_t skip, int32_t slack, int strings,
+                      int ext, uint8_t fill, const ctmr::FilterView* f, HarnessOut* out, uint32_t* stats) {
   std::vector<uint8_t> buf((size_t)len + 64, fill);
   memcpy(buf.data(), der, len);
-  StaleSim r;
+  SIM r;
   r.p = buf.data();
   r.base_phase = phase & 127u;
   r.wbytes = wbytes;
-  r.grel = -(int64_t)(phase & 3u);
+  r.grel = (int64_t)skip - (int64_t)((phase + skip) & 3u);
+  if (skip) {
+    memcpy(r.hd, buf.data(), 16);
+    r.hd_ok = true;
+  }
   r.size = (uint32_t)buf.size();
   r.fill = fill;
   r.len = len;
@@ -517,14 +567,24 @@ extern "C" int harness_walk_window_stale(const uint8_t* der, uint32_t len, uint3
   r.win.assign((size_t)wbytes + 8, 0xee);
   r.load(wbytes);
   ctmr::Walk w;
-  bool ok = ctmr::walk_cert(r, len, w, nullptr, true, strings != 0, ext != 0);
+  bool ok = ctmr::walk_cert(r, len, w, f, true, strings != 0, ext != 0);
   stats[0] = r.refills; stats[1] = r.misses; stats[2] = r.coop; stats[3] = r.deferred; stats[4] = r.partial; stats[5] = r.stray;
+  stats[6] = r.cmp_in; stats[7] = r.cmp_out;
   if (r.misses || r.deferred) {
     PaddedReader g{buf.data()};
-    ok = ctmr::walk_cert(g, len, w, nullptr, true, strings != 0, ext != 0);
+    ok = ctmr::walk_cert(g, len, w, f, true, strings != 0, ext != 0);
   }
   put_walk(out, ok, w);
   return 1;
+}
+extern "C" int harness_walk_window_stale(const uint8_t* der, uint32_t len, uint32_t phase, uint32_t wbytes, uint32_t skip,
+                                         int32_t slack, int strings, int ext, uint8_t fill, const char* filter, uint32_t flen,
+                                         int use_filter, HarnessOut* out, uint32_t* stats) {
+  const Pieces pc(filter, flen);
+  const ctmr::FilterView fv = pc.view();
+  const ctmr::FilterView* const f = use_filter ? &fv : nullptr;
+  return skip ? walk_stale<StaleSimHead>(der, len, phase, wbytes, skip, slack, strings, ext, fill, f, out, stats)
+              : walk_stale<StaleSim>(der, len, phase, wbytes, 0, slack, strings, ext, fill, f, out, stats);
 }
 
 // k_ec_resolve's loader + equation on the host: the point whose X starts at BIT `xbit` of buf (RightAlign as a bit offset)
